@@ -14,6 +14,9 @@ Prints ONE JSON line on rank 0 (contract in the task description).  The headline
   * `roofline`     - the dominant kernel family (MFMA contractions), measured live with stream events;
   * `roofline_hbm` - the HBM-bound kernels of SURVEY 8(d), each timed live on its config-2 operands;
   * `cpu_baseline` - the CPU oracle timed on this box's host cores (1 warm-up + 3 timed steps, median).
+
+`--dump-outputs DIR` writes what the last timed step of the headline precision computed (see `dump_outputs`) as
+DIR/<name>.npy, so that two builds can be compared output for output on identical (seeded) inputs.
 """
 import argparse
 import json
@@ -82,6 +85,27 @@ def cpu_baseline(B, T, L, V, threads):
                 sample="fwd+bwd of B=%d T=%d L=%d V=%d fp32, dropout 0: 1 small warm-up + 3 timed steps %s s, median" %
                        (B, T, L, V, "/".join("%.1f" % d for d in dts)))
     return base, losses
+
+
+DUMP_SAMPLE = 4 * 1024 * 1024     # elements per sampled arena: 2 x 16 MB of float32
+
+
+def dump_outputs(d, model, flat, opt):
+    """What a caller of the timed step receives after its last replay: the losses, the optimizer's step statistics,
+    and the updated weights and the gradients of that step (flat arenas of ~47 M floats each, so a fixed, seeded
+    sample of DUMP_SAMPLE sorted positions; the same positions for both)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    torch.cuda.synchronize()
+    losses = [float(model.loss.detach()), float(model._loss_ctc_t.detach()), float(model._loss_att_t.detach())]
+    np.save(os.path.join(d, "loss.npy"), np.asarray(losses, dtype=np.float64))        # loss, loss_ctc, loss_att
+    # optimizer state: step, lr, ..., grad_norm, skipped, clip_coef (train.NoamAdam.stats)
+    np.save(os.path.join(d, "optimizer_state.npy"), opt.state.detach().cpu().numpy().astype(np.float64))
+    n = flat.numel
+    g = torch.Generator().manual_seed(20240)
+    idx = torch.randperm(n, generator=g)[:min(DUMP_SAMPLE, n)].sort().values.to(flat.data.device)
+    np.save(os.path.join(d, "params_sample.npy"), flat.data[idx].float().cpu().numpy())
+    np.save(os.path.join(d, "grads_sample.npy"), flat.grad[idx].float().cpu().numpy())
 
 
 def hbm_rooflines(prec):
@@ -248,6 +272,8 @@ def run_precision(a, prec, rank, world, dev):
     ms = dt / a.steps * 1e3
     loss_val = float(model.loss.detach())
     st = opt.stats()
+    if a.dump_outputs and rank == 0 and prec == a.precision:
+        dump_outputs(a.dump_outputs, model, flat, opt)
 
     # ---- data-parallel runs explain themselves: collectives alone, the step with and without them, and the N = 1
     #      step (one graph, no phases) measured in this very process on rank 0 ----
@@ -461,7 +487,11 @@ def main():
                     help="skip the `configs` object (BASELINE configs 4 and 5 at full size, both precisions, ~40 s)")
     ap.add_argument("--rehearse-dp", action="store_true",
                     help="N=1 only: run the N>1 'graph' code path on a one-rank RCCL group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one (headline precision) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from espnet_amd import train
     rank, local_rank, world = train.init_distributed()
