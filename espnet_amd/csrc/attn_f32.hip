@@ -888,7 +888,7 @@ int launch_fwd_long_q(AttnF32Args a, hipStream_t stream) {
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
-// queries and waves per workgroup.  These kernels are bound by latency, not by their L2 traffic: measured (tools/attn_long_lq_probe.py,
+// queries and waves per workgroup.  These kernels are bound by latency, not by their L2 traffic: measured (DESIGN.md §6, item 2,
 // B = 16, forward / query-side backward TFLOP/s) 16 queries x 4 waves give 45 - 49 / 32 - 39 while TWO workgroups share a CU (LDS <= 80 KB:
 // up to ~976 keys) and 30 - 32 / 20 - 23 beyond that, where one workgroup = four waves per CU is left; 32 queries (two 16-query tiles per
 // wave: every key / value / position fragment fetched serves both) give 41 - 46 / 26 - 30 wherever they fit (1100 keys) - worse than two
@@ -897,22 +897,17 @@ int launch_fwd_long_q(AttnF32Args a, hipStream_t stream) {
 // 2048 keys (to 4096: the MFMA tiles run half empty).
 struct LongGeom { int lq, nw; };
 inline LongGeom long_geom(int T1, int T2) {
-  static const int force_lq = getenv("EAMD_ATTN_LONG_LQ") ? atoi(getenv("EAMD_ATTN_LONG_LQ")) : 0;      // A/B knobs
-  static const int force_nw = getenv("EAMD_ATTN_LONG_NW") ? atoi(getenv("EAMD_ATTN_LONG_NW")) : 0;
   const int nkt = (T2 + 15) / 16;
   auto bytes = [&](int lq, int nw) { return ((size_t)lq * (nkt * 16 + 4) + nw * 16 * PLD + 2 * nw * lq) * sizeof(float); };
   LongGeom g{16, 4};
   if (bytes(16, 4) > 160 * 1024) g = LongGeom{8, 4};
   if (bytes(g.lq, 4) > 80 * 1024) g.nw = bytes(g.lq, 8) <= 160 * 1024 ? 8 : bytes(g.lq, 6) <= 160 * 1024 ? 6 : 4;   // one workgroup per CU: more waves
-  if ((force_lq == 32 || force_lq == 16 || force_lq == 8) && bytes(force_lq, 4) <= 160 * 1024) g = LongGeom{force_lq, 4};
-  if ((force_nw == 4 || force_nw == 6 || force_nw == 8) && g.lq != 32 && bytes(g.lq, force_nw) <= 160 * 1024) g.nw = force_nw;
   (void)T1;
   return g;
 }
 template <typename T, bool REL>
 int launch_fwd_long(AttnF32Args a, hipStream_t stream) {
   const LongGeom g = long_geom(a.T1, a.T2);
-  if (g.lq == 32) return launch_fwd_long_q<T, REL, 32, 4>(a, stream);
   if (g.lq == 16) return g.nw == 8 ? launch_fwd_long_q<T, REL, 16, 8>(a, stream) : g.nw == 6 ? launch_fwd_long_q<T, REL, 16, 6>(a, stream)
                                                                                                : launch_fwd_long_q<T, REL, 16, 4>(a, stream);
   return g.nw == 8 ? launch_fwd_long_q<T, REL, 8, 8>(a, stream) : g.nw == 6 ? launch_fwd_long_q<T, REL, 8, 6>(a, stream)
@@ -937,7 +932,6 @@ int launch_bwd_long_q(AttnF32BwdArgs a, int dq_bf16, hipStream_t stream) {
 template <typename T>
 int launch_bwd_long(AttnF32BwdArgs a, int dq_bf16, hipStream_t stream) {
   const LongGeom g = long_geom(a.T1, a.T2);
-  if (g.lq == 32) return launch_bwd_long_q<T, 32, 4>(a, dq_bf16, stream);
   // (six waves: measured SLOWER than four in this kernel at 2048 keys - 1058 against 760 us - while the forward gains, 639 against 820)
   if (g.lq == 16) return g.nw == 8 ? launch_bwd_long_q<T, 16, 8>(a, dq_bf16, stream) : launch_bwd_long_q<T, 16, 4>(a, dq_bf16, stream);
   return g.nw == 8 ? launch_bwd_long_q<T, 8, 8>(a, dq_bf16, stream) : launch_bwd_long_q<T, 8, 4>(a, dq_bf16, stream);

@@ -11,72 +11,11 @@ namespace {
 
 constexpr int KMAX = 32;
 
-// y[b,t,c] = bias[c] + sum_k w[c,k] * x[b, t + k - pad, c]         (flip=0, forward)
-// y[b,t,c] =           sum_k w[c,k] * x[b, t - k + pad, c]         (flip=1, input gradient)
-// One thread = one channel x TT consecutive frames: the K taps stay in registers and the input
-// window (TT + K - 1 values) is read once, lanes along C (coalesced 256-B rows).
-// The block's 256 x K taps are fetched with coalesced loads and handed out through LDS (a direct
-// w[c*K + k] read is a 64-way scattered access per tap).
-template <int TT>
-__global__ __launch_bounds__(256) void dwconv_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                     const float* __restrict__ bias, float* __restrict__ y,
-                                                     int B, int T, int C, int K, int pad, int flip) {
-  __shared__ float wl[256 * KMAX];
-  const int c0 = blockIdx.x * blockDim.x;
-  const int c_raw = c0 + threadIdx.x;
-  const int c = min(c_raw, C - 1);          // dead lanes shadow a valid channel (no divergent exit before the barrier)
-  const int nchunk = (T + TT - 1) / TT;
-  const int b = blockIdx.y / nchunk;
-  const int t0 = (blockIdx.y % nchunk) * TT;
-  // the whole input window first, branch-free (clamped rows, zeroed afterwards): TT + K - 1 independent loads in
-  // flight together instead of one round trip per tap; window position j covers frame t0 - pad + j
-  // the block's taps likewise: KMAX independent coalesced loads per thread (a runtime-bounded copy loop waits for
-  // every load before issuing the next: K serialized round trips)
-  const int nw = min(256, C - c0) * K;
-  float tw[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q) tw[q] = w[(long)c0 * K + min((int)threadIdx.x + q * 256, nw - 1)];
-  const float* xb = x + (long)b * T * C + c;
-  float xv[TT + KMAX - 1];
-#pragma unroll
-  for (int j = 0; j < TT + KMAX - 1; ++j) {
-    const int ts = min(max(t0 - pad + j, 0), T - 1);
-    xv[j] = xb[(long)ts * C];
-  }
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-    if ((int)threadIdx.x + q * 256 < nw) wl[threadIdx.x + q * 256] = tw[q];
-  __syncthreads();
-  if (c_raw >= C) return;
-  float wr[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    int kk = flip ? K - 1 - k : k;          // flipped taps turn the gradient into the same correlation
-    wr[k] = (k < K) ? wl[threadIdx.x * K + min(max(kk, 0), K - 1)] : 0.f;
-  }
-  const float bv = (bias && !flip) ? bias[c] : 0.f;
-  float acc[TT];
-#pragma unroll
-  for (int i = 0; i < TT; ++i) acc[i] = bv;
-#pragma unroll
-  for (int j = 0; j < TT + KMAX - 1; ++j) {
-    const int ts = t0 - pad + j;
-    const float v = (ts >= 0 && ts < T && j < TT + K - 1) ? xv[j] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TT; ++i) {
-      const int k = j - i;                 // tap index feeding output t0 + i
-      if (k >= 0 && k < KMAX) acc[i] += wr[k] * v;
-    }
-  }
-  float* yb = y + (long)b * T * C + c;
-#pragma unroll
-  for (int i = 0; i < TT; ++i)
-    if (t0 + i < T) yb[(long)(t0 + i) * C] = acc[i];
-}
-
 __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, float nb, float mb, float m2b);
 
-// LDS-tiled form of the same correlation (the default): a block owns 64 channels x NWV*8 frames.  The NWV*8 + K - 1
+// y[b,t,c] = bias[c] + sum_k w[c,k] * x[b, t + k - pad, c]         (flip=0, forward)
+// y[b,t,c] =           sum_k w[c,k] * x[b, t - k + pad, c]         (flip=1, input gradient)
+// LDS-tiled (it replaced a form with one thread per channel x 8 frames): a block owns 64 channels x NWV*8 frames.  The NWV*8 + K - 1
 // input rows are fetched ONCE per block (coalesced 256-byte rows, all loads of a thread in flight together) into LDS,
 // as are the 64 x K taps; wave w then produces frames [8w, 8w+8) from LDS.  L2 -> CU traffic per output drops from
 // (8 + K - 1) / 8 input rows + a 256 x K tap block per 8 frames to (NWV*8 + K - 1) / (NWV*8) rows + a 64 x K tap block
@@ -775,25 +714,11 @@ inline int grid_for(long n) {
   return (int)b;
 }
 
-// frames per thread of the depthwise convolution: fewer frames = more workgroups in flight (the kernel is
-// latency-bound at B*T ~ 8k frames), more frames = less re-reading of the K-1 halo.  EAMD_DWCONV_TT overrides.
+// depthwise convolution: 64 channels x 64 frames per block
 inline void dwconv_launch(const float* x, const float* w, const float* bias, float* y, int B, int T, int C, int K,
                           int flip, hipStream_t s) {
-  static const int tt_env = [] { const char* e = getenv("EAMD_DWCONV_TT"); return e ? atoi(e) : 0; }();
-  const int pad = (K - 1) / 2;
-  if (tt_env == 0) {      // LDS-tiled default: 64 channels x 64 frames per block
-    hipLaunchKernelGGL((dwconv_lds_kernel<8, 0>), dim3((C + 63) / 64, B * ((T + 63) / 64)), dim3(512), 0, s, x, w, bias, y, B, T, C,
-                       K, pad, flip, (const float*)nullptr, 0, (float*)nullptr);
-    return;
-  }
-  const int tt = tt_env;
-  const int gx = (C + 255) / 256;
-  if (tt == 4)
-    hipLaunchKernelGGL(dwconv_kernel<4>, dim3(gx, B * ((T + 3) / 4)), dim3(256), 0, s, x, w, bias, y, B, T, C, K, pad, flip);
-  else if (tt == 16)
-    hipLaunchKernelGGL(dwconv_kernel<16>, dim3(gx, B * ((T + 15) / 16)), dim3(256), 0, s, x, w, bias, y, B, T, C, K, pad, flip);
-  else
-    hipLaunchKernelGGL(dwconv_kernel<8>, dim3(gx, B * ((T + 7) / 8)), dim3(256), 0, s, x, w, bias, y, B, T, C, K, pad, flip);
+  hipLaunchKernelGGL((dwconv_lds_kernel<8, 0>), dim3((C + 63) / 64, B * ((T + 63) / 64)), dim3(512), 0, s, x, w, bias, y, B, T, C,
+                     K, (K - 1) / 2, flip, (const float*)nullptr, 0, (float*)nullptr);
 }
 
 }  // namespace
@@ -827,8 +752,7 @@ int eamd_dwconv_bwd_w(const float* dy, const float* x, float* dw, float* db, int
   long gy = (512 + gx - 1) / gx;
   if (gy > total) gy = total;
   if (gy < 1) gy = 1;
-  static const int tpb_env = [] { const char* e = getenv("EAMD_DWW_TPB"); return e ? atoi(e) : 0; }();
-  const long tpb = tpb_env ? tpb_env : (total + gy - 1) / gy;
+  const long tpb = (total + gy - 1) / gy;
   gy = (total + tpb - 1) / tpb;
   hipLaunchKernelGGL(dwconv_bwd_w_kernel, dim3(gx, (unsigned)gy), dim3(WNWV * 64), 0, (hipStream_t)stream, dy, x, dw, db, B,
                      T, C, K, (K - 1) / 2, (int)tpb, 0);
@@ -991,8 +915,8 @@ int eamd_conv3x3_c1_fwd(const float* x, const float* w, const float* bias, void*
 static void conv_c1_bwd_w_grid(int B, int H, int C, int* gx, int* gy, long* rpb) {
   long nrow = (long)B * H;
   *gx = (C + 255) / 256;
-  static const int want_env = [] { const char* e = getenv("EAMD_C1W_BLOCKS"); return e ? atoi(e) : 2048; }();
-  long want = want_env / *gx; if (want < 1) want = 1;
+  constexpr int C1W_BLOCKS = 2048;
+  long want = C1W_BLOCKS / *gx; if (want < 1) want = 1;
   *rpb = (nrow + want - 1) / want; if (*rpb < 1) *rpb = 1;
   *gy = (int)((nrow + *rpb - 1) / *rpb);
 }

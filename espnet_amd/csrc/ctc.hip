@@ -696,8 +696,7 @@ extern "C" int eamd_ctc_prefix_state_dyn(const float* logp, const int32_t* lens,
     return EAMD_EINVAL;
   const int* ol_dev = olen_dev;
   const int n = nutt * per_utt;
-  static const int state_scan = getenv("EAMD_CTC_STATE_SCAN") ? atoi(getenv("EAMD_CTC_STATE_SCAN")) : 1;     // A/B knob: 0 = frame by frame
-  if (state_scan && Tmax <= 2048) {
+  if (Tmax <= 2048) {
 #define EAMD_SCAN_(Q) hipLaunchKernelGGL(ctc_prefix_state_scan_kernel<Q>, dim3(n), dim3(64), 0, (hipStream_t)stream, logp, lens, per_utt, r_prev, \
                                          (const long long*)parent, (const long long*)tok, last, olen, alive, r_out, n, Tmax, V, blank, ol_dev)
     if (Tmax <= 512) EAMD_SCAN_(8);

@@ -622,13 +622,14 @@ int eamd_add_cast_bf16(const float* a, const float* b, void* out_bf16, int64_t r
   return EAMD_OK;
 }
 
+constexpr int ACC_RPB = 64;      // rows per block of add_cast_colsum2_kernel
+
 int eamd_add_cast_colsum2(const float* a, const float* b, void* out_bf16, int64_t ld_out, float* suma, float* sumb,
                             int64_t rows, int D, void* stream) {
   if (!a || !b || !out_bf16 || !suma || !sumb || rows <= 0 || D <= 0 || ld_out < D) return EAMD_EINVAL;
   if (D % 2 || D > 512 || ld_out % 2 || (((uintptr_t)a | (uintptr_t)b) & 7) || ((uintptr_t)out_bf16 & 3)) return EAMD_EUNSUPPORTED;
-  static const int rpb = [] { const char* e = getenv("EAMD_ACC_RPB"); return e ? atoi(e) : 64; }();
-  hipLaunchKernelGGL(add_cast_colsum2_kernel<false>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream, a, b,
-                     (unsigned int*)out_bf16, (long)ld_out, suma, sumb, (long)rows, D, rpb);
+  hipLaunchKernelGGL(add_cast_colsum2_kernel<false>, dim3((unsigned)((rows + ACC_RPB - 1) / ACC_RPB)), dim3(256), 0, (hipStream_t)stream, a, b,
+                     (unsigned int*)out_bf16, (long)ld_out, suma, sumb, (long)rows, D, ACC_RPB);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
@@ -637,9 +638,8 @@ int eamd_add_colsum2_f32(const float* a, const float* b, float* out, int64_t ld_
                          int D, void* stream) {
   if (!a || !b || !out || !suma || !sumb || rows <= 0 || D <= 0 || ld_out < D) return EAMD_EINVAL;
   if (D % 2 || D > 512 || ld_out % 2 || (((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 7)) return EAMD_EUNSUPPORTED;
-  static const int rpb = [] { const char* e = getenv("EAMD_ACC_RPB"); return e ? atoi(e) : 64; }();
-  hipLaunchKernelGGL(add_cast_colsum2_kernel<true>, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, (hipStream_t)stream, a, b,
-                     (unsigned int*)out, (long)ld_out, suma, sumb, (long)rows, D, rpb);
+  hipLaunchKernelGGL(add_cast_colsum2_kernel<true>, dim3((unsigned)((rows + ACC_RPB - 1) / ACC_RPB)), dim3(256), 0, (hipStream_t)stream, a, b,
+                     (unsigned int*)out, (long)ld_out, suma, sumb, (long)rows, D, ACC_RPB);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
@@ -665,11 +665,11 @@ int eamd_colsum(const void* x, int64_t ld, float* out, int64_t rows, int D, floa
   const int ncol = pair ? D / 2 : D;                      // threads needed along the columns
   const int nthr = 256;
   const int gx = (ncol + nthr - 1) / nthr;
-  static const int min_rpb = [] { const char* e = getenv("EAMD_COLSUM_RPB"); return e ? atoi(e) : 128; }();
+  constexpr int MIN_RPB = 128;
   // ~1024 workgroups: more of them only lengthen the same-address atomic chains (measured: 2048 blocks on a
   // [151k, 256] bf16 matrix take 109 us, 1024 take 61 us)
   long want = 1024 / gx; if (want < 1) want = 1;
-  long rpb = (rows + want - 1) / want; if (rpb < (pair ? min_rpb / 2 : min_rpb)) rpb = pair ? min_rpb / 2 : min_rpb;
+  long rpb = (rows + want - 1) / want; if (rpb < (pair ? MIN_RPB / 2 : MIN_RPB)) rpb = pair ? MIN_RPB / 2 : MIN_RPB;
   if (rpb < 8) rpb = 8;
   const int gy = (int)((rows + rpb - 1) / rpb);
   if (pair) {

@@ -23,8 +23,8 @@
 //   + role programs split at the top, fragments prefetched across the barrier          192 / 167 us
 //   register-direct weights, one barrier per chunk                                      177 / 150 us
 //   + h / f copies stored from LDS by the down waves                                    156 / 145 us
-// What the s_memtime stamps of the diagnostic build (-DFFN_STAMP, tools/ffn_stamp.py) show is left: the up waves carry
-// all of the epilogue arithmetic, so the down waves wait for them at the chunk barrier.
+// What s_memtime stamps of a diagnostic build showed is left (DESIGN_HISTORY.md §B): the up waves carry all of the
+// epilogue arithmetic, so the down waves wait for them at the chunk barrier.
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
@@ -32,23 +32,8 @@
 #include "ffn_ln.h"
 #include "ln_bwd_rows.h"
 
-#ifdef FFN_STAMP
-// diagnostic build only: s_memtime stamps of one up and one down wave of workgroup 100 during body 4
-__device__ unsigned long long ffn_stamps[2][2][8][8];
-#define STAMP3(role, P, s, k)                                                                            \
-  do {                                                                                                   \
-    if (blockIdx.x == 100 && (P) == 4 && (wave == 0 || wave == 4) && lane == 0)                          \
-      ffn_stamps[BWD][role][s][k] = __builtin_amdgcn_s_memtime();                                        \
-  } while (0)
-#else
-#define STAMP3(role, P, s, k) do { } while (0)
-#endif
-
 bool eamd_ffn_bf16_ok(const eamd_ffn_t* p);                      // ffn_bf16.hip
 int eamd_ffn_bf16_launch(const eamd_ffn_t* p, int bwd, void* stream);
-bool eamd_ffn_f32_sym(int F);                                    // ffn_f32_sym.hip: the symmetric fp32 form (F % 256 == 0)
-int eamd_ffn_f32_sym_launch(const eamd_ffn_t* p, int bwd, void* stream);
-int eamd_ffn_f32_sym_pack(const float* w1, const float* w2, float* p0, float* p1, float* p2, float* p3, int F, void* stream);
 
 namespace {
 
@@ -203,7 +188,6 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
     auto step = [&](auto s_c, auto up_c, auto epi_c, int P) __attribute__((always_inline)) {
       constexpr int s = decltype(s_c)::value;
       constexpr bool UP = decltype(up_c)::value, EPI = decltype(epi_c)::value;
-      STAMP3(0, P, s, 0);
       if constexpr (UP) {
         load_b(std::integral_constant<int, (s + 3) & 3>{}, 8 * P + s + 3);
         if constexpr (s == 4) {      // behind the last epilogue quarter of the previous chunk (step 3), which still reads them
@@ -214,9 +198,7 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
         read_a(s_c, std::integral_constant<int, 1>{});
         mfma_half(std::integral_constant<int, s & 3>{}, std::integral_constant<int, 0>{});
       }
-      STAMP3(0, P, s, 1);
       if constexpr (EPI && s < 4) epi_quarter(std::integral_constant<int, s & 1>{}, std::integral_constant<int, (s / 2)>{}, P - 1);     // (row tile, row pair)
-      STAMP3(0, P, s, 2);
       if constexpr (UP) {
         __builtin_amdgcn_sched_barrier(0);
         read_a(std::integral_constant<int, (s + 1) & 7>{}, std::integral_constant<int, 0>{});
@@ -228,9 +210,7 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
             for (int j = 0; j < 2; ++j) { zold[i][j] = zacc[i][j]; zacc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
         }
       }
-      STAMP3(0, P, s, 3);
       if constexpr (s == 7) __syncthreads();
-      STAMP3(0, P, s, 4);
     };
     auto period = [&](auto up_c, auto epi_c, int P) __attribute__((always_inline)) {
       step(std::integral_constant<int, 0>{}, up_c, epi_c, P);
@@ -292,7 +272,6 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
       constexpr int s = decltype(s_c)::value;
       constexpr bool D = decltype(d_c)::value, DN = decltype(dn_c)::value;
       const int gd = 8 * (P - 2) + s;
-      STAMP3(1, P, s, 0);
       if constexpr (s + 3 < 8 ? D : DN) load_b(std::integral_constant<int, (s + 3) & 3>{}, gd + 3);
       if constexpr (D && (s == 1 || s == 3)) {
         // global copies of chunk P - 2 for backward (forward: h at s = 1, f at s = 3; backward: dz at s = 1): 32 rows x 512 bytes
@@ -315,10 +294,8 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
         if constexpr (s < 7) read_a(std::integral_constant<int, (s + 1) & 1>{}, s + 1, P & 1);
         mfma_step(std::integral_constant<int, s & 3>{}, std::integral_constant<int, s & 1>{});
       }
-      STAMP3(1, P, s, 3);
       if constexpr (s == 7) {
         __syncthreads();
-        STAMP3(1, P, s, 4);
         if constexpr (DN) read_a(std::integral_constant<int, 0>{}, 0, (P + 1) & 1);      // chunk P - 1 is complete behind this barrier
       }
     };
@@ -514,12 +491,6 @@ int check_ffn(const eamd_ffn_t* p, bool bwd) {
 
 }  // namespace
 
-#ifdef FFN_STAMP
-extern "C" int eamd_ffn_debug_stamps(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ffn_stamps), sizeof(ffn_stamps));
-}
-#endif
-
 extern "C" int eamd_ffn_pack_f32(const float* w1, const float* w2, float* fwd_first, float* fwd_second, float* bwd_first,
                                  float* bwd_second, int D, int F, void* stream) {
   if (!w1 || !w2 || !fwd_first || !fwd_second || !bwd_first || !bwd_second || F <= 0) return EAMD_EINVAL;
@@ -527,7 +498,6 @@ extern "C" int eamd_ffn_pack_f32(const float* w1, const float* w2, float* fwd_fi
   for (const void* q : {(const void*)w1, (const void*)w2, (const void*)fwd_first, (const void*)fwd_second, (const void*)bwd_first,
                         (const void*)bwd_second})
     if (!al16(q)) return EAMD_EUNSUPPORTED;
-  if (eamd_ffn_f32_sym(F)) return eamd_ffn_f32_sym_pack(w1, w2, fwd_first, fwd_second, bwd_first, bwd_second, F, stream);
   const long npiece = (long)(F / FHC) * 8 * 4 * 4 * 64;
   hipLaunchKernelGGL(ffn_pack_f32_kernel, dim3((unsigned)((npiece + 255) / 256), 4), dim3(256), 0, (hipStream_t)stream, w1, w2,
                      fwd_first, fwd_second, bwd_first, bwd_second, F);
@@ -540,7 +510,7 @@ extern "C" int eamd_ffn_pack_f32_multi(const eamd_ffn_pack_t* jobs, int njobs, v
   for (int i = 0; i < njobs; ++i) {
     const eamd_ffn_pack_t& q = jobs[i];
     if (!q.w1 || !q.w2 || !q.fwd_first || !q.fwd_second || !q.bwd_first || !q.bwd_second || q.F <= 0) return EAMD_EINVAL;
-    if (q.D != FD || q.F % FHC != 0 || q.F < 2 * FHC || eamd_ffn_f32_sym(q.F)) return EAMD_EUNSUPPORTED;
+    if (q.D != FD || q.F % FHC != 0 || q.F < 2 * FHC) return EAMD_EUNSUPPORTED;
     for (const void* a : {(const void*)q.w1, (const void*)q.w2, (const void*)q.fwd_first, (const void*)q.fwd_second,
                           (const void*)q.bwd_first, (const void*)q.bwd_second})
       if (!al16(a)) return EAMD_EUNSUPPORTED;
@@ -566,7 +536,6 @@ extern "C" int eamd_ffn_fwd(const eamd_ffn_t* p, void* stream) {
   const int rc = check_ffn(p, false);
   if (rc != EAMD_OK) return rc;
   if (p->dtype == 1) return eamd_ffn_bf16_launch(p, 0, stream);
-  if (p->hsplit <= 1 && eamd_ffn_f32_sym(p->F)) return eamd_ffn_f32_sym_launch(p, 0, stream);
   return p->act == EAMD_ACT_SWISH ? launch_ffn<false, EAMD_ACT_SWISH>(*p, (hipStream_t)stream)
                                   : launch_ffn<false, EAMD_ACT_RELU>(*p, (hipStream_t)stream);
 }
@@ -575,6 +544,5 @@ extern "C" int eamd_ffn_bwd(const eamd_ffn_t* p, void* stream) {
   const int rc = check_ffn(p, true);
   if (rc != EAMD_OK) return rc;
   if (p->dtype == 1) return eamd_ffn_bf16_launch(p, 1, stream);
-  if (p->hsplit <= 1 && eamd_ffn_f32_sym(p->F) && !p->lnb_x) return eamd_ffn_f32_sym_launch(p, 1, stream);
   return launch_ffn<true, EAMD_ACT_NONE>(*p, (hipStream_t)stream);
 }

@@ -409,9 +409,8 @@ static int gemm_check(eamd_gemm_t& p, int& tile_out) {
       // once there are two full rounds of tiles - the implicit-conv GEMMs of the subsampling front end
       // (151392 x 256 x 2304: 461 -> 335 us, 160000 x 256 x 1024: 276 -> 220 us) and the transducer's logits products
       // (37774 x 5000 x 320: config 5 46.9 -> 44.4 ms)
-      static const int kmin = [] { const char* e = getenv("EAMD_BF16_T128_KMIN"); return e ? atoi(e) : 320; }();
-      static const int nmin = [] { const char* e = getenv("EAMD_BF16_T128_NMIN"); return e ? atoi(e) : 256; }();
-      tile = (t128 >= 1024 && p.K >= kmin && p.M >= 2048 && p.N >= nmin) ? 128 : 64;
+      constexpr int T128_KMIN = 320, T128_NMIN = 256;
+      tile = (t128 >= 1024 && p.K >= T128_KMIN && p.M >= 2048 && p.N >= T128_NMIN) ? 128 : 64;
     } else {
       // measured on MI355X (tools/gemm_f32_probe.py): from ~1 tile per CU on the 128x128 tile wins (4x fewer LDS
       // stores and barriers per MFMA), below that the 64x64 tile's 4x as many workgroups do
@@ -459,11 +458,10 @@ extern "C" int eamd_gemm(const eamd_gemm_t* pp, void* stream_) {
 
   // fp32 operands asked to go through the bf16 matrix cores (precision 1, bf16 mode's leftovers: activations a producer
   // keeps in fp32): the generic kernel converts while staging behind guarded loads (30-65 TFLOP/s on skinny shapes);
-  // the implicit-conv weight gradients among them (EAMD_P1_F32=0: off) go (gather + transA: tiny output, K in the millions,
+  // the implicit-conv weight gradients among them go (gather + transA: tiny output, K in the millions,
   // bound by the operand stream) through the pipelined fp32 kernel instead - exact fp32 arithmetic, i.e. no less accurate
   // (config 4, bf16 mode: 92.5 -> 91.1 ms)
-  static const int p1_f32 = [] { const char* e = getenv("EAMD_P1_F32"); return e ? atoi(e) : 1; }();
-  if (p.precision == 1 && p1_f32 && p.gather.enabled && p.transA && !p.Hb && p.drop_p == 0.f && p.a_drop_p == 0.f &&
+  if (p.precision == 1 && p.gather.enabled && p.transA && !p.Hb && p.drop_p == 0.f && p.a_drop_p == 0.f &&
       p.b_drop_p == 0.f) {
     const int rc = eamd_gemm_f32_dispatch(p, tile, stream);
     if (rc != EAMD_EUNSUPPORTED) return rc;

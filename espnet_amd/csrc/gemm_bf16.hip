@@ -559,13 +559,12 @@ int eamd_gemm_bf16_dispatch(const eamd_gemm_t& p, int tile, hipStream_t stream) 
   if (a_ok && b_ok && tile == 64 && !p.transA && !p.transB && (p.K == 64 || p.K == 128) && p.splitk == 1 && p.C && !p.Cb &&
       !p.Hb && !p.bias && !p.aux && !p.R && !p.colsum && p.epilogue == 0 && p.beta == 0.f && p.drop_p <= 0.f &&
       p.a_act == EAMD_ACT_NONE && p.b_act == EAMD_ACT_NONE && !p.cmap.enabled) {
-    static const int direct_on = [] { const char* e = getenv("EAMD_GEMM_DIRECT"); return e ? atoi(e) : 1; }();
-    if (direct_on) return eamd_gemm_bf16_direct(p, stream);      // attention score products: one or two K-tiles
+    return eamd_gemm_bf16_direct(p, stream);      // attention score products: one or two K-tiles
   }
   if (a_ok && b_ok && tile == 64) {
-    static const int persist_min = [] { const char* e = getenv("EAMD_GEMM_PERSIST_MIN"); return e ? atoi(e) : 512; }();
+    constexpr int PERSIST_MIN_TILES = 512;
     const long ntiles = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-    if (persist_min > 0 && ntiles >= persist_min && ntiles < (1L << 30) && p.K % 256 == 0 && p.splitk == 1 &&
+    if (ntiles >= PERSIST_MIN_TILES && ntiles < (1L << 30) && p.K % 256 == 0 && p.splitk == 1 &&
         p.batch1 * p.batch2 == 1 && !p.colsum && p.a_act == EAMD_ACT_NONE && p.b_act == EAMD_ACT_NONE && !p.cmap.enabled &&
         !p.transB && !p.aux && p.epilogue < 7) {   // measured: the k-strided-B (NN) launches do not gain, aux epilogues want the prefetch
       return eamd_gemm_bf16_persist(p, (int)ntiles, stream);

@@ -577,27 +577,21 @@ __global__ __launch_bounds__(NT_, 2) void gemm_f32_group_kernel(const eamd_gemm_
 // convolution's input gradient are four x W^T products of 4, 2, 2 and 1 taps over the same rows; launched one after another
 // each ends in a partly filled last tile round (2366 tiles = 4.6 rounds of 512) and a launch gap.  The problems follow each
 // other inside one grid (groups of 8 workgroups, one per XCD, so that id & 7 stays the XCD inside a problem): config 2,
-// 2003 -> 1890 us.  Dealing the groups to the problems in turn instead (EAMD_GEMM_MULTI_ORDER=0: tiles of all reduction
-// lengths resident together, stores of one under the main loop of another) was much SLOWER, 3130 us: the four weight
-// images (2.4 MB) and four result streams then compete for each XCD's 4 MB of L2.
+// 2003 -> 1890 us.  Dealing the groups to the problems in turn instead (tiles of all reduction lengths resident together,
+// stores of one under the main loop of another) was much SLOWER, 3130 us: the four weight images (2.4 MB) and four result
+// streams then compete for each XCD's 4 MB of L2.
 struct MultiF {
   eamd_gemm_t p[EAMD_GEMM_MULTI_MAX];
   int nt[EAMD_GEMM_MULTI_MAX];
-  int n, order;
+  int n;
 };
 
 template <int BM, int BN, bool TA, bool TB, bool GAT, bool NOPAD>
 __global__ __launch_bounds__(NT_, 2) void gemm_f32_multi_kernel(const MultiF m) {
   const int g = (int)blockIdx.x >> 3;
-  int cls, bid;
-  if (m.order == 0) {
-    cls = g % m.n;
-    bid = (g / m.n) * 8 + ((int)blockIdx.x & 7);
-  } else {
-    const int per = (int)gridDim.x / (8 * m.n);
-    cls = g / per;
-    bid = (g - cls * per) * 8 + ((int)blockIdx.x & 7);
-  }
+  const int per = (int)gridDim.x / (8 * m.n);
+  const int cls = g / per;
+  const int bid = (g - cls * per) * 8 + ((int)blockIdx.x & 7);
   if (bid >= m.nt[cls]) return;            // this problem has fewer tiles than the largest one of the launch
   const eamd_gemm_t p = m.p[cls];          // wave-uniform copy: scalar loads up front, none inside the tile
   gemm_f32_body<BM, BN, TA, TB, GAT, false, false, NOPAD>(p, bid, m.nt[cls], 0);
@@ -672,8 +666,6 @@ bool aligned16f(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) ==
 // Returns EAMD_EUNSUPPORTED when the operands do not meet the branch-free staging conditions (16-byte aligned chunk
 // starts that stay inside the operand); the caller then takes the generic kernel.
 int eamd_gemm_f32_dispatch(const eamd_gemm_t& p, int tile, hipStream_t stream) {
-  static const int on = [] { const char* e = getenv("EAMD_GEMM_F32_FAST"); return e ? atoi(e) : 1; }();
-  if (!on) return EAMD_EUNSUPPORTED;
   if (p.Cb || (p.Hb && !p.h_dtype) || p.aux_dtype || (!p.C && p.epilogue != 7)) return EAMD_EUNSUPPORTED;
   if (p.Hb && p.drop_p <= 0.f) return EAMD_EINVAL;
   if (p.drop_p < 0.f || p.drop_p >= 1.f) return EAMD_EINVAL;
@@ -717,8 +709,7 @@ static int multi_launch_t(const MultiF& m, int grid, hipStream_t stream) {
 }
 
 int eamd_gemm_f32_multi(const eamd_gemm_t* ps, const int* tiles, int n, hipStream_t stream) {
-  static const int on = [] { const char* e = getenv("EAMD_GEMM_MULTI"); return e ? atoi(e) : 1; }();
-  if (!on || n < 2 || n > EAMD_GEMM_MULTI_MAX) return EAMD_EUNSUPPORTED;
+  if (n < 2 || n > EAMD_GEMM_MULTI_MAX) return EAMD_EUNSUPPORTED;
   MultiF m;
   bool nopad = true;
   int maxnt = 0;
@@ -740,8 +731,6 @@ int eamd_gemm_f32_multi(const eamd_gemm_t* ps, const int* tiles, int n, hipStrea
   }
   for (int i = n; i < EAMD_GEMM_MULTI_MAX; ++i) { m.p[i] = ps[0]; m.nt[i] = 0; }
   m.n = n;
-  static const int order = [] { const char* e = getenv("EAMD_GEMM_MULTI_ORDER"); return e ? atoi(e) : 1; }();
-  m.order = order;
   const int grid = (maxnt + 7) / 8 * 8 * n;
   return nopad ? multi_launch_t<true>(m, grid, stream) : multi_launch_t<false>(m, grid, stream);
 }

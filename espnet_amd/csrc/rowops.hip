@@ -1282,8 +1282,8 @@ int eamd_layernorm_fwd(const float* x, const float* gamma, const float* beta, fl
 }
 
 static void ln_bwd_grid(int rows, int* nblk, int* rpb) {
-  static const int per = [] { const char* e = getenv("EAMD_LNB_RPB"); return e ? atoi(e) : 16; }();
-  int n = min(4096, (rows + per - 1) / per);
+  constexpr int LNB_RPB = 16;
+  int n = min(4096, (rows + LNB_RPB - 1) / LNB_RPB);
   *rpb = (rows + n - 1) / n;
   *nblk = (rows + *rpb - 1) / *rpb;
 }
@@ -1306,9 +1306,9 @@ static int layernorm_bwd_impl(const float* dy, const float* x, const float* gamm
   if (drop16 && (drop_p < 0.f || drop_p >= 1.f || !drop_step || ((uintptr_t)drop16 & (drop_f32 ? 15 : 7)))) return EAMD_EINVAL;
   int nblk, rpb;
   ln_bwd_grid(rows, &nblk, &rpb);
-  static const int ws_min = [] { const char* e = getenv("EAMD_LNB_WS_MIN"); return e ? atoi(e) : 32; }();
-  float* ws = (deferred || nblk >= ws_min) ? workspace : nullptr;   // few blocks: direct atomics are cheaper than a second launch
-  static const int nthr = [] { const char* e = getenv("EAMD_LNB_THREADS"); return e ? atoi(e) : 512; }();      // config 2, in the step: 256 threads 9.7 us, 512 -> 8.8 us, 1024 (32-row blocks) 9.0 us
+  constexpr int LNB_WS_MIN = 32;
+  float* ws = (deferred || nblk >= LNB_WS_MIN) ? workspace : nullptr;   // few blocks: direct atomics are cheaper than a second launch
+  constexpr int nthr = 512;      // config 2, in the step: 256 threads 9.7 us, 512 -> 8.8 us, 1024 (32-row blocks) 9.0 us
   const bool al = (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx | (uintptr_t)dres) & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
   size_t sm = (size_t)(nthr / 64) * 2 * D * sizeof(float);
@@ -1496,10 +1496,9 @@ int eamd_linear_rows_f32(const float* x, const float* W, const float* bias, cons
   if (ldx < K || ldr < N) return EAMD_EINVAL;
   if (M > 1024 || K % 4 != 0 || ldx % 4 != 0 || a_act > EAMD_ACT_SWISH || act > 2) return EAMD_EUNSUPPORTED;
   if (((uintptr_t)x | (uintptr_t)W) & 15) return EAMD_EUNSUPPORTED;
-  static const int rows_mfma = getenv("EAMD_ROWS_MFMA") ? atoi(getenv("EAMD_ROWS_MFMA")) : 0;      // A/B knob: the 16 x 16 tiles for M <= 16 too
-  if (M > 16 || (rows_mfma && K % 16 == 0)) {
+  if (M > 16) {
     if (K % 16 != 0) return EAMD_EUNSUPPORTED;
-    if (K >= 1024 && M > 16) {                               // a long reduction: the waves of a workgroup split K
+    if (K >= 1024) {                               // a long reduction: the waves of a workgroup split K
       hipLaunchKernelGGL(linear_mfma16_ksplit_f32_kernel, dim3((N + 15) / 16, (M + 15) / 16), dim3(256), 0, (hipStream_t)stream, x, W,
                          bias, R, y, M, N, K, a_act, act, alpha, (long)ldx, (long)ldr);
       EAMD_LAUNCH_CHECK();
@@ -1510,8 +1509,7 @@ int eamd_linear_rows_f32(const float* x, const float* W, const float* bias, cons
     EAMD_LAUNCH_CHECK();
     return EAMD_OK;
   }
-  static const int rows_wide = getenv("EAMD_ROWS_WIDE") ? atoi(getenv("EAMD_ROWS_WIDE")) : 1;      // A/B knob: 0 = the staged kernel for every K
-  if (rows_wide && K >= 1024 && K <= 4096) {               // the waves of a workgroup split K
+  if (K >= 1024 && K <= 4096) {               // the waves of a workgroup split K
     constexpr int CB = 2;
     const dim3 grid((N + CB - 1) / CB);
 #define EAMD_ROWS_WIDE_(QN) hipLaunchKernelGGL((linear_rows_wide_f32_kernel<QN, CB>), grid, dim3(256), 0, (hipStream_t)stream, x, W, bias, R, y, M, \

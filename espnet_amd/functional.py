@@ -6,7 +6,6 @@ the flat gradient arena (``param._eamd_grad`` installed by espnet_amd.train.Flat
 present, otherwise they are returned to autograd like any other Function would.
 """
 import math
-import os
 
 import torch
 
@@ -238,8 +237,7 @@ class LinearFn(torch.autograd.Function):
 # reference: positionwise_feed_forward.py:12-32, conformer/encoder_layer.py:97-103,141-146,
 #            transformer/encoder_layer.py / decoder_layer.py:123-128 (scale = 1, ReLU)
 # =================================================================================================
-import os as _os
-FFN_FACTOR = _os.environ.get("EAMD_FFN_FACTOR", "1") != "0"   # tests flip this to keep the pre-activation and re-derive mask / activation derivative in backward
+FFN_FACTOR = True   # tests flip this to keep the pre-activation and re-derive mask / activation derivative in backward
 
 
 class FFNBlockFn(torch.autograd.Function):
@@ -510,7 +508,7 @@ def attn_scores_fwd(qu, qv, k, p, mask, B, T1, T2, H, dk):
 FUSE_ATTN = True   # tests flip this to compare against the GEMM / softmax / GEMM path
 # attention blocks whose probabilities (P + dropped copy) exceed this many MB do not keep them for backward but run the fused
 # forward again there (MHABlockFn): memory kept per block O(T') instead of O(T'^2).  < 0: never; 0: always.
-ATTN_RECOMPUTE_MB = float(os.environ.get("EAMD_ATTN_RECOMPUTE_MB", "256"))
+ATTN_RECOMPUTE_MB = 256.0
 ATTN_TAP = None    # a list while E2E.calculate_all_attentions runs: every attention block appends its probabilities
 
 
@@ -628,7 +626,7 @@ def attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk, Pd=None, attn_drop
         # dp[j, h, :] = sum_{b,i} dbd[h, b, i, j] * qv[b, i, h, :]   (reduction over B*T1 rows, split-K)
         ops.gemm(dbd, qv, dpt, T2, dk, B * T1, ldp, D, ldd, transA=1, transB=1, batch=(1, H),
                  sA=(0, B * T1 * ldp), sB=(0, dk), sC=(0, dk), c_off=dp_off,
-                 splitk=int(os.environ.get("EAMD_DPOS_SK", "0")) or max(2, ops.auto_splitk(T2, dk, B * T1) // 2))
+                 splitk=max(2, ops.auto_splitk(T2, dk, B * T1) // 2))
         # (measured at config 2, 4 tiles x 4 heads: split-K 9 -> 26.7 us, 16 -> 20.7 us, 24 -> 22.4, 32 -> 23.9)
     return dqu, dqv, dkk, dv, dp
 
@@ -1152,9 +1150,9 @@ def _conv3s2_bwd(dy, y_in, wd, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc, adt):
     # 128x128 tile at just under two rounds of two workgroups per CU - 36 tiles x split-K 28 = 1008 workgroups - takes
     # 1.58 ms; 64x64 tiles x split-K 16 = 2304 workgroups 1.70 ms; 128x128 at 1.5 or 3 rounds 1.63-1.73 ms
     f32_big = (not ops.fast()) and Cc % 128 == 0
-    tile = int(os.environ.get("EAMD_CONV_DW_TILE", "128" if f32_big else "64"))
+    tile = 128 if f32_big else 64
     ntile = (9 * Cc // tile) * ((Cc + tile - 1) // tile)
-    want = int(os.environ.get("EAMD_CONV_DW_WGS", "0")) or (1024 if ops.fast() else 1008 if f32_big else 2304)
+    want = 1024 if ops.fast() else 1008 if f32_big else 2304
     sk = max(2, min(64, (want + ntile - 1) // ntile, max(1, M // 256)))
     ops.gemm(y_in, dy, dwf, 9 * Cc, Cc, M, 9 * Cc, Cc, Cc, transA=1, transB=1, gather=g, splitk=sk, tile=tile)
     ops.conv2_weight_grad(dwf, dw_buf, Cc, Cc)

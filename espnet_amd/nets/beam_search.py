@@ -721,14 +721,7 @@ class BeamSearch(torch.nn.Module):
                         G["S0"]["c_s"].copy_(fresh["c_s"])
                         if G["S0"]["c_r"] is not C_["c_r0"]:
                             G["S0"]["c_r"].copy_(C_["c_r0"])
-                dry = os.environ.get("EAMD_STEP_GRAPH_DRY") == "1"       # diagnostic: the static buffers without capture / replay
-                Sd = G["S0"]
                 for i in range(max(maxlens)):
-                    if dry:
-                        Sd, rec = self._batch_step(i, C_, Sd)
-                        if run.add(rec, last=(i == max(maxlens) - 1)):
-                            break
-                        continue
                     if i >= 1 and self.graph_one and G.get("dyn") is not False:
                         # every step >= 1: ONE graph (the step index lives on the device); its state is loaded from step 0's outputs
                         if G.get("dyn") is None:

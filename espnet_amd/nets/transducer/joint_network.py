@@ -1,5 +1,4 @@
 """reference: espnet/nets/pytorch_backend/transducer/joint_network.py:8-48"""
-import os
 import torch
 
 from ... import functional as F_
@@ -7,6 +6,7 @@ from ... import ops
 from ... import rnn_functional as R_
 
 _ACTS = {"tanh": ops.ACT_TANH, "relu": ops.ACT_RELU, "swish": ops.ACT_SWISH}
+RNNT_CHUNK_ROWS = 1 << 16      # loss(): lattice nodes per chunk of the streamed logits
 
 
 class JointNetwork(torch.nn.Module):
@@ -48,7 +48,7 @@ class JointNetwork(torch.nn.Module):
         """transducer loss from encoder states (B,T,D_enc) and prediction-network states (B,U,D_dec) without the
         (B,T,U,V) logits (rnn_functional.JointRNNTLossFn): mean over the batch of -log P(y | x)"""
         if chunk_rows is None:
-            chunk_rows = int(os.environ.get("EAMD_RNNT_CHUNK_ROWS", str(1 << 16)))
+            chunk_rows = RNNT_CHUNK_ROWS
         e = F_.LinearFn.apply(h_enc, self.lin_enc.weight, self.lin_enc.bias)
         d = F_.LinearFn.apply(h_dec, self.lin_dec.weight, None)
         return R_.JointRNNTLossFn.apply(e, d, self.lin_out.weight, self.lin_out.bias, target.contiguous(), pred_len.contiguous(),

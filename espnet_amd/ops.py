@@ -294,19 +294,19 @@ def gemm_multi(items):
 # launch whose workgroups look their problem up in a device table (eamd_gemm_group_plan / eamd_gemm_group_launch).
 GROUP_WGRAD = True            # tests flip this to reach the one-launch-per-GEMM path
 STACK_WGRAD_MAX_ROWS = 64     # weight gradients of at most this many rows are stacked along the reduction until the flush (0: off)
-GROUP_WGRAD_MAX_TILES = int(os.environ.get("EAMD_GROUP_MAX_TILES", "384"))    # 64x64 output tiles: larger weight gradients fill the chip on their own
-# measured at config 2 (tools/group_sweep.sh): grouping everything up to 384 output tiles (all but the vocabulary-sized
+GROUP_WGRAD_MAX_TILES = 384    # 64x64 output tiles: larger weight gradients fill the chip on their own
+# measured at config 2 (DESIGN_HISTORY.md §B): grouping everything up to 384 output tiles (all but the vocabulary-sized
 # gradients) with half the stand-alone split count is best in both precisions - 34.09 ms fp32 / 14.20 ms bf16 against
 # 35.0 / 15.04 ungrouped; the queue supplies the parallelism the extra splits (and their atomics) bought before
-GROUP_WGRAD_SK_DIV = int(os.environ.get("EAMD_GROUP_SK_DIV", "2"))
+GROUP_WGRAD_SK_DIV = 2
 # fp32 operands only (measured: 33.45 -> 32.80 ms; with bf16 operands the 128x128 tile loses, 14.17 -> 14.3+ ms): problems
 # of at least this many 64x64 tiles - the FFN weights - take 128x128 tiles in a second grouped launch, with about
 # GROUP_WGRAD_T128_WGS workgroups (tiles x K-splits) each
-GROUP_WGRAD_TILE128_MIN = int(os.environ.get("EAMD_GROUP_T128_MIN", "100"))
-GROUP_WGRAD_T128_WGS = int(os.environ.get("EAMD_GROUP_T128_WGS", "96"))
+GROUP_WGRAD_TILE128_MIN = 100
+GROUP_WGRAD_T128_WGS = 96
 # operand bytes the queue may keep alive before it is flushed early (the operands of every queued problem stay
 # allocated until the grouped launch has been issued)
-GROUP_WGRAD_MAX_BYTES = int(os.environ.get("EAMD_GROUP_MAX_BYTES", str(16 << 30)))     # config 2 queues 4.6 GB per backward pass
+GROUP_WGRAD_MAX_BYTES = 16 << 30     # config 2 queues 4.6 GB per backward pass
 _wgroup = {"on": False, "items": [], "ranges": [], "bytes": 0, "stack": {}, "pinned": [], "reserve": [], "arenas": {}}
 
 
@@ -363,29 +363,8 @@ def _wgroup_staging(nbytes):
     return torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
 
 
-# EAMD_WGRAD_GROUP_SIDE=1: the grouped launches leave on a SECOND stream (the backward pass's input-gradient chain goes on beside
-# them; their operands are kept alive until wgrad_join) - with EAMD_GROUP_MAX_BYTES set so that a backward pass flushes several
-# times.  An experiment knob: see DESIGN.md for what it measured.
-WGROUP_SIDE = os.environ.get("EAMD_WGRAD_GROUP_SIDE", "0") == "1"
-
-
 def wgrad_group_flush():
     """launch everything queued so far: one grouped launch per tile size (a single queued GEMM goes out on its own)"""
-    if WGROUP_SIDE and (_wgroup["items"] or _wgroup["stack"]):
-        cur = torch.cuda.current_stream()
-        side = _wgroup.get("side")
-        if side is None or side.device != cur.device:
-            side = _wgroup["side"] = torch.cuda.Stream(device=cur.device)
-        _wgroup.setdefault("held", []).append(([it[1] for it in _wgroup["items"]], list(_wgroup["stack"].values())))
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            _wgroup_flush_now()
-        _wgroup["side_used"] = True
-        return
-    _wgroup_flush_now()
-
-
-def _wgroup_flush_now():
     stack, _wgroup["stack"] = _wgroup["stack"], {}
     for dW, db, dys, xs in stack.values():          # stacked small-M weight gradients: one product per weight
         if len(dys) == 1:
@@ -466,7 +445,7 @@ def auto_splitk(m_out, n_out, k_red):
 
 
 # ---- nn.Linear pieces -------------------------------------------------------------------------
-LINEAR_ROWS = os.environ.get("EAMD_LINEAR_ROWS", "1") != "0"      # eamd_linear_rows_f32 for few rows without autograd
+LINEAR_ROWS = True      # eamd_linear_rows_f32 for few rows without autograd
 _infer = 0      # > 0 inside an explicit inference region (ops.inference / @ops.inference_call: searches, F_.run's direct forward)
 
 
@@ -498,10 +477,10 @@ def inference_call(fn):
 # 13.1 us of the 64 x 64 tiles for N = 256 / 768 at K = 256 (those are 20 / 60 workgroups walking K alone), the same for N = 2048,
 # SLOWER for K = 2048 (33 against 26 us with split-K: every wave re-reads its 32 rows of both operands) and for the output
 # layer (N = 5000: 29.7 against 17.8 us) - so it takes the narrow products only
-LINEAR_ROWS_MAX = int(os.environ.get("EAMD_LINEAR_ROWS_MAX", "16"))
-LINEAR_ROWS_BLOCK_MAX = int(os.environ.get("EAMD_LINEAR_ROWS_BLOCK_MAX", "1024"))      # ... up to this many rows, K <= 512, N <= 1024
+LINEAR_ROWS_MAX = 16
+LINEAR_ROWS_BLOCK_MAX = 1024      # ... up to this many rows, K <= 512, N <= 1024
 # ... and the long reductions (K >= 1024: the waves of a workgroup split K, one 16 x 16 tile per workgroup) - A/B knob
-LINEAR_ROWS_KSPLIT = os.environ.get("EAMD_LINEAR_ROWS_KSPLIT", "1") != "0"
+LINEAR_ROWS_KSPLIT = True
 
 
 def linear_fwd(x, W, b, out=None, *, act=EPI_NONE, R=None, alpha=1.0, a_act=ACT_NONE, out_dtype=torch.float32,
@@ -564,8 +543,8 @@ class _ZeroArena:
 
 
 _zarena = _ZeroArena()
-ZERO_ARENA = os.environ.get("EAMD_ZERO_ARENA", "1") != "0"
-ZERO_ARENA_MAX = int(os.environ.get("EAMD_ZERO_ARENA_MAX_MB", "1024")) << 20     # larger demands go to torch.zeros
+ZERO_ARENA = True
+ZERO_ARENA_MAX = 1024 << 20     # larger demands go to torch.zeros
 
 
 def _capture_id():
@@ -653,8 +632,8 @@ def linear_bwd_x(dy, W, out=None, *, beta=0.0, epilogue=EPI_NONE, aux=None, alph
 
 
 # ---- fused position-wise feed-forward (csrc/ffn_f32.hip) ------------------------------------------
-FUSED_FFN = os.environ.get("EAMD_FUSED_FFN", "1") != "0"
-FUSED_FFN_MIN_ROWS = int(os.environ.get("EAMD_FUSED_FFN_MIN_ROWS", "4096"))     # 32 rows per workgroup: fewer rows leave CUs idle
+FUSED_FFN = True
+FUSED_FFN_MIN_ROWS = 4096     # 32 rows per workgroup: fewer rows leave CUs idle
 
 
 def ffn_fused_ok(x, w1, w2, act):
@@ -672,7 +651,7 @@ def ffn_fused_ok(x, w1, w2, act):
 # fp32 operands, few rows (the decoder's 3232 target positions = 101 row blocks on 256 CUs): two workgroups per row block, each over
 # half of the hidden units, adding their halves of the second product into a zeroed result (eamd_ffn_t.hsplit).  Measured at
 # config 2's decoder: one workgroup per block 147 us whatever the grid, the GEMM pair 104 us, split in two 77 us.
-FUSED_FFN_HSPLIT_MIN_ROWS = int(os.environ.get("EAMD_FUSED_FFN_HSPLIT_MIN_ROWS", "1536"))
+FUSED_FFN_HSPLIT_MIN_ROWS = 1536
 
 
 def ffn_hsplit(M, F, bf):
@@ -702,7 +681,7 @@ def _ffn_call(name, p, keep):
     check(fn(C.byref(p), stream_ptr()), name)
 
 
-FFN_LN_FUSED = os.environ.get("EAMD_FFN_LN", "1") != "0"      # the LayerNorm in front of a fused FFN runs inside its kernel
+FFN_LN_FUSED = True      # the LayerNorm in front of a fused FFN runs inside its kernel
 
 
 def ffn_fwd(x, w1, b1, w2, b2, *, act, alpha=1.0, R=None, drop=(0.0, 0, 0.0, 0), save=True, packed=None, ln=None):
@@ -764,7 +743,7 @@ def ffn_pack(w1, w2):
 def ffn_prepack(pairs):
     """pairs: list of (w1 [F, 256], w2 [256, F]) fp32 parameters: the packed images of ALL these feed-forward blocks in one
     launch (eamd_ffn_pack_f32_multi); ffn_pack() hands them out until rowproj_prepack_end().  fp32 mode only (no-op otherwise)."""
-    if fast() or not pairs or os.environ.get("EAMD_FFN_F32_FORM", "") == "sym" or not _rp["active"]:
+    if fast() or not pairs or not _rp["active"]:
         return
     arr = (_lib.FfnPackT * len(pairs))()
     n = 0
@@ -787,7 +766,7 @@ def ffn_prepack(pairs):
 
 def ffn_bwd_lnb_ok(M, F, dt):
     """eamd_ffn_bwd can run the LayerNorm backward as its epilogue (fp32 operands, one workgroup per row block)"""
-    return dt == torch.float32 and ffn_hsplit(M, F, False) == 1 and os.environ.get("EAMD_FFN_F32_FORM", "") != "sym"
+    return dt == torch.float32 and ffn_hsplit(M, F, False) == 1
 
 
 def ffn_bwd(dy, w1, w2, f, *, alpha=1.0, packed=None, lnb=None):
@@ -817,8 +796,8 @@ def ffn_bwd(dy, w1, w2, f, *, alpha=1.0, packed=None, lnb=None):
 
 
 # ---- row-block projections (csrc/rowproj_f32.hip) ---------------------------------------------------
-ROWPROJ = os.environ.get("EAMD_ROWPROJ", "1") != "0"
-ROWPROJ_MIN_ROWS = int(os.environ.get("EAMD_ROWPROJ_MIN_ROWS", "4096"))       # 32 rows per workgroup: fewer rows leave CUs idle
+ROWPROJ = True
+ROWPROJ_MIN_ROWS = 4096       # 32 rows per workgroup: fewer rows leave CUs idle
 
 
 def rowproj_ok(M, K, N):
@@ -944,10 +923,6 @@ def wgrad_group_end():
 def wgrad_join():
     """launch the queued weight-gradient GEMMs and make the current stream wait for all weight-gradient work issued so far"""
     wgrad_group_flush()
-    if _wgroup.get("side_used"):
-        torch.cuda.current_stream().wait_stream(_wgroup["side"])
-        _wgroup["side_used"] = False
-        _wgroup["held"] = []
     st = _wgrad["stream"]
     if st is not None and _wgrad["used"]:
         torch.cuda.current_stream().wait_stream(st)
@@ -1308,7 +1283,7 @@ def decode_self_attn(qkv, Kc, Vc, slot_at, pos, H, pos_dev=None):
     return ctx
 
 
-SRC_ATTN_SPLITS = int(os.environ.get("EAMD_SRC_ATTN_SPLITS", "4"))      # key splits of the grouped source attention (1: none)
+SRC_ATTN_SPLITS = 4      # key splits of the grouped source attention (1: none)
 
 
 def decode_src_attn(q, kv, k_off, v_off, ldkv, mask, G, g, T, H, group=False):

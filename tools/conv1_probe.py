@@ -18,5 +18,4 @@ for dt in (torch.bfloat16, torch.float32):
     t = graph_time(lambda: ops.conv1_fwd(x, w, b, B, T, F, C, dt), n=20)
     print("fwd   %s %7.1f us  (%.2f TB/s written)" % (dt, t, dy.numel() * dy.element_size() / t / 1e6))
     t = graph_time(lambda: ops.conv1_bwd_w(dy, x, dw, db, B, T, F, C), n=20)
-    print("bwd_w %s %7.1f us  (%.2f TB/s read)  EAMD_C1W_BLOCKS=%s" % (dt, t, dy.numel() * dy.element_size() / t / 1e6,
-                                                                    os.environ.get("EAMD_C1W_BLOCKS")))
+    print("bwd_w %s %7.1f us  (%.2f TB/s read)" % (dt, t, dy.numel() * dy.element_size() / t / 1e6))
