@@ -1262,6 +1262,148 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     prev = wk;
   }
 }
+
+// Everything one pass of a transducer search needs from the joint network's logits, in one launch (reference:
+// beam_search_transducer.py:239-663, time_sync_decoding / align_length_sync_decoding / nsc_beam_search: log_softmax, topk on
+// logp[:, 1:], blank logp, LM scores of the chosen tokens, nsc's prefix-rescoring log-probabilities).  One workgroup per row:
+// the log-sum-exp is log_softmax_rows_kernel's (same element per thread, same reduction order: the same bits), the selection
+// topk_rows_kernel's over tokens 1..V-1 of logp = x - lse (the order of the keys is the same: token v ranks as index v - 1).
+// rec [n][1 + 2k (+ k)]: logp[blank = 0], k values, k token ids (as floats), with an LM the k raw LM log-probabilities
+// lm[lm_row[r]][token].  pairs [g][2] (row, token): pair_out[j] = logp[row][token], written by the row's workgroup.
+__global__ __launch_bounds__(256) void transducer_expand_rows_kernel(const float* __restrict__ x, long ld, int V, int k,
+                                                                     const float* __restrict__ lm, const int32_t* __restrict__ lm_row,
+                                                                     const int32_t* __restrict__ pairs, int g,
+                                                                     float* __restrict__ rec, float* __restrict__ pair_out) {
+  __shared__ float red[16];
+  __shared__ __attribute__((aligned(16))) unsigned tmax[256];
+  __shared__ unsigned long long cand[TOPK_CAP];
+  __shared__ unsigned long long sk[4];
+  __shared__ unsigned long long wk;
+  __shared__ unsigned tau;
+  __shared__ int cnt;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int row = blockIdx.x;
+  const float* xr = x + (long)row * ld;
+  const int W = 1 + 2 * k + (lm ? k : 0);
+  float* out = rec + (long)row * W;
+  const float* lmr = lm ? lm + (long)lm_row[row] * V : nullptr;
+  constexpr int RMAX = 24;
+  const bool inreg = V <= RMAX * 256;
+  // ---- log-sum-exp: log_softmax_rows_kernel's two paths
+  unsigned reg[RMAX];
+  float lse;
+  if (inreg) {
+    float mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < RMAX; ++q) {
+      const int v = t + 256 * q;
+      const float e = v < V ? xr[v] : -INFINITY;
+      reg[q] = __float_as_uint(e);
+      mx = fmaxf(mx, e);
+    }
+    mx = block_max(mx, red);
+    float se = 0.f;
+#pragma unroll
+    for (int q = 0; q < RMAX; ++q)
+      if (t + 256 * q < V) se += __expf(__uint_as_float(reg[q]) - mx);
+    se = block_sum(se, red);
+    lse = mx + __logf(se);
+  } else {
+    float mx = -INFINITY;
+    for (int v = t; v < V; v += 256) mx = fmaxf(mx, xr[v]);
+    mx = block_max(mx, red);
+    float se = 0.f;
+    for (int v = t; v < V; v += 256) se += __expf(xr[v] - mx);
+    se = block_sum(se, red);
+    lse = mx + __logf(se);
+  }
+  if (t == 0) out[0] = xr[0] - lse;
+  for (int j = t; j < g; j += 256) {
+    if (pairs[2 * j] == row) {
+      const int tok = pairs[2 * j + 1];
+      pair_out[j] = (tok >= 0 && tok < V) ? xr[tok] - lse : __int_as_float(0x7fc00000);
+    }
+  }
+  auto emit = [&](int r, unsigned long long key) {        // rank r of the selection
+    const int v = (int)(0xFFFFFFFFu - (unsigned)key);
+    out[1 + r] = topk_value((unsigned)(key >> 32));
+    out[1 + k + r] = (float)v;
+    if (lmr) out[1 + 2 * k + r] = lmr[v];
+  };
+  // ---- top-k of logp[1:V): topk_rows_kernel's selection, the row register-resident as order-preserving bits (0 = no element)
+  if (inreg) {
+    unsigned tm = 0;
+#pragma unroll
+    for (int q = 0; q < RMAX; ++q) {
+      const int v = t + 256 * q;
+      reg[q] = (v >= 1 && v < V) ? topk_bits(__uint_as_float(reg[q]) - lse) : 0u;
+      tm = max(tm, reg[q]);
+    }
+    tmax[t] = tm;
+    if (t == 0) { tau = 0xFFFFFFFFu; cnt = 0; }
+    __syncthreads();
+    int above = 0;
+#pragma unroll 8
+    for (int j = 0; j < 256; j += 4) {
+      const uint4 v = *reinterpret_cast<const uint4*>(&tmax[j]);
+      above += (v.x > tm) + (v.y > tm) + (v.z > tm) + (v.w > tm);
+    }
+    if (above < k && tm != 0u) atomicMin(&tau, tm);
+    __syncthreads();
+    const unsigned th = tau;
+#pragma unroll
+    for (int q = 0; q < RMAX; ++q) {
+      if (reg[q] >= th && reg[q] != 0u) {
+        const int p = atomicAdd(&cnt, 1);
+        if (p < TOPK_CAP) cand[p] = topk_key(reg[q], (unsigned)(t + 256 * q));
+      }
+    }
+    __syncthreads();
+    const int c = cnt;
+    if (c <= TOPK_CAP) {
+      for (int j = t; j < c; j += 256) {
+        const unsigned long long my = cand[j];
+        int r = 0;
+        for (int q = 0; q < c; ++q) r += cand[q] > my;
+        if (r < k) emit(r, my);
+      }
+      return;
+    }
+    __syncthreads();
+  }
+  unsigned long long prev = 0xFFFFFFFFFFFFFFFFull;
+  for (int r = 0; r < k; ++r) {
+    unsigned long long best = 0;
+    if (inreg) {
+#pragma unroll
+      for (int q = 0; q < RMAX; ++q) {
+        const unsigned long long key = topk_key(reg[q], (unsigned)(t + 256 * q));
+        if (reg[q] != 0u && key < prev && key > best) best = key;
+      }
+    } else {
+      for (int v = t + 1; v < V; v += 256) {       // the re-reading rounds of topk_rows_kernel, starting at token 1
+        const unsigned long long key = topk_key(topk_bits(xr[v] - lse), (unsigned)v);
+        if (key < prev && key > best) best = key;
+      }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const unsigned long long o = __shfl_xor(best, m);
+      best = o > best ? o : best;
+    }
+    if (lane == 0) sk[w] = best;
+    __syncthreads();
+    if (t == 0) {
+      unsigned long long f = sk[0];
+#pragma unroll
+      for (int q = 1; q < 4; ++q) f = sk[q] > f ? sk[q] : f;
+      wk = f;
+      emit(r, f);
+    }
+    __syncthreads();
+    prev = wk;
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -1550,6 +1692,17 @@ int eamd_topk_rows_i32(const float* x, int64_t ld, int rows, int n, int k, float
   if (!x || !vals || !idx || rows <= 0 || n <= 0 || k <= 0 || k > n || ld < n) return EAMD_EINVAL;
   if (k > 64) return EAMD_EUNSUPPORTED;
   hipLaunchKernelGGL(topk_rows_kernel<false>, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, ld, n, k, vals, idx, idx32, TopkSum{{nullptr, nullptr, nullptr, nullptr}, {0.f, 0.f, 0.f, 0.f}, nullptr, -1});
+  EAMD_LAUNCH_CHECK();
+  return EAMD_OK;
+}
+
+int eamd_transducer_expand_rows(const float* logits, int64_t ld, int n, int V, int k, const float* lm, const int32_t* lm_row,
+                                const int32_t* pairs, int g, float* rec, float* pair_out, void* stream) {
+  if (!logits || !rec || n <= 0 || V < 2 || ld < V || k < 1 || g < 0 || (lm && !lm_row) || (g > 0 && (!pairs || !pair_out)))
+    return EAMD_EINVAL;
+  if (k > 64 || k > V - 1 || V > (1 << 24)) return EAMD_EUNSUPPORTED;
+  hipLaunchKernelGGL(transducer_expand_rows_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, logits, (long)ld, V, k, lm, lm_row,
+                     pairs, g, rec, pair_out);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }

@@ -1,4 +1,4 @@
-"""Transducer decoding on the device primitives: greedy search and the default (Graves) beam search.
+"""Transducer decoding on the device primitives: greedy search, the default (Graves) beam search, tsd, alsd and nsc.
 
 What the searches compute is pinned by the reference (espnet/nets/beam_search_transducer.py:130-237: one symbol per
 frame at most in the greedy search; the A / B hypothesis sets of Graves 2012 in the default search, RNNLM shallow
@@ -17,13 +17,28 @@ computed is this package's own design:
     nodes first seen + joint rows + top-k, one device-to-host copy); children created during the frame are scored
     lazily, again all pending ones in one batch, when the first of them is selected for expansion.
 
-Prediction networks take part through one of two protocols: `step(tokens, states)` (batched; DecoderRNNT) or the
-reference's per-hypothesis plug-in method `score(hyp, cache, init_tensor)` (any TransducerDecoderInterface).
-The time-synchronous / alignment-length-synchronous / N-step-constrained searches of the reference are outside the
-hot-path scope (greedy + default) and are not provided."""
+  * time-synchronous (tsd), alignment-length-synchronous (alsd) and N-step-constrained (nsc) searches (reference:
+    :239-663): every PASS scores all pending (encoder row, node) pairs in one joint_rows call, and one
+    transducer_expand_rows launch hands the host what the pass needs - blank log-probability, the k best non-blank
+    (log-probability, token) pairs, the LM log-probability of each chosen token, nsc's prefix-rescoring terms - through
+    ONE blocking device-to-host copy (`_expand`, counted in `host_reads`).
+
+Prediction networks take part through one of three protocols: `step(tokens, states)` (batched; DecoderRNNT),
+`batch_step(yseqs)` (DecoderTT: the reference's batch_score, whose outputs depend on the batch a prefix is first computed
+in - the searches call it with the reference's hypothesis lists, in the reference's order) or the reference's
+per-hypothesis plug-in method `score(hyp, cache, init_tensor)` (any TransducerDecoderInterface; greedy and default only).
+
+tsd / alsd / nsc reproduce the reference as recorded in the fixtures, its quirks included: tsd's last symbol expansion
+still scores and expands (`v < max_sym_exp` always holds); alsd never scores frame 0, `recombine_hyps` returns its input
+(duplicates stay, the first occurrence's score grows in place) and B is returned unsorted when no hypothesis reached the
+last frame; nsc's prefix rescoring mutates scores in length order and adds the last step's blank only when nstep != 1.
+Once an LM term is added, tsd / alsd scores are float32 0-d tensors in the reference (score + lm_weight * tensor): they are
+carried the same way here.  One reference behaviour is NOT copied: its prediction / LM caches are keyed by
+"".join(str(x) for x in yseq), which collides once V > 10 ([1, 23] and [12, 3]); the trie's node ids do not."""
 from dataclasses import dataclass, field
 from typing import Any, List
 
+import numpy as np
 import torch
 
 from .. import ops
@@ -83,6 +98,19 @@ class _Pred:
     state: dict = field(default_factory=dict)     # node -> state AFTER consuming the node's token
     lm_state: dict = field(default_factory=dict)
     lm_logp: dict = field(default_factory=dict)   # node -> host list of LM log-probabilities of the next token
+    lm_dev: dict = field(default_factory=dict)    # node -> (device [m, V] LM log-probabilities, row): tsd / alsd / nsc
+
+
+_SEARCHES = {"default": "_default", "tsd": "_tsd", "alsd": "_alsd", "nsc": "_nsc"}
+
+
+class _Hyp:
+    """a hypothesis of the tsd / alsd / nsc searches: mutable score (the reference updates scores in place) + trie node"""
+
+    __slots__ = ("score", "node")
+
+    def __init__(self, score, node):
+        self.score, self.node = score, node
 
 
 class BeamSearchTransducer:
@@ -94,12 +122,18 @@ class BeamSearchTransducer:
         self.blank = decoder.blank
         if self.blank != 0:
             raise NotImplementedError("blank id must be 0 (the non-blank top-k is taken over ids 1..V-1)")
-        if beam_size > 1 and search_type != "default":
-            raise NotImplementedError("search_type %r: the greedy (beam_size <= 1) and default searches are provided" % search_type)
+        self.batched = hasattr(decoder, "step")
+        if beam_size > 1 and search_type not in _SEARCHES:
+            raise NotImplementedError("search_type %r: one of %s" % (search_type, ", ".join(_SEARCHES)))
+        if beam_size > 1 and search_type != "default" and not (self.batched or hasattr(decoder, "batch_step")):
+            raise NotImplementedError("search_type %r needs a prediction network with a batched step (step or batch_step)"
+                                      % search_type)
+        self.search_type = search_type
         self.lm, self.lm_weight = lm, lm_weight
+        self.max_sym_exp, self.u_max, self.nstep, self.prefix_alpha = max_sym_exp, u_max, nstep, prefix_alpha
         self.score_norm = score_norm
         self.frame_chunk = frame_chunk
-        self.batched = hasattr(decoder, "step")
+        self.passes = self.host_reads = 0      # tsd / alsd / nsc: search passes and blocking host reads of the last call
 
     @ops.inference_call
     def __call__(self, h):
@@ -107,7 +141,9 @@ class BeamSearchTransducer:
         if hasattr(self.decoder, "att"):          # rnnt-att: forget the previous utterance's encoder projections
             self.decoder.att[0].reset()
         with torch.no_grad():
-            return self._greedy(h) if self.beam_size <= 1 else self._default(h)
+            if self.beam_size <= 1:
+                return self._greedy(h)
+            return getattr(self, _SEARCHES[self.search_type])(h)
 
     # ---- prediction network, once per trie node ---------------------------------------------------------------------
     def _start(self, h):
@@ -227,3 +263,236 @@ class BeamSearchTransducer:
         if self.score_norm:
             return sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True)
         return sorted(hyps, key=lambda x: x.score, reverse=True)
+
+    # ---- tsd / alsd / nsc: passes --------------------------------------------------------------------------------------
+    def _batch_pred(self, nodes):
+        """prediction outputs of `nodes` (one of the reference's batch_score calls: the hypotheses in its order)"""
+        if self.batched:
+            self._ensure_pred(nodes)
+            return
+        todo = [n for n in dict.fromkeys(nodes) if n not in self._pred.out]      # first computation wins
+        if todo:
+            y = self.decoder.batch_step([self._tree.labels(n) for n in todo])
+            for i, n in enumerate(todo):
+                self._pred.out[n] = y[i]
+
+    def _ensure_lm(self, nodes):
+        """LM log-probabilities of the token after each node, all missing nodes in one batch (buff_predict)"""
+        pr, tr = self._pred, self._tree
+        todo = [n for n in dict.fromkeys(nodes) if n not in pr.lm_dev]
+        if 0 in todo:                           # the root: from the LM's zero state, alone (it is only ever first)
+            todo.remove(0)
+            self._lm_batch([0], None)
+        if todo:
+            prev = [pr.lm_state[tr.parent[n]] for n in todo]
+            self._lm_batch(todo, {key: [torch.stack([p[key][l] for p in prev]) for l in range(len(prev[0][key]))]
+                                  for key in prev[0]})
+
+    def _lm_batch(self, todo, state):
+        pr = self._pred
+        tok = torch.tensor([self._tree.token[n] for n in todo], dtype=torch.long).to(self._init_tensor.device)
+        new, logp = self.lm.predict(state, tok)
+        for i, n in enumerate(todo):
+            pr.lm_state[n] = {key: [layer[i] for layer in new[key]] for key in new}
+            pr.lm_dev[n] = (logp, i)
+
+    def _expand(self, enc_rows, nodes, k, pairs=None):
+        """one search pass on len(nodes) (encoder row, node) pairs: joint rows + eamd_transducer_expand_rows, ONE blocking
+        read -> ops.transducer_expand_rows's (rows, pair log-probabilities)"""
+        logits = self.decoder.joint_network.joint_rows(enc_rows, torch.stack([self._pred.out[n] for n in nodes]))
+        lm = lm_row = None
+        if self.lm is not None:
+            self._ensure_lm(nodes)
+            mats, lm_row = {}, []
+            for n in nodes:
+                m, r = self._pred.lm_dev[n]
+                base = mats.setdefault(id(m), (m, sum(x.shape[0] for x, _b in mats.values())))[1]
+                lm_row.append(base + r)
+            lm = next(iter(mats.values()))[0] if len(mats) == 1 else torch.cat([m for m, _b in mats.values()])
+        self.passes += 1
+        self.host_reads += 1
+        return ops.transducer_expand_rows(logits, k, lm=lm, lm_row=lm_row, pairs=pairs)
+
+    def _lm_term(self, lm_lp):
+        """lm_weight * beam_lm_scores[i, k] of the reference: a float32 0-d tensor (the score it is added to becomes one)"""
+        return self.lm_weight * torch.tensor(lm_lp, dtype=torch.float32)
+
+    def _sort_nbest(self, hyps):
+        if self.score_norm:
+            hyps = sorted(hyps, key=lambda x: x.score / len(self._tree.labels(x.node)), reverse=True)
+        else:
+            hyps = sorted(hyps, key=lambda x: x.score, reverse=True)
+        return self._result(hyps)
+
+    def _result(self, hyps):
+        return [Hypothesis(score=float(x.score), yseq=self._tree.labels(x.node)) for x in hyps]
+
+    def _start_passes(self, h):
+        self._start(h)
+        self.passes = self.host_reads = 0
+        return self.decoder.joint_network.project_enc(h)
+
+    # ---- time synchronous decoding (reference :239-347) ----------------------------------------------------------------
+    def _tsd(self, h):
+        enc = self._start_passes(h)
+        beam = min(self.beam_size, self.vocab_size)
+        k = min(beam, self.vocab_size - 1)
+        B = [_Hyp(0.0, 0)]
+        for t in range(enc.shape[0]):
+            A = []
+            C = B
+            for _v in range(self.max_sym_exp):          # the reference's `v < max_sym_exp` always holds: every pass expands
+                nodes = [c.node for c in C]
+                self._batch_pred(nodes)
+                rows, _ = self._expand(enc[t].unsqueeze(0).expand(len(C), -1), nodes, k)
+                seq_A = [a.node for a in A]
+                for c, (blank_lp, _ext, _lm) in zip(C, rows):
+                    if c.node not in seq_A:
+                        A.append(_Hyp(c.score + blank_lp, c.node))
+                    else:
+                        a = A[seq_A.index(c.node)]
+                        a.score = np.logaddexp(a.score, c.score + blank_lp)
+                D = []
+                for c, (_b, ext, lm_lp) in zip(C, rows):
+                    for j, (lp, tok) in enumerate(ext):
+                        s = c.score + lp
+                        if lm_lp is not None:
+                            s += self._lm_term(lm_lp[j])
+                        D.append(_Hyp(s, self._tree.child(c.node, tok)))
+                C = sorted(D, key=lambda x: x.score, reverse=True)[:beam]
+            B = sorted(A, key=lambda x: x.score, reverse=True)[:beam]
+        return self._sort_nbest(B)
+
+    # ---- alignment-length synchronous decoding (reference :349-464) ----------------------------------------------------
+    def _alsd(self, h):
+        enc = self._start_passes(h)
+        beam = min(self.beam_size, self.vocab_size)
+        k = min(beam, self.vocab_size - 1)
+        T = enc.shape[0]
+        u_max = min(self.u_max, T - 1)
+        depth = [0]                                     # node -> u = len(yseq) - 1
+        B = [_Hyp(0.0, 0)]
+        final = []
+        for i in range(T + u_max):
+            B_, ts = [], []
+            for b in B:
+                while len(depth) <= b.node:
+                    depth.append(depth[self._tree.parent[len(depth)]] + 1)
+                t = i - depth[b.node] + 1               # >= 1: frame 0 is never scored (reference)
+                if t > T - 1:
+                    continue
+                B_.append(b)
+                ts.append(t)
+            if not B_:
+                continue
+            nodes = [b.node for b in B_]
+            self._batch_pred(nodes)
+            rows, _ = self._expand(enc[torch.tensor(ts, dtype=torch.long).to(enc.device)], nodes, k)
+            A = []
+            for b, t, (blank_lp, ext, lm_lp) in zip(B_, ts, rows):
+                nb = _Hyp(b.score + blank_lp, b.node)
+                A.append(nb)
+                if t == T - 1:
+                    final.append(nb)
+                for j, (lp, tok) in enumerate(ext):
+                    s = b.score + lp
+                    if lm_lp is not None:
+                        s += self._lm_term(lm_lp[j])
+                    A.append(_Hyp(s, self._tree.child(b.node, tok)))
+            B = sorted(A, key=lambda x: x.score, reverse=True)[:beam]
+            seen = []                                   # recombine_hyps (transducer/utils.py:181-203): B itself is kept
+            for b in B:
+                if b.node in [f.node for f in seen]:
+                    f = seen[[f.node for f in seen].index(b.node)]
+                    f.score = np.logaddexp(f.score, b.score)
+                else:
+                    seen.append(b)
+        if final:
+            return self._sort_nbest(final)
+        return self._result(B)
+
+    # ---- N-step constrained beam search (reference :466-663) -----------------------------------------------------------
+    def _nsc(self, h):
+        enc = self._start_passes(h)
+        beam = min(self.beam_size, self.vocab_size)
+        k = min(beam, self.vocab_size - 1)
+        tr = self._tree
+        self._batch_pred([0])
+        if self.lm is not None:
+            self._ensure_lm([0])
+        labels = {}
+
+        def seq(node):
+            if node not in labels:
+                labels[node] = tr.labels(node)
+            return labels[node]
+
+        kept = [_Hyp(0.0, 0)]
+        for t in range(enc.shape[0]):
+            hyps = sorted(kept, key=lambda x: len(seq(x.node)), reverse=True)
+            # prefix rescoring: hyps[j] gains logaddexp(., hyps[i].score + the log-probabilities of the rest of its labels) for
+            # every shorter hyps[i] that is a prefix of it within prefix_alpha labels.  Scores read are those of i > j, not yet
+            # updated, so every needed term comes from the pass below: rows = the prefix nodes, pairs = (row, next label)
+            todo = []
+            for j in range(len(hyps) - 1):
+                yj = seq(hyps[j].node)
+                for i in range(j + 1, len(hyps)):
+                    yi = seq(hyps[i].node)
+                    if len(yi) < len(yj) and yj[:len(yi)] == yi and len(yj) - len(yi) <= self.prefix_alpha:
+                        todo.append((j, i))
+            nodes = [x.node for x in hyps]
+            pairs, terms = [], []
+            if todo:
+                row_of = {n: r for r, n in reversed(list(enumerate(nodes)))}
+                for j, i in todo:
+                    yj = seq(hyps[j].node)
+                    path, n = [], hyps[j].node          # path[m] = node of yj[:m + 1]
+                    while n >= 0:
+                        path.append(n)
+                        n = tr.parent[n]
+                    path.reverse()
+                    idx = []
+                    for m in range(len(seq(hyps[i].node)) - 1, len(yj) - 1):
+                        if path[m] not in row_of:
+                            row_of[path[m]] = len(nodes)
+                            nodes.append(path[m])
+                        idx.append(len(pairs))
+                        pairs.append((row_of[path[m]], yj[m + 1]))
+                    terms.append(idx)
+            self._batch_pred(nodes)
+            rows, pair_lp = self._expand(enc[t].unsqueeze(0).expand(len(nodes), -1), nodes, k, pairs)
+            for (j, i), idx in zip(todo, terms):
+                curr = hyps[i].score + pair_lp[idx[0]]
+                for q in idx[1:]:
+                    curr += pair_lp[q]
+                hyps[j].score = np.logaddexp(hyps[j].score, curr)
+            S = []
+            for n in range(self.nstep):
+                if n > 0:
+                    if not hyps:
+                        break
+                    rows, _ = self._expand(enc[t].unsqueeze(0).expand(len(hyps), -1), [x.node for x in hyps], k)
+                V = []
+                for x, (blank_lp, ext, lm_lp) in zip(hyps, rows):
+                    for j, (lp, tok) in enumerate(ext):
+                        s = x.score + lp
+                        if lm_lp is not None:
+                            s += self.lm_weight * lm_lp[j]
+                        V.append(_Hyp(s, tr.child(x.node, tok)))
+                    nb = _Hyp(x.score + blank_lp, x.node)
+                    S.append(nb)
+                    V.append(nb)
+                V = sorted(V, key=lambda x: x.score, reverse=True)
+                in_hyps = {x.node for x in hyps}
+                V = [v for v in V if v.node not in in_hyps][:beam]          # substract (transducer/utils.py:75-93)
+                self._batch_pred([v.node for v in V])
+                if self.lm is not None:
+                    self._ensure_lm([v.node for v in V])
+                if n < self.nstep - 1:
+                    hyps = V[:]
+                elif self.nstep != 1 and V:
+                    last, _ = self._expand(enc[t].unsqueeze(0).expand(len(V), -1), [v.node for v in V], 1)
+                    for v, r in zip(V, last):
+                        v.score += r[0]
+            kept = sorted(S + V, key=lambda x: x.score, reverse=True)[:beam]
+        return self._sort_nbest(kept)

@@ -79,6 +79,18 @@ class DecoderTT(torch.nn.Module):
             new_state.append(x)
         return self.after_norm(x[:, -1].contiguous()), new_state
 
+    def batch_step(self, yseqs):
+        """the batched step of the tsd / alsd / nsc searches = the computation of the reference's batch_score
+        (transformer_decoder.py:158-240) for its uncached hypotheses: yseqs (n label prefixes, in the call's order) ->
+        outputs of their last positions (n, D).  The prefixes are left-padded with blank to the longest one and run with a
+        causal mask only (no padding mask), so a prefix's output depends on the batch it is computed in; the states the
+        reference passes are init_state()'s [None] * L (its create_batch_states keeps them None), i.e. every prefix is
+        recomputed in full - as here.  The caller keeps the first computation of each prefix, as the reference's cache does."""
+        dev = self.after_norm.weight.device
+        tokens = torch.tensor(pad_sequence(yseqs, self.blank), dtype=torch.long).to(dev)
+        y, _ = self._step(tokens, self.init_state())
+        return y
+
     def score(self, hyp, cache, init_tensor=None):
         """reference: transformer_decoder.py:119-156"""
         dev = self.after_norm.weight.device

@@ -1470,6 +1470,41 @@ def log_softmax_rows(x):
     return y
 
 
+def transducer_expand_rows(logits, k, lm=None, lm_row=None, pairs=None):
+    """one pass of a transducer search (eamd_transducer_expand_rows): logits fp32 [n, V] (row stride >= V, unit column
+    stride), blank = 0; lm fp32 [n_lm, V] with lm_row (n host ints), pairs [(row, token)] * g (host)
+    -> (rows, pair_logp) on the host through ONE device-to-host copy: rows[r] = (logp[r][0], [(logp, token)] * k best
+    non-blank, [raw LM log-probability of each of those tokens] or None); pair_logp[j] = logp[row_j][token_j]"""
+    n, V = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise _lib.EamdError("transducer_expand_rows: float32 [n, V] with unit column stride")
+    pairs = list(pairs or ())
+    if lm is not None:
+        lm_row = [int(i) for i in lm_row]
+        if lm.dtype != torch.float32 or not lm.is_contiguous() or lm.shape[1] != V or len(lm_row) != n \
+                or not all(0 <= i < lm.shape[0] for i in lm_row):
+            raise _lib.EamdError("transducer_expand_rows: lm contiguous float32 [n_lm, V], lm_row n indices into it")
+    if not all(0 <= r < n and 0 <= tok < V for r, tok in pairs):
+        raise _lib.EamdError("transducer_expand_rows: pairs (row < n, token < V)")
+    W = 1 + 2 * k + (k if lm is not None else 0)
+    g = len(pairs)
+    idx = (lm_row if lm is not None else []) + [int(v) for p in pairs for v in p]
+    idx_dev = torch.tensor(idx, dtype=torch.int32).to(logits.device, non_blocking=True) if idx else None
+    out = torch.empty(n * W + g, device=logits.device, dtype=torch.float32)
+    nl = n if lm is not None else 0
+    check(_lib.lib().eamd_transducer_expand_rows(
+        ptr(logits), C.c_int64(logits.stride(0)), n, V, k, ptr(lm), ptr(idx_dev) if lm is not None else None,
+        ptr(idx_dev, nl) if g else None, g, ptr(out), ptr(out, n * W) if g else None, stream_ptr()),
+        "eamd_transducer_expand_rows")
+    host = out.tolist()
+    rows = []
+    for r in range(n):
+        rr = host[r * W:(r + 1) * W]
+        rows.append((rr[0], list(zip(rr[1:1 + k], (int(v) for v in rr[1 + k:1 + 2 * k]))),
+                     rr[1 + 2 * k:] if lm is not None else None))
+    return rows, host[n * W:]
+
+
 # ---- element-wise ------------------------------------------------------------------------------
 def axpby(x, y, a=1.0, b=1.0, out=None):
     if out is None:

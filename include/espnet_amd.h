@@ -380,6 +380,15 @@ int eamd_argmax_rows(const float* x, int64_t ld, int32_t* out, int rows, int V, 
 int eamd_reduce_sum(const float* in, int64_t n, float* out, float scale, void* stream);
 /* reference: decoder.py:318, ctc.py:134-142. */
 int eamd_log_softmax_rows(const float* x, float* y, int rows, int V, void* stream);
+/* One pass of a transducer search on n joint-network logit rows (row stride ld, blank = 0, 1 <= k <= min(64, V - 1)): per row r,
+ * rec [n][1 + 2k (+ k with lm)] = logp[r][0], the k largest of logp[r][1:V) (value descending, equal values by ascending token,
+ * NaN as -inf, -0 as +0), their token ids as floats, and with lm ([*, V], may be NULL) lm[lm_row[r]][token] of each chosen token.
+ * pairs [g][2] (row, token; may be NULL with g = 0): pair_out[j] = logp[row][token].  logp is bit-identical to
+ * eamd_log_softmax_rows, the selection to eamd_topk_rows on columns 1..V-1.  reference: beam_search_transducer.py:239-347
+ * (time_sync_decoding), :349-464 (align_length_sync_decoding), :466-663 (nsc_beam_search: log_softmax, topk of logp[:, 1:],
+ * lm_weight * beam_lm_scores[i, k], the prefix rescoring's ytu[token]). */
+int eamd_transducer_expand_rows(const float* logits, int64_t ld, int n, int V, int k, const float* lm, const int32_t* lm_row,
+                                const int32_t* pairs, int g, float* rec, float* pair_out, void* stream);
 /* Bookkeeping of a device-resident beam step after the selection (reference: beam_search.py:177-203, batch_beam_search.py:249-284,
  * there on host objects).  For each of the n = utterances x beam surviving slots s with winner index top_i[s] (= slot * V + token
  * inside its utterance) and score top_s[s]:
