@@ -1603,7 +1603,7 @@ int eamd_argmax_rows(const float* x, int64_t ld, int32_t* out, int rows, int V, 
 }
 
 int eamd_reduce_sum(const float* in, int64_t n, float* out, float scale, void* stream) {
-  if (!in || !out || n < 0) return EAMD_EINVAL;
+  if ((!in && n > 0) || !out || n < 0) return EAMD_EINVAL;     // n = 0: an empty tensor's NULL data pointer, sum 0
   hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, in, (long)n, out, scale);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
