@@ -19,6 +19,9 @@ for t in "$@"; do
     ops)   run test_ops python -m pytest tests/test_gpu_ops.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     model) run test_model python -m pytest tests/test_gpu_model.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     rnn)   run test_rnn python -m pytest tests/test_gpu_rnn.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
+    rows)  run test_rows python -m pytest tests/test_gpu_row_kernels.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
+    search) run test_search python -m pytest tests/test_gpu_transducer_search.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
+    rnnt)  run test_rnnt python -m pytest tests/test_gpu_transducer_loss.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     smoke) run smoke python -c "import __graft_entry__ as g; g.smoke()" ;;
     bench) run bench python bench.py --steps 5 --warmup 2 ;;
     *) echo "unknown tier $t"; exit 2 ;;
