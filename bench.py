@@ -5,15 +5,20 @@ model of BASELINE.json config 2 on synthetic 80-dim fbank (B=32 per GPU, T=1000,
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
 
-Prints ONE JSON line on rank 0 (contract in the task description).  The headline (`value`, `ms_per_step`, `dtype`,
-`roofline`) is measured at the REFERENCE's precision: fp32 storage and fp32 MFMA arithmetic everywhere
-(`--precision fp32`, the default).  The same line carries
+Prints ONE JSON line on rank 0.  The headline (`value`, `ms_per_step`, `dtype`) is measured at the REFERENCE's
+precision: fp32 storage and fp32 MFMA arithmetic everywhere (`--precision fp32`, the default).  A plain run does only
+what the headline needs: set-up, warm-up, the K timed steps, `--dump-outputs`, the line.  `--full` adds to the same line
   * `bf16`         - the same K steps in bf16-operand mode (bf16 GEMM operands / MFMA, fp32 everything else), with its
                      own roofline and its step-0 loss against the fp32 one;
   * `parity`       - step-0, dropout-0 loss of the very batch being timed: HIP (both modes) vs the CPU oracle;
   * `roofline`     - the dominant kernel family (MFMA contractions), measured live with stream events;
   * `roofline_hbm` - the HBM-bound kernels of SURVEY 8(d), each timed live on its config-2 operands;
-  * `cpu_baseline` - the CPU oracle timed on this box's host cores (1 warm-up + 3 timed steps, median).
+  * `cpu_baseline` - the CPU oracle timed on the host's cores (1 warm-up + 3 timed steps, median);
+  * `configs`      - BASELINE configs 4 and 5 at full size, both precisions (tools/bench_rnn.py);
+  * `decode`       - greedy CTC and beam searches (tools/bench_decode.py);
+  * `comm`         - N>1: the collectives alone and the step with and without them.
+Each of these is left out of a plain run (its key, where it has one, is null); the `--no-*` options drop single
+ones from a `--full` run.
 
 `--dump-outputs DIR` writes what the last timed step of the headline precision computed (see `dump_outputs`) as
 DIR/<name>.npy, so that two builds can be compared output for output on identical (seeded) inputs.
@@ -187,8 +192,9 @@ def hbm_rooflines(prec):
 
 
 def run_precision(a, prec, rank, world, dev):
-    """One full measurement at `prec`: fresh seed-0 model, K timed steps (graph replay), MFMA-family roofline.
-    Returns (result dict, step-0 dropout-0 losses dict)."""
+    """One measurement at `prec`: fresh seed-0 model, K timed steps (graph replay); with --full also the step-0
+    losses, the MFMA-family roofline and (N>1) the communication profile.
+    Returns (result dict, step-0 dropout-0 losses dict or None)."""
     import espnet_amd
     from espnet_amd import ops, train
     from espnet_amd.nets.e2e_asr_conformer import E2E
@@ -205,7 +211,7 @@ def run_precision(a, prec, rank, world, dev):
 
     # ---- step-0, dropout-0 losses on the very batch being timed (parity field) ----
     step0 = None
-    if rank == 0:
+    if a.full and rank == 0:
         torch.manual_seed(0)
         m0 = E2E(80, V, c2_args(0.0)).to(dev).train()
         m0.sync_report = False
@@ -278,7 +284,7 @@ def run_precision(a, prec, rank, world, dev):
     # ---- data-parallel runs explain themselves: collectives alone, the step with and without them, and the N = 1
     #      step (one graph, no phases) measured in this very process on rank 0 ----
     comm = None
-    if dp_step is not None:
+    if a.full and dp_step is not None:
         comm = dp_step.comm_profile(steps=8)
         if world > 1:
             worst = torch.tensor([comm["step_ms"], comm["compute_only_ms"], comm["allreduce_ms_total"]], device=dev, dtype=torch.float64)
@@ -316,7 +322,7 @@ def run_precision(a, prec, rank, world, dev):
     # bracketed by a single pair of events on that stream: device time of the kernels themselves, no host gaps - the
     # quantity the rocprofv3 kernel trace of the same command reports as the family's total duration.
     roof = None
-    if rank == 0:
+    if a.full and rank == 0:
         rec = []
         rd = reducer
         try:
@@ -464,7 +470,10 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"], help="precision of the headline")
-    ap.add_argument("--no-second-precision", action="store_true", help="skip the other precision's object")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the other precision, step-0 parity, rooflines, "
+                         "the CPU baseline, `configs`, `decode`, and `comm` for N>1 (see the module docstring)")
+    ap.add_argument("--no-second-precision", action="store_true", help="--full: skip the other precision's object")
     ap.add_argument("--batch", type=int, default=32, help="utterances per GPU")
     ap.add_argument("--frames", type=int, default=1000)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
@@ -482,9 +491,9 @@ def main():
                          "all-reduces")
     ap.add_argument("--ragged", action="store_true",
                     help="N=1: add a `ragged` object: variable-length batch stream, eager vs shape-bucketed hipGraph cache")
-    ap.add_argument("--no-decode", action="store_true", help="skip the `decode` object (greedy CTC / beam searches, ~30 s)")
+    ap.add_argument("--no-decode", action="store_true", help="--full: skip the `decode` object (greedy CTC / beam searches, ~30 s)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the `configs` object (BASELINE configs 4 and 5 at full size, both precisions, ~40 s)")
+                    help="--full: skip the `configs` object (BASELINE configs 4 and 5 at full size, both precisions, ~40 s)")
     ap.add_argument("--rehearse-dp", action="store_true",
                     help="N=1 only: run the N>1 'graph' code path on a one-rank RCCL group")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -503,11 +512,11 @@ def main():
     head, step0_head = run_precision(a, a.precision, rank, world, dev)
     other = "bf16" if a.precision == "fp32" else "fp32"
     second = step0_other = None
-    if not a.no_second_precision:
+    if a.full and not a.no_second_precision:
         second, step0_other = run_precision(a, other, rank, world, dev)
 
     hbm = None
-    if rank == 0 and not a.no_hbm_roofline:
+    if a.full and rank == 0 and not a.no_hbm_roofline:
         import espnet_amd
         espnet_amd.set_precision(a.precision)
         hbm = hbm_rooflines(a.precision)
@@ -518,17 +527,17 @@ def main():
 
     extra = None
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    if rank == 0 and world == 1 and not a.no_extra_configs:
+    if a.full and rank == 0 and world == 1 and not a.no_extra_configs:
         from tools import bench_rnn
         extra = bench_rnn.extra_configs()
 
     decode = None
-    if rank == 0 and world == 1 and not a.no_decode:
+    if a.full and rank == 0 and world == 1 and not a.no_decode:
         from tools import bench_decode
         decode = bench_decode.decode_leg(dev, c2_args)
 
     cpu = orc = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         threads = os.cpu_count() or 1
         try:
             threads = len(os.sched_getaffinity(0))

@@ -23,7 +23,7 @@ for t in "$@"; do
     search) run test_search python -m pytest tests/test_gpu_transducer_search.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     rnnt)  run test_rnnt python -m pytest tests/test_gpu_transducer_loss.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     smoke) run smoke python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench python bench.py --steps 5 --warmup 2 ;;
+    bench) run bench python bench.py --steps 5 --warmup 2 --full ;;
     *) echo "unknown tier $t"; exit 2 ;;
   esac
 done
