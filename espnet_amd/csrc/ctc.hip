@@ -47,6 +47,10 @@ __global__ __launch_bounds__(64) void ctc_prep_kernel(const long long* __restric
   if (lane == 0) lablen[b] = n;
 }
 
+// kNormalized (forced alignment of rows that already are log-probabilities): no reduction, the gather reads the rows as they are.
+// kGuardLabels (forced alignment): a label outside [0, V) is never read - its state gets log-probability -inf, so the utterance
+// has no path (the loss keeps its unchecked gather)
+template <bool kNormalized, bool kGuardLabels>
 __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const float* __restrict__ x, long st, long sb,
                                                              const int* __restrict__ ilen,
                                                              const int* __restrict__ lab,
@@ -57,6 +61,15 @@ __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const float* __rest
   const int t = blockIdx.x, b = blockIdx.y;
   if (t >= ilen[b]) return;
   const float* xr = x + t * st + b * sb;
+  if constexpr (kNormalized) {
+    const int S = 2 * lablen[b] + 1;
+    float* lpr = lp + ((long)b * T + t) * Smax;
+    for (int s = threadIdx.x; s < S; s += blockDim.x) {
+      const int l = (s & 1) ? lab[(long)b * Lmax + (s >> 1)] : blank;
+      lpr[s] = (kGuardLabels && (l < 0 || l >= V)) ? -INFINITY : xr[l];
+    }
+    return;
+  }
   // one pass over the row: running maximum and rescaled sum per thread (16-byte loads where the row allows)
   float mx = -INFINITY, se = 0.f;
   if (((reinterpret_cast<uintptr_t>(xr) & 15) == 0) && (V % 4 == 0)) {
@@ -83,6 +96,9 @@ __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const float* __rest
   float* lpr = lp + ((long)b * T + t) * Smax;
   for (int s = threadIdx.x; s < S; s += blockDim.x) {
     int l = (s & 1) ? lab[(long)b * Lmax + (s >> 1)] : blank;
+    if constexpr (kGuardLabels) {
+      if (l < 0 || l >= V) { lpr[s] = -INFINITY; continue; }
+    }
     lpr[s] = xr[l] - lse;
   }
 }
@@ -262,7 +278,7 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
 
   hipLaunchKernelGGL(ctc_prep_kernel, dim3(B), dim3(64), 0, s, (const long long*)ys_pad, Lmax, ignore_id, lab, lablen, B);
   EAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_lse_gather_kernel, dim3(T, B), dim3(256), 0, s, acts, (long)stride_t, (long)stride_b, ilens,
+  hipLaunchKernelGGL((ctc_lse_gather_kernel<false, false>), dim3(T, B), dim3(256), 0, s, acts, (long)stride_t, (long)stride_b, ilens,
                      lab, lablen, Lm, lse, lp, T, V, Smax, blank);
   EAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(B, 2), dim3(threads), 2 * (Smax + 4) * sizeof(float), s, lp, ilens,
@@ -274,6 +290,215 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
                        (long)gstride_b, T, V, Smax, blank, grad_scale);
     EAMD_LAUNCH_CHECK();
   }
+  return EAMD_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// CTC forced alignment (Viterbi over the extended-label lattice).  reference: ctc.py:153-216 (CTC.forced_align, one utterance,
+// numpy loop over frames x states); here a batch, on the caller's stream, four launches:
+//   prep          : ctc_prep_kernel (labels compacted)
+//   lse_gather    : ctc_lse_gather_kernel<normalized, true> (log-softmax over V and the 2L+1 state emissions; normalized rows:
+//                   gather only; a label outside [0, V) gets -inf instead of a read)
+//   viterbi       : one workgroup per utterance: the max-plus scan of ctc_alpha_beta_kernel's alpha recursion (a thread owns 4
+//                   consecutive states, the previous column's last two states of each thread exchanged through LDS, one barrier
+//                   per frame, emissions prefetched PF frames ahead), backpointers as one byte per (t, s) into the workspace
+//   backtrack     : one wave per utterance: the walk back from the end state, writing states, tokens and segment bounds.
+// Recursion and tie-break as the reference: delta[t,s] = max(stay, s-1, s-2 where allowed) + lp[t,s] in fp32 (first maximum:
+// stay before s-1 before s-2), end state S-1 before S-2.  Departures: state 0 has no s-1 (numpy reads index -1 there, the last
+// state), an infeasible pair (T_b < L_b + adjacent repeats) gives score -inf and -1 outputs, L_b = 0 gives the all-blank path.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr int kAlignMaxThreads = 1024;            // 4 states per thread: S <= 4096
+
+__global__ __launch_bounds__(kAlignMaxThreads) void ctc_viterbi_kernel(const float* __restrict__ lp, const int* __restrict__ ilen,
+                                                                        const int* __restrict__ lab, const int* __restrict__ lablen,
+                                                                        int Lmax, int Lout, unsigned char* __restrict__ bp,
+                                                                        float* __restrict__ score, int* __restrict__ endst,
+                                                                        int* __restrict__ states, long long* __restrict__ tokens,
+                                                                        int* __restrict__ seg_start, int* __restrict__ seg_end, int T,
+                                                                        int Spad, int blank) {
+  __shared__ float2 xch[2][kAlignMaxThreads + 1];   // [buffer][1 + thread]: states 4 tid + 2, 4 tid + 3; slot 0 = (-inf, -inf)
+  __shared__ float endv[2];
+  constexpr int PF = 8;
+  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int Tb = min(ilen[b], T);
+  const int L = lablen[b];
+  const int S = 2 * L + 1;
+  const int s0 = 4 * tid;
+  int* st_b = states + (long)b * T;
+  long long* tk_b = tokens + (long)b * T;
+  int* ss_b = seg_start + (long)b * Lout;
+  int* se_b = seg_end + (long)b * Lout;
+  const int* lab_b = lab + (long)b * Lmax;
+  // frames behind the utterance and label slots behind its labels: -1
+  for (int t = max(Tb, 0) + tid; t < T; t += nt) { st_b[t] = -1; tk_b[t] = -1; }
+  for (int i = L + tid; i < Lout; i += nt) { ss_b[i] = -1; se_b[i] = -1; }
+  if (Tb <= 0) {
+    if (tid == 0) score[b] = L == 0 ? 0.f : -INFINITY;
+    for (int i = tid; i < min(L, Lout); i += nt) { ss_b[i] = -1; se_b[i] = -1; }
+    return;
+  }
+  const bool active = s0 < S;
+  // the transitions each of the 4 states may take: s-2 only for a label state whose label differs from the one before it
+  unsigned skip = 0;
+  if (active) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int s = s0 + k;
+      if ((s & 1) && s >= 3 && s < S) {
+        const int y = lab_b[s >> 1];
+        if (y != blank && y != lab_b[(s - 2) >> 1]) skip |= 1u << k;
+      }
+    }
+  }
+  const float* lpb = lp + (long)b * T * Spad;
+  unsigned* bpw = reinterpret_cast<unsigned*>(bp + (long)b * T * Spad);
+  const long rw = Spad / 4;                        // 4-state words per frame
+  float d[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) d[k] = (s0 + k < 2 && s0 + k < S) ? lpb[s0 + k] : -INFINITY;
+  if (tid == 0) { xch[0][0] = make_float2(-INFINITY, -INFINITY); xch[1][0] = make_float2(-INFINITY, -INFINITY); }
+  xch[0][tid + 1] = make_float2(d[2], d[3]);
+  __syncthreads();
+  int p = 0;
+  const float4* lp4 = reinterpret_cast<const float4*>(lpb) + tid;
+  float4 er[PF];
+#pragma unroll
+  for (int i = 0; i < PF; ++i) er[i] = (active && 1 + i < Tb) ? lp4[(1 + i) * rw] : make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int t0 = 1; t0 < Tb; t0 += PF) {
+    float4 en[PF];
+#pragma unroll
+    for (int i = 0; i < PF; ++i) en[i] = (active && t0 + PF + i < Tb) ? lp4[(t0 + PF + i) * rw] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < PF; ++i) {
+      const int t = t0 + i;
+      if (t < Tb) {                                  // block-uniform
+        const float2 nb = xch[p][tid];              // previous column, states s0 - 2 and s0 - 1
+        const float prv[6] = {nb.x, nb.y, d[0], d[1], d[2], d[3]};
+        const float e[4] = {er[i].x, er[i].y, er[i].z, er[i].w};
+        unsigned word = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float best = prv[k + 2];
+          unsigned off = 0;
+          if (prv[k + 1] > best) { best = prv[k + 1]; off = 1; }
+          if (((skip >> k) & 1u) && prv[k] > best) { best = prv[k]; off = 2; }
+          d[k] = (s0 + k < S) ? best + e[k] : -INFINITY;
+          word |= off << (8 * k);
+        }
+        if (active) bpw[t * rw + tid] = word;
+        xch[p ^ 1][tid + 1] = make_float2(d[2], d[3]);
+        __syncthreads();
+        p ^= 1;
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < PF; ++i) er[i] = en[i];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (s0 + k == S - 1) endv[0] = d[k];
+    if (s0 + k == S - 2) endv[1] = d[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const float e1 = endv[0], e2 = S >= 2 ? endv[1] : -INFINITY;
+    const float best = e2 > e1 ? e2 : e1;
+    score[b] = best;
+    endst[b] = best == -INFINITY ? -1 : (e2 > e1 ? S - 2 : S - 1);     // -1: no CTC path of Tb frames spells these labels
+  }
+}
+
+// the walk back through the backpointers: one wave per utterance, lane 0 follows the chain (one dependent byte load per frame)
+// and writes states, tokens and the segment bounds as it goes; an utterance without a path gets -1 everywhere
+__global__ __launch_bounds__(64) void ctc_backtrack_kernel(const unsigned char* __restrict__ bp, const int* __restrict__ ilen,
+                                                           const int* __restrict__ lab, const int* __restrict__ lablen, int Lmax,
+                                                           int Lout, const int* __restrict__ endst, int* __restrict__ states,
+                                                           long long* __restrict__ tokens, int* __restrict__ seg_start,
+                                                           int* __restrict__ seg_end, int T, int Spad, int blank) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int Tb = min(ilen[b], T);
+  if (Tb <= 0) return;                               // (the scan wrote every output of an empty utterance)
+  const int L = lablen[b];
+  int* st_b = states + (long)b * T;
+  long long* tk_b = tokens + (long)b * T;
+  int* ss_b = seg_start + (long)b * Lout;
+  int* se_b = seg_end + (long)b * Lout;
+  const int send = endst[b];
+  if (send < 0) {
+    for (int t = lane; t < Tb; t += 64) { st_b[t] = -1; tk_b[t] = -1; }
+    for (int i = lane; i < min(L, Lout); i += 64) { ss_b[i] = -1; se_b[i] = -1; }
+    return;
+  }
+  if (lane != 0) return;
+  const int* lab_b = lab + (long)b * Lmax;
+  const unsigned char* bpb = bp + (long)b * T * Spad;
+  int s = send, nxt = -1;                            // nxt: the state at t + 1
+  for (int t = Tb - 1; t >= 0; --t) {
+    st_b[t] = s;
+    tk_b[t] = (s & 1) ? lab_b[s >> 1] : blank;
+    if ((s & 1) && nxt != s) se_b[s >> 1] = t;
+    if (nxt >= 0 && (nxt & 1) && nxt != s) ss_b[nxt >> 1] = t + 1;
+    nxt = s;
+    if (t > 0) s -= bpb[(long)t * Spad + s];
+  }
+  if (nxt & 1) ss_b[nxt >> 1] = 0;
+}
+}  // namespace
+
+extern "C" {
+
+/* workspace bytes needed by eamd_ctc_forced_align */
+int64_t eamd_ctc_align_workspace_bytes(int B, int T, int Lmax) {
+  const int64_t Lm = Lmax > 0 ? Lmax : 1;
+  const int64_t Spad = (2 * (int64_t)Lmax + 1 + 3) / 4 * 4;
+  return (int64_t)B * Lm * 4 + (int64_t)B * 4 + 16      /* lab, lablen (+ alignment) */
+         + (int64_t)B * T * 4 + 16                      /* lse (+ alignment) */
+         + (int64_t)B * T * Spad * 4                    /* lp */
+         + (int64_t)B * T * Spad                        /* backpointers */
+         + (int64_t)B * 4                               /* end states */
+         + 256;
+}
+
+int eamd_ctc_forced_align(const float* acts, int64_t stride_t, int64_t stride_b, const int64_t* ys_pad, const int32_t* ilens,
+                          float* score, int32_t* states, int64_t* tokens, int32_t* seg_start, int32_t* seg_end, void* workspace,
+                          int B, int T, int V, int Lmax, int blank, int ignore_id, int normalized, void* stream) {
+  if (!acts || !ys_pad || !ilens || !score || !states || !tokens || !seg_start || !seg_end || !workspace || B <= 0 || T <= 0 ||
+      V <= 0 || Lmax < 0 || blank < 0 || blank >= V)
+    return EAMD_EINVAL;
+  const int Smax = 2 * Lmax + 1;
+  if (Smax > 4 * kAlignMaxThreads) return EAMD_EUNSUPPORTED;
+  const int Spad = (Smax + 3) / 4 * 4;
+  const int threads = ((Spad / 4 + 63) / 64) * 64;
+  hipStream_t s = (hipStream_t)stream;
+  const int Lm = Lmax > 0 ? Lmax : 1;
+  char* w = (char*)workspace;
+  int* lab = (int*)w; w += (size_t)B * Lm * 4;
+  int* lablen = (int*)w; w += (size_t)B * 4;
+  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
+  float* lse = (float*)w; w += (size_t)B * T * 4;
+  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
+  float* lp = (float*)w; w += (size_t)B * T * Spad * 4;     // rows of Spad (% 4 == 0) floats: a thread's 4 states are one 16-byte load
+  unsigned char* bp = (unsigned char*)w; w += (size_t)B * T * Spad;
+  int* endst = (int*)w;                              // (B T Spad is a multiple of 4)
+
+  hipLaunchKernelGGL(ctc_prep_kernel, dim3(B), dim3(64), 0, s, (const long long*)ys_pad, Lmax, ignore_id, lab, lablen, B);
+  EAMD_LAUNCH_CHECK();
+  if (normalized)
+    hipLaunchKernelGGL((ctc_lse_gather_kernel<true, true>), dim3(T, B), dim3(256), 0, s, acts, (long)stride_t, (long)stride_b, ilens,
+                       lab, lablen, Lm, nullptr, lp, T, V, Spad, blank);
+  else
+    hipLaunchKernelGGL((ctc_lse_gather_kernel<false, true>), dim3(T, B), dim3(256), 0, s, acts, (long)stride_t, (long)stride_b, ilens,
+                       lab, lablen, Lm, lse, lp, T, V, Spad, blank);
+  EAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ctc_viterbi_kernel, dim3(B), dim3(threads), 0, s, lp, ilens, lab, lablen, Lm, Lmax, bp, score, endst, states,
+                     (long long*)tokens, seg_start, seg_end, T, Spad, blank);
+  EAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ctc_backtrack_kernel, dim3(B), dim3(64), 0, s, bp, ilens, lab, lablen, Lm, Lmax, endst, states,
+                     (long long*)tokens, seg_start, seg_end, T, Spad, blank);
+  EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
 

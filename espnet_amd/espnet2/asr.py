@@ -185,6 +185,12 @@ class CTC(torch.nn.Module):
     def argmax(self, hs_pad):
         return self._ctc[0].argmax(hs_pad)
 
+    def forced_align(self, h, y, blank_id=0):
+        return self._ctc[0].forced_align(h, y, blank_id)
+
+    def forced_align_batch(self, hs_pad, hlens, ys_pad, blank_id=0):
+        return self._ctc[0].forced_align_batch(hs_pad, hlens, ys_pad, blank_id)
+
 
 class ESPnetASRModel(AbsESPnetModel):
     """reference: espnet2/asr/espnet_model.py:35-290.  frontend = None (fbank features are the input) or

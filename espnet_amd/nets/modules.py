@@ -10,6 +10,7 @@ torch.nn.Linear / Conv / BatchNorm objects below are parameter containers only (
 state_dict layout identical to the reference); their torch forward is never called.
 """
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -1231,6 +1232,17 @@ class LabelSmoothingLoss(torch.nn.Module):
         return loss
 
 
+class CTCAlignment(NamedTuple):
+    """CTC.forced_align_batch: score [B] (log-probability of the best path, -inf where there is none), states [B,T] (index in the
+    extended sequence blank,y1,blank,...,yL,blank), tokens [B,T] (token per frame), start / end [B,L] (first / last frame of each
+    label); -1 past an utterance's frames or labels and everywhere in an utterance without a path."""
+    score: torch.Tensor
+    states: torch.Tensor
+    tokens: torch.Tensor
+    start: torch.Tensor
+    end: torch.Tensor
+
+
 class CTC(torch.nn.Module):
     """reference: ctc.py:12-151 (espnet1) / espnet2/asr/ctc.py:6-111.
     ctc_type is accepted for interface parity ("warpctc" and "builtin" compute the same quantity:
@@ -1280,6 +1292,43 @@ class CTC(torch.nn.Module):
     def argmax(self, hs_pad):
         y = self.logits(hs_pad)
         return ops.argmax_rows(y.reshape(-1, y.shape[-1]).contiguous()).view(y.shape[:-1]).long()
+
+    def forced_align(self, h, y, blank_id=0):
+        """reference: ctc.py:153-216.  h (1,T,D) or (T,D); y the label ids (sequence, ndarray or tensor) -> the token of each of
+        the T frames on the best CTC path, as a list.  The same fp32 recursion and first-maximum tie-break as the reference, on
+        the true CTC lattice (the reference's state 0 also reads the last state, numpy's index -1); an empty y aligns every
+        frame to blank; ValueError when no path of T frames spells y (T < len(y) + adjacent repeats)."""
+        if h.dim() == 3:
+            assert h.shape[0] == 1, h.shape
+            h = h[0]
+        y = np.asarray(y.tolist() if isinstance(y, torch.Tensor) else y, dtype=np.int64).reshape(-1)
+        al = self.forced_align_batch(h.unsqueeze(0), [h.shape[0]], torch.from_numpy(y).unsqueeze(0), blank_id)
+        if not float(al.score[0]) > -math.inf:
+            raise ValueError("no CTC path of %d frames for %d labels" % (h.shape[0], y.size))
+        return al.tokens[0].tolist()
+
+    def forced_align_batch(self, hs_pad, hlens, ys_pad, blank_id=0):
+        """the best CTC path of every utterance of a padded batch in one pass (the reference's batch branch raises
+        NotImplementedError): hs_pad (B,T,D); hlens valid frames (list / tensor); ys_pad (B,L) padded with -1 -> CTCAlignment"""
+        odim = self.ctc_lo.out_features
+        if not 0 <= blank_id < odim:
+            raise ValueError("blank id %d outside the %d outputs" % (blank_id, odim))
+        dev = self.ctc_lo.weight.device
+        if not isinstance(ys_pad, torch.Tensor):
+            ys_pad = torch.as_tensor(np.asarray(ys_pad), dtype=torch.int64)
+        if not ys_pad.is_cuda:      # host labels: checked here at no cost (the kernel reads the label's logit unchecked)
+            yv = ys_pad[ys_pad != self.ignore_id]
+            if yv.numel() and (int(yv.min()) < 0 or int(yv.max()) >= odim):
+                raise ValueError("label ids must lie in [0, %d)" % odim)
+        ys_pad = ys_pad.to(device=dev, dtype=torch.int64).contiguous()
+        if isinstance(hlens, torch.Tensor):
+            hl = hlens.to(device=dev, dtype=torch.int32)
+        else:
+            hl = torch.as_tensor([int(v) for v in hlens], dtype=torch.int32).to(dev)
+        with torch.no_grad():
+            y = self.logits(hs_pad.to(dev).contiguous())
+            return CTCAlignment(*ops.ctc_forced_align(y.contiguous(), hl.contiguous(), ys_pad, blank=blank_id,
+                                                       ignore_id=self.ignore_id))
 
 
 def th_accuracy(correct_rows, pad_targets, ignore_label):

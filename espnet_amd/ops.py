@@ -1858,6 +1858,39 @@ def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, wan
     return nll, grad
 
 
+def ctc_forced_align(acts, ilens, ys_pad, blank=0, ignore_id=-1, normalized=False, time_major=False):
+    """best CTC path of each utterance (eamd_ctc_forced_align): acts [B,T,V] raw activations, or log-probabilities when
+    normalized (time_major: [T,B,V]); ilens [B] int32; ys_pad [B,L] int64 padded with ignore_id
+    -> score [B] f32, states [B,T] int32, tokens [B,T] int64, seg_start / seg_end [B,L] int32 (device tensors; -1 past
+    ilens / the labels and for utterances without a path, whose score is -inf - also those with a label outside [0, V),
+    which the kernel never reads).  L <= 2047."""
+    if time_major:
+        T, B, V = acts.shape
+        st, sb = B * V, V
+    else:
+        B, T, V = acts.shape
+        st, sb = V, T * V
+    L = ys_pad.shape[1]
+    assert acts.is_contiguous() and ys_pad.is_contiguous() and ys_pad.dtype == torch.int64 and acts.dtype == torch.float32
+    assert ilens.dtype == torch.int32 and ilens.numel() == B and ys_pad.shape[0] == B
+    dev = acts.device
+    if L == 0:          # no label column at all: one column of padding (the entry point takes no NULL operands)
+        seg = torch.empty(B, 0, device=dev, dtype=torch.int32)
+        out = ctc_forced_align(acts, ilens, torch.full((B, 1), ignore_id, device=dev, dtype=torch.int64), blank, ignore_id,
+                               normalized, time_major)
+        return out[:3] + (seg, seg.clone())
+    ws = torch.empty(_lib.lib().eamd_ctc_align_workspace_bytes(B, T, L), device=dev, dtype=torch.uint8)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    states = torch.empty(B, T, device=dev, dtype=torch.int32)
+    tokens = torch.empty(B, T, device=dev, dtype=torch.int64)
+    seg_start = torch.empty(B, L, device=dev, dtype=torch.int32)
+    seg_end = torch.empty(B, L, device=dev, dtype=torch.int32)
+    check(_lib.lib().eamd_ctc_forced_align(ptr(acts), C.c_int64(st), C.c_int64(sb), ptr(ys_pad), ptr(ilens), ptr(score),
+                                           ptr(states), ptr(tokens), ptr(seg_start), ptr(seg_end), ptr(ws), B, T, V, L, blank,
+                                           ignore_id, int(bool(normalized)), stream_ptr()), "eamd_ctc_forced_align")
+    return score, states, tokens, seg_start, seg_end
+
+
 def ctc_prefix_score(logp, r_prev, cand, last, olen, blank, eos):
     """logp [T,V] fp32; r_prev [nhyp,T,2]; cand [nhyp,ncand] int32; last, olen [nhyp] int32
     -> psi [nhyp,ncand], r_new [nhyp,ncand,T,2]"""

@@ -628,6 +628,20 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
                   void* workspace, int B, int T, int V, int Lmax, int blank, int ignore_id, float grad_scale,
                   void* stream);
 
+/* CTC forced alignment: the best (Viterbi) CTC path of each utterance through its labels.  reference: ctc.py:153-216
+ * (CTC.forced_align: one utterance; same recursion, fp32 scores and first-maximum tie-break).  acts, ys_pad, ilens, blank,
+ * ignore_id as eamd_ctc_loss; normalized != 0: acts rows already are log-probabilities (no log-softmax).  Outputs:
+ * score [B] (log-probability of the path; -inf if no path of ilens[b] frames spells the labels), states [B,T] (state index in
+ * the extended sequence blank,y1,blank,...,yL,blank), tokens [B,T] (token per frame), seg_start / seg_end [B,Lmax] (first and
+ * last frame of each label).  Frames >= ilens[b], label slots >= L_b and every output of an infeasible utterance are -1.
+ * Lmax <= 2047 (2 Lmax + 1 <= 4096 states), else EAMD_EUNSUPPORTED.  A label outside [0, V) is never read: it has
+ * log-probability -inf, so its utterance has no path (score -inf, -1 outputs).
+ * workspace: eamd_ctc_align_workspace_bytes(B, T, Lmax) bytes. */
+int64_t eamd_ctc_align_workspace_bytes(int B, int T, int Lmax);
+int eamd_ctc_forced_align(const float* acts, int64_t stride_t, int64_t stride_b, const int64_t* ys_pad, const int32_t* ilens,
+                          float* score, int32_t* states, int64_t* tokens, int32_t* seg_start, int32_t* seg_end, void* workspace,
+                          int B, int T, int V, int Lmax, int blank, int ignore_id, int normalized, void* stream);
+
 /* CTC prefix scores of (hypothesis, candidate) pairs for joint CTC/attention beam search.
  * reference: espnet/nets/ctc_prefix_score.py:224-310, scorers/ctc.py:11-127.
  * logp [T,V]; r_prev [nhyp,T,2]; cand [nhyp,ncand]; last/olen [nhyp]; psi [nhyp,ncand]; r_new [nhyp,ncand,T,2]. */
