@@ -4,20 +4,22 @@
 import torch
 
 from .. import ops
-from .modules import embed_output_lengths, make_non_pad_mask
+from .modules import embed_output_lengths, make_non_pad_mask, subsampled_stride
 
 
 def _lengths(ilens):
     return [int(v) for v in (ilens.tolist() if isinstance(ilens, torch.Tensor) else ilens)]
 
 
-def encode_batch(model, xs_pad, ilens):
+def encode_batch(model, xs_pad, ilens, alone=False):
     """the model's encoder on a padded batch in one call, in eval mode (the model's train / eval mode is restored after)
     -> (hs_pad (B,T',D), hlens list of valid encoder frames).  espnet2 ESPnetASRModel: encode(speech, lengths); espnet1 RNN E2E:
     enc(xs_pad, ilens); espnet1 Transformer / Conformer E2E: encoder(xs_pad, mask).  As in the reference's batches, the valid
     frames of a padded utterance are those of the subsampled mask (one more than the same utterance gets unpadded behind a conv2d
     input layer), and layers without a mask (the Conformer convolution module) see the padding of the shorter utterances: a
-    padded utterance's encoder output, and so its alignment, can differ from the one it has alone."""
+    padded utterance's encoder output, and so its alignment, can differ from the one it has alone.
+    alone=True (espnet1 Transformer / Conformer): every utterance keeps the encoder frames it has alone, and the encoder mask is
+    the one model.prepare(pad_to=) builds for them; a Transformer encoder then gives each utterance the output it has alone."""
     from ..espnet2.asr import ESPnetASRModel
     dev = next(model.parameters()).device
     il = _lengths(ilens)
@@ -36,10 +38,15 @@ def encode_batch(model, xs_pad, ilens):
             if hasattr(model, "encoder"):                                         # espnet1 Transformer / Conformer
                 tmax = max(il)
                 xs_pad = xs_pad[:, :tmax].contiguous()
-                mask = make_non_pad_mask(il, tmax).unsqueeze(-2).to(torch.uint8).to(dev)
+                mask_len = il
+                if alone:
+                    hl = [embed_output_lengths(model.encoder.embed, [n], n)[0] for n in il]
+                    stride = max(1, subsampled_stride(model.encoder.embed))
+                    mask_len = [(h - 1) * stride + 1 if h > 0 else 0 for h in hl]
+                mask = make_non_pad_mask(mask_len, tmax).unsqueeze(-2).to(torch.uint8).to(dev)
                 ops.zero_arena_off()
                 hs_pad, _ = model.encoder(xs_pad, mask)
-                return hs_pad, embed_output_lengths(model.encoder.embed, il, tmax)
+                return hs_pad, hl if alone else embed_output_lengths(model.encoder.embed, il, tmax)
     finally:
         model.train(was_training)
     raise TypeError("%s has no encoder this helper knows" % type(model).__name__)

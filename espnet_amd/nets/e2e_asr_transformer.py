@@ -183,6 +183,7 @@ class E2E(ASRInterface, torch.nn.Module):
         # host-built tensors go to the device through pinned staging copies (ops.h2d_async): the host never waits for the
         # stream here, so the next batch is prepared while the previous step still runs
         xs_pad = ops.h2d_async(xs_pad[:, :tmax], dev).contiguous()
+        ys_host = ys_pad
         ys_pad = ops.h2d_async(ys_pad, dev).contiguous()
         if hl_true is None:
             mask_len = il
@@ -196,16 +197,21 @@ class E2E(ASRInterface, torch.nn.Module):
         if tbound is not None:
             batch["tbound"] = ops.h2d_async(torch.tensor([tbound], dtype=torch.int32), dev)
         if self.decoder is not None:
-            ys_in_pad, ys_out_pad, _ = ops.add_sos_eos(ys_pad, self.sos, self.eos, self.ignore_id)
-            U = ys_in_pad.size(1)
-            # ys_in is padded with <eos>, never ignore_id, so target_mask() is the causal mask (mask.py:41-51)
-            ys_mask = subsequent_mask(U).unsqueeze(0).expand(xs_pad.size(0), U, U).to(torch.uint8).contiguous()
-            batch.update(ys_in_pad=ys_in_pad, ys_out_pad=ys_out_pad, ys_mask=ops.h2d_async(ys_mask, dev),
-                         n_valid=(ys_out_pad != self.ignore_id).sum())
+            batch.update(self.decoder_inputs(ys_host, ys_pad, dev))
         if self.mtlalpha > 0.0:
             hl = hl_true if hl_true is not None else embed_output_lengths(self.encoder.embed, il, tmax)
             batch["hs_len"] = ops.h2d_async(torch.tensor(hl, dtype=torch.int32), dev)
         return batch
+
+    def decoder_inputs(self, ys_host, ys_pad, dev):
+        """the decoder's part of prepare(): ys_in_pad, ys_out_pad, ys_mask (uint8, device) and n_valid (device) from the labels
+        (ys_host as given to prepare(), ys_pad its device copy)"""
+        ys_in_pad, ys_out_pad, _ = ops.add_sos_eos(ys_pad, self.sos, self.eos, self.ignore_id)
+        U = ys_in_pad.size(1)
+        # ys_in is padded with <eos>, never ignore_id, so target_mask() is the causal mask (mask.py:41-51)
+        ys_mask = subsequent_mask(U).unsqueeze(0).expand(ys_pad.size(0), U, U).to(torch.uint8).contiguous()
+        return dict(ys_in_pad=ys_in_pad, ys_out_pad=ys_out_pad, ys_mask=ops.h2d_async(ys_mask, dev),
+                    n_valid=(ys_out_pad != self.ignore_id).sum())
 
     def forward_core(self, batch):
         """Kernel-only part of forward (reference: e2e_asr_transformer.py:175-232)."""

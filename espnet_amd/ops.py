@@ -1891,6 +1891,42 @@ def ctc_forced_align(acts, ilens, ys_pad, blank=0, ignore_id=-1, normalized=Fals
     return score, states, tokens, seg_start, seg_end
 
 
+def maskctc_seed(logits, hlens, thr, K, mask_token, eos, blank=0, Lcap=None):
+    """Mask-CTC seed (eamd_maskctc_seed): logits [B,T',V] fp32 CTC output-layer activations, hlens [B] int32 (device) valid
+    frames -> dict of device tensors: y_in [B,Lcap] int64 (confident token or mask_token, padded with eos), tok_p [B,Lcap] (max p
+    over each token's run), len / nmask / niter / kper [B] int32, frame_id / frame_p [B,T'] (per-frame argmax of p and its p,
+    valid for t < hlens).  Lcap defaults to T'."""
+    B, T, V = logits.shape
+    Lcap = T if Lcap is None else int(Lcap)
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and hlens.dtype == torch.int32 and hlens.numel() == B
+    dev = logits.device
+    i32 = lambda *s: torch.empty(*s, device=dev, dtype=torch.int32)  # noqa: E731
+    out = dict(y_in=torch.empty(B, Lcap, device=dev, dtype=torch.int64), tok_p=torch.empty(B, Lcap, device=dev, dtype=torch.float32),
+               len=i32(B), nmask=i32(B), niter=i32(B), kper=i32(B), frame_id=i32(B, T),
+               frame_p=torch.empty(B, T, device=dev, dtype=torch.float32))
+    check(_lib.lib().eamd_maskctc_seed(ptr(logits), ptr(hlens), ptr(out["frame_id"]), ptr(out["frame_p"]), ptr(out["y_in"]),
+                                       ptr(out["tok_p"]), ptr(out["len"]), ptr(out["nmask"]), ptr(out["niter"]), ptr(out["kper"]),
+                                       B, T, V, Lcap, blank, mask_token, eos, C.c_double(float(thr)), int(K), stream_ptr()),
+          "eamd_maskctc_seed")
+    return out
+
+
+def maskctc_update(pass_, logits, y_in, lens, niter, kper, mask_token, score=None, arg=None):
+    """one Mask-CTC mask-predict pass (eamd_maskctc_update): logits [B,L,V] fp32 decoder output on y_in[:, :L]; y_in [B,ldy]
+    int64 (row-contiguous, ldy >= L) is updated in place; lens / niter / kper [B] int32.  score / arg: optional [B,L] workspaces
+    (reused across passes).  -> (score, arg); they hold the max logit and its argmax at the masked rows of active utterances."""
+    B, L, V = logits.shape
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and y_in.dtype == torch.int64 and y_in.stride(1) == 1
+    assert y_in.shape[0] == B and y_in.shape[1] >= L
+    dev = logits.device
+    if score is None:
+        score = torch.empty(B, L, device=dev, dtype=torch.float32)
+        arg = torch.empty(B, L, device=dev, dtype=torch.int32)
+    check(_lib.lib().eamd_maskctc_update(int(pass_), ptr(logits), ptr(y_in), ptr(lens), ptr(niter), ptr(kper), ptr(score), ptr(arg),
+                                         B, L, y_in.stride(0), V, mask_token, stream_ptr()), "eamd_maskctc_update")
+    return score, arg
+
+
 def ctc_prefix_score(logp, r_prev, cand, last, olen, blank, eos):
     """logp [T,V] fp32; r_prev [nhyp,T,2]; cand [nhyp,ncand] int32; last, olen [nhyp] int32
     -> psi [nhyp,ncand], r_new [nhyp,ncand,T,2]"""

@@ -933,6 +933,29 @@ int eamd_conv2_weight_prep(const float* w, void* wf, void* wd, int Co, int Ci, i
 /* dw[Co][Ci][3][3] += dwf[9][Ci][Co] */
 int eamd_conv2_weight_grad(const float* dwf, float* dw, int Co, int Ci, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask-CTC decoding (reference: pytorch_backend/e2e_asr_maskctc.py:180-249, E2E.recognize), batched.
+ * ------------------------------------------------------------------------------------------ */
+#define EAMD_MASKCTC_MAX_FRAMES 8192
+/* Greedy CTC of every utterance and the masked decoder input.  logits [B,T,V] fp32 (CTC output layer, raw); frames
+ * t < hlens[b] are read.  frame_id / frame_p [B,T]: first-index argmax of p = exp(log_softmax(logits)) and its p.
+ * The non-blank runs of frame_id give the tokens; a token's probability is the max p over its run and tok_p [B,Lcap] holds it;
+ * y_in [B,Lcap] int64 is the token where (double)tok_p >= thr, else mask_token, padded with eos (tokens past Lcap are
+ * dropped: Lcap >= max hlens keeps all).  len = #tokens, nmask = M = #masked, niter = (M >= K && K > 0) ? K : M,
+ * kper = M / niter (0 when M == 0).  T <= EAMD_MASKCTC_MAX_FRAMES and Lcap <= T, else EAMD_EUNSUPPORTED. */
+int eamd_maskctc_seed(const float* logits, const int32_t* hlens, int32_t* frame_id, float* frame_p, int64_t* y_in, float* tok_p,
+                      int32_t* len, int32_t* nmask, int32_t* niter, int32_t* kper, int B, int T, int V, int Lcap, int blank,
+                      int mask_token, int eos, double thr, int K, void* stream);
+/* Mask-predict pass `pass` (0-based).  logits [B,L,V] fp32 (decoder output on y_in[:, :L]); y_in [B, ldy] updated in place.
+ * For the masked positions l < min(len[b], L) of an utterance with pass < niter[b]: score / arg [B,L] = max logit and its
+ * first-index argmax over all V classes.  pass < niter-1: the kper[b] masked positions with the largest scores take their
+ * argmax (equal scores: the lower position first); pass == niter-1: every masked position does; pass >= niter: unchanged.
+ * A position is masked when y_in holds mask_token: a kept CTC token equal to mask_token counts from the first pass on (the
+ * reference's first pass takes the thresholded positions only; a trained CTC layer does not emit the <mask> class).
+ * L <= EAMD_MASKCTC_MAX_FRAMES, else EAMD_EUNSUPPORTED. */
+int eamd_maskctc_update(int pass, const float* logits, int64_t* y_in, const int32_t* len, const int32_t* niter,
+                        const int32_t* kper, float* score, int32_t* arg, int B, int L, int ldy, int V, int mask_token, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
