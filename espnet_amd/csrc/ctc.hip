@@ -10,6 +10,9 @@
 //   alpha_beta : one block per (b, direction): wavefront scan over T in log space, states across
 //                lanes, previous column exchanged through LDS (double buffered, 1 barrier per frame)
 //   grad       : one block per (t,b): softmax row minus per-label occupancies accumulated in LDS
+// eamd_ctc_pit_loss (permutation-invariant CTC of S speakers, below) runs the same kernels with kPit: the gather reads each
+// (speaker, utterance, frame) row once for all S label sets, the alpha scan covers the B S^2 lattices, and beta and the gradient
+// only the B S lattices that the per-utterance permutation choice (ctc_pit_select_kernel) keeps.
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
@@ -50,17 +53,20 @@ __global__ __launch_bounds__(64) void ctc_prep_kernel(const long long* __restric
 // kNormalized (forced alignment of rows that already are log-probabilities): no reduction, the gather reads the rows as they are.
 // kGuardLabels (forced alignment): a label outside [0, V) is never read - its state gets log-probability -inf, so the utterance
 // has no path (the loss keeps its unchecked gather)
-template <bool kNormalized, bool kGuardLabels>
+// kPit (PIT loss): blockIdx.z = hypothesis speaker i, rows at x + i si; the row's log-softmax is gathered for each of the nsp label
+// rows b nsp + j into lattice (i B + b) nsp + j; lse_out holds (i B + b) T + t
+template <bool kNormalized, bool kGuardLabels, bool kPit = false>
 __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const float* __restrict__ x, long st, long sb,
                                                              const int* __restrict__ ilen,
                                                              const int* __restrict__ lab,
                                                              const int* __restrict__ lablen, int Lmax,
                                                              float* __restrict__ lse_out, float* __restrict__ lp,
-                                                             int T, int V, int Smax, int blank) {
+                                                             int T, int V, int Smax, int blank, long si = 0, int nsp = 1) {
   __shared__ float red[16];
   const int t = blockIdx.x, b = blockIdx.y;
   if (t >= ilen[b]) return;
-  const float* xr = x + t * st + b * sb;
+  const int ib = kPit ? blockIdx.z * gridDim.y + b : b;        // row set (speaker, utterance)
+  const float* xr = x + t * st + b * sb + (kPit ? blockIdx.z * si : 0);
   if constexpr (kNormalized) {
     const int S = 2 * lablen[b] + 1;
     float* lpr = lp + ((long)b * T + t) * Smax;
@@ -91,32 +97,51 @@ __global__ __launch_bounds__(256) void ctc_lse_gather_kernel(const float* __rest
   mx = block_max(mx, red);
   se = block_sum(mt == -INFINITY ? 0.f : se * expf(mt - mx), red);
   const float lse = mx + logf(se);
-  if (threadIdx.x == 0) lse_out[(long)b * T + t] = lse;
-  const int S = 2 * lablen[b] + 1;
-  float* lpr = lp + ((long)b * T + t) * Smax;
-  for (int s = threadIdx.x; s < S; s += blockDim.x) {
-    int l = (s & 1) ? lab[(long)b * Lmax + (s >> 1)] : blank;
-    if constexpr (kGuardLabels) {
-      if (l < 0 || l >= V) { lpr[s] = -INFINITY; continue; }
+  if (threadIdx.x == 0) lse_out[(long)ib * T + t] = lse;
+  for (int j = 0; j < (kPit ? nsp : 1); ++j) {
+    const int r = kPit ? b * nsp + j : b;                      // label row
+    const long lat = kPit ? (long)ib * nsp + j : b;            // lattice
+    const int S = 2 * lablen[r] + 1;
+    float* lpr = lp + (lat * T + t) * Smax;
+    for (int s = threadIdx.x; s < S; s += blockDim.x) {
+      int l = (s & 1) ? lab[(long)r * Lmax + (s >> 1)] : blank;
+      if constexpr (kGuardLabels) {
+        if (l < 0 || l >= V) { lpr[s] = -INFINITY; continue; }
+      }
+      lpr[s] = xr[l] - lse;
     }
-    lpr[s] = xr[l] - lse;
   }
 }
 
-// blockIdx.y == 0: alpha (forward), == 1: beta (backward, includes the emission at t)
+// kCtcLoss: blockIdx.y == 0: alpha (forward), == 1: beta (backward, includes the emission at t); lattice, label row and output b
+// kPitAlpha: alpha of lattice k = blockIdx.x = (i B + b) nsp + j (hypothesis i, reference j), -log p into nll[(b nsp + i) nsp + j]
+// kPitBeta : beta of the lattice the permutation keeps for q = blockIdx.x = i B + b (j = perm[b nsp + i]), written to beta row q
+enum { kCtcLoss = 0, kPitAlpha = 1, kPitBeta = 2 };
+template <int kMode = kCtcLoss>
 __global__ __launch_bounds__(1024) void ctc_alpha_beta_kernel(const float* __restrict__ lp,
                                                               const int* __restrict__ ilen,
                                                               const int* __restrict__ lab,
                                                               const int* __restrict__ lablen, int Lmax,
                                                               float* __restrict__ alpha, float* __restrict__ beta,
-                                                              float* __restrict__ nll, int T, int Smax, int blank) {
+                                                              float* __restrict__ nll, int T, int Smax, int blank,
+                                                              int nb = 1, int nsp = 1, const long long* __restrict__ perm = nullptr) {
   extern __shared__ float sh[];  // [2][Smax + 4]
   constexpr int PF = 8;
-  const int b = blockIdx.x;
-  const int dir = blockIdx.y;
+  int b = blockIdx.x, r = b;                 // utterance, label row
+  long lat = b, orow = b, nslot = b;         // lattice (lp), output row, nll slot
+  if constexpr (kMode == kPitAlpha) {
+    const int k = blockIdx.x, j = k % nsp, i = k / (nsp * nb);
+    b = (k / nsp) % nb; r = b * nsp + j; lat = k; orow = k; nslot = ((long)b * nsp + i) * nsp + j;
+  } else if constexpr (kMode == kPitBeta) {
+    const int q = blockIdx.x, i = q / nb;
+    b = q % nb;
+    const int j = (int)perm[(long)b * nsp + i];
+    r = b * nsp + j; lat = (long)q * nsp + j; orow = q;
+  }
+  const int dir = kMode == kCtcLoss ? (int)blockIdx.y : (kMode == kPitAlpha ? 0 : 1);
   const int s = threadIdx.x;
   const int Tb = ilen[b];
-  const int L = lablen[b];
+  const int L = lablen[r];
   const int S = 2 * L + 1;
   const int W = Smax + 4;
   float* buf0 = sh;
@@ -125,18 +150,18 @@ __global__ __launch_bounds__(1024) void ctc_alpha_beta_kernel(const float* __res
   for (int i = threadIdx.x; i < 2 * W; i += blockDim.x) sh[i] = -INFINITY;
   __syncthreads();
   if (Tb <= 0) {
-    if (dir == 0 && s == 0) nll[b] = (L == 0) ? 0.f : INFINITY;
+    if (dir == 0 && s == 0) nll[nslot] = (L == 0) ? 0.f : INFINITY;
     return;
   }
   const bool active = s < S;
-  const int my = active ? ((s & 1) ? lab[(long)b * Lmax + (s >> 1)] : blank) : blank;
+  const int my = active ? ((s & 1) ? lab[(long)r * Lmax + (s >> 1)] : blank) : blank;
   bool skip = false;  // may take the s-2 (alpha) / s+2 (beta) transition
   if (active && (s & 1)) {
-    if (dir == 0) skip = (s >= 2) && (lab[(long)b * Lmax + ((s - 2) >> 1)] != my);
-    else          skip = (s + 2 < S) && (lab[(long)b * Lmax + ((s + 2) >> 1)] != my);
+    if (dir == 0) skip = (s >= 2) && (lab[(long)r * Lmax + ((s - 2) >> 1)] != my);
+    else          skip = (s + 2 < S) && (lab[(long)r * Lmax + ((s + 2) >> 1)] != my);
   }
-  const float* lpb = lp + (long)b * T * Smax;
-  float* out = (dir == 0 ? alpha : beta) + (long)b * T * Smax;
+  const float* lpb = lp + lat * T * Smax;
+  float* out = (dir == 0 ? alpha : beta) + orow * T * Smax;
 
   if (dir == 0) {
     float cur = -INFINITY;
@@ -172,7 +197,7 @@ __global__ __launch_bounds__(1024) void ctc_alpha_beta_kernel(const float* __res
     if (s == 0) {
       float a1 = prev[S - 1 + 2];
       float a2 = S >= 2 ? prev[S - 2 + 2] : -INFINITY;
-      nll[b] = -lse2(a1, a2);
+      nll[nslot] = -lse2(a1, a2);
     }
   } else {
     float cur = -INFINITY;
@@ -206,6 +231,9 @@ __global__ __launch_bounds__(1024) void ctc_alpha_beta_kernel(const float* __res
   }
 }
 
+// kPit: blockIdx.z = hypothesis speaker i (rows at x + i si, gradient at grad + i gsi); the lattice is the one the permutation
+// keeps, (i B + b) nsp + perm[b nsp + i], its beta row i B + b
+template <bool kPit = false>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__ x, long st, long sb,
                                                        const int* __restrict__ ilen, const int* __restrict__ lab,
                                                        const int* __restrict__ lablen, int Lmax,
@@ -213,27 +241,34 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
                                                        const float* __restrict__ alpha,
                                                        const float* __restrict__ beta, const float* __restrict__ nll,
                                                        float* __restrict__ grad, long gst, long gsb, int T, int V,
-                                                       int Smax, int blank, float scale) {
+                                                       int Smax, int blank, float scale, long si = 0, long gsi = 0,
+                                                       int nsp = 1, const long long* __restrict__ perm = nullptr) {
   extern __shared__ float occ[];  // [V]
   const int t = blockIdx.x, b = blockIdx.y;
-  float* gr = grad + t * gst + b * gsb;
+  const int i = kPit ? (int)blockIdx.z : 0;
+  float* gr = grad + t * gst + b * gsb + (kPit ? i * gsi : 0);
   if (t >= ilen[b]) {
     for (int v = threadIdx.x; v < V; v += blockDim.x) gr[v] = 0.f;
     return;
   }
   for (int v = threadIdx.x; v < V; v += blockDim.x) occ[v] = 0.f;
   __syncthreads();
-  const int S = 2 * lablen[b] + 1;
-  const long base = ((long)b * T + t) * Smax;
-  const float nl = nll[b];
+  const long q = kPit ? (long)i * gridDim.y + b : b;                   // row set (speaker, utterance), beta row
+  const int j = kPit ? (int)perm[(long)b * nsp + i] : 0;
+  const int r = kPit ? b * nsp + j : b;                                // label row
+  const long lat = kPit ? q * nsp + j : b;                             // lattice (lp, alpha)
+  const int S = 2 * lablen[r] + 1;
+  const long base = (lat * T + t) * Smax;
+  const long bbase = (q * T + t) * Smax;
+  const float nl = nll[kPit ? ((long)b * nsp + i) * nsp + j : b];
   for (int s = threadIdx.x; s < S; s += blockDim.x) {
-    int l = (s & 1) ? lab[(long)b * Lmax + (s >> 1)] : blank;
-    float g = expf(alpha[base + s] + beta[base + s] - lp[base + s] + nl);
+    int l = (s & 1) ? lab[(long)r * Lmax + (s >> 1)] : blank;
+    float g = expf(alpha[base + s] + beta[bbase + s] - lp[base + s] + nl);
     atomicAdd(&occ[l], g);
   }
   __syncthreads();
-  const float* xr = x + t * st + b * sb;
-  const float ls = lse[(long)b * T + t];
+  const float* xr = x + t * st + b * sb + (kPit ? i * si : 0);
+  const float ls = lse[q * T + t];
   for (int v = threadIdx.x; v < V; v += blockDim.x) gr[v] = (expf(xr[v] - ls) - occ[v]) * scale;
 }
 
@@ -279,15 +314,130 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
   hipLaunchKernelGGL(ctc_prep_kernel, dim3(B), dim3(64), 0, s, (const long long*)ys_pad, Lmax, ignore_id, lab, lablen, B);
   EAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL((ctc_lse_gather_kernel<false, false>), dim3(T, B), dim3(256), 0, s, acts, (long)stride_t, (long)stride_b, ilens,
-                     lab, lablen, Lm, lse, lp, T, V, Smax, blank);
+                     lab, lablen, Lm, lse, lp, T, V, Smax, blank, 0L, 1);
   EAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3(B, 2), dim3(threads), 2 * (Smax + 4) * sizeof(float), s, lp, ilens,
-                     lab, lablen, Lm, alpha, beta, nll, T, Smax, blank);
+  hipLaunchKernelGGL(ctc_alpha_beta_kernel<kCtcLoss>, dim3(B, 2), dim3(threads), 2 * (Smax + 4) * sizeof(float), s, lp, ilens,
+                     lab, lablen, Lm, alpha, beta, nll, T, Smax, blank, 1, 1, nullptr);
   EAMD_LAUNCH_CHECK();
   if (grad) {
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3(T, B), dim3(256), (size_t)V * sizeof(float), s, acts, (long)stride_t,
+    hipLaunchKernelGGL(ctc_grad_kernel<false>, dim3(T, B), dim3(256), (size_t)V * sizeof(float), s, acts, (long)stride_t,
                        (long)stride_b, ilens, lab, lablen, Lm, lse, lp, alpha, beta, nll, grad, (long)gstride_t,
-                       (long)gstride_b, T, V, Smax, blank, grad_scale);
+                       (long)gstride_b, T, V, Smax, blank, grad_scale, 0L, 0L, 1, nullptr);
+    EAMD_LAUNCH_CHECK();
+  }
+  return EAMD_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Permutation-invariant CTC of S = 2 or 3 speakers (PIT).  reference: e2e_asr_mix_transformer.py:116-135 (S^2 CTC calls, each
+// with its own log-softmax of the same speaker's logits), e2e_asr_mix.py:48-108 (PIT: the best permutation per utterance, on
+// the host).  Here five launches on the caller's stream, no host synchronisation:
+//   prep       : ctc_prep_kernel over the B S label rows (ys_pad [B, S, Lmax] is B S rows of Lmax)
+//   lse_gather : ctc_lse_gather_kernel<kPit>, one block per (t, b, i): the log-softmax of the row once, the 2L+1 emissions of each
+//                of the S label sets
+//   alpha      : ctc_alpha_beta_kernel<kPitAlpha>, one block per lattice (i, b, j): B S^2 scans in one launch
+//   select     : ctc_pit_select_kernel, one thread per utterance: the S! permutation scores, perm and pit
+//   beta, grad : ctc_alpha_beta_kernel<kPitBeta> and ctc_grad_kernel<kPit> for the B S lattices kept
+// ---------------------------------------------------------------------------------------------
+namespace {
+// the reference's PIT.permutationDFS order (swap-based depth first search, not lexicographic)
+__constant__ int kPitPerm2[2][2] = {{0, 1}, {1, 0}};
+__constant__ int kPitPerm3[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 1, 0}, {2, 0, 1}};
+
+// PIT.min_pit_sample in its fp32 arithmetic: score(p) = (sum_i in order (nll[i, p[i]] / B)) / S, the first minimum wins (torch.min)
+template <int NS>
+__global__ __launch_bounds__(64) void ctc_pit_select_kernel(const float* __restrict__ nll, long long* __restrict__ perm,
+                                                            float* __restrict__ pit, int B) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  constexpr int NP = NS == 2 ? 2 : 6;
+  const float* n = nll + (long)b * NS * NS;
+  const float fb = (float)B;
+  float best = 0.f;
+  int arg = -1;
+  for (int k = 0; k < NP; ++k) {
+    float sc = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int j = NS == 2 ? kPitPerm2[k][i] : kPitPerm3[k][i];
+      const float v = n[i * NS + j] / fb;
+      sc = i == 0 ? v : sc + v;
+    }
+    sc = sc / (float)NS;
+    if (arg < 0 || sc < best || (sc != sc && best == best)) { best = sc; arg = k; }     // NaN propagates, as torch.min
+  }
+#pragma unroll
+  for (int i = 0; i < NS; ++i) perm[(long)b * NS + i] = NS == 2 ? kPitPerm2[arg][i] : kPitPerm3[arg][i];
+  pit[b] = best;
+}
+}  // namespace
+
+extern "C" {
+
+/* workspace bytes needed by eamd_ctc_pit_loss */
+int64_t eamd_ctc_pit_workspace_bytes(int S, int B, int T, int Lmax) {
+  const int64_t Lm = Lmax > 0 ? Lmax : 1;
+  const int64_t Smax = 2 * (int64_t)Lmax + 1;
+  const int64_t R = (int64_t)B * S;                                  /* label rows, (speaker, utterance) row sets */
+  return R * Lm * 4 + R * 4 + 16                                     /* lab, lablen (+ alignment) */
+         + R * T * 4                                                 /* lse */
+         + 2 * R * S * T * Smax * 4                                  /* lp, alpha of the B S^2 lattices */
+         + R * T * Smax * 4                                          /* beta of the B S kept */
+         + 256;
+}
+
+/*
+ * acts    : [S, B, T, V] fp32 raw activations (speaker-major, V contiguous); ys_pad [B, S, Lmax] int64 padded with ignore_id;
+ * ilens   : [B] int32 (the frames of every speaker of utterance b)
+ * nll_pair: [B, S, S] out, -log p of hypothesis i against reference j (+inf where infeasible)
+ * perm    : [B, S] int64 out, the reference assigned to hypothesis i;  pit: [B] out, the chosen permutation's score
+ * grad    : optional [S, B, T, V] = grad_scale * d(sum_b sum_i nll_pair[b, i, perm[b, i]]) / d acts (zero past ilens)
+ */
+int eamd_ctc_pit_loss(const float* acts, const int64_t* ys_pad, const int32_t* ilens, float* nll_pair, int64_t* perm, float* pit,
+                      float* grad, void* workspace, int S, int B, int T, int V, int Lmax, int blank, int ignore_id, float grad_scale,
+                      void* stream) {
+  if (!acts || !ys_pad || !ilens || !nll_pair || !perm || !pit || !workspace || B <= 0 || T <= 0 || V <= 0 || Lmax < 0)
+    return EAMD_EINVAL;
+  if (S != 2 && S != 3) return EAMD_EUNSUPPORTED;
+  const int Smax = 2 * Lmax + 1;
+  const int threads = ((Smax + 63) / 64) * 64;
+  if (threads > 1024) return EAMD_EUNSUPPORTED;
+  if (grad && (size_t)V * 4 > 64 * 1024) return EAMD_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int Lm = Lmax > 0 ? Lmax : 1;
+  const size_t R = (size_t)B * S;
+  char* w = (char*)workspace;
+  int* lab = (int*)w; w += R * Lm * 4;
+  int* lablen = (int*)w; w += R * 4;
+  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
+  float* lse = (float*)w; w += R * T * 4;
+  float* lp = (float*)w; w += R * S * T * Smax * 4;
+  float* alpha = (float*)w; w += R * S * T * Smax * 4;
+  float* beta = (float*)w;
+  const long sb = (long)T * V, si = (long)B * T * V;
+
+  hipLaunchKernelGGL(ctc_prep_kernel, dim3(R), dim3(64), 0, s, (const long long*)ys_pad, Lmax, ignore_id, lab, lablen, (int)R);
+  EAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL((ctc_lse_gather_kernel<false, false, true>), dim3(T, B, S), dim3(256), 0, s, acts, (long)V, sb, ilens, lab,
+                     lablen, Lm, lse, lp, T, V, Smax, blank, si, S);
+  EAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ctc_alpha_beta_kernel<kPitAlpha>, dim3(R * S), dim3(threads), 2 * (Smax + 4) * sizeof(float), s, lp, ilens,
+                     lab, lablen, Lm, alpha, beta, nll_pair, T, Smax, blank, B, S, nullptr);
+  EAMD_LAUNCH_CHECK();
+  if (S == 2)
+    hipLaunchKernelGGL(ctc_pit_select_kernel<2>, dim3((B + 63) / 64), dim3(64), 0, s, nll_pair, (long long*)perm, pit, B);
+  else
+    hipLaunchKernelGGL(ctc_pit_select_kernel<3>, dim3((B + 63) / 64), dim3(64), 0, s, nll_pair, (long long*)perm, pit, B);
+  EAMD_LAUNCH_CHECK();
+  if (grad) {
+    hipLaunchKernelGGL(ctc_alpha_beta_kernel<kPitBeta>, dim3(R), dim3(threads), 2 * (Smax + 4) * sizeof(float), s, lp, ilens,
+                       lab, lablen, Lm, alpha, beta, nll_pair, T, Smax, blank, B, S, (const long long*)perm);
+    EAMD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctc_grad_kernel<true>, dim3(T, B, S), dim3(256), (size_t)V * sizeof(float), s, acts, (long)V, sb, ilens,
+                       lab, lablen, Lm, lse, lp, alpha, beta, nll_pair, grad, (long)V, sb, T, V, Smax, blank, grad_scale, si, si,
+                       S, (const long long*)perm);
     EAMD_LAUNCH_CHECK();
   }
   return EAMD_OK;
@@ -488,10 +638,10 @@ int eamd_ctc_forced_align(const float* acts, int64_t stride_t, int64_t stride_b,
   EAMD_LAUNCH_CHECK();
   if (normalized)
     hipLaunchKernelGGL((ctc_lse_gather_kernel<true, true>), dim3(T, B), dim3(256), 0, s, acts, (long)stride_t, (long)stride_b, ilens,
-                       lab, lablen, Lm, nullptr, lp, T, V, Spad, blank);
+                       lab, lablen, Lm, nullptr, lp, T, V, Spad, blank, 0L, 1);
   else
     hipLaunchKernelGGL((ctc_lse_gather_kernel<false, true>), dim3(T, B), dim3(256), 0, s, acts, (long)stride_t, (long)stride_b, ilens,
-                       lab, lablen, Lm, lse, lp, T, V, Spad, blank);
+                       lab, lablen, Lm, lse, lp, T, V, Spad, blank, 0L, 1);
   EAMD_LAUNCH_CHECK();
   hipLaunchKernelGGL(ctc_viterbi_kernel, dim3(B), dim3(threads), 0, s, lp, ilens, lab, lablen, Lm, Lmax, bp, score, endst, states,
                      (long long*)tokens, seg_start, seg_end, T, Spad, blank);

@@ -1393,6 +1393,45 @@ class CTCLossFn(torch.autograd.Function):
         return ops.scale_dev(grad, g.contiguous(), 1.0, out=grad), None, None, None, None, None
 
 
+class CTCRowsLossFn(torch.autograd.Function):
+    """the per-utterance vector -log p(y_b | x_b) / B on raw activations [B, T, V] (reference: ctc.py:53-61 with
+    reduction="none", CTC(reduce=False)); backward scales each utterance's rows by its own upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, acts, ys_pad, hlens, blank, ignore_id):
+        B = acts.shape[0]
+        nll, grad = ops.ctc_loss(acts.contiguous(), ys_pad, hlens, blank, ignore_id, 1.0 / B, want_grad=acts.requires_grad)
+        ctx.save_for_backward(grad)
+        return nll / B
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g.view(-1, 1, 1), None, None, None, None
+
+
+class CTCPITLossFn(torch.autograd.Function):
+    """permutation-invariant CTC (reference: e2e_asr_mix_transformer.py:116-135 with PIT.pit_process, e2e_asr_mix.py:71-108):
+    acts [S, B, T, V] raw activations of the S speakers, ys_pad [B, S, L] -> (loss_ctc = mean_b pit[b], perm [B, S]).
+    `record` (a dict, may be None) receives the pair matrix nll_pair [B, S, S] and pit [B]."""
+
+    @staticmethod
+    def forward(ctx, acts, ys_pad, hlens, blank, ignore_id, record=None):
+        S, B = acts.shape[:2]
+        nll, perm, pit, grad = ops.ctc_pit_loss(acts.contiguous(), ys_pad, hlens, blank, ignore_id, 1.0 / (S * B * B),
+                                                want_grad=acts.requires_grad)
+        if record is not None:
+            record.update(nll_pair=nll, pit=pit)
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(perm)
+        return ops.reduce_sum(pit, 1.0 / B), perm
+
+    @staticmethod
+    def backward(ctx, g, _gp):
+        (grad,) = ctx.saved_tensors
+        return ops.scale_dev(grad, g.contiguous(), 1.0, out=grad), None, None, None, None, None
+
+
 class LabelSmoothingLossFn(torch.autograd.Function):
     """reference: transformer/label_smoothing_loss.py:44-63 (normalize_length=False => / batch)."""
 

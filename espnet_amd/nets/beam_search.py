@@ -828,6 +828,20 @@ def recognize_beam(model, enc_output, recog_args, char_list=None, rnnlm=None):
     """E2E.recognize for ctc_weight < 1 (reference: e2e_asr_transformer.py:286-477 / asr/pytorch_backend/recog.py).
     rnnlm: any BatchScorerInterface language model, fused with weight recog_args.lm_weight.
     Returns [{"score": float, "yseq": [int]}] n-best, yseq starts with <sos> and ends with <eos>."""
+    bs = _recog_searcher(model, recog_args, rnnlm)
+    hyps = bs(enc_output, float(getattr(recog_args, "maxlenratio", 0.0)), float(getattr(recog_args, "minlenratio", 0.0)))
+    return _nbest(hyps, recog_args)
+
+
+def recognize_beam_batch(model, enc_outputs, recog_args, char_list=None, rnnlm=None):
+    """recognize_beam for several encoder outputs (list of (T_u, D)) in one BeamSearch.forward_batch -> one n-best list each"""
+    bs = _recog_searcher(model, recog_args, rnnlm)
+    out = bs.forward_batch(list(enc_outputs), float(getattr(recog_args, "maxlenratio", 0.0)),
+                           float(getattr(recog_args, "minlenratio", 0.0)))
+    return [_nbest(hyps, recog_args) for hyps in out]
+
+
+def _recog_searcher(model, recog_args, rnnlm):
     ctc_weight = float(getattr(recog_args, "ctc_weight", 0.0))
     if model.ctc is None:
         ctc_weight = 0.0
@@ -836,9 +850,11 @@ def recognize_beam(model, enc_output, recog_args, char_list=None, rnnlm=None):
                    length_bonus=float(getattr(recog_args, "penalty", 0.0)))
     scorers = dict(decoder=model.decoder, ctc=CTCPrefixScorer(model.ctc, model.eos) if ctc_weight > 0 else None,
                    lm=rnnlm, length_bonus=LengthBonus(model.odim))
-    bs = BeamSearch(scorers, weights, int(recog_args.beam_size), model.odim, model.sos, model.eos,
-                    pre_beam_score_key=None if ctc_weight == 1.0 else "full")
-    hyps = bs(enc_output, float(getattr(recog_args, "maxlenratio", 0.0)), float(getattr(recog_args, "minlenratio", 0.0)))
+    return BeamSearch(scorers, weights, int(recog_args.beam_size), model.odim, model.sos, model.eos,
+                      pre_beam_score_key=None if ctc_weight == 1.0 else "full")
+
+
+def _nbest(hyps, recog_args):
     nbest = int(getattr(recog_args, "nbest", 1))
     return [{"score": float(h.score), "yseq": [int(t) for t in h.yseq], "scores": h.scores} for h in hyps[:nbest]]
 

@@ -1246,7 +1246,7 @@ class CTCAlignment(NamedTuple):
 class CTC(torch.nn.Module):
     """reference: ctc.py:12-151 (espnet1) / espnet2/asr/ctc.py:6-111.
     ctc_type is accepted for interface parity ("warpctc" and "builtin" compute the same quantity:
-    sum_b -log p / B); both run the espnet_amd HIP kernel."""
+    sum_b -log p / B); both run the espnet_amd HIP kernel.  reduce=False: forward returns the vector -log p_b / B."""
 
     def __init__(self, odim, eprojs, dropout_rate, ctc_type="warpctc", reduce=True):
         super().__init__()
@@ -1260,8 +1260,6 @@ class CTC(torch.nn.Module):
         self.ignore_id = -1
         self.reduce = reduce
         self.salt = ops.new_salt()
-        if not reduce:
-            raise NotImplementedError("reduce=False is not on the path")
 
     def logits(self, hs_pad, loss_path=False):
         if loss_path:   # ctc.py:85: F.dropout(hs_pad, p) without `training=` => active in eval mode too
@@ -1277,8 +1275,32 @@ class CTC(torch.nn.Module):
             hl = ops.h2d_cached("ctclens", np.asarray([int(v) for v in hlens], dtype=np.int32), hs_pad.device)
         if not ys_pad.is_cuda:     # host labels (kept on the host for the decoder's label parsing): cached upload
             ys_pad = ops.h2d_cached("ctc_ys", ys_pad.numpy(), hs_pad.device)
-        self.loss = F_.CTCLossFn.apply(ys_hat, ys_pad.contiguous(), hl, 0, self.ignore_id)
+        if not self.reduce:
+            self.loss = F_.CTCRowsLossFn.apply(ys_hat, ys_pad.contiguous(), hl, 0, self.ignore_id)
+        else:
+            self.loss = F_.CTCLossFn.apply(ys_hat, ys_pad.contiguous(), hl, 0, self.ignore_id)
         return self.loss
+
+    def pit_loss(self, hs_list, hlens, ys_pad, record=None):
+        """permutation-invariant CTC of S speakers (reference: e2e_asr_mix_transformer.py:116-135 + PIT.pit_process).
+        hs_list: the S encoder outputs (B,T,D) as a list, or one (S,B,T,D) tensor; hlens [B] valid frames (every speaker's);
+        ys_pad (B,S,L) int64 padded with -1 -> (loss_ctc = mean_b of the best permutation's score, perm (B,S) device int64:
+        the reference assigned to hypothesis i).  Dropout draws one mask per speaker (the reference draws one per CTC call, S^2),
+        then one output-layer GEMM over the S B rows and one eamd_ctc_pit_loss."""
+        hs = hs_list if torch.is_tensor(hs_list) else torch.stack(list(hs_list))
+        S, B = hs.shape[:2]
+        dev = hs.device
+        if isinstance(hlens, torch.Tensor):
+            hl = hlens.to(device=dev, dtype=torch.int32)
+        else:
+            hl = ops.h2d_cached("ctclens", np.asarray([int(v) for v in hlens], dtype=np.int32), dev)
+        if not ys_pad.is_cuda:
+            ys_pad = ops.h2d_cached("ctc_ys", ys_pad.numpy(), dev)
+        ys_hat = self.logits(hs.reshape(S * B, hs.shape[2], hs.shape[3]), loss_path=True)
+        loss, perm = F_.CTCPITLossFn.apply(ys_hat.view(S, B, ys_hat.shape[1], ys_hat.shape[2]), ys_pad.contiguous(),
+                                           hl.contiguous(), 0, self.ignore_id, record)
+        self.loss = loss
+        return loss, perm
 
     def softmax(self, hs_pad):
         lp = self.log_softmax(hs_pad)

@@ -1858,6 +1858,27 @@ def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, wan
     return nll, grad
 
 
+def ctc_pit_loss(acts, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True):
+    """permutation-invariant CTC of S = 2 or 3 speakers (eamd_ctc_pit_loss): acts [S,B,T,V] raw activations, ys_pad [B,S,L] int64
+    padded with ignore_id, ilens [B] int32 -> nll_pair [B,S,S] (-log p of hypothesis i against reference j), perm [B,S] int64
+    (the reference assigned to hypothesis i), pit [B] (the chosen permutation's score, (sum_i nll_pair[b,i,perm]/B)/S), grad
+    [S,B,T,V] = grad_scale * d(sum_b sum_i nll_pair[b,i,perm[b,i]])/d acts (None unless want_grad).  No host synchronisation."""
+    S, B, T, V = acts.shape
+    L = ys_pad.shape[2]
+    assert acts.is_contiguous() and acts.dtype == torch.float32
+    assert ys_pad.is_contiguous() and ys_pad.dtype == torch.int64 and tuple(ys_pad.shape[:2]) == (B, S)
+    assert ilens.dtype == torch.int32 and ilens.numel() == B
+    dev = acts.device
+    ws = torch.empty(_lib.lib().eamd_ctc_pit_workspace_bytes(S, B, T, L), device=dev, dtype=torch.uint8)
+    nll = torch.empty(B, S, S, device=dev, dtype=torch.float32)
+    perm = torch.empty(B, S, device=dev, dtype=torch.int64)
+    pit = torch.empty(B, device=dev, dtype=torch.float32)
+    grad = torch.empty_like(acts) if want_grad else None
+    check(_lib.lib().eamd_ctc_pit_loss(ptr(acts), ptr(ys_pad), ptr(ilens), ptr(nll), ptr(perm), ptr(pit), ptr(grad), ptr(ws), S, B,
+                                       T, V, L, blank, ignore_id, C.c_float(grad_scale), stream_ptr()), "eamd_ctc_pit_loss")
+    return nll, perm, pit, grad
+
+
 def ctc_forced_align(acts, ilens, ys_pad, blank=0, ignore_id=-1, normalized=False, time_major=False):
     """best CTC path of each utterance (eamd_ctc_forced_align): acts [B,T,V] raw activations, or log-probabilities when
     normalized (time_major: [T,B,V]); ilens [B] int32; ys_pad [B,L] int64 padded with ignore_id

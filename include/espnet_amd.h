@@ -628,6 +628,18 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
                   void* workspace, int B, int T, int V, int Lmax, int blank, int ignore_id, float grad_scale,
                   void* stream);
 
+/* Permutation-invariant CTC of S = 2 or 3 speakers (PIT).  reference: e2e_asr_mix_transformer.py:116-135, e2e_asr_mix.py:48-108.
+ * acts [S,B,T,V] fp32 raw activations (speaker-major, V contiguous); ys_pad [B,S,Lmax] int64 padded with ignore_id; ilens [B] int32
+ * (shared by the speakers of an utterance).  nll_pair [B,S,S] = -log p of hypothesis i against reference j (+inf if infeasible);
+ * perm [B,S] int64 = the reference assigned to hypothesis i by the permutation of least (sum_i (nll_pair[b,i,perm]/B))/S (the
+ * reference's depth-first permutation order, first minimum); pit [B] = that score.  grad: optional [S,B,T,V] = grad_scale *
+ * d(sum_b sum_i nll_pair[b,i,perm[b,i]])/d(acts), zero for t >= ilens[b].  Other S: EAMD_EUNSUPPORTED; Lmax and V as
+ * eamd_ctc_loss.  workspace: eamd_ctc_pit_workspace_bytes(S, B, T, Lmax) bytes. */
+int64_t eamd_ctc_pit_workspace_bytes(int S, int B, int T, int Lmax);
+int eamd_ctc_pit_loss(const float* acts, const int64_t* ys_pad, const int32_t* ilens, float* nll_pair, int64_t* perm, float* pit,
+                      float* grad, void* workspace, int S, int B, int T, int V, int Lmax, int blank, int ignore_id, float grad_scale,
+                      void* stream);
+
 /* CTC forced alignment: the best (Viterbi) CTC path of each utterance through its labels.  reference: ctc.py:153-216
  * (CTC.forced_align: one utterance; same recursion, fp32 scores and first-maximum tie-break).  acts, ys_pad, ilens, blank,
  * ignore_id as eamd_ctc_loss; normalized != 0: acts rows already are log-probabilities (no log-softmax).  Outputs:

@@ -23,6 +23,7 @@ for t in "$@"; do
     search) run test_search python -m pytest tests/test_gpu_transducer_search.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     align) run test_align python -m pytest tests/test_gpu_ctc_align.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     maskctc) run test_maskctc python -m pytest tests/test_gpu_maskctc.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
+    mix)   run test_mix python -m pytest tests/test_gpu_asr_mix.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     rnnt)  run test_rnnt python -m pytest tests/test_gpu_transducer_loss.py -m gpu -q -s --tb=short -p no:cacheprovider ;;
     smoke) run smoke python -c "import __graft_entry__ as g; g.smoke()" ;;
     bench) run bench python bench.py --steps 5 --warmup 2 --full ;;
