@@ -675,89 +675,77 @@ __device__ __forceinline__ float lae(float a, float b) {
   const float l = e < 2.44140625e-4f ? e * (1.f - 0.5f * e) : __logf(1.f + e);
   return m + l;
 }
-__global__ void ctc_prefix_kernel(const float* __restrict__ logp, const float* __restrict__ r_prev,
-                                  const int* __restrict__ cand, const int* __restrict__ last,
-                                  const int* __restrict__ olen, float* __restrict__ psi, float* __restrict__ r_new,
-                                  int T, int V, int ncand, int blank, int eos) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  const int h = blockIdx.y;
-  if (j >= ncand) return;
-  const int c = cand[(long)h * ncand + j];
-  // a candidate outside the vocabulary is never dereferenced: its score is NaN (a selection treats NaN as -inf), its state untouched
-  if (c < 0 || c >= V) { psi[(long)h * ncand + j] = __builtin_nanf(""); return; }
-  const float* rp = r_prev + (long)h * T * 2;
-  float* rn = r_new + ((long)h * ncand + j) * T * 2;
-  const int ol = min(max(olen[h], 0), T);
-  const bool same = ol > 0 && last[h] == c;
+// The frame-by-frame recursion of one (prefix, token) pair, written ONCE for every kernel that walks it: rp = (r^n, r^b) of the
+// prefix, rn = those of prefix + c; ol = prefix length - 1, already clamped to 0 .. T; same = c repeats the prefix's last token.
+// Returns log psi before the <eos> / blank fix-up (a caller that only wants the state drops it, and its log-add chain with it).
+// NB = groups of PF frames in flight.  With one group phi is formed as the rows arrive, so a group holds it instead of the two
+// rows it is made of (8 registers less); with the ring it is formed when the group is walked.
+template <int NB>
+__device__ __forceinline__ float ctc_prefix_recursion(const float* __restrict__ logp, const float* __restrict__ rp,
+                                                      float* __restrict__ rn, int T, int V, int c, int blank, int ol, bool same) {
+  __builtin_assume(T > 0 && V > 0);      // (every caller has checked or clamped them: row offsets t * V stay one scalar multiply)
   const int start = max(ol, 1);
   // rows before start-1 are never read by later steps; keep them at log-zero like the reference's r
-  for (int t = 0; t < start - 1; ++t) { rn[2 * t] = kLogZero; rn[2 * t + 1] = kLogZero; }
-  float rn_n, rn_b;
-  if (ol == 0) { rn_n = logp[c]; rn_b = kLogZero; }
-  else { rn_n = kLogZero; rn_b = kLogZero; }
-  rn[2 * (start - 1)] = rn_n; rn[2 * (start - 1) + 1] = rn_b;
+  for (int t = 0; t < min(start - 1, T); ++t) *reinterpret_cast<float2*>(rn + 2 * t) = make_float2(kLogZero, kLogZero);
+  float rn_n = ol == 0 ? logp[c] : kLogZero, rn_b = kLogZero;
+  if (start - 1 < T) *reinterpret_cast<float2*>(rn + 2 * (start - 1)) = make_float2(rn_n, rn_b);
   float lpsi = rn_n;
   // the recursion over t is serial, its operands are not: the posteriors and the previous prefix's rows of the next PF frames
   // are requested together (each logp row is its own cache line, 20 KB apart: fetched inside the chain every frame cost a
-  // memory round trip - 344 us for 249 frames), phi is formed beside them, and only the log-add chain stays serial.
-  // Same operations in the same order as the frame-by-frame loop: results bit for bit.
+  // memory round trip - 344 us for 249 frames), and only the log-add chain stays serial.
+  // Same operations in the same order as a plain loop over the frames: results bit for bit.
   // ... and a RING of NB such groups is kept in flight (the group NB - 1 ahead is requested before the current one is walked).
   // Measured at config 2 (249 frames, 10 hypotheses x 15 candidates): 152 us with one group in flight, 157 us with the ring and
   // 8-byte state stores - neither the round trips nor the stores bound this kernel: it is ONE wave per hypothesis walking a
   // dependent chain of ~60 VALU + 8 transcendental instructions per frame with nothing else on its SIMD (0.6 us per frame).
-  constexpr int PF = 8, NB = 4;
-  float xv[NB][PF], bv[NB][PF], pn[NB][PF], pb[NB][PF];
-  auto request = [&](auto slot_c, int t0) __attribute__((always_inline)) {
-    constexpr int SL = decltype(slot_c)::value;
+  constexpr int PF = 8;
+  constexpr bool kPhiOnArrival = NB == 1;
+  float xv[NB][PF], bv[NB][PF], pn[NB][PF], pb[NB][PF];      // slots are indexed by unrolled constants only: registers
+  auto phi_of = [&](float n_, float b_) __attribute__((always_inline)) { return same ? b_ : lae(n_, b_); };
+  auto request = [&](int sl, int t0) __attribute__((always_inline)) {
 #pragma unroll
     for (int q = 0; q < PF; ++q) {
       const int t = min(max(t0 + q, 1), T - 1);          // (frames behind the end: the last one again; T = 1: frame 0, never walked)
       const int tp = max(t - 1, 0);
-      xv[SL][q] = logp[(long)t * V + c];
-      bv[SL][q] = logp[(long)t * V + blank];
-      pn[SL][q] = rp[2 * tp];
-      pb[SL][q] = rp[2 * tp + 1];
+      xv[sl][q] = logp[(long)t * V + c];
+      bv[sl][q] = logp[(long)t * V + blank];
+      pn[sl][q] = rp[2 * tp];
+      pb[sl][q] = rp[2 * tp + 1];
+      if (kPhiOnArrival) pb[sl][q] = phi_of(pn[sl][q], pb[sl][q]);      // (pn is then dead)
     }
   };
-  auto walk = [&](auto slot_c, int t0) __attribute__((always_inline)) {
-    constexpr int SL = decltype(slot_c)::value;
+  auto walk = [&](int sl, int t0) __attribute__((always_inline)) {
 #pragma unroll
     for (int q = 0; q < PF; ++q) {
       const int t = t0 + q;
       if (t < T) {
-        const float phi = same ? pb[SL][q] : lae(pn[SL][q], pb[SL][q]);
-        const float nn = lae(rn_n, phi) + xv[SL][q];
-        const float nb = lae(rn_n, rn_b) + bv[SL][q];
-        lpsi = lae(lpsi, phi + xv[SL][q]);
+        const float phi = kPhiOnArrival ? pb[sl][q] : phi_of(pn[sl][q], pb[sl][q]);
+        const float nn = lae(rn_n, phi) + xv[sl][q];
+        const float nb = lae(rn_n, rn_b) + bv[sl][q];
+        lpsi = lae(lpsi, phi + xv[sl][q]);
         rn_n = nn; rn_b = nb;
         *reinterpret_cast<float2*>(rn + 2 * t) = make_float2(nn, nb);        // one 8-byte store per frame
       }
     }
   };
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  using S2 = std::integral_constant<int, 2>;
-  using S3 = std::integral_constant<int, 3>;
-  request(S0{}, start);
-  request(S1{}, start + PF);
-  request(S2{}, start + 2 * PF);
-  for (int t0 = start; t0 < T; t0 += NB * PF) {
-    request(S3{}, t0 + 3 * PF);
-    walk(S0{}, t0);
-    request(S0{}, t0 + 4 * PF);
-    walk(S1{}, t0 + PF);
-    request(S1{}, t0 + 5 * PF);
-    walk(S2{}, t0 + 2 * PF);
-    request(S2{}, t0 + 6 * PF);
-    walk(S3{}, t0 + 3 * PF);
+  if constexpr (NB == 1) {      // (spelled out: as a ring of one the same loop is allocated 7 registers more)
+    for (int t0 = start; t0 < T; t0 += PF) { request(0, t0); walk(0, t0); }
+  } else {
+#pragma unroll
+    for (int k = 0; k < NB - 1; ++k) request(k, start + k * PF);
+    for (int t0 = start; t0 < T; t0 += NB * PF) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) {
+        request((k + NB - 1) % NB, t0 + (k + NB - 1) * PF);
+        walk(k, t0 + k * PF);
+      }
+    }
   }
-  if (c == eos) lpsi = lae(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
-  if (c == blank) lpsi = kLogZero;
-  psi[(long)h * ncand + j] = lpsi;
+  return lpsi;
 }
-// The same recursion for the hypotheses of SEVERAL utterances in one launch: hypothesis h belongs to utterance h / per_utt,
+// One thread = one (hypothesis, candidate) of SEVERAL utterances in one launch: hypothesis h belongs to utterance h / per_utt,
 // whose posteriors are logp[u] ([Tmax, V], lens[u] valid frames); r_prev / r_new rows are padded to Tmax (rows from lens[u] on
-// are never read).
+// are never read).  lens == nullptr: every utterance has Tmax frames (eamd_ctc_prefix_score: one utterance, per_utt = nhyp).
 __global__ void ctc_prefix_batch_kernel(const float* __restrict__ logp_all, const int* __restrict__ lens, int per_utt,
                                         const float* __restrict__ r_prev, const int* __restrict__ cand,
                                         const int* __restrict__ last, const int* __restrict__ olen, float* __restrict__ psi,
@@ -766,75 +754,14 @@ __global__ void ctc_prefix_batch_kernel(const float* __restrict__ logp_all, cons
   const int h = blockIdx.y;
   if (j >= ncand) return;
   const int u = h / per_utt;
-  const int T = min(max(lens[u], 1), Tmax);                 // a length outside 1 .. Tmax never becomes an address
+  const int T = lens ? min(max(lens[u], 1), Tmax) : Tmax;   // a length outside 1 .. Tmax never becomes an address
   const float* logp = logp_all + (long)u * Tmax * V;
   const int c = cand[(long)h * ncand + j];
+  // a candidate outside the vocabulary is never dereferenced: its score is NaN (a selection treats NaN as -inf), its state untouched
   if (c < 0 || c >= V) { psi[(long)h * ncand + j] = __builtin_nanf(""); return; }
   const float* rp = r_prev + (long)h * Tmax * 2;
-  float* rn = r_new + ((long)h * ncand + j) * Tmax * 2;
   const int ol = min(max(olen[h], 0), T);
-  const bool same = ol > 0 && last[h] == c;
-  const int start = max(ol, 1);
-  for (int t = 0; t < min(start - 1, T); ++t) { rn[2 * t] = kLogZero; rn[2 * t + 1] = kLogZero; }
-  float rn_n, rn_b;
-  if (ol == 0) { rn_n = logp[c]; rn_b = kLogZero; }
-  else { rn_n = kLogZero; rn_b = kLogZero; }
-  if (start - 1 < T) { rn[2 * (start - 1)] = rn_n; rn[2 * (start - 1) + 1] = rn_b; }
-  float lpsi = rn_n;
-  // the recursion over t is serial, its operands are not: the posteriors and the previous prefix's rows of the next PF frames
-  // are requested together (each logp row is its own cache line, 20 KB apart: fetched inside the chain every frame cost a
-  // memory round trip - 344 us for 249 frames), phi is formed beside them, and only the log-add chain stays serial.
-  // Same operations in the same order as the frame-by-frame loop: results bit for bit.
-  // ... and a RING of NB such groups is kept in flight (the group NB - 1 ahead is requested before the current one is walked).
-  // Measured at config 2 (249 frames, 10 hypotheses x 15 candidates): 152 us with one group in flight, 157 us with the ring and
-  // 8-byte state stores - neither the round trips nor the stores bound this kernel: it is ONE wave per hypothesis walking a
-  // dependent chain of ~60 VALU + 8 transcendental instructions per frame with nothing else on its SIMD (0.6 us per frame).
-  constexpr int PF = 8, NB = 4;
-  float xv[NB][PF], bv[NB][PF], pn[NB][PF], pb[NB][PF];
-  auto request = [&](auto slot_c, int t0) __attribute__((always_inline)) {
-    constexpr int SL = decltype(slot_c)::value;
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int t = min(max(t0 + q, 1), T - 1);          // (frames behind the end: the last one again; T = 1: frame 0, never walked)
-      const int tp = max(t - 1, 0);
-      xv[SL][q] = logp[(long)t * V + c];
-      bv[SL][q] = logp[(long)t * V + blank];
-      pn[SL][q] = rp[2 * tp];
-      pb[SL][q] = rp[2 * tp + 1];
-    }
-  };
-  auto walk = [&](auto slot_c, int t0) __attribute__((always_inline)) {
-    constexpr int SL = decltype(slot_c)::value;
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int t = t0 + q;
-      if (t < T) {
-        const float phi = same ? pb[SL][q] : lae(pn[SL][q], pb[SL][q]);
-        const float nn = lae(rn_n, phi) + xv[SL][q];
-        const float nb = lae(rn_n, rn_b) + bv[SL][q];
-        lpsi = lae(lpsi, phi + xv[SL][q]);
-        rn_n = nn; rn_b = nb;
-        *reinterpret_cast<float2*>(rn + 2 * t) = make_float2(nn, nb);        // one 8-byte store per frame
-      }
-    }
-  };
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  using S2 = std::integral_constant<int, 2>;
-  using S3 = std::integral_constant<int, 3>;
-  request(S0{}, start);
-  request(S1{}, start + PF);
-  request(S2{}, start + 2 * PF);
-  for (int t0 = start; t0 < T; t0 += NB * PF) {
-    request(S3{}, t0 + 3 * PF);
-    walk(S0{}, t0);
-    request(S0{}, t0 + 4 * PF);
-    walk(S1{}, t0 + PF);
-    request(S1{}, t0 + 5 * PF);
-    walk(S2{}, t0 + 2 * PF);
-    request(S2{}, t0 + 6 * PF);
-    walk(S3{}, t0 + 3 * PF);
-  }
+  float lpsi = ctc_prefix_recursion<4>(logp, rp, r_new + ((long)h * ncand + j) * Tmax * 2, T, V, c, blank, ol, ol > 0 && last[h] == c);
   if (c == eos) lpsi = lae(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
   if (c == blank) lpsi = kLogZero;
   psi[(long)h * ncand + j] = lpsi;
@@ -894,7 +821,7 @@ __global__ __launch_bounds__(64) void ctc_prefix_psi_kernel(const float* __restr
 }
 
 // forward variables of the surviving continuations: slot s continues the hypothesis of slot parent[s] with token tok[s]; the
-// recursion of ctc_prefix_batch_kernel for that one (hypothesis, candidate) pair, written straight into r_out[s] ([n, Tmax, 2]).
+// recursion (ctc_prefix_recursion) for that one (hypothesis, candidate) pair, written straight into r_out[s] ([n, Tmax, 2]).
 // dead[s] != 0 (an ended or empty slot): the row is filled with log-zero.
 __global__ __launch_bounds__(64) void ctc_prefix_state_kernel(const float* __restrict__ logp_all, const int* __restrict__ lens, int per_utt,
                                                               const float* __restrict__ r_prev, const long long* __restrict__ parent,
@@ -917,35 +844,8 @@ __global__ __launch_bounds__(64) void ctc_prefix_state_kernel(const float* __res
   }
   const float* rp = r_prev + hh * Tmax * 2;
   ol = min(max(ol, 0), T);
-  const bool same = ol > 0 && last[hh] == c;
-  const int start = max(ol, 1);
-  for (int t = 0; t < min(start - 1, T); ++t) *reinterpret_cast<float2*>(rn + 2 * t) = make_float2(kLogZero, kLogZero);
-  float rn_n, rn_b;
-  if (ol == 0) { rn_n = logp[c]; rn_b = kLogZero; }
-  else { rn_n = kLogZero; rn_b = kLogZero; }
-  if (start - 1 < T) *reinterpret_cast<float2*>(rn + 2 * (start - 1)) = make_float2(rn_n, rn_b);
-  constexpr int PF = 8;
-  for (int t0 = start; t0 < T; t0 += PF) {
-    float xv[PF], bv[PF], phi[PF];
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int t = min(t0 + q, T - 1);
-      xv[q] = logp[(long)t * V + c];
-      bv[q] = logp[(long)t * V + blank];
-      const float pn = rp[2 * (t - 1)], pb = rp[2 * (t - 1) + 1];
-      phi[q] = same ? pb : lae(pn, pb);
-    }
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int t = t0 + q;
-      if (t < T) {
-        const float nn = lae(rn_n, phi[q]) + xv[q];
-        const float nb = lae(rn_n, rn_b) + bv[q];
-        rn_n = nn; rn_b = nb;
-        *reinterpret_cast<float2*>(rn + 2 * t) = make_float2(nn, nb);
-      }
-    }
-  }
+  // one group of 8 frames in flight: with the ring of four this kernel would take 128 registers more for its single wave
+  ctc_prefix_recursion<1>(logp, rp, rn, T, V, c, blank, ol, ol > 0 && last[hh] == c);
 }
 
 // The same forward variables as a PARALLEL scan (Tmax <= 2048: 8 / 16 / 32 frames per lane): r^n does not read r^b -
@@ -1104,8 +1004,9 @@ extern "C" int eamd_ctc_prefix_score(const float* logp, const float* r_prev, con
                                      int blank, int eos, void* stream) {
   if (!logp || !r_prev || !cand || !last || !olen || !psi || !r_new || nhyp <= 0 || ncand <= 0 || T <= 0 || V <= 0)
     return EAMD_EINVAL;
-  hipLaunchKernelGGL(ctc_prefix_kernel, dim3((ncand + 63) / 64, nhyp), dim3(64), 0, (hipStream_t)stream, logp, r_prev,
-                     cand, last, olen, psi, r_new, T, V, ncand, blank, eos);
+  // one utterance of T frames whose hypotheses are all its own: no lengths array (nullptr = every utterance fills the buffer)
+  hipLaunchKernelGGL(ctc_prefix_batch_kernel, dim3((ncand + 63) / 64, nhyp), dim3(64), 0, (hipStream_t)stream, logp,
+                     (const int*)nullptr, nhyp, r_prev, cand, last, olen, psi, r_new, T, V, ncand, blank, eos);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }

@@ -259,137 +259,6 @@ class BeamSearch(torch.nn.Module):
             return type(tree)(BeamSearch._tree_index(v, idx) for v in tree)
         raise TypeError(type(tree))
 
-    def _forward_device(self, x, maxlenratio, minlenratio):
-        from .. import ops
-        T, V, n, dev = x.shape[0], self.n_vocab, self.beam_size, x.device
-        maxlen = T if maxlenratio == 0 else max(1, int(maxlenratio * T))
-        NEG = -float("inf")
-        names = list(self.full_scorers.keys())
-        pname = next(iter(self.part_scorers), None)
-        ctc = self.part_scorers[pname] if pname is not None else None
-        allk = names + ([pname] if pname is not None else [])
-        yseq = torch.full((n, maxlen + 2), self.eos, dtype=torch.int64, device=dev)
-        yseq[:, 0] = self.sos
-        hyp = torch.full((n,), NEG, device=dev, dtype=torch.float32)
-        hyp[0] = 0.0
-        sc = {k: torch.zeros(n, device=dev, dtype=torch.float32) for k in allk}
-        trees = {k: None for k in names}
-        for k, d in self.full_scorers.items():       # scorers that prepare per-utterance tensors (none of the tree scorers keeps one)
-            if hasattr(d, "batch_init_state"):
-                d.batch_init_state(x)
-        if ctc is not None:
-            s0, r0 = ctc.init_state(x)
-            c_s = torch.zeros(n, device=dev, dtype=torch.float32)
-            c_r = r0.unsqueeze(0).expand(n, *r0.shape).contiguous()
-        xs = x.unsqueeze(0).expand(n, *x.shape)
-        x1 = x.unsqueeze(0)            # for scorers with shared_memory_ok: ONE memory for the n hypotheses
-        ended, pending, stop_at = [], [], None
-        arange_v = torch.arange(V, device=dev).unsqueeze(0).expand(n, V) if (ctc is not None and not self.do_pre_beam) else None
-
-        def flush():
-            """fetch the logged steps, replay the reference's bookkeeping; returns True when the search is over"""
-            nonlocal pending
-            if not pending:
-                return False
-            host = torch.stack([p for p in pending]).cpu()          # [steps, n, 3 + len(allk) + maxlen + 2]
-            pending = []
-            for row in host:
-                i = int(row[0, 0])
-                alive = 0
-                for slot in row.tolist():
-                    top_s, tok = slot[1], int(slot[2])
-                    if not math.isfinite(top_s):
-                        continue
-                    L = i + 2
-                    seq = [int(v) for v in slot[3 + len(allk): 3 + len(allk) + L]]
-                    if i == maxlen - 1:
-                        seq.append(self.eos)
-                    if seq[-1] == self.eos:
-                        scores = {k: slot[3 + j] for j, k in enumerate(allk)}
-                        if self.apply_final_score:
-                            for k, d in chain(self.full_scorers.items(), self.part_scorers.items()):
-                                f = float(d.final_score(None)) if not hasattr(d, "final_tree") else float(d.final_tree(None))
-                                scores[k] += f
-                                top_s += self.weights[k] * f
-                        ended.append(Hypothesis(yseq=torch.tensor(seq, dtype=torch.int64), score=top_s, scores=scores, states={}))
-                    else:
-                        alive += 1
-                if maxlenratio == 0.0 and end_detect([h.asdict() for h in ended], i):
-                    return True
-                if alive == 0:
-                    return True
-            return False
-
-        with torch.no_grad():
-            for i in range(maxlen):
-                L = i + 1
-                ys = yseq[:, :L]
-                weighted = torch.zeros(n, V, device=dev, dtype=torch.float32)
-                logps, newtrees = {}, {}
-                for k, d in self.full_scorers.items():
-                    logps[k], newtrees[k] = d.score_tree(ys, trees[k], x1 if getattr(d, "shared_memory_ok", False) else xs)
-                    weighted += self.weights[k] * logps[k]
-                part_ids = None
-                if self.do_pre_beam:
-                    pre = weighted if self.pre_beam_score_key == "full" else logps[self.pre_beam_score_key]
-                    part_ids = ops.topk_rows(pre.contiguous(), self.pre_beam_size)[1]
-                if ctc is not None:
-                    last = ys[:, -1].to(torch.int32).contiguous()
-                    olen = torch.full((n,), L - 1, dtype=torch.int32, device=dev)
-                    if self.partial_mode == "full":
-                        ids = part_ids if part_ids is not None else torch.arange(V, device=dev).unsqueeze(0).expand(n, V)
-                        psi, r_new = ops.ctc_prefix_score(ctc.logp, c_r, ids.to(torch.int32).contiguous(), last, olen, ctc.blank, ctc.eos)
-                        full = torch.full((n, V), -10000000000.0, device=dev, dtype=torch.float32)
-                        full.scatter_(1, ids.long(), psi)
-                        full[:, ctc.eos] = torch.logsumexp(c_r[:, -1, :], dim=-1)
-                        full[:, ctc.blank] = -10000000000.0
-                        idmap = torch.full((n, V), -1, dtype=torch.int64, device=dev)
-                        idmap.scatter_(1, ids.long(), torch.arange(ids.shape[1], device=dev).expand(n, -1))
-                        c_local = full - c_s[:, None]
-                        weighted += self.weights[pname] * c_local
-                    else:
-                        ids = part_ids if part_ids is not None else arange_v
-                        psi, r_new = ops.ctc_prefix_score(ctc.logp, c_r, ids.to(torch.int32).contiguous(), last, olen, ctc.blank, ctc.eos)
-                        c_local = psi - c_s[:, None]
-                        if part_ids is not None:
-                            kept = torch.full_like(weighted, NEG)
-                            kept.scatter_(1, ids, torch.gather(weighted, 1, ids) + self.weights[pname] * c_local)
-                            weighted = kept
-                        else:
-                            weighted += self.weights[pname] * c_local
-                weighted += hyp[:, None]
-                s1, i1 = ops.topk_rows(weighted, n)                      # per slot, then among the n x n (see _batch_step)
-                top_s, i2 = (v.view(-1) for v in ops.topk_rows(s1.view(1, n * n), n))
-                top_i = (i2 // n) * V + i1.view(-1)[i2]
-                hyp_i, tok_i = top_i // V, top_i % V
-                for k in names:
-                    sc[k] = sc[k][hyp_i] + logps[k][hyp_i, tok_i]
-                    trees[k] = self._reorder(self.full_scorers[k], newtrees[k], hyp_i)
-                if ctc is not None:
-                    if self.partial_mode == "full":
-                        sc[pname] = sc[pname][hyp_i] + c_local[hyp_i, tok_i]
-                        j = idmap[hyp_i, tok_i].clamp_min(0)
-                        c_s, c_r = full[hyp_i, tok_i], r_new[hyp_i, j]
-                    else:
-                        pos = (ids[hyp_i] == tok_i[:, None]).float().argmax(-1) if part_ids is not None else tok_i
-                        sc[pname] = sc[pname][hyp_i] + c_local[hyp_i, pos]
-                        c_s, c_r = psi[hyp_i, pos], r_new[hyp_i, pos]
-                yseq = yseq.index_select(0, hyp_i)
-                yseq[:, L] = tok_i
-                finite = torch.isfinite(top_s)
-                done = finite & (tok_i == self.eos) if i < maxlen - 1 else finite
-                rec = torch.cat([torch.full((n, 1), float(i), device=dev), top_s[:, None], tok_i[:, None].float()]
-                                + [sc[k][:, None] for k in allk] + [yseq.float()], dim=1)
-                pending.append(rec)
-                hyp = torch.where(done | ~finite, torch.full_like(top_s, NEG), top_s)
-                if len(pending) >= self.sync_every or i == maxlen - 1:
-                    if flush():
-                        break
-        nbest = sorted(ended, key=lambda h: float(h.score), reverse=True)
-        if len(nbest) == 0:
-            return [] if minlenratio < 0.1 else self.forward(x, maxlenratio, max(0.0, minlenratio - 0.1))
-        return nbest
-
     @_inference_call
     def forward_batch(self, xs, maxlenratio=0.0, minlenratio=0.0):
         """Several utterances in ONE search: xs = list of (T_b, D) encoder outputs -> list of n-best lists (what forward() returns for
@@ -398,15 +267,20 @@ class BeamSearch(torch.nn.Module):
         (eamd_ctc_prefix_score_batch), one top-`beam` per utterance - and the host reads the step log once per `sync_every` steps,
         replaying ended-hypothesis bookkeeping and end detection per utterance.  An utterance that has finished keeps its slots (dead)
         until the last one finishes.  Falls back to one forward() per utterance when the scorers cannot keep batched states.
-        With `graph_steps` the steps of a search are hipGraph replays (see _StepGraphs below)."""
-        B = len(xs)
-        if B == 0:
+        With `graph_steps` the steps of a search are hipGraph replays (see _StepGraphs below).
+        minlenratio: the search does not read it (reference beam_search.py:357-360: minlen is only logged); the reference uses it
+        for one rule, "no hypothesis ended: lower the ratio by 0.1 and search again" (:375-390).  The search here is
+        deterministic, so the repeat would end empty again: an utterance whose search ends with no hypothesis returns [] at once.
+        (The host loop of forward() follows the reference's text literally.)"""
+        if len(xs) == 0:
             return []
         from .. import ops
         ops.zero_arena_off()                    # a search never takes slices of a training step's zero arena
-        ok = self._device_loop_ok(xs[0]) and minlenratio == 0.0
-        if not ok:
-            return [self.forward(x, maxlenratio, minlenratio) for x in xs]
+        if not self._device_loop_ok(xs[0]):
+            return [self.forward(x, maxlenratio, minlenratio) for x in xs]          # (the host loop: it never comes back here)
+        return self._search_device(xs, maxlenratio)
+
+    def _search_device(self, xs, maxlenratio):
         try:
             return self._forward_batch(xs, maxlenratio)
         except _OutsideCandidates:
@@ -485,6 +359,23 @@ class BeamSearch(torch.nn.Module):
             S["c_r"] = C_["c_r0"]
         return S
 
+    def _step_plan(self, C_):
+        """which implementation a step of this search takes, from what is known before anything is launched ->
+        (candidates, split, fused): the selection runs on the beam x P pre-beam candidates (_step_candidates) and not on [n, V]
+        tensor expressions (_step_tensors) | the candidates are scored by eamd_ctc_prefix_psi and the survivors' states made by
+        eamd_ctc_prefix_state, not both by the full recursion (more than 2048 frames) | selection and bookkeeping are ONE launch
+        (eamd_beam_step), not eamd_beam_select + eamd_beam_finish"""
+        V, beam, P = C_["V"], C_["beam"], self.pre_beam_size
+        split = self.ctc_psi_parallel and C_["Tpad"] <= 2048
+        fused = self.step_kernel and beam <= 64 and beam * P <= 1023 and beam * V < 2 ** 31 and split
+        # BatchBeamSearch ("full") selects on P + 1 candidates, the pre-beam and <eos>: only with both of the above
+        full_ok = (self.step_kernel and P <= 63 and P + 1 >= beam and beam * (P + 1) <= 1023 and beam <= 64
+                   and beam * V < 2 ** 31 - 1024 and split)
+        candidates = (C_["ctc"] is not None and self.do_pre_beam and (self.partial_mode == "ids" or full_ok)
+                      and self.pre_beam_score_key == "full" and 1 <= len(C_["names"]) <= 4 and V % 4 == 0 and beam * P <= 1024
+                      and self.candidate_select)
+        return candidates, split, fused
+
     def _batch_step(self, i, C_, S, dyn=None):
         """step i of a batched search: state S -> (next state, log row [n, 3 + scorers + W]); no host synchronisation.
         dyn = dict(step=int32 device scalar, step_out=..., ring=[R, n, 3 + scorers + W]): the step index is READ FROM THE DEVICE by
@@ -492,21 +383,21 @@ class BeamSearch(torch.nn.Module):
         (_forward_batch_graphed, graph_one).  Only the candidate-selection path with scorers that take tree["dyn"] runs that way:
         anything else raises _NoDynStep and the caller keeps one graph per step."""
         from .. import ops
-        B, V, beam, n, dev = C_["B"], C_["V"], C_["beam"], C_["n"], C_["dev"]
-        names, pname, ctc, allk = C_["names"], C_["pname"], C_["ctc"], C_["allk"]
-        NEG = -float("inf")
-        L = i + 1
-        yseq, hyp, trees = S["yseq"], S["hyp"], dict(S["trees"])
-        ys = yseq[:, :L] if dyn is None else yseq
-        sdev = dyn["step"] if dyn is not None else None
-        if dyn is not None:
+        n, dev, ctc = C_["n"], C_["dev"], C_["ctc"]
+        plan = self._step_plan(C_)
+        trees = dict(S["trees"])
+        ys = S["yseq"][:, :i + 1] if dyn is None else S["yseq"]
+        if dyn is not None:      # everything that can end a capture of this step, before its first kernel
             if ctc is None or "c_r" not in S or "last32" not in S or "tok" not in S:
                 raise _NoDynStep("state")
-            for k in names:        # the scorers read the newest tokens and the position from device memory
+            for k in C_["names"]:        # the scorers read the newest tokens and the position from device memory
                 if isinstance(trees[k], dict):
-                    trees[k] = dict(trees[k], dyn=(sdev, S["tok"]))
+                    trees[k] = dict(trees[k], dyn=(dyn["step"], S["tok"]))
                 elif not getattr(self.full_scorers[k], "stateless_tree", False):
                     raise _NoDynStep("scorer " + k)
+            for ok, what in zip(plan, ("tensor-expression path", "CTC candidates", "selection kernel")):
+                if not ok:
+                    raise _NoDynStep(what)
         # CTC forward variables of the running hypotheses: ready (first step / the full-recursion path), or still to be made from the
         # previous step's selection - then on a second stream BESIDE the decoder stack below (eamd_ctc_prefix_state: ~160 us of
         # frame-by-frame recursion that nothing in this step needs before the candidates are scored)
@@ -519,9 +410,9 @@ class BeamSearch(torch.nn.Module):
                 side = self._ctc_stream(dev)
                 side.wait_stream(torch.cuda.current_stream(dev))
                 with torch.cuda.stream(side):
-                    ops.ctc_prefix_state(C_["logp"], C_["lens_d"], beam, *pend, ctc.blank, out=c_r_now)
+                    ops.ctc_prefix_state(C_["logp"], C_["lens_d"], C_["beam"], *pend, ctc.blank, out=c_r_now)
             else:
-                ops.ctc_prefix_state(C_["logp"], C_["lens_d"], beam, *pend, ctc.blank, out=c_r_now)
+                ops.ctc_prefix_state(C_["logp"], C_["lens_d"], C_["beam"], *pend, ctc.blank, out=c_r_now)
         logps, newtrees = {}, {}
         for k, d in self.full_scorers.items():
             # scorers that take it get the memory of the B utterances, not of the B * beam slots (shared_memory_ok)
@@ -530,77 +421,84 @@ class BeamSearch(torch.nn.Module):
                 logps[k], newtrees[k] = d.score_tree(ys, trees[k], mem, memory_mask=mm)
             else:
                 logps[k], newtrees[k] = d.score_tree(ys, trees[k], mem)
-        P = self.pre_beam_size
-        full_fast = (self.partial_mode == "full" and self.step_kernel and P <= 63 and P + 1 >= beam and beam * (P + 1) <= 1023
-                     and beam <= 64 and beam * V < 2 ** 31 - 1024
-                     and self.ctc_psi_parallel and C_["Tpad"] <= 2048)
-        if (ctc is not None and self.do_pre_beam and (self.partial_mode == "ids" or full_fast) and self.pre_beam_score_key == "full"
-                and 1 <= len(names) <= 4 and V % 4 == 0 and beam * P <= 1024 and self.candidate_select
-                and all(logps[k].dtype == torch.float32 and logps[k].is_contiguous() for k in names)):
-            # BeamSearch with a pre-beam: the step's selection on the beam x P candidates (csrc/decode.hip: eamd_weighted_sum,
-            # eamd_beam_select) - same scores in the same order of operations as the tensor expressions below, 12 launches fewer
-            # BatchBeamSearch ("full": the partial scorer reports a whole [n, V] row - log-zero outside the pre-beam, <eos> always
-            # scored; nothing is masked): the same selection on P + 1 candidates, the pre-beam and <eos>.  Every other token's
-            # score is ~ -3e9 (weight x log-zero): it can only win where an utterance has fewer live candidates than `beam` -
-            # the host sees that in the step log (a winner below -1e9) and repeats the search on the tensor expressions.
-            if full_fast:
-                pre, part_ids, cand32 = ops.weighted_topk_rows([logps[k] for k in names], [self.weights[k] for k in names], P,
-                                                               extra=ctc.eos)
-            elif self.step_kernel and P <= 64:      # the weighted sum is formed inside the pre-beam's top-k launch
-                pre, part_ids, cand32 = ops.weighted_topk_rows([logps[k] for k in names], [self.weights[k] for k in names], P)
-            else:
-                pre = ops.weighted_sum([logps[k] for k in names], [self.weights[k] for k in names])
-                _, part_ids, cand32 = ops.topk_rows(pre, P, idx32=True)
-            # the newest token of every prefix as int32: the previous step's selection wrote it (eamd_beam_step), <sos> at step 0
-            last = S["last32"] if "last32" in S else (C_["sos32"] if i == 0 else ys[:, -1].to(torch.int32).contiguous())
-            if side is not None:
-                torch.cuda.current_stream(dev).wait_stream(side)
-                side = None
-            psi = ops.ctc_prefix_psi(C_["logp"], C_["lens_d"], beam, c_r_now, cand32, last, L - 1 if dyn is None else 0, ctc.blank, ctc.eos,
-                                     olen_dev=sdev) if self.ctc_psi_parallel else None
-            if dyn is not None and psi is None:
-                raise _NoDynStep("CTC candidates")
-            r_new = None
-            if psi is None:       # more than 2048 frames: the full recursion for every candidate
-                olen = torch.full((n,), L - 1, dtype=torch.int32, device=dev)
-                psi, r_new = ops.ctc_prefix_score_batch(C_["logp"], C_["lens_d"], beam, c_r_now, cand32, last, olen, ctc.blank, ctc.eos)
-            slot_done = None
-            if self.step_kernel and beam <= 64 and beam * P <= 1023 and beam * V < 2 ** 31 and r_new is None:
-                # one scorer with a slot table (the cached decoder): its re-ordering rides in the same launch
-                tabled = [k for k in names if isinstance(newtrees[k], dict) and "slot" in newtrees[k] and "pos" in newtrees[k]]
-                slot_in = newtrees[tabled[0]]["slot"] if len(tabled) == 1 else None
-                res = ops.beam_step(
-                    pre, part_ids, psi, S["c_s"], hyp, self.weights[pname], B, beam, L, i, self.eos, C_["maxlen_d"].view(-1),
-                    S["sc"], [logps[k] for k in names], yseq,
-                    dyn=(sdev, dyn["step_out"], dyn["ring"]) if dyn is not None else None, slot_in=slot_in)
-                sc_new, yseq, hyp_new, hyp_i, tok_i, tok32, cs_new, rec = res[:8]
-                if slot_in is not None:
-                    slot_done = (tabled[0], res[8])
-            elif dyn is not None:
-                raise _NoDynStep("selection kernel")
-            else:
-                top_s, top_i, c_loc = ops.beam_select(pre, part_ids, psi, S["c_s"], hyp, self.weights[pname], B, beam)
-                sc_new, yseq, hyp_new, hyp_i, tok_i, pos, rec = ops.beam_finish(
-                    top_s.reshape(-1), top_i.reshape(-1), beam, V, L, i, self.eos, C_["maxlen_d"].view(-1),
-                    S["sc"], [logps[k] for k in names], c_loc, False, part_ids, yseq)
-                cs_new, tok32 = psi[hyp_i, pos], tok_i.to(torch.int32)
-            for k in names:
-                if slot_done is not None and k == slot_done[0]:
-                    trees[k] = dict(newtrees[k], slot=slot_done[1])
-                else:
-                    trees[k] = self._reorder(self.full_scorers[k], newtrees[k], hyp_i)
-            T_ = dict(sc=sc_new, trees=trees, yseq=yseq, hyp=hyp_new, c_s=cs_new, last32=tok32, tok=tok_i)
-            if r_new is not None:
-                T_["c_r"] = r_new[hyp_i, pos]
-            elif dyn is not None or self.ctc_side_stream is False or (self.ctc_side_stream == "capture" and C_["Tpad"] <= 2048):
-                # the survivors' forward variables right away (a parallel scan of a few us up to 2048 frames)
-                T_["c_r"] = ops.ctc_prefix_state(C_["logp"], C_["lens_d"], beam, c_r_now, hyp_i, tok_i, last, L - 1 if dyn is None else 0,
-                                                 hyp_new, ctc.blank, olen_dev=sdev)
-            else:     # ... or at the start of the next step, on a second stream beside its decoder stack (see the top of this function)
-                T_["c_pend"] = (c_r_now, hyp_i, tok_i, last, L - 1, hyp_new)
-            return T_, rec
-        if dyn is not None:
+        front = (ys, trees, newtrees, logps, c_r_now, side)
+        if plan[0] and all(lp.dtype == torch.float32 and lp.is_contiguous() for lp in logps.values()):
+            return self._step_candidates(i, C_, S, dyn, plan, *front)
+        if dyn is not None:      # (what a scorer returns is known only once it has run: this one raise stays behind the launches)
             raise _NoDynStep("tensor-expression path")
+        return self._step_tensors(i, C_, S, *front)
+
+    def _step_candidates(self, i, C_, S, dyn, plan, ys, trees, newtrees, logps, c_r_now, side):
+        """BeamSearch with a pre-beam: the step's selection on the beam x P candidates (csrc/decode.hip: eamd_weighted_sum,
+        eamd_beam_select) - same scores in the same order of operations as the tensor expressions of _step_tensors, 12 launches fewer.
+        BatchBeamSearch ("full": the partial scorer reports a whole [n, V] row - log-zero outside the pre-beam, <eos> always
+        scored; nothing is masked): the same selection on P + 1 candidates, the pre-beam and <eos>.  Every other token's
+        score is ~ -3e9 (weight x log-zero): it can only win where an utterance has fewer live candidates than `beam` -
+        the host sees that in the step log (a winner below -1e9) and repeats the search on the tensor expressions."""
+        from .. import ops
+        B, V, beam, n, dev = C_["B"], C_["V"], C_["beam"], C_["n"], C_["dev"]
+        names, pname, ctc = C_["names"], C_["pname"], C_["ctc"]
+        _, split, fused = plan
+        L, P = i + 1, self.pre_beam_size
+        yseq, hyp = S["yseq"], S["hyp"]
+        sdev = dyn["step"] if dyn is not None else None
+        lps, wts = [logps[k] for k in names], [self.weights[k] for k in names]
+        if self.step_kernel and P <= 64:      # the weighted sum is formed inside the pre-beam's top-k launch
+            pre, part_ids, cand32 = ops.weighted_topk_rows(lps, wts, P, extra=ctc.eos if self.partial_mode == "full" else -1)
+        else:
+            pre = ops.weighted_sum(lps, wts)
+            _, part_ids, cand32 = ops.topk_rows(pre, P, idx32=True)
+        # the newest token of every prefix as int32: the previous step's selection wrote it (eamd_beam_step), <sos> at step 0
+        last = S["last32"] if "last32" in S else (C_["sos32"] if i == 0 else ys[:, -1].to(torch.int32).contiguous())
+        if side is not None:
+            torch.cuda.current_stream(dev).wait_stream(side)
+        olen = L - 1 if dyn is None else 0
+        slot_done = r_new = None
+        if split:
+            psi = ops.ctc_prefix_psi(C_["logp"], C_["lens_d"], beam, c_r_now, cand32, last, olen, ctc.blank, ctc.eos, olen_dev=sdev)
+        else:       # more than 2048 frames: the full recursion for every candidate
+            olen_d = torch.full((n,), L - 1, dtype=torch.int32, device=dev)
+            psi, r_new = ops.ctc_prefix_score_batch(C_["logp"], C_["lens_d"], beam, c_r_now, cand32, last, olen_d, ctc.blank, ctc.eos)
+        if fused:
+            # one scorer with a slot table (the cached decoder): its re-ordering rides in the same launch
+            tabled = [k for k in names if isinstance(newtrees[k], dict) and "slot" in newtrees[k] and "pos" in newtrees[k]]
+            slot_in = newtrees[tabled[0]]["slot"] if len(tabled) == 1 else None
+            res = ops.beam_step(
+                pre, part_ids, psi, S["c_s"], hyp, self.weights[pname], B, beam, L, i, self.eos, C_["maxlen_d"].view(-1),
+                S["sc"], lps, yseq, dyn=(sdev, dyn["step_out"], dyn["ring"]) if dyn is not None else None, slot_in=slot_in)
+            sc_new, yseq, hyp_new, hyp_i, tok_i, tok32, cs_new, rec = res[:8]
+            if slot_in is not None:
+                slot_done = (tabled[0], res[8])
+        else:
+            top_s, top_i, c_loc = ops.beam_select(pre, part_ids, psi, S["c_s"], hyp, self.weights[pname], B, beam)
+            sc_new, yseq, hyp_new, hyp_i, tok_i, pos, rec = ops.beam_finish(
+                top_s.reshape(-1), top_i.reshape(-1), beam, V, L, i, self.eos, C_["maxlen_d"].view(-1),
+                S["sc"], lps, c_loc, False, part_ids, yseq)
+            cs_new, tok32 = psi[hyp_i, pos], tok_i.to(torch.int32)
+        for k in names:
+            if slot_done is not None and k == slot_done[0]:
+                trees[k] = dict(newtrees[k], slot=slot_done[1])
+            else:
+                trees[k] = self._reorder(self.full_scorers[k], newtrees[k], hyp_i)
+        T_ = dict(sc=sc_new, trees=trees, yseq=yseq, hyp=hyp_new, c_s=cs_new, last32=tok32, tok=tok_i)
+        if r_new is not None:
+            T_["c_r"] = r_new[hyp_i, pos]
+        elif dyn is not None or self.ctc_side_stream is False or (self.ctc_side_stream == "capture" and C_["Tpad"] <= 2048):
+            # the survivors' forward variables right away (a parallel scan of a few us up to 2048 frames)
+            T_["c_r"] = ops.ctc_prefix_state(C_["logp"], C_["lens_d"], beam, c_r_now, hyp_i, tok_i, last, olen, hyp_new, ctc.blank,
+                                             olen_dev=sdev)
+        else:     # ... or at the start of the next step, on a second stream beside its decoder stack (see _batch_step)
+            T_["c_pend"] = (c_r_now, hyp_i, tok_i, last, L - 1, hyp_new)
+        return T_, rec
+
+    def _step_tensors(self, i, C_, S, ys, trees, newtrees, logps, c_r_now, side):
+        """the step as tensor expressions over all V tokens of every slot: any scorer set, with or without a pre-beam"""
+        from .. import ops
+        B, V, beam, n, dev = C_["B"], C_["V"], C_["beam"], C_["n"], C_["dev"]
+        names, pname, ctc = C_["names"], C_["pname"], C_["ctc"]
+        NEG = -float("inf")
+        L = i + 1
+        yseq, hyp = S["yseq"], S["hyp"]
         if side is not None:
             torch.cuda.current_stream(dev).wait_stream(side)
         weighted = torch.zeros(n, V, device=dev, dtype=torch.float32)
@@ -802,10 +700,8 @@ class BeamSearch(torch.nn.Module):
         """x: (T, D) encoder output.  Returns the ended hypotheses, best first."""
         from .. import ops
         ops.zero_arena_off()
-        if self._device_loop_ok(x):
-            if minlenratio == 0.0:       # one utterance = a batch of one: the same step code (selection / bookkeeping kernels, graphs)
-                return self.forward_batch([x], maxlenratio, minlenratio)[0]
-            return self._forward_device(x, maxlenratio, minlenratio)
+        if self._device_loop_ok(x):      # one utterance = a batch of one: the same step code (selection / bookkeeping kernels, graphs)
+            return self._search_device([x], maxlenratio)[0]       # (minlenratio: see forward_batch)
         T = x.shape[0]
         maxlen = T if maxlenratio == 0 else max(1, int(maxlenratio * T))
         with torch.no_grad():

@@ -1253,6 +1253,36 @@ def test_decode_c2width_golden(cw, ratio, pen):
             c2width_compare(cls.__name__ + ".forward_batch", together[u], g, tags[u])
 
 
+def test_decode_c2width_minlenratio_is_the_same_search():
+    """minlenratio > 0 runs the one device loop: the search does not read the ratio (the reference only logs minlen), so the n-best
+    of bs(enc, maxlenratio=0.2, minlenratio=0.3) and of forward_batch(..., minlenratio=0.3) are those of minlenratio=0.0 of the
+    same object - ids, scores and per-scorer scores with ==, for BeamSearch and BatchBeamSearch"""
+    from espnet_amd.nets.batch_beam_search import BatchBeamSearch
+    from espnet_amd.nets.beam_search import BeamSearch
+    from espnet_amd.nets.ctc_prefix_score import LengthBonus
+    SW, model, g, encs = c2width_setup()
+    spec = SW.DECODE_R4
+
+    def same(a, b):
+        assert len(a) == len(b) and len(a) > 0
+        for x, y in zip(a, b):
+            assert x.yseq.tolist() == y.yseq.tolist() and float(x.score) == float(y.score)
+            assert x.scores.keys() == y.scores.keys() and all(float(x.scores[k]) == float(y.scores[k]) for k in x.scores)
+    for cls in (BeamSearch, BatchBeamSearch):
+        scorers = model.scorers()
+        scorers["length_bonus"] = LengthBonus(spec["odim"])
+        bs = cls(scorers, dict(decoder=0.7, ctc=0.3, length_bonus=0.1), spec["beam"], spec["odim"], model.sos, model.eos,
+                 pre_beam_score_key="full")
+        assert bs._device_loop_ok(encs[0])
+        same(bs(encs[0], maxlenratio=0.2, minlenratio=0.3), bs(encs[0], maxlenratio=0.2, minlenratio=0.0))
+        with_ratio, without = bs.forward_batch(encs, maxlenratio=0.2, minlenratio=0.3), bs.forward_batch(encs, maxlenratio=0.2, minlenratio=0.0)
+        assert len(with_ratio) == len(without) == len(encs)
+        for a, b in zip(with_ratio, without):
+            same(a, b)
+        print(f"[parity] {cls.__name__} minlenratio 0.3 == 0.0: {len(with_ratio[0])}-best of {len(encs)} utterances identical, "
+              f"best {float(with_ratio[0][0].score):.4f}")
+
+
 def test_decode_c2width_step_graphs():
     """graph_steps at the benchmarked width against the same reference searches (child process, tests/step_graph_check.py c2width):
     every search runs three times - eager, capture, replay - single utterances and the three utterances in one search"""

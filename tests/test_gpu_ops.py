@@ -1790,6 +1790,74 @@ def test_ctc_prefix_score_vs_float64(ops, lens):
     assert worst["psi"] <= 1.0 and worst["r"] <= max(1.0, 1.05 * worst["r32"]) and worst["rs"] <= 1.0
 
 
+def test_ctc_prefix_state_beyond_2048_frames_equals_full_recursion(ops):
+    """more than 2048 frames: eamd_ctc_prefix_state walks the frames one by one (no scan) - the same ctc_prefix_recursion as
+    eamd_ctc_prefix_score_batch, one group of frames in flight instead of four.  Over three chained steps (utterances of 2100 and
+    1300 frames, |V| = 600, 4 hypotheses x 9 candidates; slot s continues hypothesis parent[s] - a permutation inside each
+    utterance - with one of its candidates; one dead slot) its rows are BIT-EQUAL to the (hypothesis, candidate) rows of the
+    batched launch from frame max(step, 1) - 1 on.  The float64 oracle first: every compared row is finite and ends with
+    probability mass (no all-log-zero state), so the equality is one of computed values."""
+    import sys, os
+    from conftest import ROOT
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import asr_oracle as O
+    V, per, P, blank, eos = 600, 4, 9, 0, 599
+    lens = [2100, 1300]
+    U, Tmax = len(lens), max(lens)
+    g = torch.Generator().manual_seed(2100)
+    logits = 2.5 * torch.randn(U, Tmax, V, generator=g)
+    logits[:, :, blank] += 9.0
+    logp = torch.log_softmax(logits, -1)
+    logp_d = logp.to(DEV).contiguous()
+    lens_d = torch.tensor(lens, dtype=torch.int32, device=DEV)
+    r_prev = np.zeros((U, per, Tmax, 2))
+    for u in range(U):
+        r_prev[u, :, :lens[u]] = O.ctc_prefix_init(logp[u, :lens[u]].double().numpy(), blank, np.float64)[None]
+    last = np.full((U, per), eos, dtype=np.int64)
+    differ = 0
+    for step in range(3):
+        cand = torch.randint(1, V - 1, (U, per, P), generator=g).numpy()
+        cand[:, :, 0], cand[:, :, 1] = eos, blank
+        if step > 0:
+            cand[:, :, 2] = last                                                  # the repeated-label branch
+        pick = torch.randint(2, P, (U, per), generator=g).numpy()
+        t0 = max(step, 1) - 1
+        r64 = []
+        for u in range(U):
+            T = lens[u]
+            _, r = O.ctc_prefix_step(logp[u, :T].double().numpy(), last[u], step, cand[u], r_prev[u][:, :T], blank, eos, np.float64)
+            rows = r[:, 2:, t0:]                                                  # (every hypothesis x every candidate a slot may take)
+            assert np.isfinite(rows).all() and np.logaddexp(rows[:, :, -1, 0], rows[:, :, -1, 1]).min() > -1e9
+            r64.append(r)
+        n = U * per
+        cand_d = torch.from_numpy(cand.reshape(n, P)).to(torch.int32).to(DEV)
+        last_d = torch.from_numpy(last.reshape(-1)).to(torch.int32).to(DEV)
+        olen_d = torch.full((n,), step, dtype=torch.int32, device=DEV)
+        rp_d = torch.from_numpy(r_prev.reshape(n, Tmax, 2)).float().to(DEV)
+        _, r_b = ops.ctc_prefix_score_batch(logp_d, lens_d, per, rp_d, cand_d, last_d, olen_d, blank, eos)
+        parent = torch.cat([u * per + torch.randperm(per, generator=g) for u in range(U)])
+        tok = torch.tensor([int(cand.reshape(n, P)[int(parent[s]), pick.reshape(-1)[s]]) for s in range(n)])
+        alive = torch.zeros(n, device=DEV)
+        alive[5] = -float("inf")
+        r_s = ops.ctc_prefix_state(logp_d, lens_d, per, rp_d, parent.to(DEV), tok.to(DEV), last_d, step, alive, blank)
+        torch.cuda.synchronize()
+        for s in range(n):
+            T = lens[s // per]
+            if s == 5:
+                assert float(r_s[s, :T].max()) == -10000000000.0
+                continue
+            want = r_b[int(parent[s]), int(pick.reshape(-1)[s]), t0:T]
+            assert bool(torch.isfinite(want).all())
+            differ += int((r_s[s, t0:T] != want).sum())
+            assert float(r_s[s, :t0].max()) <= -9.9e9 if t0 > 0 else True
+        for u in range(U):
+            for h in range(per):
+                r_prev[u, h, :lens[u]] = r64[u][h, pick[u, h]]
+                last[u, h] = cand[u, h, pick[u, h]]
+    print("[parity] ctc_prefix_state beyond 2048 frames vs the batched recursion's rows: %d elements differ (bit-equal asked)" % differ)
+    assert differ == 0
+
+
 @pytest.mark.parametrize("M", [7968, 100, 32])
 def test_rowproj_vs_float64(ops, M):
     """eamd_rowproj (32 rows per workgroup through the whole product, packed weight images) against float64:
