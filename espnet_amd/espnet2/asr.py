@@ -217,7 +217,21 @@ class ESPnetASRModel(AbsESPnetModel):
         self.rnnt_decoder = None
         self.criterion_att = M.LabelSmoothingLoss(size=vocab_size, padding_idx=ignore_id, smoothing=lsm_weight,
                                                   normalize_length=length_normalized_loss)
-        self.error_calculator = None
+        if report_cer or report_wer:       # reference: espnet_model.py:89-94
+            from ..nets.e2e_asr_common import ErrorCalculator
+            self.error_calculator = ErrorCalculator(self.token_list, sym_space, sym_blank, report_cer, report_wer)
+        else:
+            self.error_calculator = None
+
+    @staticmethod
+    def _rate(counts):
+        """(errors [B], ref_len [B]) int32 -> float32 scalar on the device: the integer sums divided in float64, which rounds
+        like the reference's float(sum(eds)) / sum(lens); NaN where the reference has None (cer_ctc) or raises
+        ZeroDivisionError (cer, wer): every reference of the batch is empty.  No host read."""
+        if counts is None:
+            return None
+        err, n = counts
+        return (err.sum().to(torch.float64) / n.sum().to(torch.float64)).to(torch.float32)
 
     def encode(self, speech, speech_lengths):
         """reference: espnet_model.py:178-213 (features = speech when frontend is None; SpecAug in training mode
@@ -250,13 +264,23 @@ class ESPnetASRModel(AbsESPnetModel):
         text = text[:, : max(tl)].contiguous()
         encoder_out, encoder_out_lens = self.encode(speech, speech_lengths)
         loss_att = acc_att = loss_ctc = None
+        cer_att = wer_att = cer_ctc = None
+        scoring = not self.training and self.error_calculator is not None
         if self.ctc_weight != 1.0:
             ys_in_pad, ys_out_pad, _ = ops.add_sos_eos(text, self.sos, self.eos, self.ignore_id)
             decoder_out, _ = self.decoder(encoder_out, encoder_out_lens, ys_in_pad, [v + 1 for v in tl])
             loss_att = self.criterion_att(decoder_out, ys_out_pad, n_tokens=sum(tl) + len(tl))
             acc_att = M.th_accuracy(self.criterion_att.correct_rows, ys_out_pad, self.ignore_id)
+            if scoring:                      # espnet_model.py:258-262
+                with torch.no_grad():
+                    Bo, U, V = decoder_out.shape
+                    ys_hat = ops.argmax_rows(decoder_out.detach().reshape(Bo * U, V).contiguous()).view(Bo, U)
+                    cer_att, wer_att = [self._rate(c) for c in self.error_calculator.counts(ys_hat, text)]
         if self.ctc_weight != 0.0:
             loss_ctc = self.ctc(encoder_out, encoder_out_lens.to(torch.int32), text, tl)
+            if scoring:                      # espnet_model.py:276-280: argmax over every frame of the padded batch
+                with torch.no_grad():
+                    cer_ctc = self._rate(self.error_calculator.counts(self.ctc.argmax(encoder_out), text, is_ctc=True))
         if self.ctc_weight == 0.0:
             loss = loss_att
         elif self.ctc_weight == 1.0:
@@ -264,8 +288,8 @@ class ESPnetASRModel(AbsESPnetModel):
         else:
             loss = F_.WeightedSumFn.apply(loss_ctc, loss_att, self.ctc_weight)
         stats = dict(loss=loss.detach(), loss_att=loss_att.detach() if loss_att is not None else None,
-                     loss_ctc=loss_ctc.detach() if loss_ctc is not None else None, acc=acc_att, cer=None, wer=None,
-                     cer_ctc=None)
+                     loss_ctc=loss_ctc.detach() if loss_ctc is not None else None, acc=acc_att, cer=cer_att, wer=wer_att,
+                     cer_ctc=cer_ctc)
         # force_gatherable (espnet2/torch_utils/device_funcs.py): scalars -> (1,) tensors on the loss device
         dev = loss.device
         stats = {k: (v.detach().reshape(1) if isinstance(v, torch.Tensor) else v) for k, v in stats.items()}

@@ -84,8 +84,20 @@ class E2E(ASRInterface, torch.nn.Module):
         self.att = att_for(args)
         self.dec = decoder_for(args, odim, self.sos, self.eos, self.att, None)
         self.init_like_chainer()
-        self.report_cer = False
-        self.report_wer = False
+        # options for the validation beam search (reference: e2e_asr.py:160-180)
+        self.report_cer = bool(getattr(args, "report_cer", False))
+        self.report_wer = bool(getattr(args, "report_wer", False))
+        if self.report_cer or self.report_wer:
+            import argparse
+            self.recog_args = argparse.Namespace(
+                beam_size=args.beam_size, penalty=args.penalty, ctc_weight=args.ctc_weight, maxlenratio=args.maxlenratio,
+                minlenratio=args.minlenratio, lm_weight=args.lm_weight, rnnlm=args.rnnlm, nbest=args.nbest,
+                space=args.sym_space, blank=args.sym_blank)
+        self.error_calculator = None
+        if self.char_list is not None and (self.mtlalpha != 0 or self.report_cer or self.report_wer):
+            from .e2e_asr_common import ErrorCalculator
+            self.error_calculator = ErrorCalculator(self.char_list, self.space, self.blank, self.report_cer, self.report_wer)
+        self._cer_ctc_n = self._cer_n = self._wer_n = None
         self.rnnlm = None
         self.logzero = -10000000000.0
         self.loss = None
@@ -113,6 +125,7 @@ class E2E(ASRInterface, torch.nn.Module):
         else:
             self.loss_att, acc, _ = self.dec(hs_pad, hlens, ys_pad)
         self.acc = acc
+        self._score(hs_pad, hlens, ys_pad)
         alpha = self.mtlalpha
         if alpha == 0:
             self.loss = self.loss_att
@@ -121,6 +134,63 @@ class E2E(ASRInterface, torch.nn.Module):
         else:
             self.loss = F_.WeightedSumFn.apply(self.loss_ctc, self.loss_att, alpha)
         return self.loss
+
+    def _score(self, hs_pad, hlens, ys_pad):
+        """per-utterance error counts of this batch as device tensors (reference: e2e_asr.py:237-315); the rates are the
+        properties cer_ctc / cer / wer, which read them when asked"""
+        self._cer_ctc_n = self._cer_n = self._wer_n = None
+        ec = self.error_calculator
+        if ec is None:
+            return
+        with torch.no_grad():
+            ys_dev = ys_pad if ys_pad.is_cuda else ops.h2d_async(ys_pad, hs_pad.device)
+            if self.mtlalpha != 0:          # greedy CTC, in training too
+                self._cer_ctc_n = ec.counts_ctc_text(self.ctc.argmax(hs_pad), ys_dev)
+            if self.training or not (self.report_cer or self.report_wer):
+                return
+            lpz = self.ctc.log_softmax(hs_pad) if self.recog_args.ctc_weight > 0.0 else None
+            nbest_hyps = self.dec.recognize_beam_batch(hs_pad, hlens, lpz, self.recog_args, self.char_list, self.rnnlm)
+            y_hats = [nbest_hyp[0]["yseq"][1:-1] for nbest_hyp in nbest_hyps]      # without <sos> and <eos>
+            host = torch.full((len(y_hats), max(1, max(len(y) for y in y_hats))), -1, dtype=torch.int32)
+            for b, y in enumerate(y_hats):
+                host[b, : len(y)] = torch.tensor([int(v) for v in y], dtype=torch.int32)
+            ys_hat = ops.h2d_async(host, hs_pad.device)
+            # the whole hypothesis is scored (no ymax): a reference row without padding, as wide as the hypotheses, lifts it
+            t = ec._tables_on(ys_hat.device)
+            ref = ys_dev.to(torch.int32).contiguous()
+            if self.report_cer:
+                h, hn = ec._units(ys_hat, t["hyp"], drop_cp=0x20)
+                r, rn = ec._units(ref, t["ref"], drop_cp=0x20)
+                self._cer_n = (ops.edit_distance(h, hn, r, rn), rn)
+            if self.report_wer:
+                h, hn = ec._units(ys_hat, t["hyp"], mode=ops.TEXT_WORDS)
+                r, rn = ec._units(ref, t["ref"], mode=ops.TEXT_WORDS)
+                self._wer_n = (ops.edit_distance(h, hn, r, rn), rn)
+
+    @property
+    def cer_ctc(self):
+        """mean over the utterances with a non-empty reference of errors / reference length (e2e_asr.py:258-263); None when
+        there is none or CTC / the token list is absent.  One host read of the 2B counts, Python arithmetic as the reference."""
+        if self._cer_ctc_n is None:
+            return None
+        eds, lens = torch.stack(self._cer_ctc_n).tolist()
+        cers = [e / n for e, n in zip(eds, lens) if n > 0]
+        return sum(cers) / len(cers) if cers else None
+
+    @property
+    def cer(self):
+        """float(sum errors) / sum lengths of the validation beam search's 1-best; 0.0 in training or without --report-cer"""
+        if self._cer_n is None:
+            return 0.0
+        (e, n), = self.error_calculator.sums(self._cer_n)
+        return float(e) / n
+
+    @property
+    def wer(self):
+        if self._wer_n is None:
+            return 0.0
+        (e, n), = self.error_calculator.sums(self._wer_n)
+        return float(e) / n
 
     def scorers(self):
         from .ctc_prefix_score import CTCPrefixScorer

@@ -76,6 +76,8 @@ class E2E(E2ETransformer):
             return E2EConformer._build_encoder(self, idim, args)
         return E2ETransformer._build_encoder(self, idim, args)
 
+    reports_errors = False     # error_calculator stays None here (CER / WER reporting)
+
     def __init__(self, idim, odim, args, ignore_id=-1):
         odim += 1  # for the mask token
         super().__init__(idim, odim, args, ignore_id)

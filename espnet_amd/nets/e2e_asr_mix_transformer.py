@@ -100,6 +100,8 @@ class E2E(E2ETransformer):
                            help="Number of speaker differentiate encoder layers for multi-speaker speech recognition task.")
         return parser
 
+    reports_errors = False     # error_calculator stays None here (CER / WER reporting)
+
     def __init__(self, idim, odim, args, ignore_id=-1):
         from .e2e_asr_transformer import fill_missing_args
         super().__init__(idim, odim, args, ignore_id)

@@ -102,7 +102,14 @@ class E2E(ASRInterface, torch.nn.Module):
         self.odim = odim
         self.criterion = TransLoss(args.trans_type, self.blank_id)
         self.default_parameters(args)
-        self.error_calculator = None
+        if getattr(args, "report_cer", False) or getattr(args, "report_wer", False):      # e2e_asr_transducer.py:478-495
+            from .e2e_asr_common import ErrorCalculatorTransducer
+            self.error_calculator = ErrorCalculatorTransducer(
+                self.decoder if "transformer" in args.dtype else self.dec, args.char_list, args.sym_space, args.sym_blank,
+                args.report_cer, args.report_wer)
+        else:
+            self.error_calculator = None
+        self.cer = self.wer = None
         self.loss = None
         self.rnnlm = None
 
@@ -158,6 +165,7 @@ class E2E(ASRInterface, torch.nn.Module):
             self.loss = self.dec.joint_network.loss(hs_pad, self.dec.hidden(ys_in_pad), target, pred_len, target_len,
                                                     hs_mask if isinstance(hs_mask, (list, tuple)) else pred_len.tolist(),
                                                     self.blank_id)
+            self._score(hs_pad, ys_pad)
             return self.loss
         elif self.rnnt_mode == "rnnt":
             pred_pad = self.dec(hs_pad, ys_in_pad)
@@ -165,7 +173,16 @@ class E2E(ASRInterface, torch.nn.Module):
             pred_pad = self.dec(hs_pad, ys_in_pad, hs_mask)      # host-side encoder lengths (pred_len on the device)
         self.pred_pad = pred_pad
         self.loss = self.criterion(pred_pad, target, pred_len, target_len)
+        self._score(hs_pad, ys_pad)
         return self.loss
+
+    def _score(self, hs_pad, ys_pad):
+        """cer / wer of the greedy search's hypotheses in eval mode (e2e_asr_transducer.py:552-556); None otherwise"""
+        if self.training or self.error_calculator is None:
+            self.cer = self.wer = None
+        else:
+            ys_dev = ys_pad if ys_pad.is_cuda else ops.h2d_async(ys_pad, hs_pad.device)
+            self.cer, self.wer = self.error_calculator(hs_pad.detach(), ys_dev)
 
     def encode_transformer(self, x):
         """x ndarray (T, D) -> encoder states (T', d)   (e2e_asr_transducer.py:565-580)"""

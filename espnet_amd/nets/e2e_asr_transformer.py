@@ -92,6 +92,8 @@ class E2E(ASRInterface, torch.nn.Module):
     def get_total_subsampling_factor(self):
         return 4  # conv2d input layer (e2e_asr_transformer.py:66-68)
 
+    reports_errors = True    # --report-cer / --report-wer build an ErrorCalculator (the Mask-CTC and multi-speaker E2Es do not)
+
     def _build_encoder(self, idim, args):
         if args.transformer_encoder_selfattn_layer_type != "selfattn":
             raise NotImplementedError("encoder selfattention_layer_type must be selfattn for the Transformer E2E")
@@ -131,7 +133,12 @@ class E2E(ASRInterface, torch.nn.Module):
             self.ctc = CTC(odim, args.adim, args.dropout_rate, ctc_type=args.ctc_type, reduce=True)
         else:
             self.ctc = None
-        self.error_calculator = None   # host-side edit distance: out of scope
+        if self.reports_errors and (args.report_cer or args.report_wer):       # reference: e2e_asr_transformer.py:142-151
+            from .e2e_asr_common import ErrorCalculator
+            self.error_calculator = ErrorCalculator(args.char_list, args.sym_space, args.sym_blank, args.report_cer,
+                                                    args.report_wer)
+        else:
+            self.error_calculator = None
         self.rnnlm = None
         self.sync_report = True        # float(loss) x3 like the reference; False defers the D2H copies
         self.reset_parameters(args)
@@ -244,6 +251,18 @@ class E2E(ASRInterface, torch.nn.Module):
         else:
             self.loss = F_.WeightedSumFn.apply(loss_ctc, loss_att, alpha)
         self._loss_ctc_t, self._loss_att_t = loss_ctc, loss_att
+        # per-utterance error counts of the validation batch, as device tensors next to _acc_t (e2e_asr_transformer.py:205-217:
+        # the CTC argmax runs over all T' frames of the padded batch, cer / wer over the teacher-forced decoder argmax)
+        self._cer_ctc_n = self._cer_n = self._wer_n = None
+        if not self.training and self.error_calculator is not None:
+            with torch.no_grad():
+                if self.mtlalpha > 0.0:
+                    ys_hat = self.ctc.argmax(hs_pad.view(batch["B"], -1, self.adim))
+                    self._cer_ctc_n = self.error_calculator.counts(ys_hat, batch["ys_pad"], is_ctc=True)
+                if self.decoder is not None:
+                    B, U, V = pred_pad.shape
+                    ys_hat = ops.argmax_rows(pred_pad.detach().reshape(B * U, V).contiguous()).view(B, U)
+                    self._cer_n, self._wer_n = self.error_calculator.counts(ys_hat, batch["ys_pad"])
         return self.loss
 
     def forward(self, xs_pad, ilens, ys_pad):
@@ -260,8 +279,15 @@ class E2E(ASRInterface, torch.nn.Module):
         la = float(self._loss_att_t.detach()) if self._loss_att_t is not None else None
         self.acc = float(self._acc_t) if self.decoder is not None else None
         loss_data = float(self.loss.detach())
+        cer_ctc = cer = wer = None
+        if self.error_calculator is not None:
+            # float(sum errors) / sum lengths like the reference; cer_ctc is None when every reference is empty
+            n_ctc, n_cer, n_wer = self.error_calculator.sums(self._cer_ctc_n, self._cer_n, self._wer_n)
+            cer_ctc = float(n_ctc[0]) / n_ctc[1] if n_ctc is not None and n_ctc[1] > 0 else None
+            cer = float(n_cer[0]) / n_cer[1] if n_cer is not None else None
+            wer = float(n_wer[0]) / n_wer[1] if n_wer is not None else None
         if loss_data < CTC_LOSS_THRESHOLD and not math.isnan(loss_data):
-            self.reporter.report(lc, la, self.acc, None, None, None, loss_data)
+            self.reporter.report(lc, la, self.acc, cer_ctc, cer, wer, loss_data)
         return loss_data
 
     # ---- inference ------------------------------------------------------------------------------

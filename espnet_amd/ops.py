@@ -1835,6 +1835,41 @@ def ctc_collapse(ids, hlens, blank):
     return out, outlen
 
 
+TEXT_CHARS, TEXT_WORDS = 0, 1      # include/espnet_amd.h: EAMD_TEXT_CHARS / EAMD_TEXT_WORDS
+
+
+def text_units(ids, tok_off, tok_cp, cap, limit=None, collapse=False, drop_cp=-1, mode=TEXT_CHARS):
+    """padded id rows -> symbol rows (eamd_text_units): ids [B,L] int32 (-1 padding), limit [B] int32 or None, the token
+    table tok_off [V+1] / tok_cp int32 (CSR of code points), cap >= L * longest token -> out [B,cap] int64, outlen [B] int32"""
+    B, L = ids.shape
+    assert ids.dtype == torch.int32 and ids.is_contiguous() and tok_off.dtype == torch.int32 and tok_cp.dtype == torch.int32
+    assert limit is None or (limit.dtype == torch.int32 and limit.numel() == B)
+    V = tok_off.numel() - 1
+    dev = ids.device
+    scratch = torch.empty(B, cap, device=dev, dtype=torch.int32)
+    out = torch.empty(B, cap, device=dev, dtype=torch.int64)
+    outlen = torch.empty(B, device=dev, dtype=torch.int32)
+    check(_lib.lib().eamd_text_units(ptr(ids), ptr(limit), ptr(tok_off), ptr(tok_cp), ptr(scratch), ptr(out), ptr(outlen),
+                                     B, L, V, cap, int(bool(collapse)), int(drop_cp), int(mode), stream_ptr()),
+          "eamd_text_units")
+    return out, outlen
+
+
+def edit_distance(a, alen, b, blen):
+    """batched Levenshtein distance (eamd_edit_distance): a [B,lda], b [B,ldb] int64 symbols, alen / blen [B] int32
+    -> dist [B] int32"""
+    B, lda = a.shape
+    ldb = b.shape[1]
+    assert a.dtype == torch.int64 and b.dtype == torch.int64 and a.is_contiguous() and b.is_contiguous() and b.shape[0] == B
+    assert alen.dtype == torch.int32 and blen.dtype == torch.int32 and alen.numel() == B and blen.numel() == B
+    ws_bytes = _lib.lib().eamd_edit_distance_workspace_bytes(B, lda, ldb)
+    ws = torch.empty(ws_bytes, device=a.device, dtype=torch.uint8)
+    dist = torch.empty(B, device=a.device, dtype=torch.int32)
+    check(_lib.lib().eamd_edit_distance(ptr(a), lda, ptr(alen), ptr(b), ldb, ptr(blen), ptr(dist), ptr(ws),
+                                        C.c_int64(ws_bytes), B, stream_ptr()), "eamd_edit_distance")
+    return dist
+
+
 # ---- CTC -----------------------------------------------------------------------------------------
 def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True, time_major=False):
     """acts [B,T,V] raw activations (time_major: [T,B,V], warp-ctc's layout - read in place through the entry point's

@@ -968,6 +968,32 @@ int eamd_maskctc_seed(const float* logits, const int32_t* hlens, int32_t* frame_
 int eamd_maskctc_update(int pass, const float* logits, int64_t* y_in, const int32_t* len, const int32_t* niter,
                         const int32_t* kper, float* score, int32_t* arg, int B, int L, int ldy, int V, int mask_token, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Error-rate scoring (reference: espnet/nets/e2e_asr_common.py:103-246, ErrorCalculator), on the device.
+ * ------------------------------------------------------------------------------------------ */
+#define EAMD_TEXT_CHARS 0
+#define EAMD_TEXT_WORDS 1
+/* Padded id rows -> the symbol sequences the reference's string handling produces.  ids [B,L] int32; of row b the entries
+ * ids[b, :limit[b]] are considered (limit NULL: all L; values are clamped to [0, L]).  collapse != 0 keeps the first entry of
+ * every run of equal entries (itertools.groupby over the row, -1 entries included).  Every remaining id in [0, V) is replaced
+ * by its code points tok_cp[tok_off[id] : tok_off[id+1]] (CSR, int32 Unicode code points; an empty range drops the id); -1 and
+ * ids outside [0, V) are skipped.  mode EAMD_TEXT_CHARS: one symbol per code point, code points equal to drop_cp (0x20, or -1
+ * for none) removed, like .replace(" ", "").  mode EAMD_TEXT_WORDS: the stream is split on runs of 0x20 like str.split() and
+ * every word becomes one 64-bit hash of its code points (drop_cp is not used).  editdistance.eval compares hashes of the list
+ * items as well, so the hash loses nothing the reference keeps.
+ * out [B,cap] int64, outlen [B]; scratch [B,cap] int32.  cap >= L * (longest token) holds every row; code points past cap are
+ * dropped.  out[b, outlen[b]:] is left unwritten. */
+int eamd_text_units(const int32_t* ids, const int32_t* limit, const int32_t* tok_off, const int32_t* tok_cp,
+                    int32_t* scratch, int64_t* out, int32_t* outlen, int B, int L, int V, int cap, int collapse,
+                    int drop_cp, int mode, void* stream);
+/* Batched Levenshtein distance, unit insert / delete / substitute costs.  a [B,lda], b [B,ldb] 64-bit symbols; alen / blen [B]
+ * (clamped to [0, lda] / [0, ldb]); elements past the lengths are never read.  dist[b] = distance of a[b, :alen[b]] and
+ * b[b, :blen[b]] (an empty side gives the other's length).  workspace: eamd_edit_distance_workspace_bytes(B, lda, ldb) bytes
+ * (two DP rows per pair; a smaller workspace_bytes is refused).  No length cap beyond the workspace. */
+int64_t eamd_edit_distance_workspace_bytes(int B, int lda, int ldb);
+int eamd_edit_distance(const int64_t* a, int lda, const int32_t* alen, const int64_t* b, int ldb, const int32_t* blen,
+                       int32_t* dist, void* workspace, int64_t workspace_bytes, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
