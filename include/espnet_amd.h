@@ -595,7 +595,8 @@ int eamd_bn_apply(const float* x, const float* mean, const float* rstd, const fl
  * (b, t) with t = row % T; bound = device int32 scalar, read at run time): rows with t >= bound[0] take no part in the
  * statistics / sums, count as B * bound rows, and receive dx = 0 - what conformer/convolution.py:56-79 computes on the
  * batch cropped to its own length.  eamd_mask_time zeroes those rows of an [rows, C] tensor in place (the depthwise
- * convolution then sees the zero padding the reference has there). */
+ * convolution then sees the zero padding the reference has there).
+ * Rows from the bound on are not read (x and dy may hold anything there, NaN included) and dx is written as 0 there. */
 int eamd_bn_stats_bounded(const float* x, float* workspace, float* mean, float* rstd, float* running_mean,
                           float* running_var, int64_t* num_batches_tracked, int64_t M, int C, float eps, float momentum, int T,
                           const int32_t* bound, void* stream);
@@ -611,7 +612,7 @@ int eamd_bn_bwd(const float* dy, const float* x, const float* mean, const float*
 int eamd_conv1_fwd(const float* x, const float* w, const float* bias, void* y, int B, int T, int F, int C,
                    int y_bf16, void* stream);
 /* weight / bias gradient (accumulated; dy already ReLU-masked).  workspace: eamd_conv1_bwd_w_workspace(B,T,C) floats
- * of scratch for the two-stage reduction (NULL => f32 atomics straight into dw / db). */
+ * of scratch for the two-stage reduction (required: NULL is EAMD_EINVAL). */
 int64_t eamd_conv1_bwd_w_workspace(int B, int T, int C);
 int eamd_conv1_bwd_w(const void* dy, const float* x, float* dw, float* db, float* workspace, int B, int T, int F,
                      int C, int dy_bf16, void* stream);
