@@ -720,24 +720,25 @@ class BeamSearch(torch.nn.Module):
         return nbest
 
 
-def recognize_beam(model, enc_output, recog_args, char_list=None, rnnlm=None):
+def recognize_beam(model, enc_output, recog_args, char_list=None, rnnlm=None, ngram=None):
     """E2E.recognize for ctc_weight < 1 (reference: e2e_asr_transformer.py:286-477 / asr/pytorch_backend/recog.py).
     rnnlm: any BatchScorerInterface language model, fused with weight recog_args.lm_weight.
+    ngram: an n-gram scorer (nets.ngram: NgramFullScorer / NgramPartScorer), fused with weight recog_args.ngram_weight (recog.py:68-87).
     Returns [{"score": float, "yseq": [int]}] n-best, yseq starts with <sos> and ends with <eos>."""
-    bs = _recog_searcher(model, recog_args, rnnlm)
+    bs = _recog_searcher(model, recog_args, rnnlm, ngram)
     hyps = bs(enc_output, float(getattr(recog_args, "maxlenratio", 0.0)), float(getattr(recog_args, "minlenratio", 0.0)))
     return _nbest(hyps, recog_args)
 
 
-def recognize_beam_batch(model, enc_outputs, recog_args, char_list=None, rnnlm=None):
+def recognize_beam_batch(model, enc_outputs, recog_args, char_list=None, rnnlm=None, ngram=None):
     """recognize_beam for several encoder outputs (list of (T_u, D)) in one BeamSearch.forward_batch -> one n-best list each"""
-    bs = _recog_searcher(model, recog_args, rnnlm)
+    bs = _recog_searcher(model, recog_args, rnnlm, ngram)
     out = bs.forward_batch(list(enc_outputs), float(getattr(recog_args, "maxlenratio", 0.0)),
                            float(getattr(recog_args, "minlenratio", 0.0)))
     return [_nbest(hyps, recog_args) for hyps in out]
 
 
-def _recog_searcher(model, recog_args, rnnlm):
+def _recog_searcher(model, recog_args, rnnlm, ngram=None):
     ctc_weight = float(getattr(recog_args, "ctc_weight", 0.0))
     if model.ctc is None:
         ctc_weight = 0.0
@@ -746,6 +747,8 @@ def _recog_searcher(model, recog_args, rnnlm):
                    length_bonus=float(getattr(recog_args, "penalty", 0.0)))
     scorers = dict(decoder=model.decoder, ctc=CTCPrefixScorer(model.ctc, model.eos) if ctc_weight > 0 else None,
                    lm=rnnlm, length_bonus=LengthBonus(model.odim))
+    if ngram is not None:      # recog.py:68-87 (the reference's argparse default of --ngram-weight is 0.1)
+        scorers["ngram"], weights["ngram"] = ngram, float(getattr(recog_args, "ngram_weight", 0.1))
     return BeamSearch(scorers, weights, int(recog_args.beam_size), model.odim, model.sos, model.eos,
                       pre_beam_score_key=None if ctc_weight == 1.0 else "full")
 

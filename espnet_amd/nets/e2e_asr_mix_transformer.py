@@ -198,13 +198,13 @@ class E2E(E2ETransformer):
         return [h.squeeze(0) for h in hs]
 
     @ops.inference_call
-    def recognize(self, x, recog_args, char_list=None, rnnlm=None, use_jit=False):
+    def recognize(self, x, recog_args, char_list=None, rnnlm=None, use_jit=False, ngram=None):
         """reference: e2e_asr_mix_transformer.py:438-462 -> one n-best list per speaker (the reference's recog for each)"""
         from .beam_search import recognize_beam
-        return [recognize_beam(self, h, recog_args, char_list, rnnlm) for h in self.encode(x)]
+        return [recognize_beam(self, h, recog_args, char_list, rnnlm, ngram=ngram) for h in self.encode(x)]
 
     @ops.inference_call
-    def recognize_batch(self, xs, recog_args, char_list=None, rnnlm=None):
+    def recognize_batch(self, xs, recog_args, char_list=None, rnnlm=None, ngram=None):
         """xs: list of (T_b, idim) features -> [B][S] n-best lists, each what recognize() gives for that utterance: the padded batch
         is encoded once (every utterance keeps its single-utterance encoder output, nets.ctc_align.encode_batch(alone=True)) and
         the S B searches run in one BeamSearch.forward_batch"""
@@ -216,7 +216,7 @@ class E2E(E2ETransformer):
         hs, hl = encode_batch(self, xs_pad, ilens, alone=True)
         S = self.num_spkrs
         encs = [hs[s][b, :hl[b]] for b in range(len(xs)) for s in range(S)]
-        out = recognize_beam_batch(self, encs, recog_args, char_list, rnnlm)
+        out = recognize_beam_batch(self, encs, recog_args, char_list, rnnlm, ngram=ngram)
         return [out[b * S:(b + 1) * S] for b in range(len(xs))]
 
 

@@ -306,9 +306,10 @@ class E2E(ASRInterface, torch.nn.Module):
         return enc_output.squeeze(0)
 
     @ops.inference_call
-    def recognize(self, x, recog_args, char_list=None, rnnlm=None, use_jit=False):
+    def recognize(self, x, recog_args, char_list=None, rnnlm=None, use_jit=False, ngram=None):
         """reference: e2e_asr_transformer.py:259-477 (greedy CTC when ctc_weight == 1, else joint
-        CTC/attention beam search through the scorer interface)."""
+        CTC/attention beam search through the scorer interface).  ngram: an n-gram scorer (nets.ngram), fused with weight
+        recog_args.ngram_weight as asr/pytorch_backend/recog.py:68-87 does."""
         enc_output = self.encode(x).unsqueeze(0)
         if self.mtlalpha == 1.0:
             recog_args.ctc_weight = 1.0
@@ -321,7 +322,16 @@ class E2E(ASRInterface, torch.nn.Module):
                 raise NotImplementedError("Pure CTC beam search is not implemented.")
             return [{"score": 0.0, "yseq": [self.sos] + hyp}]
         from .beam_search import recognize_beam
-        return recognize_beam(self, enc_output.squeeze(0), recog_args, char_list, rnnlm)
+        return recognize_beam(self, enc_output.squeeze(0), recog_args, char_list, rnnlm, ngram=ngram)
+
+    @ops.inference_call
+    def recognize_batch(self, xs, recog_args, char_list=None, rnnlm=None, ngram=None):
+        """xs: list of (T_b, idim) features -> one n-best list each, what recognize() gives for that utterance: every utterance is
+        encoded alone and the searches run in one BeamSearch.forward_batch"""
+        if self.mtlalpha == 1.0 or (self.mtlalpha > 0 and recog_args.ctc_weight == 1.0):
+            return [self.recognize(x, recog_args, char_list, rnnlm) for x in xs]          # greedy CTC: no search to batch
+        from .beam_search import recognize_beam_batch
+        return recognize_beam_batch(self, [self.encode(x) for x in xs], recog_args, char_list, rnnlm, ngram=ngram)
 
     def greedy_ctc_batch(self, xs_pad, ilens):
         """Batched greedy CTC (embarrassingly parallel per utterance): token ids [B, T'] padded -1."""

@@ -1870,6 +1870,28 @@ def edit_distance(a, alen, b, blen):
     return dist
 
 
+def ngram_score(lm, ctx_prev, tok, first=False):
+    """the n-gram LM's rows of n hypotheses in one launch (eamd_ngram_score).  lm: the tables of nets.ngram.ArpaLM, on the device;
+    ctx_prev [n, N-1] int32 word ids, most recent first, -1 = empty (a row stride of 0 - one row expanded - is read in place);
+    tok [n] int64, any stride (ys[:, -1] needs no copy): the newest token of every row; first: the newest word is <s>
+    -> (logp [n, V] fp32 log10-probabilities, ctx_new [n, N-1] int32)"""
+    n, Cw = ctx_prev.shape
+    V = lm.uni_tok.numel()
+    assert Cw == lm.order - 1 and ctx_prev.dtype == torch.int32 and (Cw == 0 or ctx_prev.stride(1) == 1)
+    assert tok.dtype == torch.int64 and tok.dim() == 1 and tok.numel() == n
+    dev = tok.device
+    if lm.uni_tok.device != dev or ctx_prev.device != dev:
+        raise _lib.EamdError("ngram_score: tables, contexts and tokens on one device")
+    logp = torch.empty(n, V, device=dev, dtype=torch.float32)
+    ctx_new = torch.empty(n, Cw, device=dev, dtype=torch.int32)
+    check(_lib.lib().eamd_ngram_score(
+        ptr(lm.tok2word), ptr(lm.uni_tok), ptr(lm.node_bo), ptr(lm.child_start), ptr(lm.child_word), ptr(lm.child_node),
+        ptr(lm.succ_start), ptr(lm.succ_tok), ptr(lm.succ_lp), lm.node_bo.numel(), V, lm.order, lm.bos, lm.unk,
+        ptr(ctx_prev) if Cw else None, C.c_int64(ctx_prev.stride(0) if Cw else 0), ptr(tok), C.c_int64(tok.stride(0) if n > 1 else 1),
+        int(bool(first)), ptr(logp), ptr(ctx_new) if Cw else None, n, stream_ptr()), "eamd_ngram_score")
+    return logp, ctx_new
+
+
 # ---- CTC -----------------------------------------------------------------------------------------
 def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True, time_major=False):
     """acts [B,T,V] raw activations (time_major: [T,B,V], warp-ctc's layout - read in place through the entry point's

@@ -995,6 +995,25 @@ int64_t eamd_edit_distance_workspace_bytes(int B, int lda, int ldb);
 int eamd_edit_distance(const int64_t* a, int lda, const int32_t* alen, const int64_t* b, int ldb, const int32_t* blen,
                        int32_t* dist, void* workspace, int64_t workspace_bytes, int B, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * n-gram LM shallow fusion (reference: espnet/nets/scorers/ngram.py:12-102), csrc/ngram.hip.
+ * ------------------------------------------------------------------------------------------ */
+/* logp [n, V] = log10 p(word(v) | context) of an ARPA back-off model of order N <= 8 for n hypotheses, one workgroup each.
+ * Tables (espnet_amd/nets/ngram.py, ArpaLM): tok2word [V] token id -> LM word id; uni_tok [V] unigram log10-prob by token id;
+ * a trie of contexts, most recent word first, of n_nodes nodes (node 0 = the empty context): node_bo [n_nodes] back-off
+ * weights, child_start [n_nodes + 1] ranges into child_word / child_node (edges of a node sorted by word), succ_start
+ * [n_nodes + 1] ranges into succ_tok / succ_lp (the n-grams that extend the node's context, expanded to token ids in [0, V)).
+ * ctx_prev [n, N - 1] int32 (row stride ctx_ld elements, 0 = one row shared by all): word ids, most recent first, -1 = empty.
+ * tok: the newest token of row r at tok[r * tok_ld] (a column of the int64 prefix matrix); an id outside [0, V) is the word
+ * `unk`.  first != 0: the newest word is `bos` whatever the token.  ctx_new [n, N - 1] = (newest word, ctx_prev[0 .. N-3]).
+ * The walk along ctx_new stops at the first -1 or unknown context (depth D); acc_j = sum_{i=j+1..D} node_bo[node_i];
+ * logp[v] = uni_tok[v] + acc_0, then for j = 1 .. D in this order logp[t] = lp + acc_j over the successors of node_j.
+ * N == 1: ctx_prev / ctx_new may be NULL.  N > 8: EAMD_EUNSUPPORTED. */
+int eamd_ngram_score(const int32_t* tok2word, const float* uni_tok, const float* node_bo, const int32_t* child_start,
+                     const int32_t* child_word, const int32_t* child_node, const int32_t* succ_start, const int32_t* succ_tok,
+                     const float* succ_lp, int n_nodes, int V, int N, int bos, int unk, const int32_t* ctx_prev, int64_t ctx_ld,
+                     const int64_t* tok, int64_t tok_ld, int first, float* logp, int32_t* ctx_new, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
