@@ -120,6 +120,7 @@ SYMBOLS = [
     "eamd_joint_fwd", "eamd_joint_bwd", "eamd_rnnt_workspace", "eamd_rnnt_loss", "eamd_rnnt_grad", "eamd_rnnt_node_stats", "eamd_rnnt_node_stats_part", "eamd_rnnt_row_coef", "eamd_rnnt_alpha_beta", "eamd_rnnt_node_grad",
     "eamd_conv3x3_c1_fwd", "eamd_conv3x3_c1_bwd_w_workspace", "eamd_conv3x3_c1_bwd_w", "eamd_attloc_fwd", "eamd_attloc_bwd_energy", "eamd_attloc_bwd_workspace", "eamd_attloc_bwd_energy_conv", "eamd_attloc_bwd_conv",
     "eamd_att_dot_energy_fwd", "eamd_att_dot_energy_bwd", "eamd_att_ctx_fwd", "eamd_att_ctx_bwd",
+    "eamd_bf_workspace_bytes", "eamd_bf_psd", "eamd_bf_psd_bwd", "eamd_bf_mvdr", "eamd_bf_mvdr_bwd", "eamd_bf_apply", "eamd_bf_apply_bwd",
 ]
 
 
@@ -142,6 +143,7 @@ def lib():
         _lib.eamd_conv1_bwd_w_workspace.restype = C.c_int64
         _lib.eamd_lstm_seq_sync_bytes.restype = C.c_int64
         _lib.eamd_conv3x3_c1_bwd_w_workspace.restype = C.c_int64
+        _lib.eamd_bf_workspace_bytes.restype = C.c_int64
         for s in SYMBOLS:
             getattr(_lib, s)  # AttributeError here = header/library mismatch
     return _lib

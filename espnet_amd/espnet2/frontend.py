@@ -1,8 +1,12 @@
 """Log-mel frontend on the device: waveform -> STFT -> power spectrum -> mel filterbank -> log.
 
-reference: espnet2/asr/frontend/default.py:18-133 (DefaultFrontend with frontend_conf's WPE / beamformer switched
-off, its default), espnet2/layers/stft.py:16-111 (Stft over torch.stft), espnet2/layers/log_mel.py:8-75 (LogMel over
-librosa.filters.mel).  Same class names, constructor arguments and `forward(input, input_lengths) -> (feats, lens)`.
+reference: espnet2/asr/frontend/default.py:18-133 (DefaultFrontend), espnet2/layers/stft.py:16-111 (Stft over torch.stft),
+espnet2/layers/log_mel.py:8-75 (LogMel over librosa.filters.mel).  Same class names, constructor arguments and
+`forward(input, input_lengths) -> (feats, lens)`.
+
+frontend_conf with use_beamformer builds the mask-based MVDR beamformer of nets/frontends (default.py:58-94): a
+multi-channel waveform (B, L, C) then goes Stft.forward -> Frontend -> power spectrum -> LogMel.  WPE is refused.  Without
+an enabled frontend_conf, and for single-channel input, the path below is unchanged.
 
 MI355X mapping: the DFT of all frames is ONE fp32 MFMA GEMM - the reflect-padded waveform is read in place as
 overlapping rows (leading dimension = hop length), the window is folded into the [2F, n_fft] basis - followed by one
@@ -19,6 +23,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from ..nets.frontends.frontend import Frontend
 from ..nets.modules import make_pad_mask
 
 try:  # pragma: no cover - only when the reference package is importable
@@ -191,8 +196,17 @@ class LogMel(torch.nn.Module):
 
 
 class DefaultFrontend(AbsFrontend):
-    """Stft -> power spectrum -> LogMel.  frontend_conf (WPE / MVDR beamformer of espnet/nets/pytorch_backend/frontends)
-    is speech enhancement, outside this path: only its switched-off default is accepted."""
+    """Stft -> [Frontend: MVDR beamformer] -> power spectrum -> LogMel.
+
+    frontend_conf: the keyword arguments of nets.frontends.frontend.Frontend (use_beamformer, btype, blayers, bunits,
+    bprojs, bnmask, badim, ref_channel, bdropout_rate); use_wpe=True raises NotImplementedError.  With use_beamformer a
+    3-D input (B, L, C) is beamformed to one channel (in training mode Frontend draws, as the reference does, between
+    beamforming and passing the channels through, of which one is then picked at random).  None or all switches off:
+    `frontend` is None and a 3-D input is reduced to one channel before the STFT, as before.
+
+    The features carry no gradient back to the front-end (log-mel, SpecAug, MVN and the subsampling convolution have no
+    input gradient), so in training mode an enabled beamformer must be frozen (every parameter requires_grad=False);
+    the beamformer by itself (nets.frontends) is differentiable for spectrum-level training."""
 
     def __init__(self, fs=16000, n_fft=512, win_length=None, hop_length=128, window="hann", center=True,
                  normalized=False, onesided=True, n_mels=80, fmin=None, fmax=None, htk=False, frontend_conf=None):
@@ -200,18 +214,38 @@ class DefaultFrontend(AbsFrontend):
         if isinstance(fs, str):
             mult = {"k": 1000, "m": 1000000}.get(fs[-1].lower())
             fs = int(float(fs[:-1]) * mult) if mult else int(fs)
-        if frontend_conf is not None and (frontend_conf.get("use_wpe") or frontend_conf.get("use_beamformer")):
-            raise NotImplementedError("WPE / beamformer enhancement is outside the hot-path scope")
         self.stft = Stft(n_fft=n_fft, win_length=win_length, hop_length=hop_length, center=center, window=window,
                          normalized=normalized, onesided=onesided)
-        self.frontend = None
+        if frontend_conf is not None and (frontend_conf.get("use_wpe") or frontend_conf.get("use_beamformer")):
+            self.frontend = Frontend(idim=n_fft // 2 + 1, **frontend_conf)
+        else:
+            self.frontend = None
         self.logmel = LogMel(fs=fs, n_fft=n_fft, n_mels=n_mels, fmin=fmin, fmax=fmax, htk=htk)
         self.n_mels = n_mels
 
     def output_size(self):
         return self.n_mels
 
+    def _enhanced(self, input, input_lengths):
+        """(B, L, C) waveform -> Stft.forward -> Frontend -> one channel -> power spectrum -> LogMel (default.py:76-116)"""
+        if self.training and any(p.requires_grad for p in self.frontend.parameters()):
+            raise NotImplementedError(
+                "training the beamformer jointly from the ASR loss is not implemented: nothing downstream of the front-end "
+                "(log-mel, SpecAug, MVN, the subsampling convolution) returns a gradient to the features.  Freeze the "
+                "front-end (requires_grad_(False) on DefaultFrontend.frontend) or train it separately at spectrum level")
+        spec, feats_lens = self.stft(input, torch.as_tensor(input_lengths).cpu())   # (B, T, C, F, 2), padded frames zero
+        with torch.no_grad():
+            h, _, _ = self.frontend(spec, feats_lens)
+            if h.dim() == 5:                                                         # default.py:96-105
+                ch = np.random.randint(h.size(2)) if self.training else 0
+                h = h[:, :, ch]
+            power = h[..., 0] ** 2 + h[..., 1] ** 2
+        feats, _ = self.logmel(power, feats_lens)
+        return feats, feats_lens
+
     def forward(self, input, input_lengths):
+        if self.frontend is not None and input.dim() == 3:
+            return self._enhanced(input, input_lengths)
         if input.dim() == 3:      # default.py:107-115: one channel, random in training, the first otherwise
             ch = np.random.randint(input.size(2)) if self.training else 0
             input = input[:, :, ch]

@@ -1,0 +1,62 @@
+"""DNN mask based MVDR beamformer (Ochiai et al. 2017, https://arxiv.org/abs/1703.04783).
+reference: espnet/nets/pytorch_backend/frontends/dnn_beamformer.py (same class names, constructor arguments and
+parameter names).  Spectra are float32 [B, T, C, F, 2] (Stft.forward's layout), see beamformer.py."""
+import torch
+
+from ... import functional as F_
+from ... import ops
+from ... import rnn_functional as R_
+from .beamformer import apply_beamforming_vector, get_mvdr_vector, get_power_spectral_density_matrix
+from .mask_estimator import MaskEstimator
+
+
+class DNN_Beamformer(torch.nn.Module):
+    def __init__(self, bidim, btype="blstmp", blayers=3, bunits=300, bprojs=320, bnmask=2, dropout_rate=0.0, badim=320,
+                 ref_channel: int = -1, beamformer_type="mvdr"):
+        super().__init__()
+        if bnmask != 2:
+            raise NotImplementedError("bnmask=%d: the multi-speaker beamformer (one MVDR filter per speaker mask) is not "
+                                      "implemented, only (speech, noise) masks" % bnmask)
+        self.mask = MaskEstimator(btype, bidim, blayers, bunits, bprojs, dropout_rate, nmask=bnmask)
+        self.ref = AttentionReference(bidim, badim)
+        self.ref_channel = ref_channel
+        self.nmask = bnmask
+        if beamformer_type != "mvdr":
+            raise ValueError("Not supporting beamformer_type={}".format(beamformer_type))
+        self.beamformer_type = beamformer_type
+
+    def forward(self, data, ilens, return_all=False):
+        """data [B,T,C,F,2], ilens [B] -> (enhanced [B,T,F,2], ilens, mask_speech [B,T,C,F]);
+        return_all: a dict of the intermediate results (psd_speech, psd_noise, u, ws) as a fourth value"""
+        B, T, C, F, _ = data.shape
+        logits = self.mask.logits(data, ilens)                                       # [2, B, C, Tm, F]
+        psd, feat = get_power_spectral_density_matrix(data, logits, return_feature=True)
+        if self.ref_channel < 0:
+            u, _ = self.ref(feat, ilens)
+        else:                                                                        # fixed reference microphone
+            u = torch.zeros(B, C, device=data.device, dtype=torch.float32)
+            u[:, self.ref_channel] = 1.0
+        ws = get_mvdr_vector(psd[0], psd[1], u)
+        enhanced = apply_beamforming_vector(ws, data)
+        with torch.no_grad():                                                        # the caller's view of the speech mask
+            mask_speech = torch.sigmoid(logits[0]).permute(0, 2, 1, 3)
+            if mask_speech.size(1) < T:
+                mask_speech = torch.nn.functional.pad(mask_speech, [0, 0, 0, 0, 0, T - mask_speech.size(1)], value=0)
+        if return_all:
+            return enhanced, ilens, mask_speech, dict(psd_speech=psd[0], psd_noise=psd[1], u=u, ws=ws)
+        return enhanced, ilens, mask_speech
+
+
+class AttentionReference(torch.nn.Module):
+    def __init__(self, bidim, att_dim):
+        super().__init__()
+        self.mlp_psd = torch.nn.Linear(bidim, att_dim)
+        self.gvec = torch.nn.Linear(att_dim, 1)
+
+    def forward(self, psd_feat, ilens, scaling: float = 2.0):
+        """psd_feat [B,C,F]: the amplitude of the speech PSD's off-diagonal row means, which the reference forms from
+        psd_in (dnn_beamformer.py:163-170) and eamd_bf_psd writes next to the PSD -> (u [B,C], ilens)"""
+        mlp_psd = F_.LinearFn.apply(psd_feat, self.mlp_psd.weight, self.mlp_psd.bias)
+        e = F_.LinearFn.apply(R_.ActFn.apply(mlp_psd, ops.ACT_TANH), self.gvec.weight, self.gvec.bias).squeeze(-1)
+        u = torch.softmax(scaling * e, dim=-1)                                       # [B, C]: C <= 8 numbers per utterance
+        return u, ilens

@@ -1892,6 +1892,111 @@ def ngram_score(lm, ctx_prev, tok, first=False):
     return logp, ctx_new
 
 
+# ---- MVDR beamforming front-end (csrc/beamformer.hip) ----------------------------------------------
+BF_PSD, BF_PSD_BWD, BF_MVDR_BWD, BF_APPLY_BWD = 0, 1, 2, 3
+BF_TCHUNK = 64               # EAMD_BF_TCHUNK: frames per workgroup of the kernels that split the time axis
+
+
+def _bf_f32(*ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.EamdError("beamformer kernels take contiguous float32 tensors, complex as a trailing (re, im) axis")
+
+
+def _bf_workspace(op, S, B, T, Cn, F, device):
+    n = _lib.lib().eamd_bf_workspace_bytes(op, S, B, T, Cn, F)
+    if n < 0:
+        raise _lib.EamdError(f"eamd_bf_workspace_bytes refused S={S} B={B} T={T} C={Cn} F={F} (2 <= C <= 8)")
+    return torch.empty(n // 4, device=device, dtype=torch.float32)
+
+
+def bf_psd(x, z, out=None):
+    """x [B,T,C,F,2], mask logits z [S,B,C,Tm,F] -> (psd [S,B,F,C,C,2], feat [B,C,F], nrm [S,B,F]); out: the same triple to
+    write into (eamd_bf_psd)"""
+    B, T, Cn, F, two = x.shape
+    S, Tm = z.shape[0], z.shape[3]
+    assert two == 2 and z.shape == (S, B, Cn, Tm, F) and Tm <= T
+    _bf_f32(x, z)
+    if out is None:
+        out = (torch.empty(S, B, F, Cn, Cn, 2, device=x.device, dtype=torch.float32), torch.empty(B, Cn, F, device=x.device, dtype=torch.float32),
+               torch.empty(S, B, F, device=x.device, dtype=torch.float32))
+    psd, feat, nrm = out
+    assert psd.shape == (S, B, F, Cn, Cn, 2) and feat.shape == (B, Cn, F) and nrm.shape == (S, B, F)
+    _bf_f32(psd, feat, nrm)
+    ws = _bf_workspace(BF_PSD, S, B, Tm, Cn, F, x.device)
+    check(_lib.lib().eamd_bf_psd(ptr(x), ptr(z), ptr(psd), ptr(feat), ptr(nrm), ptr(ws), S, B, T, Tm, Cn, F, stream_ptr()),
+          "eamd_bf_psd")
+    return psd, feat, nrm
+
+
+def bf_psd_bwd(x, z, psd, nrm, gpsd, gfeat, out=None):
+    """-> dz [S,B,C,Tm,F] (eamd_bf_psd_bwd); gpsd / gfeat: None = zero"""
+    B, T, Cn, F, _ = x.shape
+    S, Tm = z.shape[0], z.shape[3]
+    assert psd.shape == (S, B, F, Cn, Cn, 2) and nrm.shape == (S, B, F)
+    assert gpsd is None or gpsd.shape == psd.shape
+    assert gfeat is None or gfeat.shape == (B, Cn, F)
+    _bf_f32(x, z, psd, nrm, gpsd, gfeat)
+    dz = torch.empty_like(z) if out is None else out
+    assert dz.shape == z.shape
+    _bf_f32(dz)
+    ws = _bf_workspace(BF_PSD_BWD, S, B, Tm, Cn, F, x.device)
+    check(_lib.lib().eamd_bf_psd_bwd(ptr(x), ptr(z), ptr(psd), ptr(nrm), ptr(gpsd), ptr(gfeat), ptr(dz), ptr(ws), S, B, T, Tm,
+                                     Cn, F, stream_ptr()), "eamd_bf_psd_bwd")
+    return dz
+
+
+def bf_mvdr(psd_s, psd_n, u, out=None):
+    """psd_s, psd_n [B,F,C,C,2], u [B,C] -> w [B,F,C,2] (eamd_bf_mvdr)"""
+    B, F, Cn = psd_s.shape[:3]
+    assert psd_s.shape == (B, F, Cn, Cn, 2) and psd_n.shape == psd_s.shape and u.shape == (B, Cn)
+    _bf_f32(psd_s, psd_n, u)
+    w = torch.empty(B, F, Cn, 2, device=psd_s.device, dtype=torch.float32) if out is None else out
+    assert w.shape == (B, F, Cn, 2)
+    _bf_f32(w)
+    check(_lib.lib().eamd_bf_mvdr(ptr(psd_s), ptr(psd_n), ptr(u), ptr(w), B, F, Cn, stream_ptr()), "eamd_bf_mvdr")
+    return w
+
+
+def bf_mvdr_bwd(psd_s, psd_n, u, gw, out=None):
+    """-> (gpsd_s, gpsd_n [B,F,C,C,2], gu [B,C]) (eamd_bf_mvdr_bwd)"""
+    B, F, Cn = psd_s.shape[:3]
+    assert psd_n.shape == psd_s.shape and u.shape == (B, Cn) and gw.shape == (B, F, Cn, 2)
+    _bf_f32(psd_s, psd_n, u, gw)
+    gs, gn, gu = (torch.empty_like(psd_s), torch.empty_like(psd_n), torch.empty_like(u)) if out is None else out
+    assert gs.shape == psd_s.shape and gn.shape == psd_s.shape and gu.shape == u.shape
+    _bf_f32(gs, gn, gu)
+    ws = _bf_workspace(BF_MVDR_BWD, 1, B, 1, Cn, F, u.device)
+    check(_lib.lib().eamd_bf_mvdr_bwd(ptr(psd_s), ptr(psd_n), ptr(u), ptr(gw), ptr(gs), ptr(gn), ptr(gu), ptr(ws), B, F, Cn,
+                                      stream_ptr()), "eamd_bf_mvdr_bwd")
+    return gs, gn, gu
+
+
+def bf_apply(w, x, out=None):
+    """w [B,F,C,2], x [B,T,C,F,2] -> y [B,T,F,2] = sum_c conj(w) x (eamd_bf_apply)"""
+    B, T, Cn, F, _ = x.shape
+    assert w.shape == (B, F, Cn, 2)
+    _bf_f32(w, x)
+    y = torch.empty(B, T, F, 2, device=x.device, dtype=torch.float32) if out is None else out
+    assert y.shape == (B, T, F, 2)
+    _bf_f32(y)
+    check(_lib.lib().eamd_bf_apply(ptr(w), ptr(x), ptr(y), B, T, Cn, F, stream_ptr()), "eamd_bf_apply")
+    return y
+
+
+def bf_apply_bwd(gy, x, out=None):
+    """gy [B,T,F,2], x [B,T,C,F,2] -> gw [B,F,C,2] (eamd_bf_apply_bwd)"""
+    B, T, Cn, F, _ = x.shape
+    assert gy.shape == (B, T, F, 2)
+    _bf_f32(gy, x)
+    gw = torch.empty(B, F, Cn, 2, device=x.device, dtype=torch.float32) if out is None else out
+    assert gw.shape == (B, F, Cn, 2)
+    _bf_f32(gw)
+    ws = _bf_workspace(BF_APPLY_BWD, 1, B, T, Cn, F, x.device)
+    check(_lib.lib().eamd_bf_apply_bwd(ptr(gy), ptr(x), ptr(gw), ptr(ws), B, T, Cn, F, stream_ptr()), "eamd_bf_apply_bwd")
+    return gw
+
+
 # ---- CTC -----------------------------------------------------------------------------------------
 def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True, time_major=False):
     """acts [B,T,V] raw activations (time_major: [T,B,V], warp-ctc's layout - read in place through the entry point's

@@ -1014,6 +1014,40 @@ int eamd_ngram_score(const int32_t* tok2word, const float* uni_tok, const float*
                      const float* succ_lp, int n_nodes, int V, int N, int bos, int unk, const int32_t* ctx_prev, int64_t ctx_ld,
                      const int64_t* tok, int64_t tok_ld, int first, float* logp, int32_t* ctx_new, int n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask-based MVDR beamforming front-end (reference: espnet/nets/pytorch_backend/frontends/beamformer.py:6-84,
+ * dnn_beamformer.py:163-170), csrc/beamformer.hip.  All fp32; a complex number is an interleaved (re, im) pair with
+ * frequency the fastest axis, as Stft.forward writes it.  2 <= C <= 8 channels (anything else: EAMD_EUNSUPPORTED).
+ * No atomics: every reduction over time is chunk partials in a workspace plus an ordered sum, the same bits on
+ * every launch.  A complex gradient g is the tensor with dL = Re sum conj(g) dv (PyTorch's convention), stored as
+ * its value is.  NULL or non-positive arguments: EAMD_EINVAL before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define EAMD_BF_TCHUNK 64        /* frames per workgroup of the kernels that split the time axis */
+enum { EAMD_BF_PSD = 0, EAMD_BF_PSD_BWD = 1, EAMD_BF_MVDR_BWD = 2, EAMD_BF_APPLY_BWD = 3 };
+/* bytes of the workspace of entry point `op` (for EAMD_BF_PSD / _PSD_BWD, T is the mask length Tm; S is ignored by the
+ * last two); negative for arguments the entry point would refuse */
+int64_t eamd_bf_workspace_bytes(int op, int S, int B, int T, int C, int F);
+/* x [B,T,C,F,2]; z [S,B,C,Tm,F] mask LOGITS (Tm <= T).  Per (s, b, f):  m[t] = mean_c sigmoid(z[s,b,c,t,f]) for t < Tm and
+ * 0 for Tm <= t < T;  n = sum_t m[t] + 1e-15 over ALL Tm frames (the reference does not zero the masks of frames past an
+ * utterance's length, mask_estimator.py:67);  psd [S,B,F,C,C,2] = sum_t m[t] x_t x_t^H / n, exactly Hermitian;
+ * nrm [S,B,F] = n (kept for the backward);  feat [B,C,F] = |sum_{e != c} psd[0,b,f,c,e]| / (C - 1). */
+int eamd_bf_psd(const float* x, const float* z, float* psd, float* feat, float* nrm, void* workspace, int S, int B, int T,
+                int Tm, int C, int F, void* stream);
+/* dz [S,B,C,Tm,F] from gpsd [S,B,F,C,C,2] and gfeat [B,C,F] (either may be NULL = zero), the sigmoid's derivative
+ * included; psd / nrm as eamd_bf_psd wrote them.  x gets no gradient.  A feature that is exactly 0 passes no gradient.
+ * Two passes over x and z: the mean sum_t m[t] g[t] / n that is subtracted from every frame's g[t] = x_t^H H x_t / n is
+ * formed from the same fp32 g[t], so that sums of dz over time keep the accuracy of an fp32 autograd. */
+int eamd_bf_psd_bwd(const float* x, const float* z, const float* psd, const float* nrm, const float* gpsd, const float* gfeat,
+                    float* dz, void* workspace, int S, int B, int T, int Tm, int C, int F, void* stream);
+/* psd_s, psd_n [B,F,C,C,2], u [B,C] real -> w [B,F,C,2]:  A = psd_n + 1e-15 I, N = A^-1 psd_s (Gauss-Jordan, partial
+ * pivoting), w = N u / (trace(N) + 1e-15).  psd_s == 0 and psd_n == 0 give exactly 0. */
+int eamd_bf_mvdr(const float* psd_s, const float* psd_n, const float* u, float* w, int B, int F, int C, void* stream);
+int eamd_bf_mvdr_bwd(const float* psd_s, const float* psd_n, const float* u, const float* gw, float* gpsd_s, float* gpsd_n,
+                     float* gu, void* workspace, int B, int F, int C, void* stream);
+/* y [B,T,F,2] = sum_c conj(w[b,f,c]) x[b,t,c,f];  backward: gw [B,F,C,2] = sum_t conj(gy[b,t,f]) x[b,t,c,f] */
+int eamd_bf_apply(const float* w, const float* x, float* y, int B, int T, int C, int F, void* stream);
+int eamd_bf_apply_bwd(const float* gy, const float* x, float* gw, void* workspace, int B, int T, int C, int F, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
