@@ -121,6 +121,7 @@ SYMBOLS = [
     "eamd_conv3x3_c1_fwd", "eamd_conv3x3_c1_bwd_w_workspace", "eamd_conv3x3_c1_bwd_w", "eamd_attloc_fwd", "eamd_attloc_bwd_energy", "eamd_attloc_bwd_workspace", "eamd_attloc_bwd_energy_conv", "eamd_attloc_bwd_conv",
     "eamd_att_dot_energy_fwd", "eamd_att_dot_energy_bwd", "eamd_att_ctx_fwd", "eamd_att_ctx_bwd",
     "eamd_bf_workspace_bytes", "eamd_bf_psd", "eamd_bf_psd_bwd", "eamd_bf_mvdr", "eamd_bf_mvdr_bwd", "eamd_bf_apply", "eamd_bf_apply_bwd",
+    "eamd_ft_logmel_fwd", "eamd_ft_logmel_bwd", "eamd_ft_mvn_fwd", "eamd_ft_mvn_bwd", "eamd_conv3x3_c1_bwd_x",
 ]
 
 

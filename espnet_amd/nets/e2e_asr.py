@@ -12,6 +12,8 @@ import torch
 from .. import functional as F_
 from .. import ops
 from .asr_interface import ASRInterface
+from .frontends.feature_transform import feature_transform_for
+from .frontends.frontend import frontend_for
 from .modules import CTC
 from .rnn.attentions import att_for
 from .rnn.decoders import decoder_for
@@ -57,8 +59,29 @@ def set_forget_bias_to_one(bias):
     bias.data[n // 4: n // 2].fill_(1.0)
 
 
+def to_spectrum(x, device=None):
+    """the input forms of a frontend model (what the reference's to_torch_tensor accepts) -> float32 with a trailing
+    (re, im) axis: a complex tensor or numpy array, a dict with "real" and "imag", or a float tensor that already carries
+    the axis"""
+    if isinstance(x, dict):
+        if "real" not in x or "imag" not in x:
+            raise ValueError("has 'real' and 'imag' keys: {}".format(list(x)))
+        x = torch.stack([torch.as_tensor(x["real"]), torch.as_tensor(x["imag"])], dim=-1)
+    elif isinstance(x, np.ndarray):
+        x = torch.from_numpy(x)
+    if not torch.is_tensor(x):
+        raise ValueError("a frontend model takes a complex spectrum (tensor, numpy array or real/imag dict), not %r" % type(x))
+    if x.is_complex():
+        x = torch.view_as_real(x.resolve_conj())
+    elif x.size(-1) != 2:
+        raise ValueError("a real tensor must carry the trailing (re, im) axis, got shape {}".format(tuple(x.shape)))
+    x = x.to(torch.float32)
+    return x.contiguous() if device is None else x.to(device).contiguous()
+
+
 class E2E(ASRInterface, torch.nn.Module):
-    """reference: e2e_asr.py:57-338 (single encoder, no frontend)"""
+    """reference: e2e_asr.py:57-338 (single encoder; use_frontend: the MVDR beamformer and the espnet1 feature transform
+    in front of it, trained from the ASR loss)"""
 
     def __init__(self, idim, odim, args):
         torch.nn.Module.__init__(self)
@@ -76,9 +99,12 @@ class E2E(ASRInterface, torch.nn.Module):
         self.subsample = get_subsample(args, mode="asr", arch="rnn")
         if getattr(args, "lsm_type", ""):
             raise NotImplementedError("unigram label smoothing needs the training json (out of the hot-path scope)")
-        if getattr(args, "use_frontend", False):
-            raise NotImplementedError("speech-enhancement frontend is out of the hot-path scope")
-        self.frontend = None
+        if getattr(args, "use_frontend", False):      # e2e_asr.py:141-146: idim counts the bins of the spectrum
+            self.frontend = frontend_for(args, idim)
+            self.feature_transform = feature_transform_for(args, (idim - 1) * 2)
+            idim = args.n_mels
+        else:
+            self.frontend = None
         self.enc = encoder_for(args, idim, self.subsample)
         self.ctc = CTC(odim, args.eprojs, args.dropout_rate, ctc_type=args.ctc_type)
         self.att = att_for(args)
@@ -110,8 +136,23 @@ class E2E(ASRInterface, torch.nn.Module):
         for i in range(len(self.dec.decoder)):
             set_forget_bias_to_one(self.dec.decoder[i].bias_ih)
 
+    def _features(self, xs_pad, ilens):
+        """frontend -> feature transform (e2e_asr.py:215-217): a spectrum [B,T,C,F] in any form to_spectrum takes ->
+        (log-mel features on the parameters' device, lengths).  In training the frontend draws on the host per call
+        (pass-through or beamformer, then the channel), so such a step runs eagerly: a captured and replayed graph would
+        freeze the draw."""
+        dev = next(self.parameters()).device
+        if self.training and dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a training step with a frontend draws on the host at every call: run it eagerly, a captured "
+                               "graph would replay one frozen draw")
+        xs_pad = to_spectrum(xs_pad, dev)
+        hs_pad, hlens, _ = self.frontend(xs_pad, ilens)
+        return self.feature_transform(hs_pad, hlens)
+
     def forward(self, xs_pad, ilens, ys_pad):
         """xs_pad (B,Tmax,idim), ilens (B), ys_pad (B,Lmax) -> loss (e2e_asr.py:205-338)"""
+        if self.frontend is not None:
+            xs_pad, ilens = self._features(xs_pad, ilens)
         if xs_pad.is_cuda:
             if self.training and torch.is_grad_enabled():
                 ops.zero_arena_begin(xs_pad.device)      # the decoder loop's zero-filled buffers: one fill per step
@@ -201,9 +242,13 @@ class E2E(ASRInterface, torch.nn.Module):
         self.eval()
         ops.zero_arena_off()                    # recognition: no slices of a training step's zero arena
         p = next(self.parameters())
-        h = torch.as_tensor(x, device=p.device, dtype=p.dtype).unsqueeze(0)
         with torch.no_grad():
-            hs, _, _ = self.enc(h, [x.shape[0]])
+            if self.frontend is not None:
+                x = to_spectrum(x)
+                h, hlens = self._features(x.unsqueeze(0), [x.shape[0]])
+            else:
+                h, hlens = torch.as_tensor(x, device=p.device, dtype=p.dtype).unsqueeze(0), [x.shape[0]]
+            hs, _, _ = self.enc(h, hlens)
         return hs.squeeze(0)
 
     @ops.inference_call
@@ -212,10 +257,15 @@ class E2E(ASRInterface, torch.nn.Module):
         self.eval()
         ops.zero_arena_off()
         p = next(self.parameters())
-        ilens = [int(x.shape[0]) for x in xs]
-        feats = [torch.as_tensor(x, device=p.device, dtype=p.dtype) for x in xs]
+        if self.frontend is not None:
+            feats = [to_spectrum(x, p.device) for x in xs]
+        else:
+            feats = [torch.as_tensor(x, device=p.device, dtype=p.dtype) for x in xs]
+        ilens = [int(x.shape[0]) for x in feats]
         xs_pad = torch.nn.utils.rnn.pad_sequence(feats, batch_first=True)
         with torch.no_grad():
+            if self.frontend is not None:
+                xs_pad, ilens = self._features(xs_pad, ilens)
             hs_pad, hlens, _ = self.enc(xs_pad, ilens)
             if recog_args.ctc_weight > 0.0:
                 lpz, normalize = self.ctc.log_softmax(hs_pad), False
@@ -223,6 +273,24 @@ class E2E(ASRInterface, torch.nn.Module):
                 lpz, normalize = None, True
             return self.dec.recognize_beam_batch(hs_pad, hlens, lpz, recog_args, char_list, rnnlm, normalize_score=normalize,
                                                  ctc_scoring_num=ctc_scoring_num)
+
+    @ops.inference_call
+    def enhance(self, xs):
+        """xs list of spectra (T_b, C, F) -> (enhanced (B,T,F,2), speech mask (B,T,C,F), ilens) as numpy arrays
+        (e2e_asr.py:447-470; the model's training mode is restored)"""
+        if self.frontend is None:
+            raise RuntimeError("Frontend does't exist")
+        prev = self.training
+        self.eval()
+        p = next(self.parameters())
+        xs = [to_spectrum(x, p.device) for x in xs]
+        ilens = np.fromiter((x.shape[0] for x in xs), dtype=np.int64)
+        xs_pad = torch.nn.utils.rnn.pad_sequence(xs, batch_first=True)
+        with torch.no_grad():
+            enhanced, _, mask = self.frontend(xs_pad, ilens)
+        if prev:
+            self.train()
+        return enhanced.cpu().numpy(), None if mask is None else mask.cpu().numpy(), ilens
 
     @ops.inference_call
     def recognize(self, x, recog_args, char_list=None, rnnlm=None):

@@ -2408,6 +2408,17 @@ def conv3x3_c1_bwd_w(dy, x, dw, db, B, T, F, Cc):
                                   1 if dy.dtype == torch.bfloat16 else 0, stream_ptr()), "eamd_conv3x3_c1_bwd_w")
 
 
+def conv3x3_c1_bwd_x(dy, w, B, T, F, Cc, out=None):
+    """dy [B,T,F,C] fp32 / bf16, w [C,1,3,3] -> dx [B,T,F] fp32"""
+    assert dy.numel() == B * T * F * Cc and w.numel() == Cc * 9 and dy.is_contiguous() and w.is_contiguous()
+    assert dy.dtype in (torch.float32, torch.bfloat16) and w.dtype == torch.float32
+    dx = torch.empty(B, T, F, device=dy.device, dtype=torch.float32) if out is None else out
+    assert dx.shape == (B, T, F) and dx.dtype == torch.float32 and dx.is_contiguous()
+    check(_lib.lib().eamd_conv3x3_c1_bwd_x(ptr(dy), ptr(w), ptr(dx), B, T, F, Cc, 1 if dy.dtype == torch.bfloat16 else 0,
+                                           stream_ptr()), "eamd_conv3x3_c1_bwd_x")
+    return dx
+
+
 def joint_fwd(enc, dec, act, out_dtype=torch.float32):
     B, T, J = enc.shape
     U = dec.shape[1]
@@ -2796,6 +2807,72 @@ def logmel(spec, ld, rows_per_utt, melmat, lo, hi, flens, B, T, F, log_scale=1.0
                                  ptr(flens) if flens is not None else None, ptr(out), B, T, F, M, C.c_float(log_scale),
                                  int(power_input), stream_ptr()), "eamd_logmel")
     return out
+
+
+# ---- espnet1 feature transform (csrc/feature_transform.hip; see include/espnet_amd.h) ---------------------------------
+def _ft_f32(*ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.EamdError("feature-transform kernels take contiguous float32 tensors")
+
+
+def _ft_out(out, shape, device):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    assert tuple(out.shape) == tuple(shape)
+    _ft_f32(out)
+    return out
+
+
+def ft_logmel_fwd(spec, melmat, lo, hi, lens, out=None):
+    """spec [B,T,F,2], melmat [F,M], lo/hi [M] int32, lens [B] int32 -> log(|spec|^2 melmat + 1e-20) [B,T,M], padded frames 0"""
+    B, T, F, two = spec.shape
+    M = melmat.shape[1]
+    assert two == 2 and melmat.shape[0] == F and lo.numel() == M and hi.numel() == M and lens.numel() == B
+    assert lo.dtype == torch.int32 and hi.dtype == torch.int32 and lens.dtype == torch.int32
+    _ft_f32(spec, melmat)
+    out = _ft_out(out, (B, T, M), spec.device)
+    check(_lib.lib().eamd_ft_logmel_fwd(ptr(spec), ptr(melmat), ptr(lo), ptr(hi), ptr(lens), ptr(out), B, T, F, M,
+                                        stream_ptr()), "eamd_ft_logmel_fwd")
+    return out
+
+
+def ft_logmel_bwd(spec, g, melmat, lo, hi, mlo, mhi, lens, out=None):
+    """gradient of ft_logmel_fwd with respect to spec: [B,T,F,2]; mlo/mhi [F] int32 = the filters that cover each bin"""
+    B, T, F, two = spec.shape
+    M = melmat.shape[1]
+    assert two == 2 and g.shape == (B, T, M) and melmat.shape[0] == F and mlo.numel() == F and mhi.numel() == F
+    assert all(t.dtype == torch.int32 for t in (lo, hi, mlo, mhi, lens)) and lo.numel() == M and hi.numel() == M
+    _ft_f32(spec, g, melmat)
+    gspec = _ft_out(out, spec.shape, spec.device)
+    check(_lib.lib().eamd_ft_logmel_bwd(ptr(spec), ptr(g), ptr(melmat), ptr(lo), ptr(hi), ptr(mlo), ptr(mhi), ptr(lens),
+                                        ptr(gspec), B, T, F, M, stream_ptr()), "eamd_ft_logmel_bwd")
+    return gspec
+
+
+def ft_mvn_fwd(x, lens, bias=None, scale=None, apply_utt=True, norm_means=True, norm_vars=False, eps=1e-20, out=None):
+    """x [B,T,M] -> GlobalMVN (bias, scale given) then utterance_mvn (apply_utt) of the espnet1 feature transform"""
+    B, T, M = x.shape
+    _ft_f32(x, bias, scale)
+    assert lens is None or (lens.dtype == torch.int32 and lens.numel() == B)
+    y = _ft_out(out, x.shape, x.device)
+    ws = torch.empty(2 * B * M, device=x.device, dtype=torch.float32) if apply_utt else None
+    check(_lib.lib().eamd_ft_mvn_fwd(ptr(x), ptr(y), ptr(lens), ptr(bias), ptr(scale), ptr(ws), int(bool(apply_utt)),
+                                     int(bool(norm_means)), int(bool(norm_vars)), C.c_float(eps), B, T, M, stream_ptr()),
+          "eamd_ft_mvn_fwd")
+    return y
+
+
+def ft_mvn_bwd(gy, lens, scale=None, apply_utt=True, out=None):
+    """gradient of ft_mvn_fwd(norm_vars=False) with respect to x"""
+    B, T, M = gy.shape
+    _ft_f32(gy, scale)
+    assert lens is None or (lens.dtype == torch.int32 and lens.numel() == B)
+    gx = _ft_out(out, gy.shape, gy.device)
+    ws = torch.empty(B * M, device=gy.device, dtype=torch.float32) if apply_utt else None
+    check(_lib.lib().eamd_ft_mvn_bwd(ptr(gy), ptr(gx), ptr(lens), ptr(scale), ptr(ws), int(bool(apply_utt)), B, T, M,
+                                     stream_ptr()), "eamd_ft_mvn_bwd")
+    return gx
 
 
 def unfold1d(x, B, T, Cc, k):

@@ -417,7 +417,9 @@ class VGG2LFn(torch.autograd.Function):
         dy2 = ops.act_bwd_any(dy2, y2, ACT_RELU)
         dy1 = _conv3x3_bwd(dy2.view(-1, C1), y1, wd12, sink.buf(2), sink.buf(3), B, T, F, C1, C1, y1.view(-1, C1))
         ops.conv3x3_c1_bwd_w(dy1, x, sink.buf(0), sink.buf(1), B, T, F, C1)
-        return (None,) + sink.results()
+        # features that come out of a trainable front-end (E2E(use_frontend=True)) take the input gradient as well
+        dx = ops.conv3x3_c1_bwd_x(dy1, ctx.pr[0].contiguous(), B, T, F, C1) if ctx.needs_input_grad[0] else None
+        return (dx,) + sink.results()
 
 
 # =================================================================================================
@@ -642,3 +644,46 @@ class JointRNNTLossFn(torch.autograd.Function):
             de[b, t0:t0 + nt].copy_(de_c[0])
             ops.axpby(dd[b], dd_c[0], 1.0, 1.0, out=dd[b])
         return (de, dd) + sink.results() + (None,) * 7
+
+
+# =================================================================================================
+# espnet1 feature transform between the beamformer and the encoder (frontends/feature_transform.py):
+# the chain through which the ASR loss reaches the spectrum, hence the beamformer's mask estimator
+# =================================================================================================
+class FtLogMelFn(torch.autograd.Function):
+    """spec [B,T,F,2] -> log(|spec|^2 melmat + 1e-20) [B,T,M], padded frames 0 (feature_transform.py:67,123-132);
+    lo/hi [M] and mlo/mhi [F]: the non-zero ranges of melmat's columns and rows (int32)"""
+
+    @staticmethod
+    def forward(ctx, spec, melmat, lo, hi, mlo, mhi, lens):
+        spec = spec.contiguous()
+        ctx.save_for_backward(spec, melmat, lo, hi, mlo, mhi, lens)
+        return ops.ft_logmel_fwd(spec, melmat, lo, hi, lens)
+
+    @staticmethod
+    def backward(ctx, g):
+        spec, melmat, lo, hi, mlo, mhi, lens = ctx.saved_tensors
+        gspec = ops.ft_logmel_bwd(spec, g.contiguous(), melmat, lo, hi, mlo, mhi, lens) if ctx.needs_input_grad[0] else None
+        return (gspec,) + (None,) * 6
+
+
+class FtMvnFn(torch.autograd.Function):
+    """GlobalMVN (bias / scale, or None) then utterance_mvn (apply_utt) on [B,T,M], feature_transform.py:180-247 to the
+    letter; the gradient exists without norm_vars only (the reference's own backward fails with it)"""
+
+    @staticmethod
+    def forward(ctx, x, lens, bias, scale, apply_utt, norm_means, norm_vars, eps):
+        x = x.contiguous()
+        ctx.save_for_backward(lens, scale)
+        ctx.cfg = (apply_utt, norm_vars)
+        return ops.ft_mvn_fwd(x, lens, bias, scale, apply_utt, norm_means, norm_vars, eps)
+
+    @staticmethod
+    def backward(ctx, gy):
+        lens, scale = ctx.saved_tensors
+        apply_utt, norm_vars = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        if apply_utt and norm_vars:
+            raise RuntimeError("utterance_mvn(norm_vars=True) has no backward")
+        return (ops.ft_mvn_bwd(gy.contiguous(), lens, scale, apply_utt),) + (None,) * 7

@@ -715,6 +715,30 @@ int eamd_logmel(const float* spec, int64_t ld, int64_t rows_per_utt, const float
                 const int32_t* hi, const int32_t* flens, float* out, int B, int T, int F, int M, float log_scale,
                 int power_input, void* stream);
 
+/* ---- espnet1 feature transform between the beamformer and the RNN encoder (csrc/feature_transform.hip) ----
+ * reference: espnet/nets/pytorch_backend/frontends/feature_transform.py:45-75,123-132,180-247.  fp32, no atomics.
+ * These differ from the espnet2 layers above (epsilon added instead of clamped; statistics over ALL T frames).
+ * spec [B,T,F,2] interleaved (re, im), contiguous (the beamformer's output); melmat [F,M]; lo/hi [M] bin range of each
+ * filter, mlo/mhi [F] filter range covering each bin; lens [B].
+ * fwd: out[b,t,m] = log(sum_f |spec|^2 melmat[f,m] + 1e-20), 0 for t >= lens[b].
+ * bwd: gspec[b,t,f] = 2 (re, im) sum_m melmat[f,m] g[b,t,m] / (mel[b,t,m] + 1e-20) with mel recomputed from spec; 0 for
+ *      t >= lens[b] and for a bin without power.  EAMD_EUNSUPPORTED when 4 (F [+ M]) floats of LDS exceed 64 KiB. */
+int eamd_ft_logmel_fwd(const float* spec, const float* melmat, const int32_t* lo, const int32_t* hi, const int32_t* lens,
+                       float* out, int B, int T, int F, int M, void* stream);
+int eamd_ft_logmel_bwd(const float* spec, const float* g, const float* melmat, const int32_t* lo, const int32_t* hi,
+                       const int32_t* mlo, const int32_t* mhi, const int32_t* lens, float* gspec, int B, int T, int F, int M,
+                       void* stream);
+/* GlobalMVN then utterance MVN, literally (both masked_fill calls of the reference are not in place):
+ *   z = (x + bias[m]) * scale[m] on every frame (bias / scale both NULL: z = x);
+ *   apply_utt: mean = sum over all T frames of z / lens[b]; without norm_vars y = z - mean (whatever norm_means is);
+ *   with norm_vars var = max(sum_T (z - mean)^2 / lens[b], eps) and y = (norm_means ? z - mean : z) / sqrt(var).
+ * bwd (norm_vars = 0 only): gx = scale * (gy - sum_T gy / lens[b]); without apply_utt gx = scale * gy.
+ * workspace: 2*B*M floats (fwd), B*M floats (bwd); needed with apply_utt only. */
+int eamd_ft_mvn_fwd(const float* x, float* y, const int32_t* lens, const float* bias, const float* scale, float* workspace,
+                    int apply_utt, int norm_means, int norm_vars, float eps, int B, int T, int M, void* stream);
+int eamd_ft_mvn_bwd(const float* gy, float* gx, const int32_t* lens, const float* scale, float* workspace, int apply_utt,
+                    int B, int T, int M, void* stream);
+
 /* ---- recurrent layers (RNN paths) ------------------------------
  * One LSTM step on gate pre-activations gates[B,4H] = x W_ih^T + b_ih + h W_hh^T + b_hh (the products are
  * eamd_gemm calls), gate order i,f,g,o as torch.nn.LSTM / LSTMCell.
@@ -810,6 +834,10 @@ int eamd_conv3x3_c1_fwd(const float* x, const float* w, const float* bias, void*
 int64_t eamd_conv3x3_c1_bwd_w_workspace(int B, int T, int C);
 int eamd_conv3x3_c1_bwd_w(const void* dy, const float* x, float* dw, float* db, float* workspace, int B, int T, int F,
                           int C, int dy_bf16, void* stream);
+/* ... and its input gradient: dx[b,t,f] = sum_c sum_{i,j} dy[b,t+1-i,f+1-j,c] w[c,i,j] (taps outside the plane skipped);
+ * dy [B,T,F,C] fp32 or bf16 (ReLU-masked), w [C,1,3,3], dx [B,T,F] fp32.  C % 4 == 0; one dy row plus 27 F floats of
+ * LDS (EAMD_EUNSUPPORTED otherwise). */
+int eamd_conv3x3_c1_bwd_x(const void* dy, const float* w, float* dx, int B, int T, int F, int C, int dy_bf16, void* stream);
 /* Location-aware attention, one decoder step.  reference: rnn/attentions.py:300-380 (AttLoc.forward).
  *   conv = Conv2d(1,C,(1,K))(att_prev) (K = 2*aconv_filts+1, no bias); e = gvec . tanh(W_att conv + pre_enc +
  *   dec_proj) + gb, -inf for t >= lens[b]; w = softmax(scaling * e); ctx = sum_t w * enc_h.
