@@ -114,7 +114,7 @@ SYMBOLS = [
     "eamd_dropout", "eamd_rng_advance", "eamd_dwconv_fwd", "eamd_dwconv_glu_fwd", "eamd_dwconv_glu_bwd_x", "eamd_dwconv_glu_bwd_w", "eamd_dwconv_bwd_x", "eamd_dwconv_bwd_w", "eamd_bn_nslab",
     "eamd_bn_stats", "eamd_bn_finalize", "eamd_bn_apply", "eamd_bn_bwd", "eamd_bn_stats_bounded", "eamd_bn_bwd_bounded", "eamd_mask_time", "eamd_conv1_fwd", "eamd_conv1_bwd_w_workspace", "eamd_conv1_bwd_w",
     "eamd_conv2_weight_prep", "eamd_conv2_weight_grad", "eamd_add_sos_eos", "eamd_ctc_collapse",
-    "eamd_ctc_workspace_bytes", "eamd_ctc_loss", "eamd_ctc_pit_workspace_bytes", "eamd_ctc_pit_loss", "eamd_ctc_align_workspace_bytes", "eamd_ctc_forced_align", "eamd_maskctc_seed", "eamd_maskctc_update", "eamd_text_units", "eamd_edit_distance_workspace_bytes", "eamd_edit_distance", "eamd_ngram_score", "eamd_ctc_prefix_score", "eamd_ctc_prefix_score_batch", "eamd_ctc_prefix_psi", "eamd_ctc_prefix_state", "eamd_grad_norm", "eamd_sched_step", "eamd_adam_step", "eamd_adadelta_step", "eamd_add_gradient_noise",
+    "eamd_ctc_workspace_bytes", "eamd_ctc_loss", "eamd_ctc_pit_workspace_bytes", "eamd_ctc_pit_loss", "eamd_ctc_align_workspace_bytes", "eamd_ctc_forced_align", "eamd_maskctc_seed", "eamd_maskctc_update", "eamd_text_units", "eamd_edit_distance_workspace_bytes", "eamd_edit_distance", "eamd_ngram_score", "eamd_ngram_score_pairs", "eamd_ctc_beam_workspace_bytes", "eamd_ctc_prefix_beam", "eamd_ctc_prefix_score", "eamd_ctc_prefix_score_batch", "eamd_ctc_prefix_psi", "eamd_ctc_prefix_state", "eamd_grad_norm", "eamd_sched_step", "eamd_adam_step", "eamd_adadelta_step", "eamd_add_gradient_noise",
     "eamd_specaug", "eamd_global_mvn", "eamd_utterance_mvn", "eamd_reflect_pad", "eamd_logmel", "eamd_unfold1d", "eamd_fold1d", "eamd_attloc_convmax_fwd", "eamd_attloc_convmax_bwd", "eamd_layernorm_bwd_drop",
     "eamd_lstm_cell_fwd", "eamd_lstm_cell_bwd", "eamd_lstm_step_fwd", "eamd_lstm_step_bwd", "eamd_lstm_seq_sync_bytes", "eamd_lstm_seq_fwd", "eamd_lstm_seq_bwd", "eamd_lstm_seq_status", "eamd_lstm_seq_status_merge", "eamd_gru_cell_fwd", "eamd_gru_cell_bwd", "eamd_maxpool2x2_fwd", "eamd_maxpool2x2_bwd", "eamd_mask_rows",
     "eamd_joint_fwd", "eamd_joint_bwd", "eamd_rnnt_workspace", "eamd_rnnt_loss", "eamd_rnnt_grad", "eamd_rnnt_node_stats", "eamd_rnnt_node_stats_part", "eamd_rnnt_row_coef", "eamd_rnnt_alpha_beta", "eamd_rnnt_node_grad",
@@ -145,6 +145,7 @@ def lib():
         _lib.eamd_lstm_seq_sync_bytes.restype = C.c_int64
         _lib.eamd_conv3x3_c1_bwd_w_workspace.restype = C.c_int64
         _lib.eamd_bf_workspace_bytes.restype = C.c_int64
+        _lib.eamd_ctc_beam_workspace_bytes.restype = C.c_int64
         for s in SYMBOLS:
             getattr(_lib, s)  # AttributeError here = header/library mismatch
     return _lib

@@ -17,6 +17,7 @@
 //              context overwrites the shorter one - the ORDER of the passes is the back-off rule.
 //   The row stays in global memory between the passes (V is unbounded; a pass is one coalesced sweep or a short scatter).
 #include "common.h"
+#include "ngram_query.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -129,9 +130,48 @@ __global__ __launch_bounds__(kThreads) void ngram_score_kernel(NgramArgs a) {
   }
 }
 
+// eamd_ngram_score_pairs: one lane per (context, token) pair (ngram_query.h)
+__global__ __launch_bounds__(kThreads) void ngram_pairs_kernel(NgramQueryTables g, const int32_t* __restrict__ ctx,
+                                                               const long long* __restrict__ tok, float* __restrict__ lp,
+                                                               int32_t* __restrict__ ctx_new, int n) {
+  const long r = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (r >= n) return;
+  int c[kNgramMaxCtx], node[kNgramMaxCtx + 1];
+  float acc[kNgramMaxCtx + 1];
+#pragma unroll
+  for (int i = 0; i < kNgramMaxCtx; ++i) c[i] = i < g.C ? ctx[r * g.C + i] : -1;
+  const int depth = ngram_walk(g, c, node, acc);
+  const long long t = tok[r];
+  const bool known = t >= 0 && t < g.V;
+  lp[r] = known ? ngram_point(g, depth, node, acc, (int)t) : -INFINITY;
+#pragma unroll
+  for (int i = 0; i < kNgramMaxCtx; ++i)
+    if (i < g.C) ctx_new[r * g.C + i] = i == 0 ? (known ? g.tok2word[t] : g.unk) : c[i - 1];
+}
+
 }  // namespace
 
 extern "C" {
+
+int eamd_ngram_score_pairs(const int32_t* tok2word, const float* uni_tok, const float* node_bo, const int32_t* child_start,
+                           const int32_t* child_word, const int32_t* child_node, const int32_t* succ_start,
+                           const int32_t* qsucc_tok, const float* qsucc_lp, int n_nodes, int V, int N, int unk,
+                           const int32_t* ctx, const int64_t* tok, float* lp, int32_t* ctx_new, int n, void* stream) {
+  if (!tok2word || !uni_tok || !node_bo || !child_start || !child_word || !child_node || !succ_start || !qsucc_tok || !qsucc_lp ||
+      !tok || !lp)
+    return EAMD_EINVAL;
+  if (n < 1 || V < 1 || N < 1 || n_nodes < 1) return EAMD_EINVAL;
+  if (N > kNgramMaxCtx + 1) return EAMD_EUNSUPPORTED;
+  if (N > 1 && (!ctx || !ctx_new)) return EAMD_EINVAL;
+  NgramQueryTables g;
+  g.tok2word = tok2word; g.uni_tok = uni_tok; g.node_bo = node_bo; g.child_start = child_start; g.child_word = child_word;
+  g.child_node = child_node; g.succ_start = succ_start; g.qsucc_tok = qsucc_tok; g.qsucc_lp = qsucc_lp;
+  g.n_nodes = n_nodes; g.V = V; g.C = N - 1; g.unk = unk;
+  hipLaunchKernelGGL(ngram_pairs_kernel, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream, g, ctx,
+                     (const long long*)tok, lp, ctx_new, n);
+  EAMD_LAUNCH_CHECK();
+  return EAMD_OK;
+}
 
 int eamd_ngram_score(const int32_t* tok2word, const float* uni_tok, const float* node_bo, const int32_t* child_start,
                      const int32_t* child_word, const int32_t* child_node, const int32_t* succ_start, const int32_t* succ_tok,

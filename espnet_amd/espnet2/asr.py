@@ -191,6 +191,9 @@ class CTC(torch.nn.Module):
     def forced_align_batch(self, hs_pad, hlens, ys_pad, blank_id=0):
         return self._ctc[0].forced_align_batch(hs_pad, hlens, ys_pad, blank_id)
 
+    def prefix_beam_search(self, hs_pad, hlens, **kw):
+        return self._ctc[0].prefix_beam_search(hs_pad, hlens, **kw)
+
 
 class ESPnetASRModel(AbsESPnetModel):
     """reference: espnet2/asr/espnet_model.py:35-290.  frontend = None (fbank features are the input) or

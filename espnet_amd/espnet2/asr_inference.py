@@ -14,6 +14,7 @@ from .. import ops
 
 from ..nets.batch_beam_search import BatchBeamSearch
 from ..nets.beam_search import BeamSearch, Hypothesis
+from ..nets.ctc_prefix_beam import CTCPrefixBeamSearch
 from ..nets.ctc_prefix_score import CTCPrefixScorer, LengthBonus
 from ..nets.scorer_interface import BatchScorerInterface
 
@@ -46,7 +47,23 @@ class CharTokenizer:
 class Speech2Text:
     def __init__(self, asr_model, lm=None, token_list=None, tokenizer=None, device="cuda", maxlenratio=0.0,
                  minlenratio=0.0, batch_size=1, beam_size=20, ctc_weight=0.5, lm_weight=1.0, penalty=0.0, nbest=1,
-                 graph_steps=False):
+                 graph_steps=False, ctc_search="label", ngram=None, ngram_weight=0.0, ctc_cand_size=None):
+        """ctc_search (not in the reference): "label" decodes through the label-synchronous BeamSearch whatever the weights;
+        "time" with ctc_weight == 1.0 runs the time-synchronous CTC prefix beam search (nets.ctc_prefix_beam) with an optional
+        n-gram LM (ngram: an ArpaLM or n-gram scorer, ngram_weight) and ctc_cand_size candidates per frame"""
+        if ctc_search not in ("label", "time"):
+            raise ValueError("ctc_search: 'label' or 'time', not %r" % (ctc_search,))
+        if ctc_search == "time" and ctc_weight != 1.0:
+            raise ValueError("ctc_search='time' is the pure-CTC search: ctc_weight must be 1.0, not %r" % (ctc_weight,))
+        if ctc_search == "label" and (ngram is not None or ctc_cand_size is not None):
+            raise ValueError("ngram / ctc_cand_size belong to ctc_search='time': the label-synchronous search would ignore them")
+        if ctc_search == "time" and lm is not None:
+            raise ValueError("ctc_search='time' fuses n-gram LMs only (ngram=): a neural lm is not fused time-synchronously")
+        self.ctc_search, self.ctc_prefix_beam = ctc_search, None
+        if ctc_search == "time":
+            self.ctc_prefix_beam = dict(beam_size=beam_size, cand_size=ctc_cand_size, nbest=min(nbest, beam_size), penalty=penalty,
+                                        ngram=ngram, ngram_weight=ngram_weight if ngram is not None else 0.0)
+            CTCPrefixBeamSearch(**self.ctc_prefix_beam)            # the limits are checked here, before any model work
         asr_model.to(device).eval()
         token_list = token_list if token_list is not None else getattr(asr_model, "token_list", None)
         vocab = len(token_list) if token_list is not None else asr_model.vocab_size
@@ -78,7 +95,12 @@ class Speech2Text:
         lengths = torch.full([1], speech.size(1), dtype=torch.long)
         enc, _ = self.asr_model.encode(speech=speech, speech_lengths=lengths)
         assert len(enc) == 1, len(enc)
-        nbest_hyps = self.beam_search(x=enc[0], maxlenratio=self.maxlenratio, minlenratio=self.minlenratio)
+        if self.ctc_search == "time":
+            hyps = self.asr_model.ctc.prefix_beam_search(enc, [enc.shape[1]], **self.ctc_prefix_beam)[0]
+            nbest_hyps = [Hypothesis(yseq=torch.tensor(h["yseq"], dtype=torch.long), score=h["score"], scores=dict(ctc=h["score"]),
+                                     states=dict()) for h in hyps]
+        else:
+            nbest_hyps = self.beam_search(x=enc[0], maxlenratio=self.maxlenratio, minlenratio=self.minlenratio)
         results = []
         for hyp in nbest_hyps[: self.nbest]:
             assert isinstance(hyp, Hypothesis), type(hyp)

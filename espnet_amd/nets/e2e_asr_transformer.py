@@ -307,28 +307,53 @@ class E2E(ASRInterface, torch.nn.Module):
 
     @ops.inference_call
     def recognize(self, x, recog_args, char_list=None, rnnlm=None, use_jit=False, ngram=None):
-        """reference: e2e_asr_transformer.py:259-477 (greedy CTC when ctc_weight == 1, else joint
+        """reference: e2e_asr_transformer.py:259-477 (greedy CTC when ctc_weight == 1 and beam_size == 1, else joint
         CTC/attention beam search through the scorer interface).  ngram: an n-gram scorer (nets.ngram), fused with weight
-        recog_args.ngram_weight as asr/pytorch_backend/recog.py:68-87 does."""
-        enc_output = self.encode(x).unsqueeze(0)
+        recog_args.ngram_weight as asr/pytorch_backend/recog.py:68-87 does.  ctc_weight == 1 with beam_size > 1 (the reference
+        raises there): the time-synchronous CTC prefix beam search of nets.ctc_prefix_beam."""
         if self.mtlalpha == 1.0:
             recog_args.ctc_weight = 1.0
+        if self.mtlalpha > 0 and recog_args.ctc_weight == 1.0 and recog_args.beam_size > 1:
+            self._refuse_rnnlm_for_pure_ctc(rnnlm)
+            enc_output = self.encode(x)
+            return self._ctc_prefix_beam(enc_output.unsqueeze(0), [enc_output.shape[0]], recog_args, ngram)[0]
+        enc_output = self.encode(x).unsqueeze(0)
         if self.mtlalpha > 0 and recog_args.ctc_weight == 1.0:
             with torch.no_grad():
                 ids = self.ctc.argmax(enc_output).to(torch.int32)
                 hyp, n = ops.ctc_collapse(ids.contiguous(), None, self.blank)
             hyp = hyp[0, : int(n[0])].tolist()
-            if recog_args.beam_size > 1:
-                raise NotImplementedError("Pure CTC beam search is not implemented.")
             return [{"score": 0.0, "yseq": [self.sos] + hyp}]
         from .beam_search import recognize_beam
         return recognize_beam(self, enc_output.squeeze(0), recog_args, char_list, rnnlm, ngram=ngram)
 
+    @staticmethod
+    def _refuse_rnnlm_for_pure_ctc(rnnlm):
+        if rnnlm is not None:
+            raise ValueError("a neural LM (rnnlm) cannot be fused into the time-synchronous pure-CTC beam search: "
+                             "pass an n-gram LM (ngram=) or decode with ctc_weight < 1")
+
+    def _ctc_prefix_beam(self, hs_pad, hlens, recog_args, ngram):
+        """the pure-CTC beam search on encoder output (B,T',D): beam_size, nbest, penalty, ctc_cand_size and ngram_weight of
+        recog_args -> one n-best list per utterance"""
+        if self.blank != 0 or self.eos != self.odim - 1:
+            raise ValueError("CTC prefix beam search: blank = 0 and eos = odim - 1, not %d / %d" % (self.blank, self.eos))
+        return self.ctc.prefix_beam_search(
+            hs_pad, hlens, beam_size=recog_args.beam_size, cand_size=getattr(recog_args, "ctc_cand_size", None),
+            nbest=min(getattr(recog_args, "nbest", 1), recog_args.beam_size), penalty=getattr(recog_args, "penalty", 0.0),
+            ngram=ngram, ngram_weight=getattr(recog_args, "ngram_weight", 0.0) if ngram is not None else 0.0)
+
     @ops.inference_call
     def recognize_batch(self, xs, recog_args, char_list=None, rnnlm=None, ngram=None):
         """xs: list of (T_b, idim) features -> one n-best list each, what recognize() gives for that utterance: every utterance is
-        encoded alone and the searches run in one BeamSearch.forward_batch"""
+        encoded alone and the searches run in one BeamSearch.forward_batch (pure CTC with beam_size > 1: in one launch of the
+        CTC prefix beam search)"""
         if self.mtlalpha == 1.0 or (self.mtlalpha > 0 and recog_args.ctc_weight == 1.0):
+            if recog_args.beam_size > 1:
+                self._refuse_rnnlm_for_pure_ctc(rnnlm)
+                encs = [self.encode(x) for x in xs]
+                hs_pad = torch.nn.utils.rnn.pad_sequence(encs, batch_first=True)
+                return self._ctc_prefix_beam(hs_pad, [e.shape[0] for e in encs], recog_args, ngram)
             return [self.recognize(x, recog_args, char_list, rnnlm) for x in xs]          # greedy CTC: no search to batch
         from .beam_search import recognize_beam_batch
         return recognize_beam_batch(self, [self.encode(x) for x in xs], recog_args, char_list, rnnlm, ngram=ngram)

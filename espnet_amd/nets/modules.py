@@ -1352,6 +1352,17 @@ class CTC(torch.nn.Module):
             return CTCAlignment(*ops.ctc_forced_align(y.contiguous(), hl.contiguous(), ys_pad, blank=blank_id,
                                                        ignore_id=self.ignore_id))
 
+    def prefix_beam_search(self, hs_pad, hlens, **kw):
+        """time-synchronous CTC prefix beam search of a padded batch (nets.ctc_prefix_beam.CTCPrefixBeamSearch, not in the
+        reference): hs_pad (B,T,D) encoder output; hlens valid frames (list / tensor); kw: beam_size, cand_size, nbest, penalty,
+        ngram, ngram_weight -> per utterance the n-best list [{"score", "yseq"}].  Output layer, log-softmax, candidate top-K and
+        the search are enqueued back to back; one device-to-host copy fetches the result"""
+        from .ctc_prefix_beam import CTCPrefixBeamSearch
+        search = CTCPrefixBeamSearch(blank=0, eos=self.ctc_lo.out_features - 1, **kw)
+        dev = self.ctc_lo.weight.device
+        with torch.no_grad():
+            return search.forward_batch(self.log_softmax(hs_pad.to(dev).contiguous()), hlens)
+
 
 def th_accuracy(correct_rows, pad_targets, ignore_label):
     """reference: nets_utils.py:299-319; numerator comes from the fused loss kernel."""

@@ -21,6 +21,8 @@ model out so that eamd_ngram_score (csrc/ngram.hip) writes the row as the dense 
       succ_start  [M + 1]        n-grams that extend node m's context: succ_tok / succ_lp[succ_start[m] : succ_start[m + 1]],
                                  already expanded to token ids (a word several tokens map to: one entry per token; a word no
                                  token maps to: none).  The root's successors are the dense row uni_tok.
+      qsucc_tok / qsucc_lp       the same ranges once more, sorted by token id inside a node: what a point query of one
+                                 (context, token) pair bisects (eamd_ngram_score_pairs, the CTC prefix beam search)
 
 The scorers' state is the context: int32 [N - 1] word ids, most recent first, -1 for an empty slot.
 """
@@ -34,6 +36,7 @@ UNK_MISSING_LOGPROB = -100.0       # kenlm's default `unknown_missing_logprob` f
 #                                    kenlm is not available to the tests, so this value is taken from its documentation
 
 _TABLES = ("tok2word", "uni_tok", "node_bo", "child_start", "child_word", "child_node", "succ_start", "succ_tok", "succ_lp")
+_QUERY_TABLES = ("qsucc_tok", "qsucc_lp")      # for point queries (csrc/ngram_query.h); eamd_ngram_score does not read them
 
 
 def _parse_arpa(path):
@@ -188,10 +191,12 @@ class ArpaLM:
         self.node_bo, self.child_start = t(node_bo, np.float32), t(child_start, np.int32)
         self.child_word, self.child_node = t(child_word, np.int32), t(np.arange(1, M), np.int32)
         self.succ_start, self.succ_tok, self.succ_lp = t(succ_start, np.int32), t(s_tok[o], np.int32), t(s_lp[rep][o], np.float32)
+        q = np.lexsort((s_tok[o], s_node[rep][o])) if len(rep) else np.zeros(0, dtype=np.int64)     # by node, then by token
+        self.qsucc_tok, self.qsucc_lp = t(s_tok[o][q], np.int32), t(s_lp[rep][o][q], np.float32)
         self.n_vocab = V
 
     def to(self, device):
-        for k in _TABLES:
+        for k in _TABLES + _QUERY_TABLES:
             setattr(self, k, getattr(self, k).to(device))
         return self
 

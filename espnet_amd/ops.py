@@ -1892,6 +1892,87 @@ def ngram_score(lm, ctx_prev, tok, first=False):
     return logp, ctx_new
 
 
+def _ngram_query_args(lm):
+    """the table arguments eamd_ngram_score_pairs and eamd_ctc_prefix_beam share"""
+    return (ptr(lm.tok2word), ptr(lm.uni_tok), ptr(lm.node_bo), ptr(lm.child_start), ptr(lm.child_word), ptr(lm.child_node),
+            ptr(lm.succ_start), ptr(lm.qsucc_tok), ptr(lm.qsucc_lp), lm.node_bo.numel())
+
+
+def ngram_score_pairs(lm, ctx, tok):
+    """point queries on the n-gram LM (eamd_ngram_score_pairs): ctx [n, N-1] int32 contexts (most recent word first, -1 = empty),
+    tok [n] int64 -> (lp [n] = log10 p(word(tok) | ctx), bit-equal to the element of ngram_score's row, ctx_new [n, N-1])"""
+    n, Cw = ctx.shape
+    V = lm.uni_tok.numel()
+    assert Cw == lm.order - 1 and ctx.dtype == torch.int32 and ctx.is_contiguous()
+    assert tok.dtype == torch.int64 and tok.dim() == 1 and tok.numel() == n and tok.is_contiguous()
+    dev = tok.device
+    if lm.uni_tok.device != dev or ctx.device != dev:
+        raise _lib.EamdError("ngram_score_pairs: tables, contexts and tokens on one device")
+    lp = torch.empty(n, device=dev, dtype=torch.float32)
+    ctx_new = torch.empty(n, Cw, device=dev, dtype=torch.int32)
+    check(_lib.lib().eamd_ngram_score_pairs(*_ngram_query_args(lm), V, lm.order, lm.unk, ptr(ctx) if Cw else None, ptr(tok), ptr(lp),
+                                            ptr(ctx_new) if Cw else None, n, stream_ptr()), "eamd_ngram_score_pairs")
+    return lp, ctx_new
+
+
+CTC_BEAM_MAX_W, CTC_BEAM_MAX_K, CTC_BEAM_MAX_T = 32, 32, 2048      # csrc/ctc_beam.hip
+
+
+def ctc_beam_candidates(logp, cand_size):
+    """the per-frame candidates of the CTC prefix beam search for all B T rows at once: eamd_topk_rows_i32 on columns 1 .. V-2 of
+    logp [B, T, V] (contiguous fp32) -> (values [B T, K] fp32, ids [B T, K] int32 counted from column 1)"""
+    B, T, V = logp.shape
+    if logp.dtype != torch.float32 or not logp.is_contiguous():
+        raise _lib.EamdError("ctc_prefix_beam: contiguous float32 [B, T, V]")
+    K = int(cand_size)
+    if not 1 <= K <= min(CTC_BEAM_MAX_K, V - 2):
+        raise _lib.EamdError("ctc_prefix_beam: 1 <= candidates <= min(%d, V - 2)" % CTC_BEAM_MAX_K)
+    rows = B * T
+    cval = torch.empty(rows, K, device=logp.device, dtype=torch.float32)
+    cidx = torch.empty(rows, K, device=logp.device, dtype=torch.int64)
+    cid = torch.empty(rows, K, device=logp.device, dtype=torch.int32)
+    check(_lib.lib().eamd_topk_rows_i32(ptr(logp, 1), C.c_int64(V), rows, V - 2, K, ptr(cval), ptr(cidx), ptr(cid), stream_ptr()),
+          "eamd_topk_rows")
+    return cval, cid
+
+
+def ctc_prefix_beam_search(logp, cval, cid, hlens, beam_size, nbest, penalty=0.0, lm=None, ngram_weight=0.0, ws=None, out=None):
+    """eamd_ctc_prefix_beam alone (one launch, one workgroup per utterance) on the candidates of ctc_beam_candidates; ws / out:
+    the workspace and result buffer of an earlier call with the same shapes, else allocated here -> (out, ws)"""
+    B, T, V = logp.shape
+    K = cval.shape[1]
+    assert hlens.dtype == torch.int32 and hlens.numel() == B and hlens.is_contiguous() and hlens.device == logp.device
+    assert cval.shape == (B * T, K) and cid.shape == (B * T, K) and cid.dtype == torch.int32
+    W = int(beam_size)
+    if not (1 <= nbest <= W <= CTC_BEAM_MAX_W and T <= CTC_BEAM_MAX_T):
+        raise _lib.EamdError("ctc_prefix_beam: 1 <= nbest <= beam <= %d, T <= %d" % (CTC_BEAM_MAX_W, CTC_BEAM_MAX_T))
+    dev = logp.device
+    ws_bytes = _lib.lib().eamd_ctc_beam_workspace_bytes(B, T, W)
+    if ws is None:
+        ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty(B, nbest, 2 + T, device=dev, dtype=torch.int32)
+    assert ws.numel() >= ws_bytes and out.shape == (B, nbest, 2 + T) and out.dtype == torch.int32 and out.is_contiguous()
+    if lm is not None:
+        if lm.uni_tok.device != dev or lm.uni_tok.numel() != V:
+            raise _lib.EamdError("ctc_prefix_beam: the n-gram tables on the device of logp, over the same %d tokens" % V)
+        tables, order, bos, unk = _ngram_query_args(lm), lm.order, lm.bos, lm.unk
+    else:
+        tables, order, bos, unk = (None,) * 9 + (0,), 0, 0, 0
+    check(_lib.lib().eamd_ctc_prefix_beam(ptr(logp), C.c_int64(V), ptr(cval), ptr(cid), ptr(hlens), B, T, V, W, K, int(nbest),
+                                          C.c_float(penalty), *tables, order, bos, unk, C.c_float(ngram_weight), ptr(ws),
+                                          C.c_int64(ws.numel()), ptr(out), stream_ptr()), "eamd_ctc_prefix_beam")
+    return out, ws
+
+
+def ctc_prefix_beam(logp, hlens, beam_size, cand_size, nbest, penalty=0.0, lm=None, ngram_weight=0.0):
+    """time-synchronous CTC prefix beam search of a padded batch: ctc_beam_candidates, then ctc_prefix_beam_search.  logp [B, T, V]
+    contiguous fp32 log-softmax rows, hlens [B] int32 on the device, lm: nets.ngram.ArpaLM on the device or None
+    -> int32 [B, nbest, 2 + T] on the device: the bits of the fp32 score, the length (-1: no hypothesis), the tokens"""
+    cval, cid = ctc_beam_candidates(logp, cand_size)
+    return ctc_prefix_beam_search(logp, cval, cid, hlens, beam_size, nbest, penalty, lm, ngram_weight)[0]
+
+
 # ---- MVDR beamforming front-end (csrc/beamformer.hip) ----------------------------------------------
 BF_PSD, BF_PSD_BWD, BF_MVDR_BWD, BF_APPLY_BWD = 0, 1, 2, 3
 BF_TCHUNK = 64               # EAMD_BF_TCHUNK: frames per workgroup of the kernels that split the time axis

@@ -1041,6 +1041,37 @@ int eamd_ngram_score(const int32_t* tok2word, const float* uni_tok, const float*
                      const int32_t* child_word, const int32_t* child_node, const int32_t* succ_start, const int32_t* succ_tok,
                      const float* succ_lp, int n_nodes, int V, int N, int bos, int unk, const int32_t* ctx_prev, int64_t ctx_ld,
                      const int64_t* tok, int64_t tok_ld, int first, float* logp, int32_t* ctx_new, int n, void* stream);
+/* Point queries on the same model, one lane per pair: lp [n] = log10 p(word(tok[i]) | ctx[i]) for ctx [n, N - 1] (contiguous; word
+ * ids, most recent first, -1 = empty) and tok [n] (contiguous); ctx_new [n, N - 1] = (word(tok[i]), ctx[i][0 .. N-3]).  The walk
+ * and the order of the back-off additions are those of eamd_ngram_score: lp[i] is bit-equal to element tok[i] of the row that
+ * eamd_ngram_score writes for a hypothesis whose ctx_new is ctx[i].  qsucc_tok / qsucc_lp: the successors of every node (the
+ * ranges of succ_start) sorted by token id (ArpaLM.qsucc_tok / qsucc_lp).  A token outside [0, V): lp = -inf, word `unk`. */
+int eamd_ngram_score_pairs(const int32_t* tok2word, const float* uni_tok, const float* node_bo, const int32_t* child_start,
+                           const int32_t* child_word, const int32_t* child_node, const int32_t* succ_start,
+                           const int32_t* qsucc_tok, const float* qsucc_lp, int n_nodes, int V, int N, int unk,
+                           const int32_t* ctx, const int64_t* tok, float* lp, int32_t* ctx_new, int n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Time-synchronous CTC prefix beam search (Hannun et al. 2014) with n-gram fusion, csrc/ctc_beam.hip.  Not in the reference.
+ * ------------------------------------------------------------------------------------------ */
+/* The n-best prefixes of B utterances in one launch (one workgroup each, the frame loop inside).  logp [B, T, V] log-softmax
+ * rows (row stride ld >= V; only column 0, the blank, is read), cand_val / cand_id [B, T, K]: the K largest of columns 1 .. V-2
+ * of every row, value descending, cand_id counted from column 1 (eamd_topk_rows_i32 on logp + 1 with n = V - 2), hlens [B]
+ * frames per utterance (clamped to [0, T]).  blank = 0, <eos> = V - 1 (never appended).  Beam state: distinct prefixes l with
+ * (pb, pnb); per frame pb'(l) += tot + logp[blank]; for c among the frame's candidates pnb'(l) += pnb + logp[c] and
+ * pnb'(l+c) += pb + logp[c] if c == last(l), else pnb'(l+c) += tot + logp[c] (+= : logaddexp, tot = logaddexp(pb, pnb)); equal
+ * prefixes share one entry.  Kept: the W entries of largest finite s = logaddexp(pb', pnb') + ngram_weight LM(l) + penalty |l|,
+ * LM(l) = sum_i log10 p(w_i | <s> w_<i) of the ARPA tables (tok2word == NULL: no LM; else as eamd_ngram_score_pairs, order
+ * N <= 8); after the last frame s += ngram_weight log10 p(</s> | context).
+ * out [B, nbest, 2 + T] int32: the bits of the fp32 score, the length (-1: no such hypothesis), the tokens; best first.
+ * workspace: eamd_ctc_beam_workspace_bytes(B, T, W) bytes, 8-byte aligned.  1 <= nbest <= W <= 32, 1 <= K <= min(32, V - 2),
+ * T <= 2048, else EAMD_EUNSUPPORTED / EAMD_EINVAL before any launch. */
+int64_t eamd_ctc_beam_workspace_bytes(int B, int T, int W);
+int eamd_ctc_prefix_beam(const float* logp, int64_t ld, const float* cand_val, const int32_t* cand_id, const int32_t* hlens, int B,
+                         int T, int V, int W, int K, int nbest, float penalty, const int32_t* tok2word, const float* uni_tok,
+                         const float* node_bo, const int32_t* child_start, const int32_t* child_word, const int32_t* child_node,
+                         const int32_t* succ_start, const int32_t* qsucc_tok, const float* qsucc_lp, int n_nodes, int N, int bos,
+                         int unk, float ngram_weight, void* workspace, int64_t workspace_bytes, int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mask-based MVDR beamforming front-end (reference: espnet/nets/pytorch_backend/frontends/beamformer.py:6-84,
