@@ -6,6 +6,7 @@ streams (tensor.data_ptr(), torch.cuda.current_stream()).
 """
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -105,49 +106,52 @@ class LstmSeqBwdT(C.Structure):
 
 _lib = None
 
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "espnet_amd.h")
+_BY_VALUE = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float,
+             "double": C.c_double}
+
+
+def parse_prototypes(text):
+    """header text -> {name: (restype, [argtypes])} for every `<type> eamd_*(<params>);`.  A parameter with a `*` is a
+    c_void_p (it takes None, an address, byref(struct) and ctypes arrays); the by-value types are those of _BY_VALUE, anything
+    else is an EamdError naming the prototype (the header is regular: this is not a C parser)."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"\b(\w+)\s+(eamd_\w+)\s*\(([^()]*)\)\s*;", text):
+        def ctype(decl, named):
+            if "*" in decl:
+                return C.c_void_p
+            words = [w for w in decl.split() if w != "const"]
+            base = " ".join(words[:-1] if named else words)
+            if base not in _BY_VALUE:
+                raise EamdError(f"{name}: cannot bind by-value type '{base}' of '{decl.strip()}'")
+            return _BY_VALUE[base]
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        protos[name] = (ctype(ret, False), [ctype(p, True) for p in params])
+    return protos
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = parse_prototypes(_f.read())
 # every symbol include/espnet_amd.h declares (tests check they are all exported)
-SYMBOLS = [
-    "eamd_abi_version", "eamd_gemm", "eamd_gemm_multi", "eamd_gemm_group_plan", "eamd_gemm_group_launch", "eamd_ffn_fwd", "eamd_ffn_bwd", "eamd_ffn_pack_f32", "eamd_ffn_pack_bf16", "eamd_ffn_pack_f32_multi", "eamd_rowproj", "eamd_rowproj_pack_f32", "eamd_rowproj_lnb_workspace", "eamd_layernorm_fwd", "eamd_layernorm_bwd_workspace", "eamd_layernorm_bwd_drop_f32", "eamd_layernorm_bwd", "eamd_layernorm_bwd_reduce", "eamd_attn_fwd", "eamd_attn_bwd_q", "eamd_attn_fwd_f32", "eamd_attn_bwd_q_f32", "eamd_attn_bwd_kv_f32", "eamd_attn_bwd_kv", "eamd_softmax_fwd",
-    "eamd_softmax_bwd", "eamd_lsm_loss", "eamd_argmax_rows", "eamd_reduce_sum", "eamd_log_softmax_rows", "eamd_transducer_expand_rows", "eamd_topk_rows", "eamd_topk_rows_i32", "eamd_weighted_topk_rows", "eamd_beam_step", "eamd_beam_step_dyn", "eamd_decode_self_attn_dyn", "eamd_beam_slots_dyn", "eamd_ctc_prefix_psi_dyn", "eamd_ctc_prefix_state_dyn", "eamd_embed_pe_dyn", "eamd_copy_jobs", "eamd_embed_pe_ld", "eamd_linear_rows_f32", "eamd_linear_rows_ln_f32", "eamd_decode_self_attn", "eamd_beam_slots", "eamd_decode_src_attn", "eamd_decode_src_attn_group", "eamd_decode_src_attn_split", "eamd_decode_src_attn_split_workspace", "eamd_weighted_sum", "eamd_beam_select", "eamd_beam_finish",
-    "eamd_axpby", "eamd_cast_bf16", "eamd_scale_dev", "eamd_act_fwd", "eamd_act_bwd", "eamd_glu_fwd", "eamd_glu_bwd",
-    "eamd_add_bias2", "eamd_add_cast_bf16", "eamd_add_block_f32", "eamd_add_cast_colsum2", "eamd_add_colsum2_f32", "eamd_colsum", "eamd_embed_pe", "eamd_embed_bwd", "eamd_posenc", "eamd_posenc_scaled", "eamd_posenc_scaled_bwd", "eamd_permute4",
-    "eamd_dropout", "eamd_rng_advance", "eamd_dwconv_fwd", "eamd_dwconv_glu_fwd", "eamd_dwconv_glu_bwd_x", "eamd_dwconv_glu_bwd_w", "eamd_dwconv_bwd_x", "eamd_dwconv_bwd_w", "eamd_bn_nslab",
-    "eamd_bn_stats", "eamd_bn_finalize", "eamd_bn_apply", "eamd_bn_bwd", "eamd_bn_stats_bounded", "eamd_bn_bwd_bounded", "eamd_mask_time", "eamd_conv1_fwd", "eamd_conv1_bwd_w_workspace", "eamd_conv1_bwd_w",
-    "eamd_conv2_weight_prep", "eamd_conv2_weight_grad", "eamd_add_sos_eos", "eamd_ctc_collapse",
-    "eamd_ctc_workspace_bytes", "eamd_ctc_loss", "eamd_ctc_pit_workspace_bytes", "eamd_ctc_pit_loss", "eamd_ctc_align_workspace_bytes", "eamd_ctc_forced_align", "eamd_maskctc_seed", "eamd_maskctc_update", "eamd_text_units", "eamd_edit_distance_workspace_bytes", "eamd_edit_distance", "eamd_ngram_score", "eamd_ngram_score_pairs", "eamd_ctc_beam_workspace_bytes", "eamd_ctc_prefix_beam", "eamd_ctc_prefix_score", "eamd_ctc_prefix_score_batch", "eamd_ctc_prefix_psi", "eamd_ctc_prefix_state", "eamd_grad_norm", "eamd_sched_step", "eamd_adam_step", "eamd_adadelta_step", "eamd_add_gradient_noise",
-    "eamd_specaug", "eamd_global_mvn", "eamd_utterance_mvn", "eamd_reflect_pad", "eamd_logmel", "eamd_unfold1d", "eamd_fold1d", "eamd_attloc_convmax_fwd", "eamd_attloc_convmax_bwd", "eamd_layernorm_bwd_drop",
-    "eamd_lstm_cell_fwd", "eamd_lstm_cell_bwd", "eamd_lstm_step_fwd", "eamd_lstm_step_bwd", "eamd_lstm_seq_sync_bytes", "eamd_lstm_seq_fwd", "eamd_lstm_seq_bwd", "eamd_lstm_seq_status", "eamd_lstm_seq_status_merge", "eamd_gru_cell_fwd", "eamd_gru_cell_bwd", "eamd_maxpool2x2_fwd", "eamd_maxpool2x2_bwd", "eamd_mask_rows",
-    "eamd_joint_fwd", "eamd_joint_bwd", "eamd_rnnt_workspace", "eamd_rnnt_loss", "eamd_rnnt_grad", "eamd_rnnt_node_stats", "eamd_rnnt_node_stats_part", "eamd_rnnt_row_coef", "eamd_rnnt_alpha_beta", "eamd_rnnt_node_grad",
-    "eamd_conv3x3_c1_fwd", "eamd_conv3x3_c1_bwd_w_workspace", "eamd_conv3x3_c1_bwd_w", "eamd_attloc_fwd", "eamd_attloc_bwd_energy", "eamd_attloc_bwd_workspace", "eamd_attloc_bwd_energy_conv", "eamd_attloc_bwd_conv",
-    "eamd_att_dot_energy_fwd", "eamd_att_dot_energy_bwd", "eamd_att_ctx_fwd", "eamd_att_ctx_bwd",
-    "eamd_bf_workspace_bytes", "eamd_bf_psd", "eamd_bf_psd_bwd", "eamd_bf_mvdr", "eamd_bf_mvdr_bwd", "eamd_bf_apply", "eamd_bf_apply_bwd",
-    "eamd_ft_logmel_fwd", "eamd_ft_logmel_bwd", "eamd_ft_mvn_fwd", "eamd_ft_mvn_bwd", "eamd_conv3x3_c1_bwd_x",
-]
+SYMBOLS = list(PROTOTYPES)
 
 
 def lib():
-    """Load the HIP shared library (once).  Raises if it has not been built."""
+    """Load the HIP shared library (once) and give every entry point the header's prototype: ctypes then converts plain
+    Python ints / floats to the declared widths and refuses a wrong argument count or type.  Raises if it has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise EamdError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C espnet_amd/csrc` (there is no CPU fallback)")
-        _lib = C.CDLL(LIB_PATH)
-        _lib.eamd_ctc_workspace_bytes.restype = C.c_int64
-        _lib.eamd_ctc_align_workspace_bytes.restype = C.c_int64
-        _lib.eamd_ctc_pit_workspace_bytes.restype = C.c_int64
-        _lib.eamd_edit_distance_workspace_bytes.restype = C.c_int64
-        _lib.eamd_layernorm_bwd_workspace.restype = C.c_int64
-        _lib.eamd_rnnt_workspace.restype = C.c_int64
-        _lib.eamd_attloc_bwd_workspace.restype = C.c_int64
-        _lib.eamd_conv1_bwd_w_workspace.restype = C.c_int64
-        _lib.eamd_lstm_seq_sync_bytes.restype = C.c_int64
-        _lib.eamd_conv3x3_c1_bwd_w_workspace.restype = C.c_int64
-        _lib.eamd_bf_workspace_bytes.restype = C.c_int64
-        _lib.eamd_ctc_beam_workspace_bytes.restype = C.c_int64
-        for s in SYMBOLS:
-            getattr(_lib, s)  # AttributeError here = header/library mismatch
+        handle = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(handle, name)  # AttributeError here = header/library mismatch
+            fn.restype = restype
+            fn.argtypes = argtypes
+        _lib = handle
     return _lib
 
 
@@ -156,11 +160,11 @@ _cur_device = getattr(torch._C, "_cuda_getDevice", None)
 
 
 def stream_ptr():
-    """the current HIP stream of the current device.  torch.cuda.current_stream() builds a Stream object through several
-    Python layers (2.8 us per call, paid by every launch of an eager decode step); the raw getter is one C call"""
+    """the current HIP stream of the current device, as an address.  torch.cuda.current_stream() builds a Stream object through
+    several Python layers (2.8 us per call, paid by every launch of an eager decode step); the raw getter is one C call"""
     if _raw_stream is not None and _cur_device is not None:
-        return C.c_void_p(_raw_stream(_cur_device()))
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _raw_stream(_cur_device())
+    return torch.cuda.current_stream().cuda_stream
 
 
 EAMD_EUNSUPPORTED = -2   # include/espnet_amd.h
@@ -172,14 +176,14 @@ def check(rc, what):
 
 
 def ptr(t, offset=0):
-    """Device pointer of a tensor (+ element offset); None -> NULL."""
+    """Device address of a tensor (+ element offset) as an int; None -> NULL."""
     if t is None:
         return None
     if not t.is_cuda:
         raise EamdError("espnet_amd kernels need GPU tensors (no CPU fallback in the product path)")
     if offset == 0:
-        return C.c_void_p(t.data_ptr())
-    return C.c_void_p(t.data_ptr() + offset * t.element_size())
+        return t.data_ptr()
+    return t.data_ptr() + offset * t.element_size()
 
 
 def f32(t):

@@ -933,12 +933,6 @@ __global__ __launch_bounds__(64) void ctc_prefix_state_scan_kernel(const float* 
 }
 }  // namespace
 
-extern "C" int eamd_ctc_prefix_psi(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev,
-                                   const int32_t* cand, const int32_t* last, int olen, float* psi, int ncand, int Tmax, int V, int blank,
-                                   int eos, void* stream) {
-  return eamd_ctc_prefix_psi_dyn(logp, lens, nutt, per_utt, r_prev, cand, last, olen, nullptr, psi, ncand, Tmax, V, blank, eos, stream);
-}
-
 extern "C" int eamd_ctc_prefix_psi_dyn(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev,
                                        const int32_t* cand, const int32_t* last, int olen, const int32_t* olen_dev, float* psi, int ncand,
                                        int Tmax, int V, int blank, int eos, void* stream) {
@@ -955,12 +949,6 @@ extern "C" int eamd_ctc_prefix_psi_dyn(const float* logp, const int32_t* lens, i
 #undef EAMD_PSI_
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
-}
-
-extern "C" int eamd_ctc_prefix_state(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev,
-                                     const int64_t* parent, const int64_t* tok, const int32_t* last, int olen, const float* alive,
-                                     float* r_out, int Tmax, int V, int blank, void* stream) {
-  return eamd_ctc_prefix_state_dyn(logp, lens, nutt, per_utt, r_prev, parent, tok, last, olen, nullptr, alive, r_out, Tmax, V, blank, stream);
 }
 
 extern "C" int eamd_ctc_prefix_state_dyn(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev,

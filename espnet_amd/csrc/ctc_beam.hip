@@ -9,7 +9,7 @@
 // backtrace at the end.
 //
 // Frame t, N = beam (K + 1) table entries: per prefix l one "stay" entry (l itself) and K extensions l + c, c in the frame's
-// candidate list C_t (the K largest of columns 1 .. V-2, made beforehand by eamd_topk_rows for all frames at once):
+// candidate list C_t (the K largest of columns 1 .. V-2, made beforehand by eamd_topk_rows_i32 for all frames at once):
 //   A  per prefix j: the position of last(j) in C_t, and the beam prefix i that spells parent(j) - then the extension
 //      (i, last(j)) IS j: its mass is gathered by j's stay entry and the extension's own entry is struck (at most one i per j,
 //      so the merge is a gather by the receiver).  Identity is exact: len(i) + 1 == len(j), last2(j) == last(i), and

@@ -9,9 +9,9 @@
 //   eamd_linear_rows_ln_f32   y = alpha * act(LayerNorm(x) W^T + b) + R for M <= 16 rows: the pre-norm of a sub-block inside the
 //                             product that follows it (norm1 + q/k/v, norm2 + q of the source attention, norm3 + w_1, after_norm
 //                             + the output layer)
-//   eamd_decode_self_attn     appends this step's k / v rows and attends the newest position over the prefix (one wave per
+//   eamd_decode_self_attn_dyn appends this step's k / v rows and attends the newest position over the prefix (one wave per
 //                             (hypothesis, head), d_k = 64)
-//   eamd_beam_slots           the slot table behind a beam step's selection
+//   eamd_beam_slots_dyn       the slot table behind a beam step's selection
 #include <stdlib.h>
 #include "common.h"
 #include "../../include/espnet_amd.h"
@@ -295,11 +295,6 @@ int eamd_linear_rows_ln_f32(const float* x, const float* gamma, const float* bet
   return EAMD_OK;
 }
 
-int eamd_decode_self_attn(const float* qkv, int64_t ldq, float* kcache, float* vcache, const int32_t* slot_at, int Lcap, int pos,
-                          int n, int H, int D, float* ctx, void* stream) {
-  return eamd_decode_self_attn_dyn(qkv, ldq, kcache, vcache, slot_at, Lcap, pos, nullptr, n, H, D, ctx, stream);
-}
-
 int eamd_decode_self_attn_dyn(const float* qkv, int64_t ldq, float* kcache, float* vcache, const int32_t* slot_at, int Lcap, int pos,
                               const int32_t* pos_dev, int n, int H, int D, float* ctx, void* stream) {
   if (!qkv || !kcache || !vcache || !slot_at || !ctx || n <= 0 || H <= 0 || D <= 0 || Lcap <= 0 || (!pos_dev && pos < 0)) return EAMD_EINVAL;
@@ -309,10 +304,6 @@ int eamd_decode_self_attn_dyn(const float* qkv, int64_t ldq, float* kcache, floa
                      vcache, slot_at, Lcap, pos, n, D, ctx, 0.125f, pos_dev);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
-}
-
-int eamd_beam_slots(const int32_t* slot_in, int32_t* slot_out, const int64_t* hyp, int n, int Lcap, int pos, void* stream) {
-  return eamd_beam_slots_dyn(slot_in, slot_out, hyp, n, Lcap, pos, nullptr, stream);
 }
 
 int eamd_beam_slots_dyn(const int32_t* slot_in, int32_t* slot_out, const int64_t* hyp, int n, int Lcap, int pos, const int32_t* pos_dev,
@@ -560,14 +551,6 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
 }  // namespace
 
 extern "C" {
-
-int eamd_beam_step(const float* pre, const int64_t* ids, const float* psi, const float* c_s, const float* hyp, float w_ctc, int nutt,
-                   int beam, int P, int V, int W, int L, int step, int eos, const int64_t* maxlen, int ns, int nf, const float* sc_in,
-                   const float* const* logps, const int64_t* yseq_in, float* c_local, float* sc_out, int64_t* yseq_out, float* hyp_out,
-                   int64_t* hyp_i, int64_t* tok_i, int32_t* tok32, float* cs_out, float* rec, void* stream) {
-  return eamd_beam_step_dyn(pre, ids, psi, c_s, hyp, w_ctc, nutt, beam, P, V, W, L, step, eos, maxlen, ns, nf, sc_in, logps, yseq_in, c_local,
-                            sc_out, yseq_out, hyp_out, hyp_i, tok_i, tok32, cs_out, rec, nullptr, nullptr, 0, nullptr, nullptr, 0, stream);
-}
 
 int eamd_beam_step_dyn(const float* pre, const int64_t* ids, const float* psi, const float* c_s, const float* hyp, float w_ctc, int nutt,
                        int beam, int P, int V, int W, int L, int step, int eos, const int64_t* maxlen, int ns, int nf, const float* sc_in,

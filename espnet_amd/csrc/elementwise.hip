@@ -684,16 +684,6 @@ int eamd_colsum(const void* x, int64_t ld, float* out, int64_t rows, int D, floa
   return EAMD_OK;
 }
 
-int eamd_embed_pe(const int64_t* tok, const float* table, const float* pe, float* out, int64_t rows, int U,
-                  int D, float scale, int pos_offset, void* stream) {
-  return eamd_embed_pe_ld(tok, 1, table, pe, out, rows, U, D, scale, pos_offset, stream);
-}
-
-int eamd_embed_pe_ld(const int64_t* tok, int64_t ldt, const float* table, const float* pe, float* out, int64_t rows, int U,
-                     int D, float scale, int pos_offset, void* stream) {
-  return eamd_embed_pe_dyn(tok, ldt, table, pe, out, rows, U, D, scale, pos_offset, nullptr, stream);
-}
-
 int eamd_embed_pe_dyn(const int64_t* tok, int64_t ldt, const float* table, const float* pe, float* out, int64_t rows, int U,
                       int D, float scale, int pos_offset, const int32_t* pos_dev, void* stream) {
   if (!tok || !table || !out || rows <= 0 || U <= 0 || D <= 0 || ldt < 1) return EAMD_EINVAL;

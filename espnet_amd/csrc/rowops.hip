@@ -1669,10 +1669,6 @@ int eamd_linear_rows_f32(const float* x, const float* W, const float* bias, cons
   return EAMD_OK;
 }
 
-int eamd_topk_rows(const float* x, int64_t ld, int rows, int n, int k, float* vals, int64_t* idx, void* stream) {
-  return eamd_topk_rows_i32(x, ld, rows, n, k, vals, idx, nullptr, stream);
-}
-
 int eamd_weighted_topk_rows(const float* const* logps, const float* weights, int nf, int rows, int n, int k, int extra, float* pre,
                             float* vals, int64_t* idx, int32_t* idx32, void* stream) {
   if (!logps || !weights || !pre || !vals || !idx || nf < 1 || nf > 4 || rows <= 0 || n <= 0 || k <= 0 || k > n || extra >= n) return EAMD_EINVAL;

@@ -224,8 +224,8 @@ class BeamSearch(torch.nn.Module):
     device_loop = True
     sync_every = 8
     candidate_select = True       # the selection of a step on the pre-beam candidates (eamd_beam_select); tests flip it
-    step_kernel = True            # selection + bookkeeping of a pre-beam step in one launch (eamd_beam_step); tests flip it
-    ctc_psi_parallel = True       # candidates scored by eamd_ctc_prefix_psi, survivors' states by eamd_ctc_prefix_state; tests flip it
+    step_kernel = True            # selection + bookkeeping of a pre-beam step in one launch (eamd_beam_step_dyn); tests flip it
+    ctc_psi_parallel = True       # candidates scored by eamd_ctc_prefix_psi_dyn, survivors' states by eamd_ctc_prefix_state_dyn; tests flip it
     ctc_side_stream = "capture"   # ... the latter on a second stream beside the next step's decoder stack: True, False, or only where
                                   # it pays: more than 2048 frames (the frame-by-frame recursion, 130 us at 249 frames; up to 2048 the
                                   # states are a parallel scan of a few us) in a captured step graph (the fork and the join cost
@@ -362,9 +362,9 @@ class BeamSearch(torch.nn.Module):
     def _step_plan(self, C_):
         """which implementation a step of this search takes, from what is known before anything is launched ->
         (candidates, split, fused): the selection runs on the beam x P pre-beam candidates (_step_candidates) and not on [n, V]
-        tensor expressions (_step_tensors) | the candidates are scored by eamd_ctc_prefix_psi and the survivors' states made by
-        eamd_ctc_prefix_state, not both by the full recursion (more than 2048 frames) | selection and bookkeeping are ONE launch
-        (eamd_beam_step), not eamd_beam_select + eamd_beam_finish"""
+        tensor expressions (_step_tensors) | the candidates are scored by eamd_ctc_prefix_psi_dyn and the survivors' states made by
+        eamd_ctc_prefix_state_dyn, not both by the full recursion (more than 2048 frames) | selection and bookkeeping are ONE launch
+        (eamd_beam_step_dyn), not eamd_beam_select + eamd_beam_finish"""
         V, beam, P = C_["V"], C_["beam"], self.pre_beam_size
         split = self.ctc_psi_parallel and C_["Tpad"] <= 2048
         fused = self.step_kernel and beam <= 64 and beam * P <= 1023 and beam * V < 2 ** 31 and split
@@ -399,7 +399,7 @@ class BeamSearch(torch.nn.Module):
                 if not ok:
                     raise _NoDynStep(what)
         # CTC forward variables of the running hypotheses: ready (first step / the full-recursion path), or still to be made from the
-        # previous step's selection - then on a second stream BESIDE the decoder stack below (eamd_ctc_prefix_state: ~160 us of
+        # previous step's selection - then on a second stream BESIDE the decoder stack below (eamd_ctc_prefix_state_dyn: ~160 us of
         # frame-by-frame recursion that nothing in this step needs before the candidates are scored)
         c_r_now, side = S.get("c_r"), None
         if ctc is not None and c_r_now is None:
@@ -448,7 +448,7 @@ class BeamSearch(torch.nn.Module):
         else:
             pre = ops.weighted_sum(lps, wts)
             _, part_ids, cand32 = ops.topk_rows(pre, P, idx32=True)
-        # the newest token of every prefix as int32: the previous step's selection wrote it (eamd_beam_step), <sos> at step 0
+        # the newest token of every prefix as int32: the previous step's selection wrote it (eamd_beam_step_dyn), <sos> at step 0
         last = S["last32"] if "last32" in S else (C_["sos32"] if i == 0 else ys[:, -1].to(torch.int32).contiguous())
         if side is not None:
             torch.cuda.current_stream(dev).wait_stream(side)
@@ -531,7 +531,7 @@ class BeamSearch(torch.nn.Module):
                 else:
                     weighted += self.weights[pname] * c_local
         weighted += hyp[:, None]
-        # one launch of eamd_topk_rows (value descending, ties by ascending index).  torch.topk takes its multi-block path for
+        # one launch of eamd_topk_rows_i32 (value descending, ties by ascending index).  torch.topk takes its multi-block path for
         # these sizes: six launches and a sort - and zeroes its counters with memset nodes, which a captured graph replays
         # wrongly on this ROCm from the second launch on (espnet_amd/graphs.py; the round-3 step-graph fault)
         # ... in two stages: the best `beam` of an utterance's beam x V continuations lie among the best `beam` of each of its

@@ -48,10 +48,7 @@ class Swish(torch.nn.Module):
     """reference: conformer/swish.py:13-18"""
 
     def forward(self, x):
-        y = torch.empty_like(x)
-        ops._lib.check(ops._lib.lib().eamd_act_fwd(ops.ptr(x.contiguous()), ops.ptr(y), x.numel(), ops.ACT_SWISH,
-                                                   ops.stream_ptr()), "eamd_act_fwd")
-        return y
+        return ops.act_fwd_any(x.contiguous(), ops.ACT_SWISH)
 
 
 def get_activation(act):

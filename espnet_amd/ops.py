@@ -132,7 +132,7 @@ def mask_time(x, T, bound):
     """rows (b, t) of the [B*T, C] tensor x with t >= bound[0] <- 0, in place"""
     rows = x.numel() // x.shape[-1]
     assert x.is_contiguous() and rows % T == 0 and x.dtype in (torch.float32, torch.bfloat16)
-    check(_lib.lib().eamd_mask_time(ptr(x), C.c_int64(rows), x.shape[-1], T, ptr(bound), int(x.dtype == torch.bfloat16),
+    check(_lib.lib().eamd_mask_time(ptr(x), rows, x.shape[-1], T, ptr(bound), x.dtype == torch.bfloat16,
                                     stream_ptr()), "eamd_mask_time")
     return x
 
@@ -425,7 +425,7 @@ def cast_bf16(x, out=None):
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
     assert x.dtype == torch.float32 and x.is_contiguous() and out.numel() == x.numel()
-    check(_lib.lib().eamd_cast_bf16(ptr(x), ptr(out), C.c_int64(x.numel()), stream_ptr()), "eamd_cast_bf16")
+    check(_lib.lib().eamd_cast_bf16(ptr(x), ptr(out), x.numel(), stream_ptr()), "eamd_cast_bf16")
     return out
 
 
@@ -500,8 +500,8 @@ def linear_fwd(x, W, b, out=None, *, act=EPI_NONE, R=None, alpha=1.0, a_act=ACT_
         # inference on a handful of rows (one utterance's hypotheses in a beam step): one wave per output column; x and R may be
         # row-strided views (the newest position of every prefix)
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-        rc = _lib.lib().eamd_linear_rows_f32(ptr(x), ptr(W), ptr(b), ptr(R), ptr(y), M, N, K, a_act, act, C.c_float(alpha),
-                                             C.c_int64(x.stride(0)), C.c_int64(R.stride(0) if R is not None else 0), stream_ptr())
+        rc = _lib.lib().eamd_linear_rows_f32(ptr(x), ptr(W), ptr(b), ptr(R), ptr(y), M, N, K, a_act, act, alpha,
+                                             x.stride(0), R.stride(0) if R is not None else 0, stream_ptr())
         if rc == 0:
             return y
         if rc != _lib.EAMD_EUNSUPPORTED:
@@ -850,13 +850,13 @@ def rowproj_pack(jobs):
         assert W.dim() == 2 and W.dtype == torch.float32 and W.stride(1) == 1
         K, N = (W.shape[0], W.shape[1]) if trans else (W.shape[1], W.shape[0])
         # image buffers are cached per (weight storage address, shape, orientation): the weights live in persistent arenas
-        key = (W.data_ptr(), K, N, int(bool(trans)), W.device.index)
+        key = (W.data_ptr(), K, N, bool(trans), W.device.index)
         img = _rp_bufs.get(key)
         if img is None:
             if len(_rp_bufs) > 4096:
                 _rp_bufs.clear()
             img = _rp_bufs[key] = torch.empty(K * N, device=W.device, dtype=torch.float32)
-        q.w, q.image, q.K, q.N, q.ldw, q.trans = ptr(W), ptr(img), K, N, W.stride(0), int(bool(trans))
+        q.w, q.image, q.K, q.N, q.ldw, q.trans = ptr(W), ptr(img), K, N, W.stride(0), bool(trans)
         imgs.append(img)
     check(_lib.lib().eamd_rowproj_pack_f32(arr, len(jobs), stream_ptr()), "eamd_rowproj_pack_f32")
     return imgs
@@ -900,7 +900,7 @@ def rowproj(a, img, N, *, bias=None, R=None, alpha=1.0, drop=None, ln=None, affi
 
 
 def rowproj_lnb_ws(M, device):
-    return torch.empty(int(_lib.lib().eamd_rowproj_lnb_workspace(M)), device=device, dtype=torch.float32)
+    return torch.empty(_lib.lib().eamd_rowproj_lnb_workspace(M), device=device, dtype=torch.float32)
 
 
 # ---- weight-gradient side stream ---------------------------------------------------------------
@@ -983,7 +983,7 @@ def colsum(x, out, scale=1.0, rows=None, D=None, ld=None):
     D = x.shape[1] if D is None else D
     ld = D if ld is None else ld
     assert out.numel() >= D
-    check(_lib.lib().eamd_colsum(ptr(x), C.c_int64(ld), ptr(out), C.c_int64(rows), D, C.c_float(scale),
+    check(_lib.lib().eamd_colsum(ptr(x), ld, ptr(out), rows, D, scale,
                                  1 if x.dtype == torch.bfloat16 else 0, stream_ptr()), "eamd_colsum")
 
 
@@ -995,7 +995,7 @@ def layernorm_fwd(x, gamma, beta, eps, out_dtype=torch.float32):
     rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
     y32, y16 = (ptr(y), None) if out_dtype == torch.float32 else (None, ptr(y))
     check(_lib.lib().eamd_layernorm_fwd(ptr(x), ptr(gamma), ptr(beta), y32, y16, ptr(mean), ptr(rstd), rows, D,
-                                        C.c_float(eps), stream_ptr()), "eamd_layernorm_fwd")
+                                        eps, stream_ptr()), "eamd_layernorm_fwd")
     return y, mean, rstd
 
 
@@ -1059,7 +1059,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, drop=None):
     assert dy.shape == x.shape and dgamma.numel() == D and dbeta.numel() == D
     dx = torch.empty_like(x)
     L = _lib.lib()
-    nws = int(L.eamd_layernorm_bwd_workspace(rows, D))
+    nws = L.eamd_layernorm_bwd_workspace(rows, D)
     ws = torch.empty(nws, device=x.device, dtype=torch.float32)
     pg, pb = ptr(dgamma), ptr(dbeta)
     if _defer_ln(ws, dgamma, dbeta, nws // (2 * D), D):
@@ -1069,7 +1069,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, drop=None):
         fn, name = ((L.eamd_layernorm_bwd_drop, "eamd_layernorm_bwd_drop") if fast()
                     else (L.eamd_layernorm_bwd_drop_f32, "eamd_layernorm_bwd_drop_f32"))
         check(fn(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dx16),
-                 C.c_float(drop[0]), ptr(rng_state(x.device)), C.c_uint64(drop[1]), pg,
+                 drop[0], ptr(rng_state(x.device)), drop[1], pg,
                  pb, ptr(ws), rows, D, stream_ptr()), name)
         return dx, dx16
     check(L.eamd_layernorm_bwd(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx),
@@ -1111,13 +1111,12 @@ def attn_fwd(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldp, scale, drop=None, s
     cx = torch.empty(B * T1, D, device=dev, dtype=dt)
     dropping = drop is not None and drop[0] > 0.0
     Pd = torch.empty_like(P) if dropping else P
-    dargs = ((ptr(Pd), C.c_float(drop[0]), ptr(rng_state(dev)), C.c_uint64(drop[1])) if dropping
-             else (None, C.c_float(0.0), None, C.c_uint64(0)))
-    i64 = C.c_int64
-    args = (ptr(qu[0], qu[1]), i64(qu[2]), ptr(qv[0], qv[1]) if qv is not None else None, i64(qv[2] if qv is not None else 0),
-            ptr(k[0], k[1]), i64(k[2]), ptr(v[0], v[1]), i64(v[2]), ptr(pos[0], pos[1]) if pos is not None else None,
-            i64(pos[2] if pos is not None else 0),
-            ptr(mask), i64(mb), i64(mi), ptr(P), i64(ldp), ptr(cx), i64(D), B, H, T1, T2, dk, C.c_float(scale)) + dargs
+    dargs = ((ptr(Pd), drop[0], ptr(rng_state(dev)), drop[1]) if dropping
+             else (None, 0.0, None, 0))
+    args = (ptr(qu[0], qu[1]), qu[2], ptr(qv[0], qv[1]) if qv is not None else None, qv[2] if qv is not None else 0,
+            ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(pos[0], pos[1]) if pos is not None else None,
+            pos[2] if pos is not None else 0,
+            ptr(mask), mb, mi, ptr(P), ldp, ptr(cx), D, B, H, T1, T2, dk, scale) + dargs
     # relative positions on a padded batch: the rel_shift is taken over the batch's own length (shift_len: int32 device scalar)
     args = args + (ptr(shift_len) if (pos is not None and T1 == T2) else None,)
     name = "eamd_attn_fwd" if dt == torch.bfloat16 else "eamd_attn_fwd_f32"
@@ -1135,21 +1134,20 @@ def attn_bwd_q(dctx, k, v, P, dS, dbd, dq, B, T1, T2, H, dk, ldp, scale, drop=No
     """dctx / k / v / dq: (tensor, element offset, row stride) views; P, dS (and dbd or None): [H*B*T1*ldp], bf16
     (eamd_attn_bwd_q; dq fp32 or bf16) or everything fp32 (eamd_attn_bwd_q_f32).
     dS, dbd and dq are written.  Returns False if the library declines the operands (EAMD_EUNSUPPORTED)."""
-    i64 = C.c_int64
     dropping = drop is not None and drop[0] > 0.0      # the forward's attention dropout: dP <- mask * dP / (1 - p)
-    dargs = ((C.c_float(drop[0]), ptr(rng_state(P.device)), C.c_uint64(drop[1])) if dropping
-             else (C.c_float(0.0), None, C.c_uint64(0)))
+    dargs = ((drop[0], ptr(rng_state(P.device)), drop[1]) if dropping
+             else (0.0, None, 0))
     if P.dtype == torch.bfloat16:
         name = "eamd_attn_bwd_q"
-        args = (ptr(dctx[0], dctx[1]), i64(dctx[2]), ptr(k[0], k[1]), i64(k[2]), ptr(v[0], v[1]), i64(v[2]), ptr(P), i64(ldp),
-                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), i64(dq[2]), int(dq[0].dtype == torch.bfloat16), B, H, T1, T2, dk,
-                C.c_float(scale)) + dargs
+        args = (ptr(dctx[0], dctx[1]), dctx[2], ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(P), ldp,
+                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), dq[2], dq[0].dtype == torch.bfloat16, B, H, T1, T2, dk,
+                scale) + dargs
     else:
         name = "eamd_attn_bwd_q_f32"
         for t_ in (dctx[0], k[0], v[0], P, dS, dq[0]) + ((dbd,) if dbd is not None else ()):
             assert t_.dtype == torch.float32
-        args = (ptr(dctx[0], dctx[1]), i64(dctx[2]), ptr(k[0], k[1]), i64(k[2]), ptr(v[0], v[1]), i64(v[2]), ptr(P), i64(ldp),
-                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), i64(dq[2]), B, H, T1, T2, dk, C.c_float(scale)) + dargs
+        args = (ptr(dctx[0], dctx[1]), dctx[2], ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(P), ldp,
+                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), dq[2], B, H, T1, T2, dk, scale) + dargs
     args = args + (ptr(shift_len) if (dbd is not None and T1 == T2) else None,)
     fn = getattr(_lib.lib(), name)
     rc = fn(*args, stream_ptr())
@@ -1169,7 +1167,6 @@ def attn_bwd_kv(Pd, dS, dbd, dctx, qu, qv, dv, dk_, dpos, B, T1, T2, H, dk, ldp)
     (eamd_attn_bwd_kv_f32) or all bf16 (eamd_attn_bwd_kv).  dctx / qu / qv / dv / dk_ / dpos: (tensor, element offset,
     row stride) views; dv and dk_ share their row stride.  Returns False if the library declines the operands
     (EAMD_EUNSUPPORTED)."""
-    i64 = C.c_int64
     dt = Pd.dtype
     assert dt in (torch.float32, torch.bfloat16)
     for t_ in (Pd, dS, dctx[0], qu[0], dv[0], dk_[0]):
@@ -1177,14 +1174,14 @@ def attn_bwd_kv(Pd, dS, dbd, dctx, qu, qv, dv, dk_, dpos, B, T1, T2, H, dk, ldp)
     assert dv[2] == dk_[2]
     rel = dbd is not None
     if dt == torch.float32:
-        args = (ptr(Pd), ptr(dS), ptr(dbd) if rel else None, i64(ldp), ptr(dctx[0], dctx[1]), i64(dctx[2]), ptr(qu[0], qu[1]),
-                i64(qu[2]), ptr(qv[0], qv[1]) if rel else None, i64(qv[2] if rel else 0), ptr(dv[0], dv[1]), ptr(dk_[0], dk_[1]),
-                i64(dv[2]), ptr(dpos[0], dpos[1]) if rel else None, i64(dpos[2] if rel else 0), B, H, T1, T2, dk)
+        args = (ptr(Pd), ptr(dS), ptr(dbd) if rel else None, ldp, ptr(dctx[0], dctx[1]), dctx[2], ptr(qu[0], qu[1]),
+                qu[2], ptr(qv[0], qv[1]) if rel else None, qv[2] if rel else 0, ptr(dv[0], dv[1]), ptr(dk_[0], dk_[1]),
+                dv[2], ptr(dpos[0], dpos[1]) if rel else None, dpos[2] if rel else 0, B, H, T1, T2, dk)
         name = "eamd_attn_bwd_kv_f32"
     else:
         assert not rel, "the bf16 key-side launch leaves the positional product to the GEMM"
-        args = (ptr(Pd), ptr(dS), i64(ldp), ptr(dctx[0], dctx[1]), i64(dctx[2]), ptr(qu[0], qu[1]), i64(qu[2]),
-                ptr(dv[0], dv[1]), ptr(dk_[0], dk_[1]), i64(dv[2]), B, H, T1, T2, dk)
+        args = (ptr(Pd), ptr(dS), ldp, ptr(dctx[0], dctx[1]), dctx[2], ptr(qu[0], qu[1]), qu[2],
+                ptr(dv[0], dv[1]), ptr(dk_[0], dk_[1]), dv[2], B, H, T1, T2, dk)
         name = "eamd_attn_bwd_kv"
     fn = getattr(_lib.lib(), name)
     rc = fn(*args, stream_ptr())
@@ -1207,8 +1204,8 @@ def softmax_fwd(ac, bd, mask, P, nblocks, B, T1, T2, ld, scale):
         mi = 0 if mask.shape[1] == 1 else T2
     assert ac.numel() >= nblocks * T1 * ld and P.numel() >= nblocks * T1 * ld
     p32, p16 = (ptr(P), None) if P.dtype == torch.float32 else (None, ptr(P))
-    check(_lib.lib().eamd_softmax_fwd(ptr(ac), ptr(bd), ptr(mask), C.c_int64(mb), C.c_int64(mi), p32, p16, nblocks,
-                                      B, T1, T2, C.c_int64(ld), C.c_float(scale), stream_ptr()),
+    check(_lib.lib().eamd_softmax_fwd(ptr(ac), ptr(bd), ptr(mask), mb, mi, p32, p16, nblocks,
+                                      B, T1, T2, ld, scale, stream_ptr()),
           "eamd_softmax_fwd")
 
 
@@ -1219,10 +1216,10 @@ def softmax_bwd(P, dP, dbd, nblocks, T1, T2, ld, scale, dS16=None):
     if P.dtype == torch.bfloat16:
         assert dS16 is not None and dS16.dtype == torch.bfloat16 and (dbd is None or dbd.dtype == torch.bfloat16)
         check(_lib.lib().eamd_softmax_bwd(None, ptr(P), ptr(dP), None, ptr(dS16), ptr(dbd), nblocks, T1, T2,
-                                          C.c_int64(ld), C.c_float(scale), stream_ptr()), "eamd_softmax_bwd")
+                                          ld, scale, stream_ptr()), "eamd_softmax_bwd")
     else:
         check(_lib.lib().eamd_softmax_bwd(ptr(P), None, ptr(dP), ptr(dbd), None, None, nblocks, T1, T2,
-                                          C.c_int64(ld), C.c_float(scale), stream_ptr()), "eamd_softmax_bwd")
+                                          ld, scale, stream_ptr()), "eamd_softmax_bwd")
 
 
 def lsm_loss(logits, target, smoothing, inv_denom, ignore_id, want_grad=True):
@@ -1232,7 +1229,7 @@ def lsm_loss(logits, target, smoothing, inv_denom, ignore_id, want_grad=True):
     correct = torch.empty(rows, device=logits.device, dtype=torch.float32)
     grad = torch.empty_like(logits) if want_grad else None
     check(_lib.lib().eamd_lsm_loss(ptr(logits), ptr(target), ptr(loss_rows), ptr(correct), ptr(grad), rows, V,
-                                   ignore_id, C.c_float(smoothing), C.c_float(inv_denom), stream_ptr()),
+                                   ignore_id, smoothing, inv_denom, stream_ptr()),
           "eamd_lsm_loss")
     return loss_rows, correct, grad
 
@@ -1240,13 +1237,13 @@ def lsm_loss(logits, target, smoothing, inv_denom, ignore_id, want_grad=True):
 def argmax_rows(x):
     rows, V = x.shape
     out = torch.empty(rows, device=x.device, dtype=torch.int32)
-    check(_lib.lib().eamd_argmax_rows(ptr(x), C.c_int64(V), ptr(out), rows, V, stream_ptr()), "eamd_argmax_rows")
+    check(_lib.lib().eamd_argmax_rows(ptr(x), V, ptr(out), rows, V, stream_ptr()), "eamd_argmax_rows")
     return out
 
 
 def reduce_sum(x, scale=1.0):
     out = torch.empty((), device=x.device, dtype=torch.float32)
-    check(_lib.lib().eamd_reduce_sum(ptr(x), C.c_int64(x.numel()), ptr(out), C.c_float(scale), stream_ptr()),
+    check(_lib.lib().eamd_reduce_sum(ptr(x), x.numel(), ptr(out), scale, stream_ptr()),
           "eamd_reduce_sum")
     return out
 
@@ -1262,9 +1259,9 @@ def linear_rows_ln(x, gamma, beta, eps, W, b, *, act=EPI_NONE, R=None, alpha=1.0
     if (M > 16 and (K > 256 or M > LINEAR_ROWS_BLOCK_MAX or N > 1024)) or K > 1024 or x.dtype != torch.float32 or W.dtype != torch.float32 or x.stride(1) != 1 or act not in (EPI_NONE, EPI_RELU, EPI_SWISH):
         return None
     y = out if out is not None else torch.empty(M, N, device=x.device, dtype=torch.float32)
-    rc = _lib.lib().eamd_linear_rows_ln_f32(ptr(x), ptr(gamma), ptr(beta), C.c_float(eps), ptr(W), ptr(b), ptr(R), ptr(y), M, N, K,
-                                            int(act), C.c_float(alpha), C.c_int64(x.stride(0) if M > 1 else K),
-                                            C.c_int64(R.stride(0) if (R is not None and M > 1) else 0), C.c_int64(y.stride(0)), stream_ptr())
+    rc = _lib.lib().eamd_linear_rows_ln_f32(ptr(x), ptr(gamma), ptr(beta), eps, ptr(W), ptr(b), ptr(R), ptr(y), M, N, K,
+                                            int(act), alpha, x.stride(0) if M > 1 else K,
+                                            R.stride(0) if (R is not None and M > 1) else 0, y.stride(0), stream_ptr())
     if rc == _lib.EAMD_EUNSUPPORTED:
         return None
     check(rc, "eamd_linear_rows_ln_f32")
@@ -1273,13 +1270,13 @@ def linear_rows_ln(x, gamma, beta, eps, W, b, *, act=EPI_NONE, R=None, alpha=1.0
 
 def decode_self_attn(qkv, Kc, Vc, slot_at, pos, H, pos_dev=None):
     """the newest position of n hypotheses attends over its prefix; keys / values of this step (columns D.., 2D.. of qkv) are
-    appended to the time-major caches Kc / Vc [Lcap, n, D] at row `pos`; slot_at [n, Lcap] int32 (eamd_decode_self_attn) -> ctx [n, D]"""
+    appended to the time-major caches Kc / Vc [Lcap, n, D] at row `pos`; slot_at [n, Lcap] int32 (eamd_decode_self_attn_dyn) -> ctx [n, D]"""
     n = qkv.shape[0]
     Lcap, n2, D = Kc.shape
     assert n2 == n and Vc.shape == Kc.shape and slot_at.shape == (n, Lcap) and slot_at.dtype == torch.int32 and qkv.stride(1) == 1
     ctx = torch.empty(n, D, device=qkv.device, dtype=torch.float32)
-    check(_lib.lib().eamd_decode_self_attn_dyn(ptr(qkv), C.c_int64(qkv.stride(0)), ptr(Kc), ptr(Vc), ptr(slot_at), Lcap, int(pos),
-                                               ptr(pos_dev), n, H, D, ptr(ctx), stream_ptr()), "eamd_decode_self_attn")
+    check(_lib.lib().eamd_decode_self_attn_dyn(ptr(qkv), qkv.stride(0), ptr(Kc), ptr(Vc), ptr(slot_at), Lcap, int(pos),
+                                               ptr(pos_dev), n, H, D, ptr(ctx), stream_ptr()), "eamd_decode_self_attn_dyn")
     return ctx
 
 
@@ -1296,16 +1293,14 @@ def decode_src_attn(q, kv, k_off, v_off, ldkv, mask, G, g, T, H, group=False):
     splits = SRC_ATTN_SPLITS if (group and T >= 128 and G * H * SRC_ATTN_SPLITS <= 4096) else 1
     if group and splits > 1:       # the keys of an utterance over several workgroups + a merge launch (eamd_decode_src_attn_split)
         L = _lib.lib()
-        L.eamd_decode_src_attn_split_workspace.restype = C.c_int64
-        ws = torch.empty(int(L.eamd_decode_src_attn_split_workspace(G, g, H, splits)), device=q.device, dtype=torch.float32)
-        rc = L.eamd_decode_src_attn_split(ptr(q), C.c_int64(q.stride(0)), ptr(kv, k_off), ptr(kv, v_off), C.c_int64(ldkv), ptr(mask),
+        ws = torch.empty(L.eamd_decode_src_attn_split_workspace(G, g, H, splits), device=q.device, dtype=torch.float32)
+        rc = L.eamd_decode_src_attn_split(ptr(q), q.stride(0), ptr(kv, k_off), ptr(kv, v_off), ldkv, ptr(mask),
                                           G, g, T, H, D, splits, ptr(ws), ptr(ctx), stream_ptr())
         if rc != _lib.EAMD_EUNSUPPORTED:
             check(rc, "eamd_decode_src_attn_split")
             return ctx
     fn = _lib.lib().eamd_decode_src_attn_group if group else _lib.lib().eamd_decode_src_attn
-    rc = fn(ptr(q), C.c_int64(q.stride(0)), ptr(kv, k_off), ptr(kv, v_off), C.c_int64(ldkv), ptr(mask),
-                                         G, g, T, H, D, ptr(ctx), stream_ptr())
+    rc = fn(ptr(q), q.stride(0), ptr(kv, k_off), ptr(kv, v_off), ldkv, ptr(mask), G, g, T, H, D, ptr(ctx), stream_ptr())
     if rc == _lib.EAMD_EUNSUPPORTED:
         return None
     check(rc, "eamd_decode_src_attn")
@@ -1317,7 +1312,7 @@ def beam_slots(slot_in, hyp, pos, pos_dev=None):
     (pos_dev: int32 device scalar added to pos)"""
     n, Lcap = slot_in.shape
     out = torch.empty_like(slot_in)
-    check(_lib.lib().eamd_beam_slots_dyn(ptr(slot_in), ptr(out), ptr(hyp), n, Lcap, int(pos), ptr(pos_dev), stream_ptr()), "eamd_beam_slots")
+    check(_lib.lib().eamd_beam_slots_dyn(ptr(slot_in), ptr(out), ptr(hyp), n, Lcap, int(pos), ptr(pos_dev), stream_ptr()), "eamd_beam_slots_dyn")
     return out
 
 
@@ -1338,7 +1333,7 @@ def weighted_sum(logps, weights):
     out = torch.empty_like(logps[0])
     arr = (C.c_void_p * 4)(*[lp.data_ptr() for lp in logps] + [None] * (4 - len(logps)))
     wts = (C.c_float * 4)(*[float(w) for w in weights] + [0.0] * (4 - len(weights)))
-    check(_lib.lib().eamd_weighted_sum(arr, wts, len(logps), C.c_int64(out.numel()), ptr(out), stream_ptr()), "eamd_weighted_sum")
+    check(_lib.lib().eamd_weighted_sum(arr, wts, len(logps), out.numel(), ptr(out), stream_ptr()), "eamd_weighted_sum")
     return out
 
 
@@ -1370,7 +1365,7 @@ def beam_select(pre, ids, psi, c_s, hyp, w_ctc, nutt, beam):
     top_s = torch.empty(nutt, beam, device=pre.device, dtype=torch.float32)
     top_i = torch.empty(nutt, beam, device=pre.device, dtype=torch.int64)
     c_local = torch.empty(n, P, device=pre.device, dtype=torch.float32)
-    check(_lib.lib().eamd_beam_select(ptr(pre), ptr(ids), ptr(psi), ptr(c_s), ptr(hyp), C.c_float(w_ctc), nutt, beam, P, V, ptr(c_local),
+    check(_lib.lib().eamd_beam_select(ptr(pre), ptr(ids), ptr(psi), ptr(c_s), ptr(hyp), w_ctc, nutt, beam, P, V, ptr(c_local),
                                       ptr(top_s), ptr(top_i), stream_ptr()), "eamd_beam_select")
     return top_s, top_i, c_local
 
@@ -1385,12 +1380,12 @@ def topk_rows(x, k, idx32=False):
     vals = torch.empty(rows, k, device=x.device, dtype=torch.float32)
     idx = torch.empty(rows, k, device=x.device, dtype=torch.int64)
     i32 = torch.empty(rows, k, device=x.device, dtype=torch.int32) if idx32 else None
-    check(_lib.lib().eamd_topk_rows_i32(ptr(x), C.c_int64(n), rows, n, k, ptr(vals), ptr(idx), ptr(i32), stream_ptr()), "eamd_topk_rows")
+    check(_lib.lib().eamd_topk_rows_i32(ptr(x), n, rows, n, k, ptr(vals), ptr(idx), ptr(i32), stream_ptr()), "eamd_topk_rows_i32")
     return (vals, idx, i32) if idx32 else (vals, idx)
 
 
 def beam_step(pre, ids, psi, c_s, hyp, w_ctc, nutt, beam, L, step, eos, maxlen, sc_in, logps, yseq_in, dyn=None, slot_in=None):
-    """selection and bookkeeping of a BeamSearch step with a pre-beam in one launch (eamd_beam_step = eamd_beam_select +
+    """selection and bookkeeping of a BeamSearch step with a pre-beam in one launch (eamd_beam_step_dyn = eamd_beam_select +
     eamd_beam_finish) -> (sc_out [ns, n], yseq_out, hyp_out, hyp_i, tok_i, tok32, cs_out, rec)"""
     n, V = pre.shape
     P = ids.shape[1]
@@ -1426,10 +1421,10 @@ def beam_step(pre, ids, psi, c_s, hyp, w_ctc, nutt, beam, L, step, eos, maxlen, 
         assert slot_in.dtype == torch.int32 and slot_in.is_contiguous() and slot_in.shape[0] == n
         slot_out, Lcap = torch.empty_like(slot_in), slot_in.shape[1]
     arr = (C.c_void_p * 4)(*[lp.data_ptr() for lp in logps] + [None] * (4 - nf))
-    check(_lib.lib().eamd_beam_step_dyn(ptr(pre), ptr(ids), ptr(psi), ptr(c_s), ptr(hyp), C.c_float(w_ctc), nutt, beam, P, V, W, L, step, eos,
+    check(_lib.lib().eamd_beam_step_dyn(ptr(pre), ptr(ids), ptr(psi), ptr(c_s), ptr(hyp), w_ctc, nutt, beam, P, V, W, L, step, eos,
                                         ptr(maxlen), ns, nf, ptr(sc_in), arr, ptr(yseq_in), ptr(c_local), ptr(sc_out), ptr(yseq_out),
                                         ptr(hyp_out), ptr(hyp_i), ptr(tok_i), ptr(tok32), ptr(cs_out), ptr(rec), ptr(step_dev),
-                                        ptr(step_out), ring, ptr(slot_in), ptr(slot_out), Lcap, stream_ptr()), "eamd_beam_step")
+                                        ptr(step_out), ring, ptr(slot_in), ptr(slot_out), Lcap, stream_ptr()), "eamd_beam_step_dyn")
     if slot_in is not None:       # (a ninth result: the cached decoder's slot table behind the selection)
         return sc_out, yseq_out, hyp_out, hyp_i, tok_i, tok32, cs_out, rec, slot_out
     return sc_out, yseq_out, hyp_out, hyp_i, tok_i, tok32, cs_out, rec
@@ -1457,7 +1452,7 @@ def beam_finish(top_s, top_i, beam, V, L, step, eos, maxlen, sc_in, logps, c_loc
     rec = torch.empty(n, 3 + ns + W, device=dev, dtype=torch.float32)
     arr = (C.c_void_p * 4)(*[lp.data_ptr() for lp in logps] + [None] * (4 - nf))
     check(_lib.lib().eamd_beam_finish(ptr(top_s), ptr(top_i), n, beam, V, W, L, step, eos, ptr(maxlen), ns, nf, ptr(sc_in), arr,
-                                      ptr(c_local), C.c_int64(c_local.shape[1] if c_local is not None else 0), int(bool(full_mode)),
+                                      ptr(c_local), c_local.shape[1] if c_local is not None else 0, bool(full_mode),
                                       ptr(ids), ids.shape[1] if ids is not None else 0, ptr(yseq_in), ptr(sc_out), ptr(yseq_out),
                                       ptr(hyp_out), ptr(hyp_i), ptr(tok_i), ptr(pos), ptr(rec), stream_ptr()), "eamd_beam_finish")
     return sc_out, yseq_out, hyp_out, hyp_i, tok_i, pos, rec
@@ -1493,7 +1488,7 @@ def transducer_expand_rows(logits, k, lm=None, lm_row=None, pairs=None):
     out = torch.empty(n * W + g, device=logits.device, dtype=torch.float32)
     nl = n if lm is not None else 0
     check(_lib.lib().eamd_transducer_expand_rows(
-        ptr(logits), C.c_int64(logits.stride(0)), n, V, k, ptr(lm), ptr(idx_dev) if lm is not None else None,
+        ptr(logits), logits.stride(0), n, V, k, ptr(lm), ptr(idx_dev) if lm is not None else None,
         ptr(idx_dev, nl) if g else None, g, ptr(out), ptr(out, n * W) if g else None, stream_ptr()),
         "eamd_transducer_expand_rows")
     host = out.tolist()
@@ -1510,7 +1505,7 @@ def axpby(x, y, a=1.0, b=1.0, out=None):
     if out is None:
         out = torch.empty_like(x)
     assert y is None or y.numel() == x.numel()
-    check(_lib.lib().eamd_axpby(ptr(x), ptr(y), ptr(out), C.c_int64(x.numel()), C.c_float(a), C.c_float(b),
+    check(_lib.lib().eamd_axpby(ptr(x), ptr(y), ptr(out), x.numel(), a, b,
                                 stream_ptr()), "eamd_axpby")
     return out
 
@@ -1518,7 +1513,7 @@ def axpby(x, y, a=1.0, b=1.0, out=None):
 def scale_dev(x, scale_t, extra=1.0, out=None):
     if out is None:
         out = torch.empty_like(x)
-    check(_lib.lib().eamd_scale_dev(ptr(x), ptr(scale_t), ptr(out), C.c_int64(x.numel()), C.c_float(extra),
+    check(_lib.lib().eamd_scale_dev(ptr(x), ptr(scale_t), ptr(out), x.numel(), extra,
                                     stream_ptr()), "eamd_scale_dev")
     return out
 
@@ -1526,7 +1521,7 @@ def scale_dev(x, scale_t, extra=1.0, out=None):
 def glu_fwd(a, Cc):
     rows = a.shape[0]
     y = torch.empty(rows, Cc, device=a.device, dtype=torch.float32)
-    check(_lib.lib().eamd_glu_fwd(ptr(a), ptr(y), C.c_int64(rows), Cc, stream_ptr()), "eamd_glu_fwd")
+    check(_lib.lib().eamd_glu_fwd(ptr(a), ptr(y), rows, Cc, stream_ptr()), "eamd_glu_fwd")
     return y
 
 
@@ -1534,7 +1529,7 @@ def glu_bwd(dy, a, Cc, out_dtype=torch.float32):
     rows = a.shape[0]
     dx = torch.empty(a.shape, device=a.device, dtype=out_dtype)
     d32, d16 = (ptr(dx), None) if out_dtype == torch.float32 else (None, ptr(dx))
-    check(_lib.lib().eamd_glu_bwd(ptr(dy), ptr(a), d32, d16, C.c_int64(rows), Cc, stream_ptr()), "eamd_glu_bwd")
+    check(_lib.lib().eamd_glu_bwd(ptr(dy), ptr(a), d32, d16, rows, Cc, stream_ptr()), "eamd_glu_bwd")
     return dx
 
 
@@ -1546,7 +1541,7 @@ def add_bias2(q, u, v, rows=None, D=None, ldq=None, q_off=0):
     assert u.numel() == D and v.numel() == D and q.numel() >= q_off + (rows - 1) * ldq + D
     qu = torch.empty(rows, D, device=q.device, dtype=q.dtype)
     qv = torch.empty(rows, D, device=q.device, dtype=q.dtype)
-    check(_lib.lib().eamd_add_bias2(ptr(q, q_off), C.c_int64(ldq), ptr(u), ptr(v), ptr(qu), ptr(qv), C.c_int64(rows), D,
+    check(_lib.lib().eamd_add_bias2(ptr(q, q_off), ldq, ptr(u), ptr(v), ptr(qu), ptr(qv), rows, D,
                                     1 if q.dtype == torch.bfloat16 else 0, stream_ptr()), "eamd_add_bias2")
     return qu, qv
 
@@ -1560,11 +1555,11 @@ def add_cast(a, b, out=None, out_off=0, ld_out=None):
         ld_out = cols
     if out.dtype == torch.float32:
         assert out.numel() >= out_off + (rows - 1) * ld_out + cols
-        check(_lib.lib().eamd_add_block_f32(ptr(a), ptr(b), ptr(out, out_off), C.c_int64(rows), cols, C.c_int64(ld_out),
+        check(_lib.lib().eamd_add_block_f32(ptr(a), ptr(b), ptr(out, out_off), rows, cols, ld_out,
                                             stream_ptr()), "eamd_add_block_f32")
         return out
     assert out.dtype == torch.bfloat16 and out.numel() >= out_off + (rows - 1) * ld_out + cols
-    check(_lib.lib().eamd_add_cast_bf16(ptr(a), ptr(b), ptr(out, out_off), C.c_int64(rows), cols, C.c_int64(ld_out),
+    check(_lib.lib().eamd_add_cast_bf16(ptr(a), ptr(b), ptr(out, out_off), rows, cols, ld_out,
                                         stream_ptr()), "eamd_add_cast_bf16")
     return out
 
@@ -1582,7 +1577,7 @@ def add_cast_colsum2(a, b, suma, sumb, out=None, out_off=0, ld_out=None):
     L = _lib.lib()
     fn, name = ((L.eamd_add_cast_colsum2, "eamd_add_cast_colsum2") if out.dtype == torch.bfloat16
                 else (L.eamd_add_colsum2_f32, "eamd_add_colsum2_f32"))
-    rc = fn(ptr(a), ptr(b), ptr(out, out_off), C.c_int64(ld_out), ptr(suma), ptr(sumb), C.c_int64(rows), cols, stream_ptr())
+    rc = fn(ptr(a), ptr(b), ptr(out, out_off), ld_out, ptr(suma), ptr(sumb), rows, cols, stream_ptr())
     if rc == _lib.EAMD_EUNSUPPORTED:
         colsum(a, suma)
         colsum(b, sumb)
@@ -1604,22 +1599,22 @@ def embed_pe(tok, table, pe, U, scale, pos_offset=0, pos_dev=None):
     assert pe is None or (pe.shape[0] >= U + pos_offset and pe.shape[1] == D)
     out = torch.empty(rows, D, device=table.device, dtype=torch.float32)
     # pos_dev: int32 device scalar added to pos_offset (the step index of a replayed beam step)
-    check(_lib.lib().eamd_embed_pe_dyn(ptr(tok), C.c_int64(ldt), ptr(table), ptr(pe), ptr(out), C.c_int64(rows), U, D,
-                                       C.c_float(scale), pos_offset, ptr(pos_dev), stream_ptr()), "eamd_embed_pe")
+    check(_lib.lib().eamd_embed_pe_dyn(ptr(tok), ldt, ptr(table), ptr(pe), ptr(out), rows, U, D,
+                                       scale, pos_offset, ptr(pos_dev), stream_ptr()), "eamd_embed_pe_dyn")
     return out
 
 
 def embed_bwd(tok, dout, dtable, scale, pad_idx=-1):
     rows, D = dout.shape
-    check(_lib.lib().eamd_embed_bwd(ptr(tok), ptr(dout), ptr(dtable), C.c_int64(rows), D, C.c_float(scale),
-                                    C.c_int64(pad_idx), stream_ptr()), "eamd_embed_bwd")
+    check(_lib.lib().eamd_embed_bwd(ptr(tok), ptr(dout), ptr(dtable), rows, D, scale,
+                                    pad_idx, stream_ptr()), "eamd_embed_bwd")
 
 
 def posenc(x, pe, T, scale):
     rows, D = x.shape
     assert pe.shape[0] >= T and pe.shape[1] == D
     out = torch.empty_like(x)
-    check(_lib.lib().eamd_posenc(ptr(x), ptr(pe), ptr(out), C.c_int64(rows), T, D, C.c_float(scale), stream_ptr()),
+    check(_lib.lib().eamd_posenc(ptr(x), ptr(pe), ptr(out), rows, T, D, scale, stream_ptr()),
           "eamd_posenc")
     return out
 
@@ -1628,14 +1623,14 @@ def posenc_scaled(x, pe, alpha, T, scale=1.0):
     rows, D = x.shape
     assert pe.shape[0] >= T and pe.shape[1] == D and alpha.numel() == 1
     out = torch.empty_like(x)
-    check(_lib.lib().eamd_posenc_scaled(ptr(x), ptr(pe), ptr(alpha), ptr(out), C.c_int64(rows), T, D, C.c_float(scale),
+    check(_lib.lib().eamd_posenc_scaled(ptr(x), ptr(pe), ptr(alpha), ptr(out), rows, T, D, scale,
                                         stream_ptr()), "eamd_posenc_scaled")
     return out
 
 
 def posenc_scaled_bwd(dout, pe, dalpha, T):
     rows, D = dout.shape
-    check(_lib.lib().eamd_posenc_scaled_bwd(ptr(dout), ptr(pe), ptr(dalpha), C.c_int64(rows), T, D, stream_ptr()),
+    check(_lib.lib().eamd_posenc_scaled_bwd(ptr(dout), ptr(pe), ptr(dalpha), rows, T, D, stream_ptr()),
           "eamd_posenc_scaled_bwd")
 
 
@@ -1670,8 +1665,8 @@ def dropout(x, p, salt, act=ACT_NONE, out_dtype=None):
     same mask (that is the backward pass).  x fp32 or bf16."""
     out_dtype = x.dtype if out_dtype is None else out_dtype
     y = torch.empty(x.shape, device=x.device, dtype=out_dtype)
-    check(_lib.lib().eamd_dropout(ptr(x), ptr(y), C.c_int64(x.numel()), C.c_float(p), ptr(rng_state(x.device)),
-                                  C.c_uint64(salt), act, 1 if x.dtype == torch.bfloat16 else 0,
+    check(_lib.lib().eamd_dropout(ptr(x), ptr(y), x.numel(), p, ptr(rng_state(x.device)),
+                                  salt, act, 1 if x.dtype == torch.bfloat16 else 0,
                                   1 if out_dtype == torch.bfloat16 else 0, stream_ptr()), "eamd_dropout")
     return y
 
@@ -1716,7 +1711,7 @@ def dwconv_glu_fwd(a, w, bias, B, T, Cc, K, bn=None):
     mean = torch.empty(Cc, device=a.device, dtype=torch.float32)
     rstd = torch.empty(Cc, device=a.device, dtype=torch.float32)
     check(_lib.lib().eamd_bn_finalize(ptr(part), nslab, ptr(mean), ptr(rstd), ptr(running_mean), ptr(running_var), ptr(nbt), Cc,
-                                      C.c_float(eps), C.c_float(momentum), stream_ptr()), "eamd_bn_finalize")
+                                      eps, momentum, stream_ptr()), "eamd_bn_finalize")
     return y, mean, rstd
 
 
@@ -1736,40 +1731,40 @@ def dwconv_glu_bwd_w(dy, a, dw, db, B, T, Cc, K):
 
 def bn_stats(x, M, Cc, eps, momentum, running_mean, running_var, num_batches_tracked=None, bound=None):
     """bound = (T, int32 device scalar): rows (b, t) with t >= bound[0] are left out (eamd_bn_stats_bounded)"""
-    nslab = _lib.lib().eamd_bn_nslab(C.c_int64(M), Cc)
+    nslab = _lib.lib().eamd_bn_nslab(M, Cc)
     ws = torch.empty(3 * Cc * nslab, device=x.device, dtype=torch.float32)
     mean = torch.empty(Cc, device=x.device, dtype=torch.float32)
     rstd = torch.empty(Cc, device=x.device, dtype=torch.float32)
     assert num_batches_tracked is None or (num_batches_tracked.dtype == torch.int64 and num_batches_tracked.is_cuda)
     if bound is not None:
         check(_lib.lib().eamd_bn_stats_bounded(ptr(x), ptr(ws), ptr(mean), ptr(rstd), ptr(running_mean), ptr(running_var),
-                                               ptr(num_batches_tracked), C.c_int64(M), Cc, C.c_float(eps), C.c_float(momentum),
+                                               ptr(num_batches_tracked), M, Cc, eps, momentum,
                                                int(bound[0]), ptr(bound[1]), stream_ptr()), "eamd_bn_stats_bounded")
         return mean, rstd
     check(_lib.lib().eamd_bn_stats(ptr(x), ptr(ws), ptr(mean), ptr(rstd), ptr(running_mean), ptr(running_var),
-                                   ptr(num_batches_tracked), C.c_int64(M), Cc, C.c_float(eps), C.c_float(momentum), stream_ptr()),
+                                   ptr(num_batches_tracked), M, Cc, eps, momentum, stream_ptr()),
           "eamd_bn_stats")
     return mean, rstd
 
 
 def bn_apply(x, mean, rstd, gamma, beta, M, Cc, act, out_dtype=torch.float32):
     y = torch.empty(x.shape, device=x.device, dtype=out_dtype)
-    check(_lib.lib().eamd_bn_apply(ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(y), C.c_int64(M), Cc,
+    check(_lib.lib().eamd_bn_apply(ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(y), M, Cc,
                                    act, 1 if out_dtype == torch.bfloat16 else 0, stream_ptr()), "eamd_bn_apply")
     return y
 
 
 def bn_bwd(dy, x, mean, rstd, gamma, beta, dgamma, dbeta, M, Cc, act, training, bound=None):
-    nslab = _lib.lib().eamd_bn_nslab(C.c_int64(M), Cc)
+    nslab = _lib.lib().eamd_bn_nslab(M, Cc)
     ws = torch.empty((2 * nslab + 2) * Cc, device=x.device, dtype=torch.float32)
     dx = torch.empty_like(x)
     if bound is not None:
         check(_lib.lib().eamd_bn_bwd_bounded(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(ws), ptr(dx),
-                                             ptr(dgamma), ptr(dbeta), C.c_int64(M), Cc, act, int(training), int(bound[0]),
+                                             ptr(dgamma), ptr(dbeta), M, Cc, act, int(training), int(bound[0]),
                                              ptr(bound[1]), stream_ptr()), "eamd_bn_bwd_bounded")
         return dx
     check(_lib.lib().eamd_bn_bwd(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(ws), ptr(dx),
-                                 ptr(dgamma), ptr(dbeta), C.c_int64(M), Cc, act, int(training), stream_ptr()),
+                                 ptr(dgamma), ptr(dbeta), M, Cc, act, int(training), stream_ptr()),
           "eamd_bn_bwd")
     return dx
 
@@ -1785,7 +1780,7 @@ def conv1_fwd(x, w, bias, B, T, F, Cc, out_dtype=torch.float32):
 
 def conv1_bwd_w(dy, x, dw, db, B, T, F, Cc):
     L = _lib.lib()
-    ws = torch.empty(int(L.eamd_conv1_bwd_w_workspace(B, T, Cc)), device=x.device, dtype=torch.float32)
+    ws = torch.empty(L.eamd_conv1_bwd_w_workspace(B, T, Cc), device=x.device, dtype=torch.float32)
     check(L.eamd_conv1_bwd_w(ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), B, T, F, Cc,
                              1 if dy.dtype == torch.bfloat16 else 0, stream_ptr()), "eamd_conv1_bwd_w")
 
@@ -1809,8 +1804,8 @@ def permute4(src, dst, dims, dst_strides, accumulate=False):
     s0, s1, s2, s3 = dst_strides
     assert src.numel() == d0 * d1 * d2 * d3
     assert (d0 - 1) * s0 + (d1 - 1) * s1 + (d2 - 1) * s2 + (d3 - 1) * s3 < dst.numel()
-    check(_lib.lib().eamd_permute4(ptr(src), ptr(dst), d0, d1, d2, d3, C.c_int64(s0), C.c_int64(s1), C.c_int64(s2),
-                                   C.c_int64(s3), int(accumulate), stream_ptr()), "eamd_permute4")
+    check(_lib.lib().eamd_permute4(ptr(src), ptr(dst), d0, d1, d2, d3, s0, s1, s2,
+                                   s3, int(accumulate), stream_ptr()), "eamd_permute4")
 
 
 # ---- integer helpers ----------------------------------------------------------------------------
@@ -1850,7 +1845,7 @@ def text_units(ids, tok_off, tok_cp, cap, limit=None, collapse=False, drop_cp=-1
     out = torch.empty(B, cap, device=dev, dtype=torch.int64)
     outlen = torch.empty(B, device=dev, dtype=torch.int32)
     check(_lib.lib().eamd_text_units(ptr(ids), ptr(limit), ptr(tok_off), ptr(tok_cp), ptr(scratch), ptr(out), ptr(outlen),
-                                     B, L, V, cap, int(bool(collapse)), int(drop_cp), int(mode), stream_ptr()),
+                                     B, L, V, cap, bool(collapse), int(drop_cp), int(mode), stream_ptr()),
           "eamd_text_units")
     return out, outlen
 
@@ -1866,7 +1861,7 @@ def edit_distance(a, alen, b, blen):
     ws = torch.empty(ws_bytes, device=a.device, dtype=torch.uint8)
     dist = torch.empty(B, device=a.device, dtype=torch.int32)
     check(_lib.lib().eamd_edit_distance(ptr(a), lda, ptr(alen), ptr(b), ldb, ptr(blen), ptr(dist), ptr(ws),
-                                        C.c_int64(ws_bytes), B, stream_ptr()), "eamd_edit_distance")
+                                        ws_bytes, B, stream_ptr()), "eamd_edit_distance")
     return dist
 
 
@@ -1887,8 +1882,8 @@ def ngram_score(lm, ctx_prev, tok, first=False):
     check(_lib.lib().eamd_ngram_score(
         ptr(lm.tok2word), ptr(lm.uni_tok), ptr(lm.node_bo), ptr(lm.child_start), ptr(lm.child_word), ptr(lm.child_node),
         ptr(lm.succ_start), ptr(lm.succ_tok), ptr(lm.succ_lp), lm.node_bo.numel(), V, lm.order, lm.bos, lm.unk,
-        ptr(ctx_prev) if Cw else None, C.c_int64(ctx_prev.stride(0) if Cw else 0), ptr(tok), C.c_int64(tok.stride(0) if n > 1 else 1),
-        int(bool(first)), ptr(logp), ptr(ctx_new) if Cw else None, n, stream_ptr()), "eamd_ngram_score")
+        ptr(ctx_prev) if Cw else None, ctx_prev.stride(0) if Cw else 0, ptr(tok), tok.stride(0) if n > 1 else 1,
+        bool(first), ptr(logp), ptr(ctx_new) if Cw else None, n, stream_ptr()), "eamd_ngram_score")
     return logp, ctx_new
 
 
@@ -1931,8 +1926,8 @@ def ctc_beam_candidates(logp, cand_size):
     cval = torch.empty(rows, K, device=logp.device, dtype=torch.float32)
     cidx = torch.empty(rows, K, device=logp.device, dtype=torch.int64)
     cid = torch.empty(rows, K, device=logp.device, dtype=torch.int32)
-    check(_lib.lib().eamd_topk_rows_i32(ptr(logp, 1), C.c_int64(V), rows, V - 2, K, ptr(cval), ptr(cidx), ptr(cid), stream_ptr()),
-          "eamd_topk_rows")
+    check(_lib.lib().eamd_topk_rows_i32(ptr(logp, 1), V, rows, V - 2, K, ptr(cval), ptr(cidx), ptr(cid), stream_ptr()),
+          "eamd_topk_rows_i32")
     return cval, cid
 
 
@@ -1959,9 +1954,9 @@ def ctc_prefix_beam_search(logp, cval, cid, hlens, beam_size, nbest, penalty=0.0
         tables, order, bos, unk = _ngram_query_args(lm), lm.order, lm.bos, lm.unk
     else:
         tables, order, bos, unk = (None,) * 9 + (0,), 0, 0, 0
-    check(_lib.lib().eamd_ctc_prefix_beam(ptr(logp), C.c_int64(V), ptr(cval), ptr(cid), ptr(hlens), B, T, V, W, K, int(nbest),
-                                          C.c_float(penalty), *tables, order, bos, unk, C.c_float(ngram_weight), ptr(ws),
-                                          C.c_int64(ws.numel()), ptr(out), stream_ptr()), "eamd_ctc_prefix_beam")
+    check(_lib.lib().eamd_ctc_prefix_beam(ptr(logp), V, ptr(cval), ptr(cid), ptr(hlens), B, T, V, W, K, int(nbest),
+                                          penalty, *tables, order, bos, unk, ngram_weight, ptr(ws),
+                                          ws.numel(), ptr(out), stream_ptr()), "eamd_ctc_prefix_beam")
     return out, ws
 
 
@@ -2095,9 +2090,9 @@ def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, wan
     ws = torch.empty(ws_bytes, device=acts_btv.device, dtype=torch.uint8)
     nll = torch.empty(B, device=acts_btv.device, dtype=torch.float32)
     grad = torch.empty_like(acts_btv) if want_grad else None
-    check(_lib.lib().eamd_ctc_loss(ptr(acts_btv), C.c_int64(st), C.c_int64(sb), ptr(ys_pad), ptr(ilens), ptr(nll),
-                                   ptr(grad), C.c_int64(st), C.c_int64(sb), ptr(ws), B, T, V, L, blank, ignore_id,
-                                   C.c_float(grad_scale), stream_ptr()), "eamd_ctc_loss")
+    check(_lib.lib().eamd_ctc_loss(ptr(acts_btv), st, sb, ptr(ys_pad), ptr(ilens), ptr(nll),
+                                   ptr(grad), st, sb, ptr(ws), B, T, V, L, blank, ignore_id,
+                                   grad_scale, stream_ptr()), "eamd_ctc_loss")
     return nll, grad
 
 
@@ -2118,7 +2113,7 @@ def ctc_pit_loss(acts, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, wan
     pit = torch.empty(B, device=dev, dtype=torch.float32)
     grad = torch.empty_like(acts) if want_grad else None
     check(_lib.lib().eamd_ctc_pit_loss(ptr(acts), ptr(ys_pad), ptr(ilens), ptr(nll), ptr(perm), ptr(pit), ptr(grad), ptr(ws), S, B,
-                                       T, V, L, blank, ignore_id, C.c_float(grad_scale), stream_ptr()), "eamd_ctc_pit_loss")
+                                       T, V, L, blank, ignore_id, grad_scale, stream_ptr()), "eamd_ctc_pit_loss")
     return nll, perm, pit, grad
 
 
@@ -2149,9 +2144,9 @@ def ctc_forced_align(acts, ilens, ys_pad, blank=0, ignore_id=-1, normalized=Fals
     tokens = torch.empty(B, T, device=dev, dtype=torch.int64)
     seg_start = torch.empty(B, L, device=dev, dtype=torch.int32)
     seg_end = torch.empty(B, L, device=dev, dtype=torch.int32)
-    check(_lib.lib().eamd_ctc_forced_align(ptr(acts), C.c_int64(st), C.c_int64(sb), ptr(ys_pad), ptr(ilens), ptr(score),
+    check(_lib.lib().eamd_ctc_forced_align(ptr(acts), st, sb, ptr(ys_pad), ptr(ilens), ptr(score),
                                            ptr(states), ptr(tokens), ptr(seg_start), ptr(seg_end), ptr(ws), B, T, V, L, blank,
-                                           ignore_id, int(bool(normalized)), stream_ptr()), "eamd_ctc_forced_align")
+                                           ignore_id, bool(normalized), stream_ptr()), "eamd_ctc_forced_align")
     return score, states, tokens, seg_start, seg_end
 
 
@@ -2170,7 +2165,7 @@ def maskctc_seed(logits, hlens, thr, K, mask_token, eos, blank=0, Lcap=None):
                frame_p=torch.empty(B, T, device=dev, dtype=torch.float32))
     check(_lib.lib().eamd_maskctc_seed(ptr(logits), ptr(hlens), ptr(out["frame_id"]), ptr(out["frame_p"]), ptr(out["y_in"]),
                                        ptr(out["tok_p"]), ptr(out["len"]), ptr(out["nmask"]), ptr(out["niter"]), ptr(out["kper"]),
-                                       B, T, V, Lcap, blank, mask_token, eos, C.c_double(float(thr)), int(K), stream_ptr()),
+                                       B, T, V, Lcap, blank, mask_token, eos, float(thr), int(K), stream_ptr()),
           "eamd_maskctc_seed")
     return out
 
@@ -2222,7 +2217,7 @@ def ctc_prefix_score_batch(logp, lens, per_utt, r_prev, cand, last, olen, blank,
 
 
 def ctc_prefix_psi(logp, lens, per_utt, r_prev, cand, last, olen, blank, eos, olen_dev=None):
-    """log psi of the candidates as a parallel reduction over the frames (eamd_ctc_prefix_psi): logp [U, Tmax, V], r_prev
+    """log psi of the candidates as a parallel reduction over the frames (eamd_ctc_prefix_psi_dyn): logp [U, Tmax, V], r_prev
     [U * per_utt, Tmax, 2], cand [n, P] int32, last [n] int32, olen int -> psi [n, P]; None when the library declines (Tmax > 2048)"""
     U, Tmax, V = logp.shape
     nhyp, ncand = cand.shape
@@ -2233,51 +2228,51 @@ def ctc_prefix_psi(logp, lens, per_utt, r_prev, cand, last, olen, blank, eos, ol
                                             int(olen), ptr(olen_dev), ptr(psi), ncand, Tmax, V, blank, eos, stream_ptr())
     if rc == _lib.EAMD_EUNSUPPORTED:
         return None
-    check(rc, "eamd_ctc_prefix_psi")
+    check(rc, "eamd_ctc_prefix_psi_dyn")
     return psi
 
 
 def ctc_prefix_state(logp, lens, per_utt, r_prev, parent, tok, last, olen, alive, blank, out=None, olen_dev=None):
-    """forward variables of the continuations that survived a selection (eamd_ctc_prefix_state): slot s continues hypothesis
+    """forward variables of the continuations that survived a selection (eamd_ctc_prefix_state_dyn): slot s continues hypothesis
     parent[s] (whose state is r_prev[parent[s]], last token last[parent[s]], prefix length olen + 1) with token tok[s];
     alive [n] = the slots' running scores (-inf: ended / empty) -> r [n, Tmax, 2]"""
     U, Tmax, V = logp.shape
     n = parent.numel()
     r = out if out is not None else torch.empty(n, Tmax, 2, device=logp.device, dtype=torch.float32)
     check(_lib.lib().eamd_ctc_prefix_state_dyn(ptr(logp), ptr(lens), U, per_utt, ptr(r_prev), ptr(parent), ptr(tok), ptr(last), int(olen),
-                                               ptr(olen_dev), ptr(alive), ptr(r), Tmax, V, blank, stream_ptr()), "eamd_ctc_prefix_state")
+                                               ptr(olen_dev), ptr(alive), ptr(r), Tmax, V, blank, stream_ptr()), "eamd_ctc_prefix_state_dyn")
     return r
 
 
 # ---- optimizer -------------------------------------------------------------------------------------
 def grad_norm(g, ws, out):
-    check(_lib.lib().eamd_grad_norm(ptr(g), C.c_int64(g.numel()), ptr(ws), ptr(out), stream_ptr()),
+    check(_lib.lib().eamd_grad_norm(ptr(g), g.numel(), ptr(ws), ptr(out), stream_ptr()),
           "eamd_grad_norm")
 
 
 def sched_step(state, gnorm, mode, base_lr, factor, dmodel, warmup, beta1, beta2, max_norm):
-    check(_lib.lib().eamd_sched_step(ptr(state), ptr(gnorm), mode, C.c_float(base_lr), C.c_float(factor),
-                                     C.c_float(dmodel), C.c_float(warmup), C.c_float(beta1), C.c_float(beta2),
-                                     C.c_float(max_norm), stream_ptr()), "eamd_sched_step")
+    check(_lib.lib().eamd_sched_step(ptr(state), ptr(gnorm), mode, base_lr, factor,
+                                     dmodel, warmup, beta1, beta2,
+                                     max_norm, stream_ptr()), "eamd_sched_step")
 
 
 def adam_step(p, g, m, v, state, beta1, beta2, eps, weight_decay, p16=None):
     n = p.numel()
     assert g.numel() == n and m.numel() == n and v.numel() == n and (p16 is None or p16.numel() == n)
-    check(_lib.lib().eamd_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), C.c_int64(n), ptr(state), C.c_float(beta1),
-                                    C.c_float(beta2), C.c_float(eps), C.c_float(weight_decay), stream_ptr()),
+    check(_lib.lib().eamd_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), n, ptr(state), beta1,
+                                    beta2, eps, weight_decay, stream_ptr()),
           "eamd_adam_step")
 
 
 def adadelta_step(p, g, sq, acc, state, rho, weight_decay, p16=None):
-    check(_lib.lib().eamd_adadelta_step(ptr(p), ptr(g), ptr(sq), ptr(acc), ptr(p16), C.c_int64(p.numel()), ptr(state),
-                                        C.c_float(rho), C.c_float(weight_decay), stream_ptr()), "eamd_adadelta_step")
+    check(_lib.lib().eamd_adadelta_step(ptr(p), ptr(g), ptr(sq), ptr(acc), ptr(p16), p.numel(), ptr(state),
+                                        rho, weight_decay, stream_ptr()), "eamd_adadelta_step")
 
 
 def add_gradient_noise(g, sigma, salt=0x6e6f697365):
     """g += sigma * N(0, 1) over a flat fp32 gradient buffer (draws keyed by the device step counter)"""
-    check(_lib.lib().eamd_add_gradient_noise(ptr(g), C.c_int64(g.numel()), C.c_float(sigma), ptr(rng_state(g.device)),
-                                             C.c_uint64(salt), stream_ptr()), "eamd_add_gradient_noise")
+    check(_lib.lib().eamd_add_gradient_noise(ptr(g), g.numel(), sigma, ptr(rng_state(g.device)),
+                                             salt, stream_ptr()), "eamd_add_gradient_noise")
 
 
 def make_gather(Cc, taps, Ho, Wo, Hin, Win, sh, sw):
@@ -2303,13 +2298,13 @@ ACT_TANH, ACT_HARDTANH, ACT_SELU = 3, 4, 5      # eamd_act ids beyond relu / swi
 
 def act_fwd_any(x, act):
     y = torch.empty_like(x)
-    check(_lib.lib().eamd_act_fwd(ptr(x), ptr(y), C.c_int64(x.numel()), act, stream_ptr()), "eamd_act_fwd")
+    check(_lib.lib().eamd_act_fwd(ptr(x), ptr(y), x.numel(), act, stream_ptr()), "eamd_act_fwd")
     return y
 
 
 def act_bwd_any(dy, x, act):
     dx = torch.empty_like(x)
-    check(_lib.lib().eamd_act_bwd(ptr(dy), ptr(x), ptr(dx), C.c_int64(x.numel()), act, stream_ptr()), "eamd_act_bwd")
+    check(_lib.lib().eamd_act_bwd(ptr(dy), ptr(x), ptr(dx), x.numel(), act, stream_ptr()), "eamd_act_bwd")
     return dx
 
 
@@ -2393,7 +2388,7 @@ def lstm_seq_ok(njobs, B, H):
 
 def _lstm_seq_ws(dev):
     global _lstm_seq_last_ws
-    n = int(_lib.lib().eamd_lstm_seq_sync_bytes())
+    n = _lib.lib().eamd_lstm_seq_sync_bytes()
     _lstm_seq_last_ws = torch.empty(n, dtype=torch.uint8, device=dev)
     return _lstm_seq_last_ws
 
@@ -2403,7 +2398,7 @@ def lstm_seq_fwd(jobs, T, B, H):
     arr = (_lib.LstmSeqFwdT * len(jobs))()
     for q, (gx, w, b, live, h, c, y, acts, rev) in zip(arr, jobs):
         q.gx, q.w_hh, q.b_hh, q.live = ptr(gx), ptr(w), ptr(b), ptr(live)
-        q.h_out, q.c_out, q.y, q.acts, q.reverse = ptr(h), ptr(c), ptr(y), ptr(acts), int(bool(rev))
+        q.h_out, q.c_out, q.y, q.acts, q.reverse = ptr(h), ptr(c), ptr(y), ptr(acts), bool(rev)
     ws = _lstm_seq_ws(jobs[0][0].device)
     fn = _lib.lib().eamd_lstm_seq_fwd
     args = (arr, len(jobs), T, B, H, ptr(ws))
@@ -2418,7 +2413,7 @@ def lstm_seq_bwd(jobs, T, B, H):
     """jobs: list of (dy [T,B,H], w_t [H,4H], acts, c_out, live | None, dgates (out), reverse = the FORWARD direction)"""
     arr = (_lib.LstmSeqBwdT * len(jobs))()
     for q, (dy, w_t, acts, c, live, dg, rev) in zip(arr, jobs):
-        q.dy, q.w_t, q.acts, q.c_out, q.live, q.dgates, q.reverse = ptr(dy), ptr(w_t), ptr(acts), ptr(c), ptr(live), ptr(dg), int(bool(rev))
+        q.dy, q.w_t, q.acts, q.c_out, q.live, q.dgates, q.reverse = ptr(dy), ptr(w_t), ptr(acts), ptr(c), ptr(live), ptr(dg), bool(rev)
     ws = _lstm_seq_ws(jobs[0][2].device)
     fn = _lib.lib().eamd_lstm_seq_bwd
     args = (arr, len(jobs), T, B, H, ptr(ws))
@@ -2456,7 +2451,7 @@ def lstm_seq_status():
     """status word of the most recent persistent LSTM launch (synchronises): 0 = every hand-off wait completed"""
     if _lstm_seq_last_ws is None:
         return 0
-    return int(_lib.lib().eamd_lstm_seq_status(ptr(_lstm_seq_last_ws), stream_ptr()))
+    return _lib.lib().eamd_lstm_seq_status(ptr(_lstm_seq_last_ws), stream_ptr())
 
 
 def maxpool2x2_fwd(x):
@@ -2484,7 +2479,7 @@ def conv3x3_c1_fwd(x, w, bias, B, T, F, Cc, out_dtype=torch.float32):
 
 def conv3x3_c1_bwd_w(dy, x, dw, db, B, T, F, Cc):
     L = _lib.lib()
-    ws = torch.empty(int(L.eamd_conv3x3_c1_bwd_w_workspace(B, T, Cc)), device=x.device, dtype=torch.float32)
+    ws = torch.empty(L.eamd_conv3x3_c1_bwd_w_workspace(B, T, Cc), device=x.device, dtype=torch.float32)
     check(L.eamd_conv3x3_c1_bwd_w(ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), B, T, F, Cc,
                                   1 if dy.dtype == torch.bfloat16 else 0, stream_ptr()), "eamd_conv3x3_c1_bwd_w")
 
@@ -2528,7 +2523,7 @@ def rnnt_grad(logits, labels, tlens, ulens, blank, ws, gscale, scale, grad=None)
     grad = torch.empty_like(logits) if grad is None else grad
     lab = labels if labels.numel() > 0 else torch.zeros(1, device=logits.device, dtype=torch.int32)
     check(_lib.lib().eamd_rnnt_grad(ptr(logits), ptr(lab), ptr(tlens), ptr(ulens), ptr(ws), ptr(grad), B, T, U, V, blank,
-                                    ptr(gscale), C.c_float(scale), stream_ptr()), "eamd_rnnt_grad")
+                                    ptr(gscale), scale, stream_ptr()), "eamd_rnnt_grad")
     return grad
 
 
@@ -2539,23 +2534,23 @@ def rnnt_loss(logits, labels, tlens, ulens, blank, grad=None, gscale=None, scale
     assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == B * max(U - 1, 0)
     assert tlens.dtype == torch.int32 and ulens.dtype == torch.int32 and tlens.numel() == B and ulens.numel() == B
     assert grad is None or (grad.numel() == logits.numel() and grad.dtype == torch.float32)
-    ws = torch.empty(int(_lib.lib().eamd_rnnt_workspace(B, T, U)), device=logits.device, dtype=torch.float32)
+    ws = torch.empty(_lib.lib().eamd_rnnt_workspace(B, T, U), device=logits.device, dtype=torch.float32)
     loss = torch.empty(B, device=logits.device, dtype=torch.float32)
     lab = labels if labels.numel() > 0 else torch.zeros(1, device=logits.device, dtype=torch.int32)
     check(_lib.lib().eamd_rnnt_loss(ptr(logits), ptr(lab), ptr(tlens), ptr(ulens), ptr(ws), ptr(loss), ptr(grad),
-                                    B, T, U, V, blank, ptr(gscale), C.c_float(scale), stream_ptr()), "eamd_rnnt_loss")
+                                    B, T, U, V, blank, ptr(gscale), scale, stream_ptr()), "eamd_rnnt_loss")
     return (loss, ws) if return_ws else loss
 
 
 def rnnt_workspace(B, T, U, device):
-    return torch.empty(int(_lib.lib().eamd_rnnt_workspace(B, T, U)), device=device, dtype=torch.float32)
+    return torch.empty(_lib.lib().eamd_rnnt_workspace(B, T, U), device=device, dtype=torch.float32)
 
 
 def rnnt_node_stats(z_rows, labels, ws, node0, B, T, U, blank):
     """lse / log p(blank) / log p(label) of the lattice rows node0.. (z_rows [nrows, V] fp32) into the workspace"""
     nrows, V = z_rows.shape
     assert z_rows.dtype == torch.float32 and z_rows.is_contiguous() and labels.dtype == torch.int32
-    check(_lib.lib().eamd_rnnt_node_stats(ptr(z_rows), ptr(labels), ptr(ws), C.c_int64(node0), C.c_int64(nrows), B, T, U, V,
+    check(_lib.lib().eamd_rnnt_node_stats(ptr(z_rows), ptr(labels), ptr(ws), node0, nrows, B, T, U, V,
                                           blank, stream_ptr()), "eamd_rnnt_node_stats")
 
 
@@ -2584,7 +2579,7 @@ def rnnt_node_stats_fused(H2, W, b_out, col, ws, node0, B, T, U, blank):
         if ("code %d" % _lib.EAMD_EUNSUPPORTED) in str(e):
             return False
         raise
-    check(_lib.lib().eamd_rnnt_node_stats_part(ptr(part), ptr(zcol), ptr(zfix), ptr(ws), C.c_int64(node0), C.c_int64(nrows), tn,
+    check(_lib.lib().eamd_rnnt_node_stats_part(ptr(part), ptr(zcol), ptr(zfix), ptr(ws), node0, nrows, tn,
                                                B, T, U, stream_ptr()), "eamd_rnnt_node_stats_part")
     return True
 
@@ -2600,8 +2595,8 @@ def rnnt_node_grad_fused(H2, W, b_out, labels, tlens, ulens, ws, node0, B, T, U,
     dev = H2.device
     rowc = torch.empty(nrows * 3, device=dev, dtype=torch.float32)
     col = torch.empty(nrows, device=dev, dtype=torch.int32)
-    check(_lib.lib().eamd_rnnt_row_coef(ptr(labels), ptr(tlens), ptr(ulens), ptr(ws), ptr(rowc), ptr(col), C.c_int64(node0),
-                                        C.c_int64(nrows), B, T, U, stream_ptr()), "eamd_rnnt_row_coef")
+    check(_lib.lib().eamd_rnnt_row_coef(ptr(labels), ptr(tlens), ptr(ulens), ptr(ws), ptr(rowc), ptr(col), node0,
+                                        nrows, B, T, U, stream_ptr()), "eamd_rnnt_row_coef")
     dZ = torch.empty(nrows, V, device=dev, dtype=out_dtype)
     try:
         gemm(H2, W, dZ, nrows, V, J, J, J, V, bias=b_out, epilogue=EPI_ROW_GRAD, tile=128 if nrows >= 2048 else 64,
@@ -2628,8 +2623,8 @@ def rnnt_node_grad(z_rows, labels, tlens, ulens, ws, node0, B, T, U, blank, gsca
     else:
         out = torch.empty(nrows, V, device=z_rows.device, dtype=torch.bfloat16)
         g32, g16 = None, ptr(out)
-    check(_lib.lib().eamd_rnnt_node_grad(ptr(z_rows), g32, g16, ptr(labels), ptr(tlens), ptr(ulens), ptr(ws), C.c_int64(node0),
-                                         C.c_int64(nrows), B, T, U, V, blank, ptr(gscale), C.c_float(scale), stream_ptr()),
+    check(_lib.lib().eamd_rnnt_node_grad(ptr(z_rows), g32, g16, ptr(labels), ptr(tlens), ptr(ulens), ptr(ws), node0,
+                                         nrows, B, T, U, V, blank, ptr(gscale), scale, stream_ptr()),
           "eamd_rnnt_node_grad")
     return out
 
@@ -2648,7 +2643,7 @@ def attloc_fwd(att_prev, conv_w, w_att, pre_enc, dec_proj, gvec, gb, lens, enc_h
     w = torch.empty(B, T, device=dev, dtype=torch.float32)
     ctx = torch.empty(B, E, device=dev, dtype=torch.float32)
     check(_lib.lib().eamd_attloc_fwd(ptr(att_prev), ptr(conv_w), ptr(w_att), ptr(pre_enc), ptr(dec_proj), ptr(gvec),
-                                     ptr(gb), ptr(lens), ptr(enc_h), C.c_float(scaling), ptr(e), ptr(th), ptr(conv),
+                                     ptr(gb), ptr(lens), ptr(enc_h), scaling, ptr(e), ptr(th), ptr(conv),
                                      ptr(w), ptr(ctx), B, T, A, Cc, K, R, E, stream_ptr()), "eamd_attloc_fwd")
     return ctx, w, th, conv
 
@@ -2662,7 +2657,7 @@ def attloc_bwd_energy(dctx, dw_ext, w, enc_h, th, gvec, scaling, dgvec, dgb):
     df = torch.empty(B, T, A, device=dev, dtype=torch.float32)
     d_dec = zeros(B, A, device=dev)
     check(_lib.lib().eamd_attloc_bwd_energy(ptr(dctx), ptr(dw_ext), ptr(w), ptr(enc_h), ptr(th), ptr(gvec),
-                                            C.c_float(scaling), ptr(de), ptr(d_enc_h), ptr(df), ptr(dgvec), ptr(dgb),
+                                            scaling, ptr(de), ptr(d_enc_h), ptr(df), ptr(dgvec), ptr(dgb),
                                             ptr(d_dec), B, T, A, E, stream_ptr()), "eamd_attloc_bwd_energy")
     return d_enc_h, df, d_dec
 
@@ -2681,7 +2676,7 @@ def attloc_bwd_energy_conv(dctx, dw_ext, w, enc_h, th, gvec, scaling, conv, w_at
         return None
     dev = enc_h.device
     lib = _lib.lib()
-    nws = int(lib.eamd_attloc_bwd_workspace(B, T, A, Cc)) // 4
+    nws = lib.eamd_attloc_bwd_workspace(B, T, A, Cc) // 4
     ws = torch.empty(nws, device=dev, dtype=torch.float32)
     de = torch.empty(B, T, device=dev, dtype=torch.float32)
     accumulate = acc is not None and "df" in acc
@@ -2692,7 +2687,7 @@ def attloc_bwd_energy_conv(dctx, dw_ext, w, enc_h, th, gvec, scaling, conv, w_at
         df = torch.empty(B, T, A, device=dev, dtype=torch.float32)
     dconv = torch.empty(B, T, Cc, device=dev, dtype=torch.float32)
     d_dec = zeros(B, A, device=dev)
-    rc = lib.eamd_attloc_bwd_energy_conv(ptr(dctx), ptr(dw_ext), ptr(w), ptr(enc_h), ptr(th), ptr(gvec), C.c_float(scaling),
+    rc = lib.eamd_attloc_bwd_energy_conv(ptr(dctx), ptr(dw_ext), ptr(w), ptr(enc_h), ptr(th), ptr(gvec), scaling,
                                          ptr(conv), ptr(w_att), ptr(de), ptr(d_enc_h), ptr(df), ptr(dconv), ptr(dgvec),
                                          ptr(dgb), ptr(d_dec), ptr(dw_att), ptr(ws), int(accumulate), B, T, A, Cc, E,
                                          stream_ptr())
@@ -2739,7 +2734,7 @@ def mask_rows(x, keep):
     rows, D = x.shape
     assert keep.dtype == torch.uint8 and keep.numel() == rows and x.dtype == torch.float32
     y = torch.empty_like(x)
-    check(_lib.lib().eamd_mask_rows(ptr(x), ptr(keep), ptr(y), C.c_int64(rows), D, stream_ptr()), "eamd_mask_rows")
+    check(_lib.lib().eamd_mask_rows(ptr(x), ptr(keep), ptr(y), rows, D, stream_ptr()), "eamd_mask_rows")
     return y
 
 
@@ -2753,7 +2748,7 @@ def att_dot_fwd(k, q, v, lens, scaling):
     ctx = torch.empty(B, E, device=dev, dtype=torch.float32)
     L = _lib.lib()
     check(L.eamd_att_dot_energy_fwd(ptr(k), ptr(q), ptr(lens), ptr(e), B, T, A, stream_ptr()), "eamd_att_dot_energy_fwd")
-    check(L.eamd_att_ctx_fwd(ptr(e), ptr(v), C.c_float(scaling), ptr(w), ptr(ctx), B, T, E, stream_ptr()),
+    check(L.eamd_att_ctx_fwd(ptr(e), ptr(v), scaling, ptr(w), ptr(ctx), B, T, E, stream_ptr()),
           "eamd_att_ctx_fwd")
     return ctx, w
 
@@ -2768,7 +2763,7 @@ def att_dot_bwd(dctx, dw_ext, w, k, q, v, scaling):
     dq = zeros(B, A, device=dev)
     dsum = zeros(1, device=dev)
     L = _lib.lib()
-    check(L.eamd_att_ctx_bwd(ptr(dctx), ptr(dw_ext), ptr(w), ptr(v), C.c_float(scaling), ptr(de), ptr(d_v), ptr(dsum),
+    check(L.eamd_att_ctx_bwd(ptr(dctx), ptr(dw_ext), ptr(w), ptr(v), scaling, ptr(de), ptr(d_v), ptr(dsum),
                              B, T, E, stream_ptr()), "eamd_att_ctx_bwd")
     check(L.eamd_att_dot_energy_bwd(ptr(de), ptr(k), ptr(q), ptr(dk), ptr(dq), B, T, A, stream_ptr()),
           "eamd_att_dot_energy_bwd")
@@ -2860,7 +2855,7 @@ def utterance_mvn(x, lens, norm_means, norm_vars, eps):
     B, T, F = x.shape
     y = torch.empty_like(x)
     ws = torch.empty(2 * B * F, device=x.device, dtype=torch.float32)
-    check(_lib.lib().eamd_utterance_mvn(ptr(x), ptr(y), ptr(lens), ptr(ws), int(norm_means), int(norm_vars), C.c_float(eps),
+    check(_lib.lib().eamd_utterance_mvn(ptr(x), ptr(y), ptr(lens), ptr(ws), int(norm_means), int(norm_vars), eps,
                                         B, T, F, stream_ptr()), "eamd_utterance_mvn")
     return y
 
@@ -2871,7 +2866,7 @@ def reflect_pad(x, pad, ldy, tail):
     B, L = x.shape
     assert x.dtype == torch.float32 and x.is_contiguous() and ldy >= L + 2 * pad
     y = torch.zeros(B * ldy + tail, device=x.device, dtype=torch.float32)
-    check(_lib.lib().eamd_reflect_pad(ptr(x), C.c_int64(L), ptr(y), C.c_int64(ldy), B, L, pad, stream_ptr()),
+    check(_lib.lib().eamd_reflect_pad(ptr(x), L, ptr(y), ldy, B, L, pad, stream_ptr()),
           "eamd_reflect_pad")
     return y
 
@@ -2884,8 +2879,8 @@ def logmel(spec, ld, rows_per_utt, melmat, lo, hi, flens, B, T, F, log_scale=1.0
     if spec.numel() < need:
         raise _lib.EamdError(f"logmel: spectrum buffer too small ({spec.numel()} < {need})")
     out = torch.empty(B, T, M, device=spec.device, dtype=torch.float32)
-    check(_lib.lib().eamd_logmel(ptr(spec), C.c_int64(ld), C.c_int64(rows_per_utt), ptr(melmat), ptr(lo), ptr(hi),
-                                 ptr(flens) if flens is not None else None, ptr(out), B, T, F, M, C.c_float(log_scale),
+    check(_lib.lib().eamd_logmel(ptr(spec), ld, rows_per_utt, ptr(melmat), ptr(lo), ptr(hi),
+                                 ptr(flens) if flens is not None else None, ptr(out), B, T, F, M, log_scale,
                                  int(power_input), stream_ptr()), "eamd_logmel")
     return out
 
@@ -2938,8 +2933,8 @@ def ft_mvn_fwd(x, lens, bias=None, scale=None, apply_utt=True, norm_means=True, 
     assert lens is None or (lens.dtype == torch.int32 and lens.numel() == B)
     y = _ft_out(out, x.shape, x.device)
     ws = torch.empty(2 * B * M, device=x.device, dtype=torch.float32) if apply_utt else None
-    check(_lib.lib().eamd_ft_mvn_fwd(ptr(x), ptr(y), ptr(lens), ptr(bias), ptr(scale), ptr(ws), int(bool(apply_utt)),
-                                     int(bool(norm_means)), int(bool(norm_vars)), C.c_float(eps), B, T, M, stream_ptr()),
+    check(_lib.lib().eamd_ft_mvn_fwd(ptr(x), ptr(y), ptr(lens), ptr(bias), ptr(scale), ptr(ws), bool(apply_utt),
+                                     bool(norm_means), bool(norm_vars), eps, B, T, M, stream_ptr()),
           "eamd_ft_mvn_fwd")
     return y
 
@@ -2951,7 +2946,7 @@ def ft_mvn_bwd(gy, lens, scale=None, apply_utt=True, out=None):
     assert lens is None or (lens.dtype == torch.int32 and lens.numel() == B)
     gx = _ft_out(out, gy.shape, gy.device)
     ws = torch.empty(B * M, device=gy.device, dtype=torch.float32) if apply_utt else None
-    check(_lib.lib().eamd_ft_mvn_bwd(ptr(gy), ptr(gx), ptr(lens), ptr(scale), ptr(ws), int(bool(apply_utt)), B, T, M,
+    check(_lib.lib().eamd_ft_mvn_bwd(ptr(gy), ptr(gx), ptr(lens), ptr(scale), ptr(ws), bool(apply_utt), B, T, M,
                                      stream_ptr()), "eamd_ft_mvn_bwd")
     return gx
 

@@ -384,7 +384,7 @@ int eamd_log_softmax_rows(const float* x, float* y, int rows, int V, void* strea
  * rec [n][1 + 2k (+ k with lm)] = logp[r][0], the k largest of logp[r][1:V) (value descending, equal values by ascending token,
  * NaN as -inf, -0 as +0), their token ids as floats, and with lm ([*, V], may be NULL) lm[lm_row[r]][token] of each chosen token.
  * pairs [g][2] (row, token; may be NULL with g = 0): pair_out[j] = logp[row][token].  logp is bit-identical to
- * eamd_log_softmax_rows, the selection to eamd_topk_rows on columns 1..V-1.  reference: beam_search_transducer.py:239-347
+ * eamd_log_softmax_rows, the selection to eamd_topk_rows_i32 on columns 1..V-1.  reference: beam_search_transducer.py:239-347
  * (time_sync_decoding), :349-464 (align_length_sync_decoding), :466-663 (nsc_beam_search: log_softmax, topk of logp[:, 1:],
  * lm_weight * beam_lm_scores[i, k], the prefix rescoring's ytu[token]). */
 int eamd_transducer_expand_rows(const float* logits, int64_t ld, int n, int V, int k, const float* lm, const int32_t* lm_row,
@@ -414,18 +414,20 @@ int eamd_linear_rows_f32(const float* x, const float* W, const float* bias, cons
  * eamd_linear_rows_ln_f32: y[M, N] (row stride ldy) = alpha * act(LayerNorm(x; gamma, beta, eps) W^T + bias) + R for M <= 16 rows,
  *   K <= 1024 (or 16 < M <= 1024 rows at K <= 256, K % 16 == 0: 16-row blocks on the matrix cores): the pre-norm of a decoder sub-block inside the product behind it (layer_norm.py:12-38 in front of attention.py:40-61 /
  *   positionwise_feed_forward.py:28 / decoder.py:312-317); row strides 0 = dense.
- * eamd_decode_self_attn: self-attention of the NEWEST position of n hypotheses over their prefixes, keys / values cached per layer in
+ * eamd_decode_self_attn_dyn: self-attention of the NEWEST position of n hypotheses over their prefixes, keys / values cached per layer in
  *   time-major [Lcap, n, D] buffers: row (pos, slot) is written from qkv [n, ldq] = (q | k | v) of this step, rows t < pos are read
  *   at slot_at[slot][t] ([n, Lcap] int32: the slot that held this hypothesis's ancestor at position t - a beam step re-orders that
  *   table, never the caches).  d_k = 64 (D = 64 H); ctx [n, D]; no mask (a prefix has no padding).  The reference re-projects keys and
  *   values of the whole prefix at every step from cached layer outputs (decoder_layer.py:88-107): same numbers.
- * eamd_beam_slots: slot_out[i][t] = slot_in[hyp[i]][t] (t < pos), slot_out[i][pos] = hyp[i] - the table behind a selection. */
+ * eamd_beam_slots_dyn: slot_out[i][t] = slot_in[hyp[i]][t] (t < pos), slot_out[i][pos] = hyp[i] - the table behind a selection.
+ * Both: the position is pos, or *pos_dev + pos when pos_dev != NULL (a device int32: see "One hipGraph for EVERY beam step" below). */
 int eamd_linear_rows_ln_f32(const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias,
                             const float* R, float* y, int M, int N, int K, int act, float alpha, int64_t ldx, int64_t ldr,
                             int64_t ldy, void* stream);
-int eamd_decode_self_attn(const float* qkv, int64_t ldq, float* kcache, float* vcache, const int32_t* slot_at, int Lcap, int pos,
-                          int n, int H, int D, float* ctx, void* stream);
-int eamd_beam_slots(const int32_t* slot_in, int32_t* slot_out, const int64_t* hyp, int n, int Lcap, int pos, void* stream);
+int eamd_decode_self_attn_dyn(const float* qkv, int64_t ldq, float* kcache, float* vcache, const int32_t* slot_at, int Lcap, int pos,
+                              const int32_t* pos_dev, int n, int H, int D, float* ctx, void* stream);
+int eamd_beam_slots_dyn(const int32_t* slot_in, int32_t* slot_out, const int64_t* hyp, int n, int Lcap, int pos, const int32_t* pos_dev,
+                        void* stream);
 /* Source attention of a beam step (decoder_layer.py:109-121 on one query position per hypothesis): hypothesis r of nutt * g belongs to
  * utterance r / g and attends over that utterance's T memory frames; kmem / vmem address the keys / values of ONE layer inside the
  * decoder stack's shared projection of the memory ([nutt, T, ldkv] row stride ldkv); mask [nutt, T] uint8 (0 = padded frame, may be
@@ -454,34 +456,16 @@ int eamd_weighted_sum(const float* const* logps, const float* weights, int nf, i
 int eamd_beam_select(const float* pre, const int64_t* ids, const float* psi, const float* c_s, const float* hyp, float w_ctc,
                      int nutt, int beam, int P, int V, float* c_local, float* top_s, int64_t* top_i, void* stream);
 /* The k (<= 64) largest of each row of x [rows, n] (row stride ld), sorted by value descending, equal values by ascending index;
- * NaN counts as -inf.  vals / idx [rows, k].  reference: the torch.topk selections of a beam step (beam_search.py:143-176,
+ * NaN counts as -inf.  vals / idx [rows, k]; idx32 [rows, k] (may be NULL) = the indices also as int32: the candidate list
+ * eamd_ctc_prefix_psi_dyn takes.  reference: the torch.topk selections of a beam step (beam_search.py:143-176,
  * batch_beam_search.py:86-110: pre-beam over V, best `beam` of beam x V). */
-int eamd_topk_rows(const float* x, int64_t ld, int rows, int n, int k, float* vals, int64_t* idx, void* stream);
-/* ... the indices also as int32 (idx32 [rows, k], may be NULL): the candidate list eamd_ctc_prefix_psi takes. */
 int eamd_topk_rows_i32(const float* x, int64_t ld, int rows, int n, int k, float* vals, int64_t* idx, int32_t* idx32, void* stream);
 /* One hipGraph for EVERY beam step (reference: the step index `i` of beam_search.py:349-364's loop, here a device integer): the
- * variants below read the step-dependent integer from device memory - value = *dev + the host argument, which becomes an offset -
- * so a captured step does not bake it in.  eamd_beam_step_dyn reads step (L = step + 1) from step_dev, writes the log row into
- * slot step % ring of a [ring][n][3 + ns + W] ring (ring 0: as before) and leaves step + 1 in step_out; with slot_in / slot_out
- * ([n, Lcap] int32) it also does eamd_beam_slots' re-ordering of the cached decoder's slot table (position = step).  eamd_copy_jobs: up to 16
- * small device-to-device copies (sizes in bytes, multiples of 4) in one launch - the state a step hands to the next replay. */
-int eamd_decode_self_attn_dyn(const float* qkv, int64_t ldq, float* kcache, float* vcache, const int32_t* slot_at, int Lcap, int pos,
-                              const int32_t* pos_dev, int n, int H, int D, float* ctx, void* stream);
-int eamd_beam_slots_dyn(const int32_t* slot_in, int32_t* slot_out, const int64_t* hyp, int n, int Lcap, int pos, const int32_t* pos_dev,
-                        void* stream);
-int eamd_beam_step_dyn(const float* pre, const int64_t* ids, const float* psi, const float* c_s, const float* hyp, float w_ctc, int nutt,
-                       int beam, int P, int V, int W, int L, int step, int eos, const int64_t* maxlen, int ns, int nf, const float* sc_in,
-                       const float* const* logps, const int64_t* yseq_in, float* c_local, float* sc_out, int64_t* yseq_out, float* hyp_out,
-                       int64_t* hyp_i, int64_t* tok_i, int32_t* tok32, float* cs_out, float* rec, const int32_t* step_dev, int32_t* step_out,
-                       int ring, const int32_t* slot_in, int32_t* slot_out, int Lcap, void* stream);
-int eamd_ctc_prefix_psi_dyn(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev, const int32_t* cand,
-                            const int32_t* last, int olen, const int32_t* olen_dev, float* psi, int ncand, int Tmax, int V, int blank,
-                            int eos, void* stream);
-int eamd_ctc_prefix_state_dyn(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev, const int64_t* parent,
-                              const int64_t* tok, const int32_t* last, int olen, const int32_t* olen_dev, const float* alive, float* r_out,
-                              int Tmax, int V, int blank, void* stream);
-int eamd_embed_pe_dyn(const int64_t* tok, int64_t ldt, const float* table, const float* pe, float* out, int64_t rows, int U, int D,
-                      float scale, int pos_offset, const int32_t* pos_dev, void* stream);
+ * *_dyn entry points (eamd_decode_self_attn_dyn, eamd_beam_slots_dyn, eamd_beam_step_dyn, eamd_ctc_prefix_psi_dyn,
+ * eamd_ctc_prefix_state_dyn, eamd_embed_pe_dyn) read the step-dependent integer from device memory - value = *dev + the host
+ * argument, which becomes an offset; dev == NULL: the host argument alone - so a captured step does not bake it in.
+ * eamd_copy_jobs: up to 16 small device-to-device copies (sizes in bytes, multiples of 4) in one launch - the state a step hands
+ * to the next replay. */
 int eamd_copy_jobs(const void* const* src, void* const* dst, const int64_t* nbytes, int njobs, void* stream);
 /* eamd_weighted_sum + eamd_topk_rows_i32 in one launch: pre [rows, n] = sum_j weights[j] * logps[j] (written out; HOST arrays of
  * nf <= 4 device pointers / floats, the same separately rounded arithmetic), and the k largest of each of its rows.
@@ -489,16 +473,21 @@ int eamd_copy_jobs(const void* const* src, void* const* dst, const int64_t* nbyt
  * (the <eos> a "full"-mode partial scorer scores besides the pre-beam: batch_beam_search.py:221-231, scorers/ctc.py:82-96). */
 int eamd_weighted_topk_rows(const float* const* logps, const float* weights, int nf, int rows, int n, int k, int extra, float* pre,
                             float* vals, int64_t* idx, int32_t* idx32, void* stream);
-/* eamd_beam_select + eamd_beam_finish of a BeamSearch step with a pre-beam in one launch (one workgroup per utterance; same
+/* eamd_beam_step_dyn: eamd_beam_select + eamd_beam_finish of a BeamSearch step with a pre-beam in one launch (one workgroup per utterance; same
  * arithmetic): the arguments of both - ids [n, P] the candidates, ns == nf + 1 (the partial scorer's row is last), W the width of the
  * prefix buffers, L the position the new token takes - plus tok32 [n] = tok_i as int32 (the next step's `last`) and
  * cs_out [n] = psi at the chosen candidate of the extended hypothesis (the partial scorer's running prefix score).  A candidate
  * id < 0 is no candidate (it is never selected).  beam <= 64,
- * beam * P <= 1023, beam * V < 2^31.  reference: beam_search.py:143-226,296-334. */
-int eamd_beam_step(const float* pre, const int64_t* ids, const float* psi, const float* c_s, const float* hyp, float w_ctc, int nutt,
-                   int beam, int P, int V, int W, int L, int step, int eos, const int64_t* maxlen, int ns, int nf, const float* sc_in,
-                   const float* const* logps, const int64_t* yseq_in, float* c_local, float* sc_out, int64_t* yseq_out, float* hyp_out,
-                   int64_t* hyp_i, int64_t* tok_i, int32_t* tok32, float* cs_out, float* rec, void* stream);
+ * beam * P <= 1023, beam * V < 2^31.  reference: beam_search.py:143-226,296-334.
+ * step_dev != NULL: step is read from it (L = step + 1; the host L / step are ignored), the log row goes into slot step % ring of a
+ * [ring][n][3 + ns + W] ring (ring 0: rec is one [n][3 + ns + W] row set) and step + 1 is left in step_out; step_dev == NULL: the
+ * host L / step.  With slot_in / slot_out ([n, Lcap] int32; both or neither) it also does eamd_beam_slots_dyn's re-ordering of the
+ * cached decoder's slot table (position = step). */
+int eamd_beam_step_dyn(const float* pre, const int64_t* ids, const float* psi, const float* c_s, const float* hyp, float w_ctc, int nutt,
+                       int beam, int P, int V, int W, int L, int step, int eos, const int64_t* maxlen, int ns, int nf, const float* sc_in,
+                       const float* const* logps, const int64_t* yseq_in, float* c_local, float* sc_out, int64_t* yseq_out, float* hyp_out,
+                       int64_t* hyp_i, int64_t* tok_i, int32_t* tok32, float* cs_out, float* rec, const int32_t* step_dev, int32_t* step_out,
+                       int ring, const int32_t* slot_in, int32_t* slot_out, int Lcap, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Element-wise helpers.
@@ -535,12 +524,11 @@ int eamd_add_colsum2_f32(const float* a, const float* b, float* out, int64_t ld_
 int eamd_colsum(const void* x, int64_t ld, float* out, int64_t rows, int D, float scale, int x_bf16, void* stream);
 /* reference: decoder.py:83-86,251 (Embedding + PositionalEncoding), embedding.py:80-91.
  * pe may be NULL (plain nn.Embedding lookup: rnn/decoders.py:88, transducer/rnn_decoder.py:44);
- * pad_idx >= 0 in the backward = nn.Embedding(padding_idx): that row gets no gradient (-1: none). */
-int eamd_embed_pe(const int64_t* tok, const float* table, const float* pe, float* out, int64_t rows, int U,
-                  int D, float scale, int pos_offset, void* stream);
-/* ... token r read at tok[r * ldt] (the newest column of a [n, W] prefix buffer: a beam step's input). */
-int eamd_embed_pe_ld(const int64_t* tok, int64_t ldt, const float* table, const float* pe, float* out, int64_t rows, int U,
-                     int D, float scale, int pos_offset, void* stream);
+ * pad_idx >= 0 in the backward = nn.Embedding(padding_idx): that row gets no gradient (-1: none).
+ * Token r is read at tok[r * ldt] (1: dense; W: the newest column of a [n, W] prefix buffer, a beam step's input); the first position is
+ * pos_offset, or *pos_dev + pos_offset when pos_dev != NULL (see "One hipGraph for EVERY beam step" above). */
+int eamd_embed_pe_dyn(const int64_t* tok, int64_t ldt, const float* table, const float* pe, float* out, int64_t rows, int U, int D,
+                      float scale, int pos_offset, const int32_t* pos_dev, void* stream);
 int eamd_embed_bwd(const int64_t* tok, const float* dout, float* dtable, int64_t rows, int D, float scale,
                    int64_t pad_idx, void* stream);
 int eamd_posenc(const float* x, const float* pe, float* out, int64_t rows, int T, int D, float scale,
@@ -669,17 +657,19 @@ int eamd_ctc_prefix_score_batch(const float* logp, const int32_t* lens, int nutt
                                 const int32_t* cand, const int32_t* last, const int32_t* olen, float* psi, float* r_new,
                                 int ncand, int Tmax, int V, int blank, int eos, void* stream);
 /* The same scores with the serial recursion OFF a beam step's critical path (csrc/ctc.hip): log psi of a candidate is a logsumexp over
- * the frames of phi(t-1) + x(t) (ctc_prefix_score.py:290-296 never reads r[t] for it) - eamd_ctc_prefix_psi forms it as a parallel
+ * the frames of phi(t-1) + x(t) (ctc_prefix_score.py:290-296 never reads r[t] for it) - eamd_ctc_prefix_psi_dyn forms it as a parallel
  * reduction (one wave per (hypothesis, candidate); Tmax <= 2048) - and only the continuations that SURVIVE the selection need their
- * forward variables: eamd_ctc_prefix_state runs the recursion of :291-295 for slot s = (hypothesis parent[s], token tok[s]) into
+ * forward variables: eamd_ctc_prefix_state_dyn runs the recursion of :291-295 for slot s = (hypothesis parent[s], token tok[s]) into
  * r_out [n, Tmax, 2] (slots with alive[s] = -inf get log-zero rows); the caller issues it at the start of the next step on a second
  * stream beside the decoder stack.  olen = prefix length - 1 of the scored hypotheses (one value: all hypotheses of a step have the
- * same length); last [n] = their last tokens.  Same values as eamd_ctc_prefix_score_batch up to the order of the log-sum-exp. */
-int eamd_ctc_prefix_psi(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev, const int32_t* cand,
-                        const int32_t* last, int olen, float* psi, int ncand, int Tmax, int V, int blank, int eos, void* stream);
-int eamd_ctc_prefix_state(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev, const int64_t* parent,
-                          const int64_t* tok, const int32_t* last, int olen, const float* alive, float* r_out, int Tmax, int V, int blank,
-                          void* stream);
+ * same length; *olen_dev + olen when olen_dev != NULL: "One hipGraph for EVERY beam step" above); last [n] = their last tokens.
+ * Same values as eamd_ctc_prefix_score_batch up to the order of the log-sum-exp. */
+int eamd_ctc_prefix_psi_dyn(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev, const int32_t* cand,
+                            const int32_t* last, int olen, const int32_t* olen_dev, float* psi, int ncand, int Tmax, int V, int blank,
+                            int eos, void* stream);
+int eamd_ctc_prefix_state_dyn(const float* logp, const int32_t* lens, int nutt, int per_utt, const float* r_prev, const int64_t* parent,
+                              const int64_t* tok, const int32_t* last, int olen, const int32_t* olen_dev, const float* alive, float* r_out,
+                              int Tmax, int V, int blank, void* stream);
 
 /* ---- feature-side layers ----------------------------------------------
  * SpecAugment on a [B,T,F] batch (x != y).  reference: espnet2/asr/specaug/specaug.py:19-84,

@@ -50,7 +50,89 @@ def test_bad_arguments_are_rejected_without_a_gpu(lib):
     assert lib.eamd_gemm(None, None) < 0
     lib.eamd_ctc_workspace_bytes.restype = ctypes.c_int64
     assert lib.eamd_ctc_workspace_bytes(2, 10, 3) > 0
-    assert lib.eamd_layernorm_fwd(None, None, None, None, None, None, 4, 8, ctypes.c_float(1e-12), None) < 0
+    assert lib.eamd_layernorm_fwd(None, None, None, None, None, None, None, 4, 8, ctypes.c_float(1e-12), None) < 0
+
+
+def header_prototypes():
+    """(return type, name, parameter list) of every prototype, by a regex of this file's own over the comment-free header"""
+    src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    return [(r, n, [] if a.strip() in ("", "void") else a.split(","))
+            for r, n, a in re.findall(r"\b(int64_t|int)\s+(eamd_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)]
+
+
+def test_binding_takes_every_prototype_from_the_header():
+    from espnet_amd import _lib
+    L = _lib.lib()
+    protos = header_prototypes()
+    assert sorted(n for _, n, _ in protos) == declared_symbols()
+    by_value = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+                "double": ctypes.c_double}
+    wide = set()
+    for ret, name, params in protos:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        for decl, bound in zip(params, fn.argtypes):
+            want = ctypes.c_void_p if "*" in decl else by_value[decl.replace("const", "").split()[0]]
+            assert bound is want, (name, decl)
+        assert fn.restype is (ctypes.c_int64 if ret == "int64_t" else ctypes.c_int), name
+        if ret == "int64_t":
+            wide.add(name)
+    assert {"eamd_rowproj_lnb_workspace", "eamd_decode_src_attn_split_workspace"} <= wide and len(wide) == 14
+
+
+def test_binding_passes_64_bit_values_whole_and_checks_arguments():
+    from espnet_amd import _lib
+    L = _lib.lib()
+    # int64_t arguments, passed as plain ints: cut to 32 bits, (1 << 32) + 1 rows would be one slab again
+    assert L.eamd_bn_nslab(1, 64) == 1
+    assert L.eamd_bn_nslab((1 << 32) + 1, 64) > 1
+    # int64_t results: about 3.2e9 bytes by the formula in csrc/ctc.hip
+    assert L.eamd_ctc_workspace_bytes(64, 4096, 512) > 2 ** 31
+    # a plain Python float for a float parameter; NULL operands are still refused on the host
+    assert L.eamd_layernorm_fwd(None, None, None, None, None, None, None, 4, 8, 1e-12, None) < 0
+    with pytest.raises(TypeError):                       # ten arguments for eleven parameters
+        L.eamd_layernorm_fwd(None, None, None, None, None, None, 4, 8, 1e-12, None)
+    with pytest.raises((TypeError, ctypes.ArgumentError)):   # a float where the header says int
+        L.eamd_layernorm_fwd(None, None, None, None, None, None, None, 4.0, 8, 1e-12, None)
+    with pytest.raises((TypeError, ctypes.ArgumentError)):   # a c_int64 where the header says int
+        L.eamd_layernorm_fwd(None, None, None, None, None, None, None, ctypes.c_int64(4), 8, 1e-12, None)
+    # what the call sites hand to pointer parameters: None, an address, a c_void_p, byref(struct), a ctypes array
+    g = _lib.GemmT()
+    for p in (None, 0, ctypes.c_void_p(0), ctypes.byref(g), (_lib.GemmT * 2)()):
+        assert L.eamd_gemm_multi(p, 0, None) < 0
+
+
+def test_prototype_parser():
+    from espnet_amd import _lib
+    got = _lib.parse_prototypes("/* int eamd_not_this(int a); */\n"
+                                "typedef struct { int32_t n; } eamd_x_t;\n"
+                                "int eamd_a(const float* x, const float* const* rows, int64_t n, uint64_t salt, float p,\n"
+                                "           double thr, int32_t k, const eamd_x_t* d, void* stream);\n"
+                                "int64_t eamd_b(int rows);\nint eamd_c(void);\n")
+    vp = ctypes.c_void_p
+    assert got == {"eamd_a": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double,
+                                             ctypes.c_int, vp, vp]),
+                   "eamd_b": (ctypes.c_int64, [ctypes.c_int]), "eamd_c": (ctypes.c_int, [])}
+    with pytest.raises(_lib.EamdError, match="eamd_d"):
+        _lib.parse_prototypes("int eamd_d(const float* x, size_t n, void* stream);")
+    with pytest.raises(_lib.EamdError, match="eamd_e"):
+        _lib.parse_prototypes("size_t eamd_e(int n);")
+
+
+def test_only_the_binding_sets_prototypes_and_only_ops_calls_the_library():
+    pkg = os.path.join(ROOT, "espnet_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith(".py"):
+                continue
+            src = open(os.path.join(dirpath, f)).read()
+            if f == "_lib.py":
+                assert len(re.findall(r"\.restype\s*=", src)) == 1
+            elif f != "graphs.py":                                     # graphs.py binds the HIP runtime, not this library
+                assert "restype" not in src, f
+            if f not in ("ops.py", "_lib.py"):
+                assert not re.search(r"\.eamd_\w+\(", src), f
+    assert not re.search(r"\bc_(int64|uint64|float|double)\(", open(os.path.join(pkg, "ops.py")).read())
 
 
 def test_struct_layout_matches_header():

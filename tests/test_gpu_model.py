@@ -1232,7 +1232,7 @@ def test_decode_c2width_golden(cw, ratio, pen):
     """a19 at the benchmarked width (d = 256, d_k = 64, ff = 2048, |V| = 5000, beam 10, T' = 249 / 159 / 74): BeamSearch against
     the reference's BeamSearch (CTCPrefixScore) and BatchBeamSearch against its BatchBeamSearch (CTCPrefixScoreTH: <eos> scored
     outside the pre-beam), one utterance per search AND the three utterances in one search (forward_batch): the code the decode
-    bench dispatches - fused attention with T1 = beam, shared source-attention memory, two-stage eamd_topk_rows,
+    bench dispatches - fused attention with T1 = beam, shared source-attention memory, two-stage eamd_topk_rows_i32,
     eamd_ctc_prefix_score_batch over 249 frames, eamd_beam_finish.  ids exact, scores 1e-4 (c2width_compare)."""
     from espnet_amd.nets.batch_beam_search import BatchBeamSearch
     from espnet_amd.nets.beam_search import BeamSearch
@@ -2263,8 +2263,8 @@ def test_beam_candidate_selection_matches_tensor_expressions():
 
 
 def test_beam_ctc_split_matches_full_recursion():
-    """BeamSearch with the CTC prefix scores split into the parallel candidate scoring (eamd_ctc_prefix_psi) and the survivors'
-    forward variables on a second stream (eamd_ctc_prefix_state) against the full recursion for every candidate
+    """BeamSearch with the CTC prefix scores split into the parallel candidate scoring (eamd_ctc_prefix_psi_dyn) and the survivors'
+    forward variables on a second stream (eamd_ctc_prefix_state_dyn) against the full recursion for every candidate
     (eamd_ctc_prefix_score_batch): same token ids, scores within 1e-5 relative (the log-sum-exp's order differs), with and without
     the side stream, single utterances and three utterances per search, at config 2's width"""
     from espnet_amd.nets.beam_search import BeamSearch
@@ -2281,7 +2281,7 @@ def test_beam_ctc_split_matches_full_recursion():
                         pre_beam_score_key="full")
         bs.ctc_psi_parallel = mode != "full"
         bs.ctc_side_stream = mode == "split"          # True: forked in eager steps too
-        bs.step_kernel = mode != "split_inline"       # eamd_beam_step / eamd_beam_select + eamd_beam_finish
+        bs.step_kernel = mode != "split_inline"       # eamd_beam_step_dyn / eamd_beam_select + eamd_beam_finish
         one = [bs(e, maxlenratio=0.2) for e in encs]
         many = bs.forward_batch(encs, maxlenratio=0.0)
         res[mode] = [[(h.yseq.tolist(), float(h.score)) for h in nb[:10]] for nb in one + many]
@@ -2293,8 +2293,8 @@ def test_beam_ctc_split_matches_full_recursion():
 
 def test_batch_beam_candidate_selection_matches_tensor_expressions():
     """BatchBeamSearch ("full" mode: the CTC scorer reports whole [n, V] rows, log-zero outside the pre-beam, <eos> always scored):
-    the selection on the P + 1 candidates (pre-beam and <eos>: eamd_weighted_topk_rows with the extra column, eamd_ctc_prefix_psi,
-    eamd_beam_step) against the tensor expressions over all V tokens - same token ids, scores within 1e-5 relative (the candidates'
+    the selection on the P + 1 candidates (pre-beam and <eos>: eamd_weighted_topk_rows with the extra column, eamd_ctc_prefix_psi_dyn,
+    eamd_beam_step_dyn) against the tensor expressions over all V tokens - same token ids, scores within 1e-5 relative (the candidates'
     CTC scores come from the parallel reduction there and from the frame-by-frame recursion here)"""
     from espnet_amd.nets.batch_beam_search import BatchBeamSearch
     from espnet_amd.nets.ctc_prefix_score import LengthBonus

@@ -1558,7 +1558,7 @@ def test_ffn_layernorm_in_front(ops, prec, M, F, act):
 @pytest.mark.parametrize("rows,n,k", [(10, 5000, 15), (1, 50000, 10), (320, 5000, 10), (32, 50000, 10), (3, 7, 7), (5, 6144, 64), (4, 6145, 3),
                                       (6, 100, 10), (3, 300, 64), (2, 1, 1)])
 def test_topk_rows(ops, rows, n, k):
-    """eamd_topk_rows against torch.topk (the selections of a beam step: beam_search.py:143-176): values equal element for
+    """eamd_topk_rows_i32 against torch.topk (the selections of a beam step: beam_search.py:143-176): values equal element for
     element; indices equal where the values are distinct; ties (planted duplicates, -inf runs of dead beam slots, NaN = -inf) in
     ascending index order; two launches bit-equal."""
     g = torch.Generator().manual_seed(rows * 131 + n)
@@ -1689,8 +1689,8 @@ def test_ctc_prefix_score_vs_float64(ops, lens):
     recursion: candidates include <eos>, blank and the prefix's last token (the r^b-only branch), frames whose posterior is
     -inf for a candidate AND for blank (np.logaddexp(-inf, -inf) = -inf), prefixes longer than a short utterance is not needed.
     Bound: |err| <= 1e-5 + 2e-6 |ref| (fp32 ulp at |r| ~ 300 is 3e-5; the float32 numpy arithmetic of the reference itself
-    is measured beside it).  Longer utterances (700 and 1500 frames: 16 / 32 frames per lane in eamd_ctc_prefix_psi and in the
-    scan of eamd_ctc_prefix_state) under the same bound."""
+    is measured beside it).  Longer utterances (700 and 1500 frames: 16 / 32 frames per lane in eamd_ctc_prefix_psi_dyn and in the
+    scan of eamd_ctc_prefix_state_dyn) under the same bound."""
     import sys, os
     from conftest import ROOT
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -1759,8 +1759,8 @@ def test_ctc_prefix_score_vs_float64(ops, lens):
             assert float(r_b[sl, :, T:].abs().max()) == 0.0 if T < Tmax else True   # rows beyond the utterance stay zero
         # next step: each hypothesis takes one of its candidates (not blank / <eos>), state = the float64 one
         pick = torch.randint(2, P, (U, per), generator=g).numpy()
-        # the split form of a beam step: candidates scored by the parallel reduction (eamd_ctc_prefix_psi: same bound against
-        # float64), the survivors' forward variables by eamd_ctc_prefix_state: bit-equal to the full recursion's rows
+        # the split form of a beam step: candidates scored by the parallel reduction (eamd_ctc_prefix_psi_dyn: same bound against
+        # float64), the survivors' forward variables by eamd_ctc_prefix_state_dyn: bit-equal to the full recursion's rows
         psi_p = ops.ctc_prefix_psi(logp_d, lens_d, per, rp_d, cand_d, last_d, step, blank, eos)
         for u in range(U):
             chk("psi (parallel) u%d step%d" % (u, step), psi_p[u * per:(u + 1) * per].cpu().numpy(), psi64[u], "psi")
@@ -1791,7 +1791,7 @@ def test_ctc_prefix_score_vs_float64(ops, lens):
 
 
 def test_ctc_prefix_state_beyond_2048_frames_equals_full_recursion(ops):
-    """more than 2048 frames: eamd_ctc_prefix_state walks the frames one by one (no scan) - the same ctc_prefix_recursion as
+    """more than 2048 frames: eamd_ctc_prefix_state_dyn walks the frames one by one (no scan) - the same ctc_prefix_recursion as
     eamd_ctc_prefix_score_batch, one group of frames in flight instead of four.  Over three chained steps (utterances of 2100 and
     1300 frames, |V| = 600, 4 hypotheses x 9 candidates; slot s continues hypothesis parent[s] - a permutation inside each
     utterance - with one of its candidates; one dead slot) its rows are BIT-EQUAL to the (hypothesis, candidate) rows of the
@@ -1976,7 +1976,7 @@ def test_ffn_bwd_layernorm_backward_epilogue(ops):
 
 def test_decode_kernels_vs_float64(ops):
     """csrc/decode.hip: eamd_linear_rows_ln_f32 against float64 LayerNorm + Linear (+ ReLU, residual, strided rows); the cached
-    self-attention (eamd_decode_self_attn + eamd_beam_slots) over six beam steps with random re-ordering of the hypotheses
+    self-attention (eamd_decode_self_attn_dyn + eamd_beam_slots_dyn) over six beam steps with random re-ordering of the hypotheses
     against softmax attention in float64 over each hypothesis's TRUE history (keys / values gathered along its ancestry)."""
     g = torch.Generator().manual_seed(11)
     rnd = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
