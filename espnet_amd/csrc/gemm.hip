@@ -441,7 +441,8 @@ static int gemm_check(eamd_gemm_t& p, int& tile_out) {
   if (p.in_dtype == 1 && p.h_dtype != 0) return EAMD_EUNSUPPORTED;            // bf16 operands: bf16 second output
   if (p.in_dtype != 1 && ((p.Hb && !(p.h_dtype == 1 && p.precision == 0)) || (p.drop_p != 0.f && p.precision != 0)))
     return EAMD_EUNSUPPORTED;
-  if ((p.a_drop_p != 0.f || p.b_drop_p != 0.f) && (p.in_dtype != 0 || p.precision != 0)) return EAMD_EUNSUPPORTED;
+  // tanh / hardtanh / selu on a staged operand: the pipelined fp32 kernel only
+  if ((p.a_act > EAMD_ACT_SWISH || p.b_act > EAMD_ACT_SWISH) && (p.in_dtype != 0 || p.precision != 0)) return EAMD_EUNSUPPORTED;
   tile_out = tile;
   return EAMD_OK;
 }
@@ -461,15 +462,15 @@ extern "C" int eamd_gemm(const eamd_gemm_t* pp, void* stream_) {
   // the implicit-conv weight gradients among them go (gather + transA: tiny output, K in the millions,
   // bound by the operand stream) through the pipelined fp32 kernel instead - exact fp32 arithmetic, i.e. no less accurate
   // (config 4, bf16 mode: 92.5 -> 91.1 ms)
-  if (p.precision == 1 && p.gather.enabled && p.transA && !p.Hb && p.drop_p == 0.f && p.a_drop_p == 0.f &&
-      p.b_drop_p == 0.f) {
+  if (p.precision == 1 && p.gather.enabled && p.transA && !p.Hb && p.drop_p == 0.f) {
     const int rc = eamd_gemm_f32_dispatch(p, tile, stream);
     if (rc != EAMD_EUNSUPPORTED) return rc;
   }
   if (p.precision == 0) {     // reference precision: the pipelined fp32-MFMA kernel wherever its staging conditions hold
     const int rc = eamd_gemm_f32_dispatch(p, tile, stream);
     if (rc != EAMD_EUNSUPPORTED) return rc;
-    if (p.drop_p != 0.f || p.a_drop_p != 0.f || p.b_drop_p != 0.f || p.Hb) return EAMD_EUNSUPPORTED;   // generic kernel: no dropout
+    // generic kernel: no dropout, staged relu / swish only
+    if (p.drop_p != 0.f || p.Hb || p.a_act > EAMD_ACT_SWISH || p.b_act > EAMD_ACT_SWISH) return EAMD_EUNSUPPORTED;
   }
   if (stats || rowgrad) return EAMD_EUNSUPPORTED;       // the generic kernel has neither row epilogue
   if (tile == 128) {

@@ -577,8 +577,8 @@ int eamd_gemm_bf16_dispatch(const eamd_gemm_t& p, int tile, hipStream_t stream) 
 // ---- grouped weight-gradient launch (bf16 operands): see gemm_f32.hip ----
 int eamd_gemm_bf16_group_count(const eamd_gemm_t& p) {
   if (p.in_dtype != 1 || !p.transA || !p.transB || !p.C || p.Cb || p.Hb || p.aux || p.R || p.bias) return EAMD_EUNSUPPORTED;
-  if (p.gather.enabled || p.cmap.enabled || p.epilogue || p.a_act || p.b_act || p.drop_p > 0.f || p.a_drop_p > 0.f ||
-      p.b_drop_p > 0.f || p.batch1 * p.batch2 != 1 || p.splitk < 1)
+  if (p.gather.enabled || p.cmap.enabled || p.epilogue || p.a_act || p.b_act || p.drop_p > 0.f ||
+      p.batch1 * p.batch2 != 1 || p.splitk < 1)
     return EAMD_EUNSUPPORTED;
   if (p.splitk == 1 && p.beta != 1.f) return EAMD_EUNSUPPORTED;          // accumulate into the gradient buffer
   const bool a_ok = aligned16(p.A) && p.lda % 8 == 0 && p.lda >= (p.M + 7) / 8 * 8;

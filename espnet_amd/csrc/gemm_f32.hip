@@ -49,7 +49,11 @@ struct SmemF {
   __device__ float* b(int buf) { return ab + 2 * RA * LDA + buf * RB * LDB; }
 };
 
+// ACT = 1: the instantiations the model runs know relu and swish only; ACT = 2: any eamd_act id (tanh, hardtanh, selu), kept
+// apart because the general code costs the relu / swish kernels registers and scratch
+template <int ACT>
 __device__ __forceinline__ float4 act4(float4 v, int act) {
+  if constexpr (ACT == 2) return make_float4(eamd_act(v.x, act), eamd_act(v.y, act), eamd_act(v.z, act), eamd_act(v.w, act));
   if (act == EAMD_ACT_SWISH) return make_float4(eamd_swish(v.x), eamd_swish(v.y), eamd_swish(v.z), eamd_swish(v.w));
   return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
 }
@@ -59,7 +63,7 @@ __device__ __forceinline__ float4 mask4(float4 v, int nv) {
 
 // One workgroup's share of a problem: `bid` of `nblk` workgroups (tile x split-K slice), batch index `zb`.
 // gemm_f32_kernel runs it on a launch of its own; gemm_f32_group_kernel looks the problem up in a device table.
-template <int BM, int BN, bool TA, bool TB, bool GAT, bool ACT, bool ROWEPI = false, bool NOPAD = false>
+template <int BM, int BN, bool TA, bool TB, bool GAT, int ACT, bool ROWEPI = false, bool NOPAD = false>
 __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bid, const int nblk, const int zb) {
   constexpr int WM = BM / 2, WN = BN / 2;
   constexpr int MT = WM / 16, NTL = WN / 16;
@@ -183,9 +187,6 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
   constexpr int DEPTH = BM >= 128 ? 2 : 3;
   constexpr int UNROLL = DEPTH % 2 ? 2 * DEPTH : DEPTH;
   float4 ra[DEPTH][NCA], rb[DEPTH][NCB];
-  // operand-side dropout (ACT instantiations only): seeds once, one hash pair per staged 4-element chunk
-  const unsigned a_dseed = (ACT && p.a_drop_p > 0.f) ? eamd_drop_seed((const unsigned long long*)p.drop_step, p.a_drop_salt) : 0u;
-  const unsigned b_dseed = (ACT && p.b_drop_p > 0.f) ? eamd_drop_seed((const unsigned long long*)p.drop_step, p.b_drop_salt) : 0u;
   const bool do_colsum = TA && p.colsum != nullptr && !GAT && tile_n == 0;
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -291,24 +292,12 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
     float* la = sm.a(buf);
     float* lb = sm.b(buf);
     if constexpr (ACT) {
-      // activation / dropout of the staged operands, ONE chunk at a time (act -> mask -> bias-gradient sum -> LDS store,
-      // then a scheduling fence): interleaving the hashes of all chunks cost 30+ VGPRs and spilled the 128x128 variant.
-      // Mask index = element index in the operand's own [rows, ld] matrix = the chunk's load offset (chunks that were
-      // clamped in only feed rows / columns that are never stored); operands are < 2^32 elements (checked on the host).
-      const unsigned a_thr = eamd_drop_thr16(p.a_drop_p), b_thr = eamd_drop_thr16(p.b_drop_p);
-      const float a_inv = eamd_drop_inv(a_thr), b_inv = eamd_drop_inv(b_thr);
-      const unsigned a_k = TA ? (unsigned)k0 * (unsigned)p.lda : (unsigned)k0;
-      const unsigned b_k = TB ? (unsigned)k0 * (unsigned)p.ldb : (unsigned)k0;
+      // activation of the staged operands, ONE chunk at a time (act -> bias-gradient sum -> LDS store, then a scheduling
+      // fence), so that the activations of all chunks are not live at once
 #pragma unroll
       for (int i = 0; i < NCA; ++i) {
         float4 v = ra[SET][i];
-        if (p.a_act != EAMD_ACT_NONE) v = act4(v, p.a_act);
-        if (p.a_drop_p > 0.f) {
-          bool kp[4];
-          eamd_drop_keep4(a_dseed, (unsigned long long)((unsigned)a_off[i] + a_k), a_thr, kp);
-          v = make_float4(kp[0] ? v.x * a_inv : 0.f, kp[1] ? v.y * a_inv : 0.f, kp[2] ? v.z * a_inv : 0.f,
-                          kp[3] ? v.w * a_inv : 0.f);
-        }
+        if (p.a_act != EAMD_ACT_NONE) v = act4<ACT>(v, p.a_act);
         if (do_colsum) { cs[0] += v.x; cs[1] += v.y; cs[2] += v.z; cs[3] += v.w; }
         *reinterpret_cast<float4*>(&la[a_r[i] * S::LDA + a_c[i] * 4]) = v;
         __builtin_amdgcn_sched_barrier(0);
@@ -316,13 +305,7 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
 #pragma unroll
       for (int i = 0; i < NCB; ++i) {
         float4 v = rb[SET][i];
-        if (p.b_act != EAMD_ACT_NONE) v = act4(v, p.b_act);
-        if (p.b_drop_p > 0.f) {
-          bool kp[4];
-          eamd_drop_keep4(b_dseed, (unsigned long long)((unsigned)b_off[i] + b_k), b_thr, kp);
-          v = make_float4(kp[0] ? v.x * b_inv : 0.f, kp[1] ? v.y * b_inv : 0.f, kp[2] ? v.z * b_inv : 0.f,
-                          kp[3] ? v.w * b_inv : 0.f);
-        }
+        if (p.b_act != EAMD_ACT_NONE) v = act4<ACT>(v, p.b_act);
         *reinterpret_cast<float4*>(&lb[b_r[i] * S::LDB + b_c[i] * 4]) = v;
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -554,7 +537,7 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
   store_c_tile<BM, BN, true, ROWEPI>(p, acc, sm.ab, m0, n0, coff);      // operand buffers are free now (last phase ended in a barrier)
 }
 
-template <int BM, int BN, bool TA, bool TB, bool GAT, bool ACT, bool ROWEPI = false, bool NOPAD = false>
+template <int BM, int BN, bool TA, bool TB, bool GAT, int ACT, bool ROWEPI = false, bool NOPAD = false>
 __global__ __launch_bounds__(NT_, 2) void gemm_f32_kernel(const eamd_gemm_t p) {
   gemm_f32_body<BM, BN, TA, TB, GAT, ACT, ROWEPI, NOPAD>(p, blockIdx.x, gridDim.x, blockIdx.z);
 }
@@ -597,7 +580,7 @@ __global__ __launch_bounds__(NT_, 2) void gemm_f32_multi_kernel(const MultiF m) 
   gemm_f32_body<BM, BN, TA, TB, GAT, false, false, NOPAD>(p, bid, m.nt[cls], 0);
 }
 
-template <int BM, int BN, bool TA, bool TB, bool GAT, bool ACT, bool NOPAD = false>
+template <int BM, int BN, bool TA, bool TB, bool GAT, int ACT, bool NOPAD = false>
 int launch_f2(const eamd_gemm_t& p, hipStream_t stream) {
   dim3 grid(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.splitk, 1, p.batch1 * p.batch2);
   constexpr size_t smem = sizeof(SmemF<BM, BN, TA, TB>);
@@ -644,12 +627,12 @@ inline bool gather_taps_small(const eamd_gather_t& g) {
 template <int BM, int BN, bool TA, bool TB, bool GAT>
 int launch_f(const eamd_gemm_t& p, hipStream_t stream) {
   if constexpr (GAT && !TA) {
-    if (gather_nopad(p.gather) && p.epilogue < 7) return launch_f2<BM, BN, TA, TB, GAT, false, true>(p, stream);
+    if (gather_nopad(p.gather) && p.epilogue < 7) return launch_f2<BM, BN, TA, TB, GAT, 0, true>(p, stream);
   }
-  if constexpr (GAT) return launch_f2<BM, BN, TA, TB, GAT, false>(p, stream);
-  else if (p.a_act != EAMD_ACT_NONE || p.b_act != EAMD_ACT_NONE || p.a_drop_p > 0.f || p.b_drop_p > 0.f)
-    return launch_f2<BM, BN, TA, TB, GAT, true>(p, stream);
-  return launch_f2<BM, BN, TA, TB, GAT, false>(p, stream);
+  if constexpr (GAT) return launch_f2<BM, BN, TA, TB, GAT, 0>(p, stream);
+  else if (p.a_act > EAMD_ACT_SWISH || p.b_act > EAMD_ACT_SWISH) return launch_f2<BM, BN, TA, TB, GAT, 2>(p, stream);
+  else if (p.a_act != EAMD_ACT_NONE || p.b_act != EAMD_ACT_NONE) return launch_f2<BM, BN, TA, TB, GAT, 1>(p, stream);
+  return launch_f2<BM, BN, TA, TB, GAT, 0>(p, stream);
 }
 
 template <int T>
@@ -669,10 +652,6 @@ int eamd_gemm_f32_dispatch(const eamd_gemm_t& p, int tile, hipStream_t stream) {
   if (p.Cb || (p.Hb && !p.h_dtype) || p.aux_dtype || (!p.C && p.epilogue != 7)) return EAMD_EUNSUPPORTED;
   if (p.Hb && p.drop_p <= 0.f) return EAMD_EINVAL;
   if (p.drop_p < 0.f || p.drop_p >= 1.f) return EAMD_EINVAL;
-  if (p.a_drop_p < 0.f || p.a_drop_p >= 1.f || p.b_drop_p < 0.f || p.b_drop_p >= 1.f) return EAMD_EINVAL;
-  if ((p.a_drop_p > 0.f || p.b_drop_p > 0.f) && (p.gather.enabled || p.batch1 * p.batch2 != 1 || !p.drop_step)) return EAMD_EINVAL;
-  if (p.a_drop_p > 0.f && (int64_t)(p.transA ? p.K : p.M) * p.lda >= (1LL << 32)) return EAMD_EUNSUPPORTED;   // 32-bit mask index
-  if (p.b_drop_p > 0.f && (int64_t)(p.transB ? p.K : p.N) * p.ldb >= (1LL << 32)) return EAMD_EUNSUPPORTED;
   // fused result dropout: mask index = row * N + col of a contiguous [M, N] result, as eamd_dropout draws it
   if (p.drop_p > 0.f && (p.cmap.enabled || p.batch1 * p.batch2 != 1 || p.ldc != p.N || p.splitk > 1)) return EAMD_EINVAL;
   const bool a_ok = aligned16f(p.A) && p.lda % 4 == 0 && p.sA1 % 4 == 0 && p.sA2 % 4 == 0 &&
@@ -718,8 +697,7 @@ int eamd_gemm_f32_multi(const eamd_gemm_t* ps, const int* tiles, int n, hipStrea
     if (tiles[i] != 128 || p.in_dtype != 0 || p.precision != 0) return EAMD_EUNSUPPORTED;
     if (!p.gather.enabled || p.transA || !p.transB || p.splitk != 1 || p.batch1 * p.batch2 != 1) return EAMD_EUNSUPPORTED;
     if (!p.C || p.Cb || p.Hb || p.aux_dtype || p.epilogue > 5 || p.colsum) return EAMD_EUNSUPPORTED;
-    if (p.a_act != EAMD_ACT_NONE || p.b_act != EAMD_ACT_NONE || p.drop_p != 0.f || p.a_drop_p != 0.f || p.b_drop_p != 0.f)
-      return EAMD_EUNSUPPORTED;
+    if (p.a_act != EAMD_ACT_NONE || p.b_act != EAMD_ACT_NONE || p.drop_p != 0.f) return EAMD_EUNSUPPORTED;
     const bool b_ok = aligned16f(p.B) && p.ldb % 4 == 0 && p.ldb >= (p.N + 3) / 4 * 4;
     if (p.gather.C % FBK != 0 || !aligned16f(p.A) || !b_ok || !gather_taps_small(p.gather)) return EAMD_EUNSUPPORTED;
     const long nt = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
@@ -742,8 +720,8 @@ int eamd_gemm_f32_multi(const eamd_gemm_t* ps, const int* tiles, int n, hipStrea
 int eamd_gemm_f32_group_count(const eamd_gemm_t& p) {
   if (p.in_dtype != 0 || p.precision != 0 || !p.transA || !p.transB || !p.C || p.Cb || p.Hb || p.aux || p.R || p.bias)
     return EAMD_EUNSUPPORTED;
-  if (p.gather.enabled || p.cmap.enabled || p.epilogue || p.a_act || p.b_act || p.drop_p > 0.f || p.a_drop_p > 0.f ||
-      p.b_drop_p > 0.f || p.batch1 * p.batch2 != 1 || p.splitk < 1)
+  if (p.gather.enabled || p.cmap.enabled || p.epilogue || p.a_act || p.b_act || p.drop_p > 0.f ||
+      p.batch1 * p.batch2 != 1 || p.splitk < 1)
     return EAMD_EUNSUPPORTED;
   if (p.splitk == 1 && p.beta != 1.f) return EAMD_EUNSUPPORTED;          // accumulate into the gradient buffer
   const bool a_ok = aligned16f(p.A) && p.lda % 4 == 0 && p.lda >= (p.M + 3) / 4 * 4;

@@ -77,14 +77,6 @@ def _grad_in(dout, do, p_out, s_out):
     return ops.dropout(do, p_out, s_out, out_dtype=ops.act_dtype()) if p_out > 0.0 else ops.to_act(do)
 
 
-def _grad_operand(dout, do, p_out, s_out):
-    """-> (operand, a_drop) for the GEMMs that consume a block's incoming gradient: in fp32 mode the block-output dropout
-    of the gradient is applied while those GEMMs stage the operand (no dropped copy is written)"""
-    if p_out > 0.0 and ops.f32_operand_drop():
-        return do, (float(p_out), int(s_out))
-    return _grad_in(dout, do, p_out, s_out), None
-
-
 def _ln_fwd_in(x2, ln_w, ln_b, eps, adt):
     """pre-norm of a block; eps None = bare module (the reference's standalone MultiHeadedAttention /
     PositionwiseFeedForward / ConvolutionModule forward: no LayerNorm in front, no residual behind)"""
@@ -255,7 +247,7 @@ class FFNBlockFn(torch.autograd.Function):
         assert eps is not None or p_out <= 0.0
         fused = ops.fast()      # bf16-operand GEMMs carry the dropout masks in their epilogues
         h, zf = None, False
-        one = eps is not None and (ops.fast() or (ops.f32_epilogue_drop() and not ops.f32_operand_drop()))
+        one = eps is not None and (ops.fast() or ops.f32_epilogue_drop())
         ln_in = None
         if one and ops.FFN_LN_FUSED and x2.dtype == torch.float32 and D == 256:
             # the one-launch kernel below normalises its rows itself (eamd_ffn_t.ln_x): no LayerNorm launch, and the
@@ -278,13 +270,13 @@ class FFNBlockFn(torch.autograd.Function):
             ctx.save_for_backward(x2, mean, rstd, xn, z, h)
             ctx.pr = GradSink.use((ln_w, ln_b, w1, b1, w2, b2))
             ctx.cfg = (scale, act, shp, drop)
-            ctx.in_opd, ctx.zf, ctx.one_launch = False, True, True
+            ctx.zf, ctx.one_launch = True, True
             ctx.prev = _prev_drop(x)
             return _tag_out(out.view(shp), p_out, s_out)
         ctx.one_launch = False
         if act not in (ACT_RELU, ACT_SWISH):
             # hardtanh / tanh / selu (nets_utils.py:485-498): with inner dropout the dual-output epilogue below is generic
-            # over eamd_act ids; without it the activation is its own pass (eamd_act_fwd / _bwd) - no staging-side variant
+            # over eamd_act ids; without it the activation is its own pass (eamd_act_fwd / _bwd) - only the pipelined fp32 kernel stages them
             if not (p_in > 0.0 and (fused or ops.f32_epilogue_drop())):
                 z = ops.linear_fwd(xn, ops.wshadow(w1), b1)
                 h = ops.act_fwd_any(z, act)
@@ -300,11 +292,11 @@ class FFNBlockFn(torch.autograd.Function):
                 ctx.save_for_backward(x2, mean, rstd, xn, z, hop)
                 ctx.pr = GradSink.use((ln_w, ln_b, w1, b1, w2, b2))
                 ctx.cfg = (scale, act, shp, drop)
-                ctx.in_opd, ctx.zf, ctx.generic_act = False, False, True
+                ctx.zf, ctx.generic_act = False, True
                 ctx.prev = _prev_drop(x)
                 return _tag_out(out.view(shp), p_out, s_out)
         ctx.generic_act = False
-        if p_in > 0.0 and (fused or (ops.f32_epilogue_drop() and not ops.f32_operand_drop())):
+        if p_in > 0.0 and (fused or ops.f32_epilogue_drop()):
             # z and h = dropout(act(z)) from one launch (second output of the epilogue), in the operand dtype
             # ... and what is kept for backward is not z but the ready factor f = mask / (1 - p) * act'(z): the input-gradient
             # GEMM multiplies by it (EPI_MUL_AUX) instead of re-deriving the mask and the activation derivative per element
@@ -314,23 +306,20 @@ class FFNBlockFn(torch.autograd.Function):
             zf = FFN_FACTOR
         else:
             z = ops.linear_fwd(xn, ops.wshadow(w1), b1, out_dtype=adt)          # [M, F] pre-activation
-            if p_in > 0.0 and not ops.f32_operand_drop():
+            if p_in > 0.0:
                 h = ops.dropout(z, p_in, s_in, act=act)                         # drop(act(z)), materialised
+        # without inner dropout h = act(z) is never written: the W2 product applies the activation while staging z
         src, a_act = (h, ACT_NONE) if h is not None else (z, act)
-        # fp32 mode: h = drop(act(z)) is never written - the W2 product applies activation + mask while staging z
-        a_drop = (p_in, s_in) if (h is None and p_in > 0.0) else None
         if p_out > 0.0 and (fused or ops.f32_epilogue_drop()):
-            out = ops.linear_fwd(src, ops.wshadow(w2), b2, R=x2, alpha=scale, a_act=a_act, drop=(p_out, s_out), a_drop=a_drop)
+            out = ops.linear_fwd(src, ops.wshadow(w2), b2, R=x2, alpha=scale, a_act=a_act, drop=(p_out, s_out))
         elif p_out > 0.0:
-            br = ops.linear_fwd(src, ops.wshadow(w2), b2, a_act=a_act, a_drop=a_drop)
+            br = ops.linear_fwd(src, ops.wshadow(w2), b2, a_act=a_act)
             out = ops.axpby(x2, ops.dropout(br, p_out, s_out), 1.0, scale)
         else:
-            out = ops.linear_fwd(src, ops.wshadow(w2), b2, R=x2 if eps is not None else None, alpha=scale, a_act=a_act,
-                                 a_drop=a_drop)
+            out = ops.linear_fwd(src, ops.wshadow(w2), b2, R=x2 if eps is not None else None, alpha=scale, a_act=a_act)
         ctx.save_for_backward(x2, mean, rstd, xn, z, h)
         ctx.pr = GradSink.use((ln_w, ln_b, w1, b1, w2, b2))
         ctx.cfg = (scale, act, shp, drop)
-        ctx.in_opd = a_drop is not None
         ctx.zf = zf
         ctx.prev = _prev_drop(x)
         return _tag_out(out.view(shp), p_out, s_out)
@@ -343,16 +332,15 @@ class FFNBlockFn(torch.autograd.Function):
         adt = ops.act_dtype()
         sink = GradSink(ctx.pr)
         do = dout.reshape(x2.shape).contiguous()
-        # gradient of the branch output (dropout mask re-derived: as a bf16 copy, or - fp32 mode - inside the consuming GEMMs)
-        dob, g_drop = _grad_operand(dout, do, p_out, s_out)
-        inner = h is not None or ctx.in_opd          # the forward applied the inner dropout
+        # gradient of the branch output (dropout mask re-derived, as a copy in the operand dtype)
+        dob = _grad_in(dout, do, p_out, s_out)
+        inner = h is not None                         # the forward applied the inner dropout
         if h is not None:
-            ops.linear_bwd_w(dob, h, sink.buf(4), alpha=scale, db=sink.buf(5), a_drop=g_drop)
-        else:                                         # dW2 += s * drop(do)^T drop(act(z))
-            ops.linear_bwd_w(dob, z, sink.buf(4), alpha=scale, b_act=act, db=sink.buf(5), a_drop=g_drop,
-                             b_drop=(p_in, s_in) if ctx.in_opd else None)
+            ops.linear_bwd_w(dob, h, sink.buf(4), alpha=scale, db=sink.buf(5))
+        else:                                         # dW2 += s * drop(do)^T act(z)
+            ops.linear_bwd_w(dob, z, sink.buf(4), alpha=scale, b_act=act, db=sink.buf(5))
         if getattr(ctx, "generic_act", False):
-            dh = ops.linear_bwd_x(dob, ops.wshadow(w2), alpha=scale, a_drop=g_drop)
+            dh = ops.linear_bwd_x(dob, ops.wshadow(w2), alpha=scale)
             if p_in > 0.0:
                 dh = ops.dropout(dh, p_in, s_in)
             dz = ops.to_act(ops.act_bwd_any(dh, z, act))
@@ -360,7 +348,7 @@ class FFNBlockFn(torch.autograd.Function):
             dxn = ops.linear_bwd_x(dz, ops.wshadow(w1))
             dx = _ln_bwd_out(dxn, x2, ln_w, mean, rstd, do, sink.buf(0), sink.buf(1), ctx.prev, shp)
             return (dx,) + sink.results() + (None, None, None, None)
-        if ctx.one_launch and g_drop is None and dob.dtype == z.dtype:
+        if ctx.one_launch and dob.dtype == z.dtype:
             # dz = s (dob W2) (.) f and dxn = dz W1: one launch (bf16 operands: on the transposed weight copies)
             M, D = x2.shape
             if mean is not None and D == 256 and ops.ROWPROJ and ops.ffn_bwd_lnb_ok(M, w1.shape[0], dob.dtype):
@@ -381,12 +369,12 @@ class FFNBlockFn(torch.autograd.Function):
             dx = _ln_bwd_out(dxn, x2, ln_w, mean, rstd, do, sink.buf(0), sink.buf(1), ctx.prev, shp)
             return (dx,) + sink.results() + (None, None, None, None)
         if ctx.zf:       # z holds mask / (1 - p) * act'(z) already
-            dz = ops.linear_bwd_x(dob, ops.wshadow(w2), epilogue=EPI_MUL_AUX, aux=z, alpha=scale, out_dtype=adt, a_drop=g_drop)
+            dz = ops.linear_bwd_x(dob, ops.wshadow(w2), epilogue=EPI_MUL_AUX, aux=z, alpha=scale, out_dtype=adt)
         elif inner and (ops.fast() or ops.f32_epilogue_drop()):
             dz = ops.linear_bwd_x(dob, ops.wshadow(w2), epilogue=_act_epi(act), aux=z, alpha=scale, out_dtype=adt,
-                                  drop=(p_in, s_in), a_drop=g_drop)
+                                  drop=(p_in, s_in))
         else:
-            dz = ops.linear_bwd_x(dob, ops.wshadow(w2), epilogue=_act_epi(act), aux=z, alpha=scale, out_dtype=adt, a_drop=g_drop)
+            dz = ops.linear_bwd_x(dob, ops.wshadow(w2), epilogue=_act_epi(act), aux=z, alpha=scale, out_dtype=adt)
             if inner:
                 dz = ops.dropout(dz, p_in, s_in)
         ops.linear_bwd_w(dz, xn, sink.buf(2), db=sink.buf(3))
@@ -922,13 +910,13 @@ class MHABlockFn(torch.autograd.Function):
         if pre is not None and pre[0] == "pos":
             p, dp_out = pre[1].block(pre[2]), pre[1].grad_block(pre[2])
         do = dout.reshape(-1, D).contiguous()
-        dob, g_drop = _grad_operand(dout, do, p_out, s_out)
-        rp = ctx.rp if g_drop is None else None
-        ops.linear_bwd_w(dob, cx, sink.buf(8), db=sink.buf(9), a_drop=g_drop)
+        dob = _grad_in(dout, do, p_out, s_out)
+        rp = ctx.rp
+        ops.linear_bwd_w(dob, cx, sink.buf(8), db=sink.buf(9))
         if rp is not None:
             dctx = ops.rowproj(dob, rp[3], D)
         else:
-            dctx = ops.linear_bwd_x(dob, ops.wshadow(wo), out_dtype=adt, a_drop=g_drop)
+            dctx = ops.linear_bwd_x(dob, ops.wshadow(wo), out_dtype=adt)
         def again(qu_, qv_, k_, v_):
             """the probabilities this block did not keep: the fused forward once more (MHABlockFn.forward, ATTN_RECOMPUTE_MB)"""
             f = attn_fwd_fused(qu_, qv_, k_, v_, p, ctx.recompute, B, T1, T2, H, dk, drop=(p_att, s_att) if p_att > 0.0 else None,
@@ -1085,13 +1073,13 @@ class ConvModuleBlockFn(torch.autograd.Function):
         adt = ops.act_dtype()
         sink = GradSink(ctx.pr)
         do = dout.reshape(M, D).contiguous()
-        dob, g_drop = _grad_operand(dout, do, p_out, s_out)
-        rp = ctx.rp if g_drop is None else None
-        ops.linear_bwd_w(dob, e, sink.buf(8).view(Cc, Cc), db=sink.buf(9), a_drop=g_drop)
+        dob = _grad_in(dout, do, p_out, s_out)
+        rp = ctx.rp
+        ops.linear_bwd_w(dob, e, sink.buf(8).view(Cc, Cc), db=sink.buf(9))
         if rp is not None:
             de = ops.rowproj(dob, rp[3], Cc)
         else:
-            de = ops.linear_bwd_x(dob, ops.wshadow(w2).view(Cc, Cc), a_drop=g_drop)
+            de = ops.linear_bwd_x(dob, ops.wshadow(w2).view(Cc, Cc))
         # (time bound: the bounded BatchNorm backward takes dy = 0 and writes dx = 0 from the bound on)
         dd = ops.bn_bwd(de, d, bmean, brstd, g, be, sink.buf(6), sink.buf(7), M, Cc, act, training, bound=ctx.bound)
         if gl is None:       # GLU fused into the depthwise kernels: its derivative in the input-gradient store, GLU(a) on load

@@ -45,18 +45,6 @@ def f32_epilogue_drop():
 F32_EPILOGUE_DROP = True     # tests flip this to compare against the stand-alone dropout kernel
 
 
-# Off by default: measured on configs[1] the staging-side hash + activation pushes the 128x128 instantiations over the
-# 256-VGPR budget (scratch) and the 64x64 ones from 3 to 2 waves per SIMD - the GEMMs lose 2.3 ms per step where the
-# stand-alone dropout passes they replace cost 1.1 ms.  Kept (and tested) as an operator feature.
-F32_OPERAND_DROP = False
-
-
-def f32_operand_drop():
-    """fp32 mode: dropout of a GEMM operand (FFN inner dropout, every block's incoming-gradient dropout) applied while
-    the operand is staged, instead of a pass that materialises the dropped tensor"""
-    return _state["precision"] == 0 and F32_OPERAND_DROP
-
-
 def act_dtype():
     return torch.bfloat16 if fast() else torch.float32
 
@@ -145,7 +133,7 @@ _gemm_record = None
 def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, *, transA=0, transB=0, bias=None, aux=None, ldaux=0, R=None,
          ldr=0, batch=(1, 1), sA=(0, 0), sB=(0, 0), sC=(0, 0), alpha=1.0, beta=0.0, a_act=0, b_act=0,
          epilogue=0, splitk=1, tile=0, gather=None, cmap=None, a_off=0, b_off=0, c_off=0, precision=None,
-         colsum=None, Cb=None, drop=None, Hb=None, h_act=0, a_drop=None, b_drop=None, group=False, stats=None, defer=None):
+         colsum=None, Cb=None, drop=None, Hb=None, h_act=0, group=False, stats=None, defer=None):
     """A, B: both float32 or both bfloat16 (bf16 operands select the fast MFMA kernel).
     Cm: float32 result, or bfloat16 result (then no fp32 copy is written); Cb: extra bf16 copy.
     defer=list: the checked descriptor is appended to the list instead of being launched; gemm_multi(list) then issues
@@ -234,13 +222,6 @@ def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, *, transA=0, transB=0, bias=None, aux
             if Hb.dtype != (torch.bfloat16 if bf else torch.float32) or Hb.numel() < M * N:
                 raise _lib.EamdError("gemm: Hb must be an [M, N] buffer of the operand dtype")
             p.Hb, p.h_act, p.h_dtype = ptr(Hb), h_act, 0 if bf else 1
-    for which, d, ld_, off_, cols in (("a", a_drop, lda, a_off, (M if transA else K)), ("b", b_drop, ldb, b_off, (N if transB else K))):
-        if d is not None and d[0] > 0.0:    # operand-side dropout: the operand must BE the contiguous tensor the mask was drawn for
-            if bf or p.precision != 0 or ld_ != cols or off_ != 0 or b1 * b2 != 1 or gather is not None:
-                raise _lib.EamdError("gemm: operand dropout needs an fp32-MFMA launch on a dense, unbatched operand")
-            setattr(p, which + "_drop_p", float(d[0]))
-            setattr(p, which + "_drop_salt", int(d[1]))
-            p.drop_step = ptr(rng_state(A.device))
     if group and _wgroup["on"] and _in_grad_arena(Cm) and _wgroup_accepts(p):
         # Two queued problems that accumulate into the same dW may share one launch only if BOTH add with atomics:
         # splitk == 1 with beta == 1 is a plain read-modify-write of the tile, and workgroups of one launch are not
@@ -484,7 +465,7 @@ LINEAR_ROWS_KSPLIT = True
 
 
 def linear_fwd(x, W, b, out=None, *, act=EPI_NONE, R=None, alpha=1.0, a_act=ACT_NONE, out_dtype=torch.float32,
-               drop=None, Hb=None, h_act=ACT_NONE, a_drop=None):
+               drop=None, Hb=None, h_act=ACT_NONE):
     """out[M,N] = alpha * drop(act(a_act(x)[M,K] @ W[N,K]^T + b)) + R      (x, W: both fp32 or both bf16)
     drop = (p, salt): dropout fused in the epilogue (bf16 operands); with Hb the value itself is left
     alone and Hb <- dropout(h_act(value)) is written as a second bf16 output."""
@@ -494,7 +475,7 @@ def linear_fwd(x, W, b, out=None, *, act=EPI_NONE, R=None, alpha=1.0, a_act=ACT_
     if (LINEAR_ROWS and (M <= LINEAR_ROWS_MAX or (M <= LINEAR_ROWS_BLOCK_MAX and (K <= 512 or (K >= 1024 and LINEAR_ROWS_KSPLIT)) and N <= 1024
                                                   and K % 16 == 0)) and out is None and out_dtype == torch.float32 and x.dtype == torch.float32 and W.dtype == torch.float32
             and act in (EPI_NONE, EPI_RELU, EPI_SWISH) and a_act in (ACT_NONE, ACT_RELU, ACT_SWISH) and drop is None and Hb is None
-            and a_drop is None and K % 4 == 0 and _state["precision"] == 0 and _infer > 0 and not torch.is_grad_enabled()
+            and K % 4 == 0 and _state["precision"] == 0 and _infer > 0 and not torch.is_grad_enabled()
             and (R is None or (tuple(R.shape) == (M, N) and (M == 1 or R.stride(0) >= N))) and (M == 1 or x.stride(0) >= K)):
         # (an expanded, stride-0 operand with M > 1 would read as `dense` on the C side: those go to the GEMM below via .contiguous())
         # inference on a handful of rows (one utterance's hypotheses in a beam step): one wave per output column; x and R may be
@@ -509,7 +490,7 @@ def linear_fwd(x, W, b, out=None, *, act=EPI_NONE, R=None, alpha=1.0, a_act=ACT_
     x = x.contiguous()
     R = R.contiguous() if R is not None else None
     sk = 1
-    if (out_dtype if out is None else out.dtype) == torch.float32 and act == EPI_NONE and drop is None and Hb is None and a_drop is None:
+    if (out_dtype if out is None else out.dtype) == torch.float32 and act == EPI_NONE and drop is None and Hb is None:
         if R is None and alpha == 1.0:
             sk = _skinny_splitk(M, N, K)
         elif K >= 1024 and M <= 512 and x.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -522,7 +503,7 @@ def linear_fwd(x, W, b, out=None, *, act=EPI_NONE, R=None, alpha=1.0, a_act=ACT_
     elif sk > 1:
         out.zero_()
     gemm(x, W, out, M, N, K, K, K, N, bias=b, epilogue=act, R=R, ldr=N, alpha=alpha, a_act=a_act, drop=drop, Hb=Hb,
-         h_act=h_act, a_drop=a_drop, splitk=sk)
+         h_act=h_act, splitk=sk)
     return out
 
 
@@ -613,21 +594,20 @@ def _skinny_splitk(M, N, K, max_rows=64):
 
 
 def linear_bwd_x(dy, W, out=None, *, beta=0.0, epilogue=EPI_NONE, aux=None, alpha=1.0, out_dtype=torch.float32,
-                 drop=None, a_drop=None):
+                 drop=None):
     """out[M,K] = alpha * drop(epi(dy[M,N] @ W[N,K])) + beta*out"""
     M, N = dy.shape
     K = W.shape[1]
     assert W.shape[0] == N and dy.is_contiguous()
     fresh = out is None
     sk = 1
-    if fresh and out_dtype == torch.float32 and epilogue == EPI_NONE and aux is None and drop is None and a_drop is None \
-            and alpha == 1.0:
+    if fresh and out_dtype == torch.float32 and epilogue == EPI_NONE and aux is None and drop is None and alpha == 1.0:
         sk = _skinny_splitk(M, K, N)
     if out is None:
         assert beta == 0.0
         out = zeros(M, K, device=dy.device) if sk > 1 else torch.empty(M, K, device=dy.device, dtype=out_dtype)
     gemm(dy, W, out, M, K, N, N, K, K, transB=1, beta=beta, epilogue=epilogue, aux=aux, ldaux=K, alpha=alpha,
-         drop=drop, a_drop=a_drop, splitk=sk)
+         drop=drop, splitk=sk)
     return out
 
 
@@ -929,31 +909,30 @@ def wgrad_join():
         _wgrad["used"] = False
 
 
-def linear_bwd_w(dy, x, dW, *, alpha=1.0, b_act=ACT_NONE, db=None, a_drop=None, b_drop=None, group=True):
+def linear_bwd_w(dy, x, dW, *, alpha=1.0, b_act=ACT_NONE, db=None, group=True):
     """group=False: never queued for the grouped launch (per-chunk gradients of a streamed loss: queueing would keep
     every chunk's operands alive until the flush)"""
     st = _wgrad["stream"]
     if st is None:
-        return _linear_bwd_w(dy, x, dW, alpha=alpha, b_act=b_act, db=db, a_drop=a_drop, b_drop=b_drop, group=group)
+        return _linear_bwd_w(dy, x, dW, alpha=alpha, b_act=b_act, db=db, group=group)
     cur = torch.cuda.current_stream()
     st.wait_stream(cur)                 # operands were produced on the main stream
     with torch.cuda.stream(st):
-        _linear_bwd_w(dy, x, dW, alpha=alpha, b_act=b_act, db=db, a_drop=a_drop, b_drop=b_drop)
+        _linear_bwd_w(dy, x, dW, alpha=alpha, b_act=b_act, db=db)
     dy.record_stream(st)                # keep the caching allocator from recycling them early
     x.record_stream(st)
     _wgrad["used"] = True
 
 
-def _linear_bwd_w(dy, x, dW, *, alpha=1.0, b_act=ACT_NONE, db=None, a_drop=None, b_drop=None, group=True):
-    """dW[N,K] += alpha * drop_a(dy)[M,N]^T @ drop_b(b_act(x))[M,K]   (split-K, f32 atomics)
-    db[N] += alpha * column sums of drop_a(dy) (bias gradient, fused into the same launch);
-    a_drop / b_drop = (p, salt): fp32 mode only, the operand is dropped while it is staged (eamd_gemm_t.a_drop_p)"""
+def _linear_bwd_w(dy, x, dW, *, alpha=1.0, b_act=ACT_NONE, db=None, group=True):
+    """dW[N,K] += alpha * dy[M,N]^T @ b_act(x)[M,K]   (split-K, f32 atomics)
+    db[N] += alpha * column sums of dy (bias gradient, fused into the same launch)"""
     M, N = dy.shape
     K = x.shape[1]
     assert x.shape[0] == M and dW.numel() == N * K and dW.dtype == torch.float32
     grouping = group and _wgroup["on"] and _wgrad["stream"] is None
     if (grouping and M <= STACK_WGRAD_MAX_ROWS and alpha == 1.0 and b_act == ACT_NONE
-            and a_drop is None and b_drop is None and dy.is_contiguous() and x.is_contiguous() and _in_grad_arena(dW)):
+            and dy.is_contiguous() and x.is_contiguous() and _in_grad_arena(dW)):
         # one decoder step's weight gradient (M = batch rows) reads and writes the whole dW for a reduction of M: the
         # steps of a backward pass are stacked along the reduction instead and leave as ONE product at the flush
         # (config 4: 101 x (22 + 12 us) of 32 MB / 16 MB read-modify-writes -> two GEMMs with K = 3232)
@@ -975,7 +954,7 @@ def _linear_bwd_w(dy, x, dW, *, alpha=1.0, b_act=ACT_NONE, db=None, a_drop=None,
             tile = 64
             sk = max(1, sk // GROUP_WGRAD_SK_DIV)
     gemm(dy, x, dW, N, K, M, N, K, K, transA=1, transB=1, alpha=alpha, b_act=b_act, splitk=sk, tile=tile,
-         beta=1.0 if sk == 1 else 0.0, colsum=db, a_drop=a_drop, b_drop=b_drop, group=grouping)
+         beta=1.0 if sk == 1 else 0.0, colsum=db, group=grouping)
 
 
 def colsum(x, out, scale=1.0, rows=None, D=None, ld=None):

@@ -34,7 +34,8 @@ int eamd_abi_version(void);
  *
  * transA=0: A is [M,K] row-major (lda); transA=1: A is stored [K,M] (lda = stride of k).
  * transB=0: B is stored [N,K] (nn.Linear weight, ldb = stride of n); transB=1: B is [K,N].
- * a_act/b_act apply an activation to the operand while it is staged (EAMD_ACT_*).
+ * a_act/b_act apply an activation to the operand while it is staged (EAMD_ACT_*; other than relu / swish only where the
+ *   pipelined fp32 kernel takes the call: precision 0, operands meeting its 16-byte staging conditions).
  * epilogue: 0 none, 1 relu, 2 swish, 3 multiply by (aux>0), 4 multiply by dswish(aux), 5 multiply by aux,
  *   6 (only with Hb + dropout, below): C receives the factor d Hb / d v = mask / (1 - p) * h_act'(v) instead of v - the
  *   FFN forward then hands its backward a ready factor (epilogue 5 there) instead of the pre-activation.
@@ -97,13 +98,6 @@ typedef struct {
   const uint64_t* drop_step;
   void* Hb;
   int32_t h_act;
-  /* operand-side dropout (fp32-MFMA kernel, in_dtype 0 / precision 0): while an operand is staged, element i of its
-   * contiguous [rows, ld] matrix becomes keep(i) ? a_act(x) / (1 - p) : 0 with the mask eamd_dropout draws for
-   * (drop_step, salt, i) - a consumer reads dropout(act(z)) or dropout(dY) without that tensor ever being written:
-   *   W2 (drop(act(z))) in the FFN forward, dW2 += dY^T drop(act(z)), every block's incoming-gradient dropout in
-   *   backward (positionwise_feed_forward.py:27, encoder_layer.py:101-144).  Needs an unbatched, un-gathered operand. */
-  float a_drop_p, b_drop_p;
-  uint64_t a_drop_salt, b_drop_salt;
   int32_t h_dtype;     /* dtype of the second output Hb: 0 bf16, 1 fp32 (fp32-MFMA kernel: z and h = dropout(act(z)) in fp32) */
   /* epilogue 7 (row statistics; splitk 1, tile given as 64 or 128, no batch / row map): the result v = A B + bias is NOT
    * stored (C, Cb may be NULL); every workgroup leaves, for each row m of its tile and its column tile j,

@@ -735,33 +735,43 @@ def test_gemm_f32_fused_dropout_matches_dropout_kernel(ops, shape):
     report("fp32 gemm dual output h %s" % (shape,), h, ops.dropout(plain, p, salt, act=ACT_SWISH), 1e-6)
 
 
-@pytest.mark.parametrize("shape", [(300, 192, 128), (7968, 256, 2048), (1000, 2048, 256)])
-def test_gemm_f32_operand_dropout_matches_dropout_kernel(ops, shape):
-    """fp32 mode: dropout applied to a GEMM operand while it is staged (eamd_gemm_t.a_drop_p / b_drop_p) gives what
-    the product of the materialised eamd_dropout result gives - forward (A = drop(act(z))), input gradient
-    (A = drop(dy)) and weight gradient (A = drop(dy), B = drop(act(z)), bias gradient = column sums of drop(dy))"""
-    from espnet_amd.ops import ACT_SWISH, ACT_NONE
-    M, N, K = shape
-    g = torch.Generator().manual_seed(M + 3 * K)
-    z, W = torch.randn(M, K, generator=g).to(DEV), (torch.randn(N, K, generator=g) / K ** 0.5).to(DEV)
-    b, dy = torch.randn(N, generator=g).to(DEV), torch.randn(M, N, generator=g).to(DEV)
-    p_in, s_in, p_out, s_out = 0.1, 777, 0.2, 991
-    h = ops.dropout(z, p_in, s_in, act=ACT_SWISH)
-    report("operand drop fwd %s" % (shape,), ops.linear_fwd(z, W, b, a_act=ACT_SWISH, a_drop=(p_in, s_in)),
-           ops.linear_fwd(h, W, b), 2e-6)
-    dyd = ops.dropout(dy, p_out, s_out)
-    report("operand drop bwd_x %s" % (shape,), ops.linear_bwd_x(dy, W, a_drop=(p_out, s_out)), ops.linear_bwd_x(dyd, W), 2e-6)
-    # with the epilogue dropout behind it (the FFN's dz)
-    report("operand drop bwd_x + epilogue drop %s" % (shape,),
-           ops.linear_bwd_x(dy, W, a_drop=(p_out, s_out), drop=(p_in, s_in)),
-           ops.dropout(ops.linear_bwd_x(dyd, W), p_in, s_in), 2e-6)
-    dW1, db1 = torch.zeros(N, K, device=DEV), torch.zeros(N, device=DEV)
-    dW2, db2 = torch.zeros(N, K, device=DEV), torch.zeros(N, device=DEV)
-    ops.linear_bwd_w(dy, z, dW1, alpha=0.5, b_act=ACT_SWISH, db=db1, a_drop=(p_out, s_out), b_drop=(p_in, s_in))
-    ops.linear_bwd_w(dyd, h, dW2, alpha=0.5, b_act=ACT_NONE, db=db2)
-    torch.cuda.synchronize()
-    report("operand drop bwd_w %s" % (shape,), dW1, dW2, 2e-5)
-    report("operand drop bias grad %s" % (shape,), db1, db2, 2e-5)
+def _act_f64(x, act):
+    from espnet_amd.ops import ACT_NONE, ACT_RELU, ACT_SWISH, ACT_TANH
+    return {ACT_NONE: lambda v: v, ACT_RELU: torch.relu, ACT_SWISH: lambda v: v * torch.sigmoid(v), ACT_TANH: torch.tanh}[act](x)
+
+
+@pytest.mark.parametrize("transA,transB", [(0, 0), (0, 1), (1, 0), (1, 1)])
+@pytest.mark.parametrize("tile", [64, 128])
+def test_gemm_f32_staged_activation_vs_float64(ops, tile, transA, transB):
+    """fp32 mode: a_act / b_act applied while the pipelined fp32 GEMM stages an operand (the ACT instantiations of
+    gemm_f32_kernel, every layout, both tiles) against float64: each operand alone, both, two other activations, and
+    - transA - the bias-gradient column sums, which are those of the RAW A operand times alpha (linear_bwd_w's launch).
+    Two tiles per side with a ragged edge, two full K-tiles of 32 and a ragged third."""
+    from espnet_amd.ops import ACT_NONE, ACT_RELU, ACT_SWISH, ACT_TANH
+    M = N = tile + 4
+    K = 68
+    g = torch.Generator().manual_seed(tile + 2 * transA + transB)
+    A = torch.randn((K, M) if transA else (M, K), generator=g).to(DEV)        # transA: stored [K, M]
+    B = torch.randn((K, N) if transB else (N, K), generator=g).to(DEV)        # transB: stored [K, N]
+    lda, ldb, ldc = A.shape[1], B.shape[1], N
+    # what eamd_gemm_f32_dispatch asks of the operands: a later change of shape must not move the test onto the generic kernel
+    assert K % 4 == 0 and lda % 4 == 0 and ldb % 4 == 0
+    assert lda >= ((M if transA else K) + 3) // 4 * 4 and ldb >= ((N if transB else K) + 3) // 4 * 4
+    assert A.is_contiguous() and B.is_contiguous() and A.data_ptr() % 16 == 0 and B.data_ptr() % 16 == 0
+    Ad, Bd = A.double().cpu(), B.double().cpu()
+    Ad, Bd = (Ad.t() if transA else Ad), (Bd if transB else Bd.t())           # [M, K], [K, N]
+    cases = [(ACT_SWISH, ACT_NONE), (ACT_NONE, ACT_SWISH), (ACT_SWISH, ACT_SWISH), (ACT_RELU, ACT_TANH)]
+    for a_act, b_act in cases:
+        Cm = torch.full((M, N), float("nan"), device=DEV)
+        assert Cm.data_ptr() % 16 == 0
+        ops.gemm(A, B, Cm, M, N, K, lda, ldb, ldc, transA=transA, transB=transB, a_act=a_act, b_act=b_act, tile=tile)
+        report("staged act a=%d b=%d tile %d TA%d TB%d" % (a_act, b_act, tile, transA, transB), Cm,
+               _act_f64(Ad, a_act) @ _act_f64(Bd, b_act), 2e-6)
+    if transA:
+        Cm, cs = torch.full((M, N), float("nan"), device=DEV), torch.zeros(M, device=DEV)
+        ops.gemm(A, B, Cm, M, N, K, lda, ldb, ldc, transA=transA, transB=transB, b_act=ACT_SWISH, alpha=0.5, colsum=cs, tile=tile)
+        report("staged b_act + colsum: product tile %d TB%d" % (tile, transB), Cm, 0.5 * (Ad @ _act_f64(Bd, ACT_SWISH)), 2e-6)
+        report("staged b_act + colsum: column sums tile %d TB%d" % (tile, transB), cs, 0.5 * Ad.sum(1), 2e-5)
 
 
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
