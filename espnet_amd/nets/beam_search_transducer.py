@@ -13,6 +13,9 @@ computed is this package's own design:
   * greedy search: the prediction output only changes when a symbol is emitted, so a whole CHUNK of frames is scored
     against the current node in one batch, the first non-blank frame is located on the device and only that index
     and token come back to the host - launches scale with emitted symbols, not with frames;
+  * batched greedy search (`greedy_batch`): all utterances of a batch frame by frame in lock-step - a fused joint + argmax
+    launch that never stores the logits, a bookkeeping launch, a masked prediction-network step - with no host read inside the
+    frame loop and one at the end, optionally as replays of one captured frame step;
   * default beam search: at the start of a frame all carried hypotheses are scored in one batch (prediction steps for
     nodes first seen + joint rows + top-k, one device-to-host copy); children created during the frame are scored
     lazily, again all pending ones in one batch, when the first of them is selected for expansion.
@@ -217,6 +220,184 @@ class BeamSearchTransducer:
             self._ensure_pred([node])
             t += f + 1                     # at most one symbol per frame (reference greedy_search)
         return Hypothesis(score=score, yseq=self._tree.labels(node))
+
+    # ---- batched greedy ---------------------------------------------------------------------------------------------
+    # The reference's greedy search emits at most one symbol per frame, so the utterances of a batch advance through the frames in
+    # lock-step: frame t of all rows is one fused joint + argmax launch (eamd_rnnt_greedy_joint: the [B, V] logits are never stored),
+    # one bookkeeping launch (eamd_rnnt_greedy_pick) whose `live` mask says which rows emitted, and one masked prediction-network
+    # step on the existing embedding / LSTM / GRU kernels (rows that emitted nothing keep h, c and hence lin_dec's d).  Nothing is
+    # read by the host inside the frame loop; tokens, lengths and scores of all rows come back in ONE buffer at the end.
+    # The state is kept twice (frame t reads copy (t + 1) % 2 and writes copy t % 2: the one-launch LSTM step cannot update h in
+    # place), so the unit that repeats is a PAIR of frames; with `graph_steps` that pair is captured once per signature, reads the
+    # frame counter from the device and is replayed ceil(T / 2) times (a frame beyond an utterance's length is never live).
+    graph_steps = False               # opt-in, as on BeamSearch: the second call of a signature captures, later ones replay
+    graph_frame_bucket = 32
+    graph_max_signatures = 16
+    greedy_max_rows = 64              # rows per frame loop (eamd_rnnt_greedy_*, eamd_lstm_step_fwd); larger batches go in chunks
+
+    def _greedy_one(self, h):
+        if hasattr(self.decoder, "att"):
+            self.decoder.att[0].reset()
+        with torch.no_grad():
+            return self._greedy(h)
+
+    def _greedy_batched_ok(self):
+        from .transducer.rnn_decoder import DecoderRNNT
+        dec = self.decoder
+        return type(dec) is DecoderRNNT and not (dec.training and dec.dropout > 0) and ops.get_precision() == "fp32"
+
+    @ops.inference_call
+    def greedy_batch(self, hs_pad, hlens=None):
+        """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
+        -> [Hypothesis(score, yseq)] * B, yseq[0] == blank: what __call__ returns per utterance with beam_size <= 1.
+        DecoderRNNT (lstm / gru): the batched frame loop above, one blocking host read per call.  Other prediction networks:
+        a loop over the per-utterance search."""
+        B, T = hs_pad.shape[:2]
+        if not self._greedy_batched_ok():
+            if hlens is None:
+                lens = [T] * B
+            else:
+                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
+            return [self._greedy_one(hs_pad[b, :lens[b]]) for b in range(B)]
+        dev = hs_pad.device
+        with torch.no_grad():
+            if hlens is None:
+                hl = torch.full((B,), T, dtype=torch.int32, device=dev)
+            elif torch.is_tensor(hlens):
+                hl = hlens.to(device=dev, dtype=torch.int32).clamp(max=T)
+            else:
+                hl = torch.tensor([min(int(v), T) for v in hlens], dtype=torch.int32).to(dev, non_blocking=True)
+            jn = self.decoder.joint_network
+            enc = jn.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
+            res = []
+            for b0 in range(0, B, self.greedy_max_rows):
+                b1 = min(B, b0 + self.greedy_max_rows)
+                res.append(self._greedy_rows(enc[b0:b1], hl[b0:b1]))
+            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
+        hyps, o = [], 0
+        for _buf, n, ycap in res:
+            yseq = host[o:o + n * ycap].reshape(n, ycap)
+            ylen = host[o + n * ycap:o + n * ycap + n]
+            score = host[o + n * ycap + n:o + n * ycap + 2 * n].view(np.float32)
+            hyps += [Hypothesis(score=float(score[i]), yseq=yseq[i, :ylen[i]].tolist()) for i in range(n)]
+            o += n * ycap + 2 * n
+        return hyps
+
+    def _greedy_ws(self, n, Tcap, dev):
+        """the buffers of one frame loop on n rows: results (yseq | ylen | score in one int32 buffer), both copies of the
+        prediction network's state, the step's intermediates and the device frame counter"""
+        dec = self.decoder
+        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
+        G = (4 if dec.dtype == "lstm" else 3) * H
+        f = dict(device=dev, dtype=torch.float32)
+        ycap = Tcap + 1
+        ws = dict(n=n, Tcap=Tcap, ycap=ycap, graph=None, calls=0)
+        ws["res"] = torch.empty(n * ycap + 2 * n, device=dev, dtype=torch.int32)
+        ws["yseq"] = ws["res"][:n * ycap].view(n, ycap)
+        ws["ylen"] = ws["res"][n * ycap:n * ycap + n]
+        ws["score"] = ws["res"][n * ycap + n:].view(torch.float32)
+        ws["enc"] = torch.zeros(n, Tcap, J, **f)
+        ws["hl"] = torch.empty(n, device=dev, dtype=torch.int32)
+        ws["t"] = torch.zeros(1, device=dev, dtype=torch.int32)
+        ws["tok"] = torch.empty(n, device=dev, dtype=torch.int64)
+        ws["live"] = torch.empty(n, device=dev, dtype=torch.uint8)
+        ws["part"] = ops.rnnt_greedy_part(n, dec.odim, dev)
+        ws["d"] = torch.empty(n, J, **f)
+        ws["h"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
+        ws["c"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
+        ws["gx"] = [torch.empty(n, G, **f) for _ in range(L)]
+        ws["gates"] = [torch.empty(n, 4 * H, **f) for _ in range(L)]       # lstm: pre-activations / activated gates; gru: acts
+        ws["gh"] = [torch.empty(n, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        return ws
+
+    def _pred_step(self, ws, src, dst, live):
+        """prediction network on ws.tok from state copy `src` into copy `dst` (live: uint8 [n] or None = every row), then lin_dec"""
+        from .. import rnn_functional as R_
+        dec, n = self.decoder, ws["n"]
+        H = dec.dunits
+        x = ops.embed_pe(ws["tok"], dec.embed.weight, None, 1, 1.0)
+        for l, cell in enumerate(dec.decoder):
+            hp, hn, gx = ws["h"][src][l], ws["h"][dst][l], ws["gx"][l]
+            ops.linear_into(x, cell.weight_ih, cell.bias_ih, gx)
+            if dec.dtype == "lstm":
+                cp, cn, gates = ws["c"][src][l], ws["c"][dst][l], ws["gates"][l]
+                if ops.lstm_step_ok(n, H):
+                    ops.lstm_step_fwd(gx, cell.weight_hh, cell.bias_hh, hp, cp, live, hn, cn, None, gates)
+                else:
+                    R_._rec_gemm(hp, cell.weight_hh, gates, n, 4 * H, H, H, H, 4 * H, bias=cell.bias_hh, R=gx, ldr=4 * H)
+                    ops.lstm_cell_fwd(gates, cp, hp, live, hn, cn, None, gates)
+            else:
+                gh = ws["gh"][l]
+                R_._rec_gemm(hp, cell.weight_hh, gh, n, 3 * H, H, H, H, 3 * H, bias=cell.bias_hh)
+                ops.gru_cell_fwd(gx, gh, hp, live, hn, None, ws["gates"][l])
+            x = hn
+        ops.linear_into(x, dec.joint_network.lin_dec.weight, None, ws["d"])
+
+    def _frame(self, ws, parity, t, t_dev):
+        """one frame: joint + argmax, bookkeeping, masked prediction step (state copy 1 - parity -> copy parity)"""
+        jn = self.decoder.joint_network
+        ops.rnnt_greedy_joint(ws["enc"], ws["d"], jn.lin_out.weight, jn.lin_out.bias, ws["part"], jn.act_id, t, t_dev)
+        ops.rnnt_greedy_pick(ws["part"], ws["hl"], ws["yseq"], ws["ylen"], ws["score"], ws["tok"], ws["live"], ws["Tcap"],
+                             self.vocab_size, self.blank, t, t_dev)
+        self._pred_step(ws, 1 - parity, parity, ws["live"])
+
+    def _greedy_rows(self, enc, hl):
+        """the frame loop on n <= greedy_max_rows rows: enc (n, T, J) projected encoder states, hl (n,) int32 on the device
+        -> (result buffer, n, ycap), not yet read"""
+        from .. import graphs
+        n, T, _J = enc.shape
+        dev = enc.device
+        ws = None
+        if self.graph_steps:
+            fb = self.graph_frame_bucket
+            Tcap = (T + fb - 1) // fb * fb
+            dec = self.decoder
+            sig = (n, Tcap, dev.index, dec.embed.weight.data_ptr(), dec.joint_network.lin_out.weight.data_ptr())
+            if not hasattr(self, "_greedy_graphs"):
+                self._greedy_graphs = {}
+            ws = self._greedy_graphs.pop(sig, None)
+            while len(self._greedy_graphs) >= self.graph_max_signatures:
+                self._greedy_graphs.pop(next(iter(self._greedy_graphs)))
+            if ws is None:
+                ws = self._greedy_ws(n, Tcap, dev)
+            self._greedy_graphs[sig] = ws                      # most recently used last
+        else:
+            ws = self._greedy_ws(n, T, dev)
+        ws["calls"] += 1
+        ws["enc"][:, :T].copy_(enc)
+        ws["hl"].copy_(hl)
+        ws["yseq"].fill_(self.blank)
+        ws["ylen"].fill_(1)
+        ws["score"].zero_()
+        ws["tok"].fill_(self.blank)
+        for l in range(self.decoder.dlayers):
+            ws["h"][0][l].zero_()
+            ws["c"][0][l].zero_()
+        self._pred_step(ws, 0, 1, None)                        # the initial step on blank from the zero state
+        if self.graph_steps and ws["calls"] >= 2:
+            try:
+                if ws["graph"] is None:
+                    torch.cuda.synchronize()
+                    g = graphs.new_graph()
+                    with torch.cuda.graph(g):
+                        self._frame(ws, 0, 0, ws["t"])
+                        self._frame(ws, 1, 0, ws["t"])
+                    graphs.audit(g, "greedy transducer frame graph")
+                    ws["graph"] = g
+                ws["t"].zero_()
+                for _ in range((T + 1) // 2):
+                    ws["graph"].replay()
+                return ws["res"].clone(), n, ws["ycap"]
+            except Exception as e:  # noqa: BLE001 - a step that cannot be captured: eager frame loops from now on
+                import logging
+                logging.getLogger(__name__).warning("greedy transducer frame graph disabled: %s", str(e)[:200])
+                torch.cuda.synchronize()
+                self.graph_steps = False
+                self._greedy_graphs = {}
+                return self._greedy_rows(enc, hl)
+        for t in range(T):
+            self._frame(ws, t & 1, t, None)
+        return (ws["res"].clone() if self.graph_steps else ws["res"]), n, ws["ycap"]
 
     # ---- default beam search ----------------------------------------------------------------------------------------
     def _default(self, h):

@@ -153,8 +153,9 @@ class ErrorCalculator(object):
 
 
 class ErrorCalculatorTransducer(object):
-    """reference: e2e_asr_common.py:249-402.  Hypotheses from the default search with beam_size=1 on every hs_pad[b]; their
-    yseq[1:] are padded with -1, uploaded once and scored through ErrorCalculator's device path."""
+    """reference: e2e_asr_common.py:249-402.  Hypotheses from the greedy search (beam_size=1) on every hs_pad[b], all rows in one
+    BeamSearchTransducer.greedy_batch call; their yseq[1:] are padded with -1, uploaded once and scored through ErrorCalculator's
+    device path."""
 
     def __init__(self, decoder, token_list, sym_space, sym_blank, report_cer=False, report_wer=False):
         from .beam_search_transducer import BeamSearchTransducer
@@ -169,7 +170,8 @@ class ErrorCalculatorTransducer(object):
 
     def hypotheses(self, hs_pad):
         """-> ys_hat [B, Lh] int32 on hs_pad's device, -1 padded"""
-        ys_hat = [list(self.beam_search(hs_pad[b]).yseq[1:]) for b in range(int(hs_pad.size(0)))]
+        # every padded row is decoded whole, as in the reference: all rows frame by frame in one batched greedy search
+        ys_hat = [list(h.yseq[1:]) for h in self.beam_search.greedy_batch(hs_pad)]
         width = max(1, max(len(y) for y in ys_hat))
         host = torch.full((len(ys_hat), width), -1, dtype=torch.int32)
         for b, y in enumerate(ys_hat):

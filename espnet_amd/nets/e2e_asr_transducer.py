@@ -214,3 +214,32 @@ class E2E(ASRInterface, torch.nn.Module):
         if isinstance(nbest_hyps, list):
             return [asdict(n) for n in nbest_hyps]
         return asdict(nbest_hyps)
+
+    @ops.inference_call
+    def recognize_batch(self, xs, beam_search):
+        """xs: list of ndarrays (T_i, D) -> one result per utterance, each in the format `recognize` returns.
+        One padded encoder pass (as in forward: the lengths are the encoder's own output lengths); beam_size <= 1 then takes
+        BeamSearchTransducer.greedy_batch - all utterances frame by frame on the device, one host read - and beam_size > 1 runs
+        the configured search on each utterance's valid frames."""
+        from dataclasses import asdict
+        self.eval()
+        p = next(self.parameters())
+        rnn = "transformer" not in self.etype
+        if rnn:
+            xs = [x[:: int(self.subsample[0]), :] for x in xs]          # encode_rnn
+        il = [int(x.shape[0]) for x in xs]
+        xs_pad = torch.zeros(len(xs), max(il), xs[0].shape[1], dtype=p.dtype)
+        for b, x in enumerate(xs):
+            xs_pad[b, : il[b]] = torch.as_tensor(x, dtype=p.dtype)
+        xs_pad = xs_pad.to(p.device)
+        with torch.no_grad():
+            if rnn:
+                hs_pad, hlens, _ = self.enc(xs_pad, il)
+            else:
+                src_mask = ops.h2d_cached("src_mask", make_non_pad_mask(il).numpy(), xs_pad.device).unsqueeze(-2)
+                hs_pad, _ = self.encoder(xs_pad, src_mask)
+                hlens = subsampled_lengths(il, xs_pad.shape[1])
+        if beam_search.beam_size <= 1:
+            return [asdict(h) for h in beam_search.greedy_batch(hs_pad, hlens)]
+        hl = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
+        return [[asdict(n) for n in beam_search(hs_pad[b, : hl[b]])] for b in range(len(xs))]

@@ -1479,6 +1479,65 @@ def transducer_expand_rows(logits, k, lm=None, lm_row=None, pairs=None):
     return rows, host[n * W:]
 
 
+def rnnt_greedy_part(B, V, device):
+    """the tile-record buffer eamd_rnnt_greedy_joint fills and eamd_rnnt_greedy_pick reads"""
+    return torch.empty(_lib.lib().eamd_rnnt_greedy_part_floats(B, V), device=device, dtype=torch.float32)
+
+
+def rnnt_greedy_joint(enc_proj, d, w_out, b_out, part, act, t, t_dev=None):
+    """frame t (or t_dev[0] + t) of a batched greedy transducer search: the joint network's logits of all B rows as per-tile
+    (maximum, first token id, sum of exp) records in `part` - the [B, V] logits are never stored.
+    enc_proj [B, T, J], d [B, J], w_out [V, J], b_out [V]: contiguous float32"""
+    B, T, J = enc_proj.shape
+    V = w_out.shape[0]
+    for x in (enc_proj, d, w_out, b_out, part):
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise _lib.EamdError("rnnt_greedy_joint: contiguous float32 operands")
+    if tuple(d.shape) != (B, J) or tuple(w_out.shape) != (V, J) or b_out.numel() != V \
+            or part.numel() < _lib.lib().eamd_rnnt_greedy_part_floats(B, V) \
+            or (t_dev is not None and (t_dev.dtype != torch.int32 or t_dev.numel() < 1)):
+        raise _lib.EamdError("rnnt_greedy_joint: operand shapes")
+    check(_lib.lib().eamd_rnnt_greedy_joint(ptr(enc_proj), ptr(d), ptr(w_out), ptr(b_out), ptr(part), B, T, J, V, act, t,
+                                            ptr(t_dev), stream_ptr()), "eamd_rnnt_greedy_joint")
+
+
+def rnnt_greedy_pick(part, hlens, yseq, ylen, score, tok, live, T, V, blank, t, t_dev=None):
+    """the frame's decision and bookkeeping from the tile records: first maximum per row, live = frame < hlens[b] and token !=
+    blank; live rows append the token to yseq [B, ycap] int32 at ylen [B] int32, add its log-probability to score [B] float32
+    and put it in tok [B] int64 (others: blank); live [B] uint8 is the cell kernels' mask; t_dev[0] += 1 when given"""
+    B, ycap = yseq.shape
+    ok = (yseq.dtype == torch.int32 and yseq.is_contiguous() and ylen.dtype == torch.int32 and ylen.numel() == B
+          and score.dtype == torch.float32 and score.numel() == B and tok.dtype == torch.int64 and tok.numel() == B
+          and tok.is_contiguous() and live.dtype == torch.uint8 and live.numel() == B
+          and (hlens is None or (hlens.dtype == torch.int32 and hlens.numel() == B))
+          and part.dtype == torch.float32 and part.numel() >= _lib.lib().eamd_rnnt_greedy_part_floats(B, V)
+          and (t_dev is None or (t_dev.dtype == torch.int32 and t_dev.numel() >= 1)))
+    if not ok:
+        raise _lib.EamdError("rnnt_greedy_pick: operand types / shapes")
+    check(_lib.lib().eamd_rnnt_greedy_pick(ptr(part), ptr(hlens), ptr(yseq), ptr(ylen), ptr(score), ptr(tok), ptr(live), B, T, V,
+                                           ycap, blank, t, ptr(t_dev), stream_ptr()), "eamd_rnnt_greedy_pick")
+
+
+def linear_into(x, W, b, out):
+    """out[M, N] = x W^T + b into a caller-owned buffer (the static buffers a replayed decoding step reads and writes): the
+    few-row kernel of linear_fwd where it takes the shape, else the GEMM"""
+    M, K = x.shape
+    N = W.shape[0]
+    assert W.shape[1] == K and W.is_contiguous() and x.is_contiguous() and out.is_contiguous() and tuple(out.shape) == (M, N)
+    if x.dtype != torch.float32 or W.dtype != torch.float32 or out.dtype != torch.float32:
+        raise _lib.EamdError("linear_into: float32 operands")
+    if (LINEAR_ROWS and K % 4 == 0 and _state["precision"] == 0
+            and (M <= LINEAR_ROWS_MAX or (M <= LINEAR_ROWS_BLOCK_MAX and K <= 512 and N <= 1024 and K % 16 == 0))):
+        rc = _lib.lib().eamd_linear_rows_f32(ptr(x), ptr(W), ptr(b), None, ptr(out), M, N, K, ACT_NONE, EPI_NONE, 1.0, K, 0,
+                                             stream_ptr())
+        if rc == 0:
+            return out
+        if rc != _lib.EAMD_EUNSUPPORTED:
+            check(rc, "eamd_linear_rows_f32")
+    gemm(x, W, out, M, N, K, K, K, N, bias=b)
+    return out
+
+
 # ---- element-wise ------------------------------------------------------------------------------
 def axpby(x, y, a=1.0, b=1.0, out=None):
     if out is None:

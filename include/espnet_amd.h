@@ -920,6 +920,23 @@ int eamd_rnnt_row_coef(const int32_t* labels, const int32_t* tlens, const int32_
 int eamd_rnnt_node_grad(const float* logits_rows, float* grad_rows, void* grad_rows_bf16, const int32_t* labels,
                         const int32_t* tlens, const int32_t* ulens, const float* workspace, int64_t node0, int64_t nrows,
                         int B, int T, int U, int V, int blank, const float* gscale_dev, float scale, void* stream);
+/* Batched greedy transducer search, one frame of 1 <= B <= 64 utterances per call pair (csrc/rnnt_greedy.hip; reference:
+ * beam_search_transducer.py:130-161 - at most one symbol per frame, so the utterances of a batch advance in lock-step).
+ * Any J >= 1 and V >= 2; the frame index is t, or *t_dev + t when t_dev != NULL (a device int32, as pos_dev above).
+ * eamd_rnnt_greedy_joint: logits[b, v] = sum_k act(enc_proj[b, frame, k] + d[b, k]) w_out[v, k] + b_out[v] (enc_proj [B, T, J] =
+ *   lin_enc of all frames, d [B, J] = lin_dec of the prediction network's output, w_out [V, J], b_out [V] or NULL, act an eamd_act
+ *   id: none / relu / swish / tanh), never stored: part (eamd_rnnt_greedy_part_floats(B, V) floats, 16-byte aligned) receives per
+ *   (row, column tile) the tile's maximum, its lowest token id and sum exp(logit - maximum).  A frame index >= T reads frame T - 1.
+ * eamd_rnnt_greedy_pick: per row the first maximum over the tiles (lowest id among equal logits: torch.max / eamd_argmax_rows) and
+ *   logp = -log(sum exp(logit - max)); live[b] = frame < (hlens ? min(hlens[b], T) : T) && token != blank.  Live rows:
+ *   yseq[b, ylen[b]] = token (yseq [B, ycap] int32; a full row is never written past ycap), ylen[b] += 1, score[b] += logp,
+ *   tok[b] = token.  Other rows: tok[b] = blank, nothing else changes.  live [B] uint8 is the mask eamd_lstm_cell_fwd /
+ *   eamd_lstm_step_fwd / eamd_gru_cell_fwd take.  *t_dev += 1 when given.  Plain stores, no atomics. */
+int eamd_rnnt_greedy_part_floats(int B, int V);      /* 4 floats per (row, 16-column tile); 0 for B < 1 or V < 1 */
+int eamd_rnnt_greedy_joint(const float* enc_proj, const float* d, const float* w_out, const float* b_out, float* part, int B, int T,
+                           int J, int V, int act, int t, const int32_t* t_dev, void* stream);
+int eamd_rnnt_greedy_pick(const float* part, const int32_t* hlens, int32_t* yseq, int32_t* ylen, float* score, int64_t* tok,
+                          uint8_t* live, int B, int T, int V, int ycap, int blank, int t, int32_t* t_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer on flat fp32 arenas.  reference: transformer/optimizer.py:12-75 (NoamOpt),
