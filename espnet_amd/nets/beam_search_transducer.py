@@ -24,7 +24,10 @@ computed is this package's own design:
     :239-663): every PASS scores all pending (encoder row, node) pairs in one joint_rows call, and one
     transducer_expand_rows launch hands the host what the pass needs - blank log-probability, the k best non-blank
     (log-probability, token) pairs, the LM log-probability of each chosen token, nsc's prefix-rescoring terms - through
-    ONE blocking device-to-host copy (`_expand`, counted in `host_reads`).
+    ONE blocking device-to-host copy (`_expand`, counted in `host_reads`);
+  * batched alsd (`alsd_batch`): the alsd search of all utterances of a batch step by step in lock-step, hypotheses in device
+    arrays instead of the trie, the beam bookkeeping of a step in one launch (eamd_rnnt_alsd_step), no host read inside the step
+    loop and one at the end.
 
 Prediction networks take part through one of three protocols: `step(tokens, states)` (batched; DecoderRNNT),
 `batch_step(yseqs)` (DecoderTT: the reference's batch_score, whose outputs depend on the batch a prefix is first computed
@@ -591,6 +594,151 @@ class BeamSearchTransducer:
         if final:
             return self._sort_nbest(final)
         return self._result(B)
+
+    # ---- batched alsd ---------------------------------------------------------------------------------------------------
+    # Every alsd hypothesis consumes one (frame, label prefix) pair per step and the step count is fixed, so the utterances of a batch
+    # advance in lock-step as they do in greedy_batch.  Row r = b * W + w is slot w of utterance b (W = min(beam_size, V)).  One step
+    # is joint_rows_d on the rows' gathered encoder frames and lin_dec outputs, eamd_transducer_expand_rows with its record left on the
+    # device, eamd_rnnt_alsd_step (the A / B / final bookkeeping of _alsd, one workgroup per utterance: it leaves the parent row, the
+    # token, the `live` mask and the next encoder row of every slot), ONE eamd_gather_rows launch (encoder rows by frame, h / c of
+    # every layer by parent row, from state copy 1 into copy 0) and the masked prediction step of _pred_step from copy 0 back into
+    # copy 1.  The host loop only enqueues launches; finals and the last B of all utterances come back in ONE copy, and the n-best
+    # sort of the reference happens on the host after it.
+    alsd_max_rows = 256               # rows (utterances x W) per step loop; larger batches go in chunks.  A guess, not a measurement
+
+    def _alsd_batched_ok(self):
+        return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16
+
+    def _alsd_one(self, h):
+        if hasattr(self.decoder, "att"):
+            self.decoder.att[0].reset()
+        with torch.no_grad():
+            return self._alsd(h)
+
+    @ops.inference_call
+    def alsd_batch(self, hs_pad, hlens=None):
+        """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
+        -> B n-best lists, each what __call__ returns for hs_pad[b, :hlens[b]] with search_type="alsd": the final hypotheses sorted
+        by score / len(yseq) (score with score_norm=False), or B in slot order when no hypothesis reached the last frame.
+        DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16: the batched step loop above, one blocking host read per call.
+        Anything else: a loop over the per-utterance search."""
+        B, T = hs_pad.shape[:2]
+        if not self._alsd_batched_ok():
+            if hlens is None:
+                lens = [T] * B
+            else:
+                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
+            return [self._alsd_one(hs_pad[b, :lens[b]]) for b in range(B)]
+        dev = hs_pad.device
+        W = min(self.beam_size, self.vocab_size)
+        u_max = int(self.u_max)
+        with torch.no_grad():
+            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: the padded T bounds every utterance
+                steps = [T + min(u_max, T - 1)] * B
+                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
+                      else hlens.to(device=dev, dtype=torch.int32).clamp(max=T))
+            else:
+                lens = [min(int(v), T) for v in hlens]
+                steps = [t + min(u_max, t - 1) for t in lens]
+                hl = torch.tensor(lens, dtype=torch.int32).to(dev, non_blocking=True)
+            jn = self.decoder.joint_network
+            enc = jn.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
+            nmax = max(1, self.alsd_max_rows // W)
+            res = []
+            for b0 in range(0, B, nmax):
+                b1 = min(B, b0 + nmax)
+                res.append(self._alsd_rows(enc[b0:b1], hl[b0:b1], W, u_max, max(steps[b0:b1])))
+            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
+        ycap, fw, fcap = T + u_max + 1, u_max + 2, W * (u_max + 2)
+        out, o = [], 0
+
+        def take(count, shape, f64=False):
+            nonlocal o
+            a = host[o:o + count * (2 if f64 else 1)]
+            o += a.size
+            return (a.copy().view(np.float64) if f64 else a).reshape(shape)
+
+        for _buf, n in res:
+            fin_score, score = take(n * fcap, (n, fcap), True), take(n * W, (n, W), True)
+            nfin, fin_len, fin_yseq = take(n, (n,)), take(n * fcap, (n, fcap)), take(n * fcap * fw, (n, fcap, fw))
+            nhyp, ulen, yseq = take(n, (n,)), take(n * W, (n, W)), take(n * W * ycap, (n, W, ycap))
+            for b in range(n):
+                if nfin[b]:
+                    hyps = [Hypothesis(score=float(fin_score[b, j]), yseq=fin_yseq[b, j, :fin_len[b, j]].tolist())
+                            for j in range(nfin[b])]
+                    if self.score_norm:
+                        hyps = sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True)
+                    else:
+                        hyps = sorted(hyps, key=lambda x: x.score, reverse=True)
+                else:
+                    hyps = [Hypothesis(score=float(score[b, m]), yseq=yseq[b, m, :ulen[b, m] + 1].tolist()) for m in range(nhyp[b])]
+                out.append(hyps)
+        return out
+
+    def _alsd_ws(self, n, W, T, u_max, dev):
+        """the buffers of one step loop on n utterances x W slots: both parities of the search state, the finals, what
+        eamd_rnnt_alsd_step leaves for the rest of the step, both copies of the prediction network's state and the step's intermediates"""
+        dec = self.decoder
+        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
+        G = (4 if dec.dtype == "lstm" else 3) * H
+        R = n * W
+        fw, fcap = u_max + 2, W * (u_max + 2)
+        f = dict(device=dev, dtype=torch.float32)
+        i32 = dict(device=dev, dtype=torch.int32)
+        ws = dict(n=R)
+        ws["st"] = [(torch.zeros(n, W, device=dev, dtype=torch.float64), torch.zeros(n, W, **i32), torch.ones(n, **i32),
+                     torch.zeros(n, W, T + u_max + 1, **i32)) for _ in range(2)]
+        ws["fin"] = (torch.zeros(n, fcap, device=dev, dtype=torch.float64), torch.zeros(n, fcap, **i32),
+                     torch.zeros(n, fcap, fw, **i32), torch.zeros(n, **i32))
+        ws["par"] = torch.empty(R, **i32)
+        ws["frame"] = torch.empty(R, **i32)
+        ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
+        ws["live"] = torch.empty(R, device=dev, dtype=torch.uint8)
+        ws["encr"] = torch.empty(R, J, **f)
+        ws["d"] = torch.empty(R, J, **f)
+        ws["h"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(2)]
+        ws["c"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(2)]
+        ws["gx"] = [torch.empty(R, G, **f) for _ in range(L)]
+        ws["gates"] = [torch.empty(R, 4 * H, **f) for _ in range(L)]
+        ws["gh"] = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        return ws
+
+    def _alsd_rows(self, enc, hl, W, u_max, steps):
+        """the step loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device
+        -> (result buffer (int32 words: fin_score | score | nfin | fin_len | fin_yseq | nhyp | ulen | yseq), n), not yet read"""
+        n, T, J = enc.shape
+        dev = enc.device
+        dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
+        k = min(W, V - 1)
+        ws = self._alsd_ws(n, W, T, u_max, dev)
+        enc_rows = enc.reshape(n * T, J)
+        self._pred_step(ws, 0, 1, None)                        # the initial step on blank from the zero state, into copy 1
+        # step 0 scores slot 0 on frame 1 (t = i - u + 1: frame 0 is never scored), or frame 0 of a one-frame utterance
+        first = torch.arange(n, device=dev, dtype=torch.int32) * T + (hl - 1).clamp(0, 1)
+        ws["frame"].copy_(first.repeat_interleave(W))
+        ops.gather_rows([(ws["encr"], enc_rows, ws["frame"])])
+        lstm = dec.dtype == "lstm"
+        p = 0
+        for i in range(steps):
+            rec = ops.transducer_expand_rows_dev(jn.joint_rows_d(ws["encr"], ws["d"]), k)
+            ops.rnnt_alsd_step(rec, hl, ws["st"][p], ws["st"][1 - p], ws["fin"], ws["par"], ws["tok"], ws["live"], ws["frame"],
+                               V, T, u_max, i)
+            p = 1 - p
+            if i == steps - 1:
+                break
+            jobs = [(ws["encr"], enc_rows, ws["frame"])]
+            for l in range(dec.dlayers):
+                jobs.append((ws["h"][0][l], ws["h"][1][l], ws["par"]))
+                if lstm:
+                    jobs.append((ws["c"][0][l], ws["c"][1][l], ws["par"]))
+            for j0 in range(0, len(jobs), 16):
+                ops.gather_rows(jobs[j0:j0 + 16])
+            self._pred_step(ws, 0, 1, ws["live"])
+        score, ulen, nhyp, yseq = ws["st"][p]
+        fin_score, fin_len, fin_yseq, nfin = ws["fin"]
+        buf = torch.cat([fin_score.view(torch.int32).reshape(-1), score.view(torch.int32).reshape(-1), nfin, fin_len.reshape(-1),
+                         fin_yseq.reshape(-1), nhyp, ulen.reshape(-1), yseq.reshape(-1)])
+        return buf, n
 
     # ---- N-step constrained beam search (reference :466-663) -----------------------------------------------------------
     def _nsc(self, h):

@@ -36,8 +36,11 @@ class JointNetwork(torch.nn.Module):
         """decoding on rows: enc_proj_rows (n, J) projected encoder frames, y_rows (n, D_dec) or (1, D_dec) prediction
         outputs (one output against every frame) -> logits (n, V): one lin_dec GEMM, one fused add + activation, one
         lin_out GEMM for all n (frame, hypothesis) pairs"""
+        return self.joint_rows_d(enc_proj_rows, F_.LinearFn.apply(y_rows.contiguous(), self.lin_dec.weight, None))
+
+    def joint_rows_d(self, enc_proj_rows, d):
+        """joint_rows behind lin_dec: d (n, J) or (1, J) = lin_dec of the prediction outputs (a search that keeps d per row)"""
         n = enc_proj_rows.shape[0]
-        d = F_.LinearFn.apply(y_rows.contiguous(), self.lin_dec.weight, None)
         if d.shape[0] == 1:
             z = R_.JointFn.apply(enc_proj_rows.contiguous().view(1, n, -1), d.view(1, 1, -1), self.act_id)
         else:

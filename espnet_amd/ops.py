@@ -1518,6 +1518,61 @@ def rnnt_greedy_pick(part, hlens, yseq, ylen, score, tok, live, T, V, blank, t, 
                                            ycap, blank, t, ptr(t_dev), stream_ptr()), "eamd_rnnt_greedy_pick")
 
 
+def transducer_expand_rows_dev(logits, k):
+    """eamd_transducer_expand_rows without LM and pairs, its record left on the device: logits fp32 [n, V] (unit column stride) ->
+    rec fp32 [n, 1 + 2k] = (logp[r][0], the k best non-blank log-probabilities, their token ids as floats).  Nothing is read back."""
+    n, V = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise _lib.EamdError("transducer_expand_rows_dev: float32 [n, V] with unit column stride")
+    rec = torch.empty(n, 1 + 2 * k, device=logits.device, dtype=torch.float32)
+    check(_lib.lib().eamd_transducer_expand_rows(ptr(logits), logits.stride(0), n, V, k, None, None, None, 0, ptr(rec), None,
+                                                 stream_ptr()), "eamd_transducer_expand_rows")
+    return rec
+
+
+def rnnt_alsd_step(rec, hlens, state_in, state_out, fin, par, tok, live, frame, V, T, u_max, i):
+    """step i of the batched alsd transducer search (eamd_rnnt_alsd_step): rec fp32 [n * W, 1 + 2k] of this step's rows, hlens int32
+    [n] or None; state_in / state_out = (score float64 [n, W], ulen int32 [n, W], nhyp int32 [n], yseq int32 [n, W, T + u_max + 1])
+    of the two parities; fin = (fin_score float64 [n, fcap], fin_len int32 [n, fcap], fin_yseq int32 [n, fcap, u_max + 2], nfin
+    int32 [n]) with fcap = W (u_max + 2), appended in place; par int32 / tok int64 / live uint8 / frame int32 [n * W] are written"""
+    n, W = state_in[0].shape
+    k = min(W, V - 1)
+    fcap = W * (u_max + 2)
+    want = [((n, W), torch.float64), ((n, W), torch.int32), ((n,), torch.int32), ((n, W, T + u_max + 1), torch.int32)]
+    ok = rec.dtype == torch.float32 and rec.is_contiguous() and tuple(rec.shape) == (n * W, 1 + 2 * k)
+    for st in (state_in, state_out):
+        ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(st, want))
+    want_f = [((n, fcap), torch.float64), ((n, fcap), torch.int32), ((n, fcap, u_max + 2), torch.int32), ((n,), torch.int32)]
+    ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(fin, want_f))
+    ok = ok and all(x.numel() == n * W and x.dtype == d and x.is_contiguous()
+                    for x, d in ((par, torch.int32), (tok, torch.int64), (live, torch.uint8), (frame, torch.int32)))
+    ok = ok and (hlens is None or (hlens.dtype == torch.int32 and hlens.numel() == n and hlens.is_contiguous()))
+    if not ok:
+        raise _lib.EamdError("rnnt_alsd_step: operand types / shapes")
+    check(_lib.lib().eamd_rnnt_alsd_step(ptr(rec), ptr(hlens), *[ptr(x) for x in state_in], *[ptr(x) for x in state_out],
+                                         *[ptr(x) for x in fin], ptr(par), ptr(tok), ptr(live), ptr(frame), n, W, V, T, u_max, i,
+                                         stream_ptr()), "eamd_rnnt_alsd_step")
+
+
+def gather_rows(jobs):
+    """up to 16 row gathers in one launch (eamd_gather_rows): jobs = [(dst [r, w], src [m, w], idx int32 [r])], contiguous fp32
+    matrices on the device: dst[i] = src[idx[i]]"""
+    n = len(jobs)
+    assert 0 < n <= 16
+    for d, s_, ix in jobs:
+        if not (d.dtype == s_.dtype == torch.float32 and d.is_contiguous() and s_.is_contiguous() and d.dim() == s_.dim() == 2
+                and d.shape[1] == s_.shape[1] and ix.dtype == torch.int32 and ix.is_contiguous() and ix.numel() == d.shape[0]
+                and s_.shape[0] >= 1):
+            raise _lib.EamdError("gather_rows: contiguous float32 [rows, width] matrices of one width, int32 indices")
+    src = (C.c_void_p * n)(*[s_.data_ptr() for _, s_, _ in jobs])
+    dst = (C.c_void_p * n)(*[d.data_ptr() for d, _, _ in jobs])
+    idx = (C.c_void_p * n)(*[ix.data_ptr() for _, _, ix in jobs])
+    nrows = (C.c_int32 * n)(*[d.shape[0] for d, _, _ in jobs])
+    width = (C.c_int32 * n)(*[d.shape[1] for d, _, _ in jobs])
+    srows = (C.c_int32 * n)(*[s_.shape[0] for _, s_, _ in jobs])
+    check(_lib.lib().eamd_gather_rows(src, dst, idx, nrows, width, srows, n, stream_ptr()), "eamd_gather_rows")
+
+
 def linear_into(x, W, b, out):
     """out[M, N] = x W^T + b into a caller-owned buffer (the static buffers a replayed decoding step reads and writes): the
     few-row kernel of linear_fwd where it takes the shape, else the GEMM"""

@@ -937,6 +937,38 @@ int eamd_rnnt_greedy_joint(const float* enc_proj, const float* d, const float* w
                            int J, int V, int act, int t, const int32_t* t_dev, void* stream);
 int eamd_rnnt_greedy_pick(const float* part, const int32_t* hlens, int32_t* yseq, int32_t* ylen, float* score, int64_t* tok,
                           uint8_t* live, int B, int T, int V, int ycap, int blank, int t, int32_t* t_dev, void* stream);
+/* Batched alignment-length-synchronous transducer beam search without an LM, the beam bookkeeping of step i for n utterances in one
+ * launch (csrc/rnnt_alsd.hip; reference: beam_search_transducer.py:349-464 align_length_sync_decoding, transducer/utils.py:181-203
+ * recombine_hyps).  One workgroup per utterance, plain stores.  1 <= W <= 16 slots per utterance (the beam, min(beam_size, V)), k =
+ * min(W, V - 1), blank = 0; row r = b * W + w is slot w of utterance b; anything else: EAMD_EUNSUPPORTED.
+ *   rec [n * W][1 + 2k]: eamd_transducer_expand_rows' record of this step's rows (blank logp, k non-blank logp, their tokens).
+ *   hlens [n] (may be NULL = T): T_b = min(hlens[b], T) frames of the padded T, u_max_b = min(u_max, T_b - 1).
+ *   state, read from *_in and written to *_out (two copies, never the same buffer): score double [n, W], ulen int32 [n, W] = labels
+ *     without the leading blank, nhyp int32 [n] (slots 0 .. nhyp - 1 are the list B, in order), yseq int32 [n, W, ycap] with ycap =
+ *     T + u_max + 1 (a hypothesis that emits on every step stays at frame 1 and grows to T + u_max labels: the reference has no bound).
+ *   i >= T_b + u_max_b, or no slot with t = i - ulen + 1 <= T_b - 1 (`if B_:`): the state is copied unchanged.  Otherwise A = per
+ *     active slot, in slot order, (score + rec[r][0], same labels) then (score + rec[r][j], labels + token j) for j = 1 .. k - double
+ *     sums of a double and a float; B = the first W of A by score descending, stable, NaN as -inf (sorted(..., reverse=True)[:beam]);
+ *     then recombine_hyps as it behaves: an entry whose labels (length and tokens) equal an earlier first occurrence adds its score
+ *     to that one (logaddexp) and stays in B with its own score.
+ *   finals (appended in place): every blank continuation of an active slot with t == T_b - 1, in slot order, with the score after
+ *     recombination when it was selected as a first occurrence (the reference appends one object to A and to final), else the raw
+ *     one: fin_score double [n, fcap], fin_len int32 [n, fcap] (entries of the row, leading blank included), fin_yseq int32
+ *     [n, fcap, u_max + 2], nfin int32 [n], fcap = W * (u_max + 2).
+ *   for all n * W rows: par int32 = the row whose prediction-network state the new slot continues (own row when nothing changed),
+ *     tok int64 = the appended token or blank, live uint8 = 1 only for a slot that appended a token (the mask eamd_lstm_step_fwd /
+ *     eamd_lstm_cell_fwd / eamd_gru_cell_fwd take), frame int32 = b * T + clamp((i + 1) - ulen' + 1, 0, T_b - 1): the encoder row the
+ *     slot reads in step i + 1.
+ * eamd_gather_rows: up to 16 row gathers in one launch, dst_j[r, :] = src_j[idx_j[r], :] for r < nrows[j] (fp32 rows of width[j]
+ *   elements; float4 moves when the width is a multiple of 4 and the rows are 16-byte aligned).  src / dst / idx: HOST arrays of device
+ *   pointers as eamd_copy_jobs takes them, idx_j int32 on the device; nrows / width / src_rows: host arrays; an index outside
+ *   [0, src_rows[j]) reads the nearest valid row. */
+int eamd_rnnt_alsd_step(const float* rec, const int32_t* hlens, const double* score_in, const int32_t* ulen_in, const int32_t* nhyp_in,
+                        const int32_t* yseq_in, double* score_out, int32_t* ulen_out, int32_t* nhyp_out, int32_t* yseq_out,
+                        double* fin_score, int32_t* fin_len, int32_t* fin_yseq, int32_t* nfin, int32_t* par, int64_t* tok,
+                        uint8_t* live, int32_t* frame, int n, int W, int V, int T, int u_max, int i, void* stream);
+int eamd_gather_rows(const float* const* src, float* const* dst, const int32_t* const* idx, const int32_t* nrows, const int32_t* width,
+                     const int32_t* src_rows, int njobs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer on flat fp32 arenas.  reference: transformer/optimizer.py:12-75 (NoamOpt),
