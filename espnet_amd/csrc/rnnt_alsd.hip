@@ -15,6 +15,7 @@
 //                         and h / c of every prediction-network layer by par.
 // Plain stores, no atomics, no scratch buffers: a workgroup owns its utterance's rows of every output.
 #include "common.h"
+#include "rnnt_search.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -22,15 +23,6 @@ namespace {
 constexpr int AL_W = 16;                       // slots per utterance at most
 constexpr int AL_C = AL_W * (AL_W + 1);        // candidates per utterance at most: W active slots x (blank + k <= W tokens)
 constexpr int AL_THREADS = 256;
-
-// numpy.logaddexp on doubles (npy_logaddexp)
-__device__ __forceinline__ double al_logaddexp(double a, double b) {
-  if (a == b) return a + 0.693147180559945309417232121458176568;
-  const double d = a - b;
-  if (d > 0) return a + log1p(exp(-d));
-  if (d <= 0) return b + log1p(exp(d));
-  return d;                                    // NaN
-}
 
 __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
     const float* __restrict__ rec, const int* __restrict__ hlens, const double* __restrict__ score_in, const int* __restrict__ ulen_in,

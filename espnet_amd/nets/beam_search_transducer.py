@@ -27,7 +27,10 @@ computed is this package's own design:
     ONE blocking device-to-host copy (`_expand`, counted in `host_reads`);
   * batched alsd (`alsd_batch`): the alsd search of all utterances of a batch step by step in lock-step, hypotheses in device
     arrays instead of the trie, the beam bookkeeping of a step in one launch (eamd_rnnt_alsd_step), no host read inside the step
-    loop and one at the end.
+    loop and one at the end;
+  * batched tsd (`tsd_batch`): the tsd search of all utterances of a batch pass by pass in lock-step, hypotheses in M + 1 device
+    blocks (B's two parities and the C of every pass), the A / C / B bookkeeping of a pass in one launch (eamd_rnnt_tsd_step), no
+    host read inside the pass loop and one at the end.
 
 Prediction networks take part through one of three protocols: `step(tokens, states)` (batched; DecoderRNNT),
 `batch_step(yseqs)` (DecoderTT: the reference's batch_score, whose outputs depend on the batch a prefix is first computed
@@ -738,6 +741,154 @@ class BeamSearchTransducer:
         fin_score, fin_len, fin_yseq, nfin = ws["fin"]
         buf = torch.cat([fin_score.view(torch.int32).reshape(-1), score.view(torch.int32).reshape(-1), nfin, fin_len.reshape(-1),
                          fin_yseq.reshape(-1), nhyp, ulen.reshape(-1), yseq.reshape(-1)])
+        return buf, n
+
+    # ---- batched tsd ----------------------------------------------------------------------------------------------------
+    # tsd takes max_sym_exp = M passes per frame whatever the hypotheses are, so the utterances of a batch advance in lock-step here
+    # too.  Hypotheses live in M + 1 blocks of R = n * W rows (W = min(beam_size, V)): block 0 and block M are the two parities of
+    # B, block v is the C of pass v; the prediction network's h / c and lin_dec's d are stacked the same way, [(M + 1) R, .], so a
+    # block row indexes them directly.  One pass (t, v) is joint_rows_d on the frame's encoder rows and the d rows of C's block,
+    # eamd_transducer_expand_rows with its record left on the device, eamd_rnnt_tsd_step (A's update with its merges, and the
+    # selection of the next C from D or, after the last pass, of the next B from A: one workgroup per utterance, it leaves the parent
+    # block row, the token and the `live` mask of every slot) and ONE eamd_gather_rows launch by parent row: on a pass v < M - 1 h / c
+    # into a staging copy, from which the masked _pred_step writes block v + 1; at the frame's end h / c / d into B's other parity,
+    # and the next frame's encoder rows.  The host loop only enqueues; the last B of all utterances comes back in ONE copy and is
+    # sorted on the host as _sort_nbest sorts it.
+    tsd_max_rows = 256                # rows (utterances x W) per pass loop; larger batches go in chunks.  A guess, not a measurement
+
+    def _tsd_batched_ok(self):
+        return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16 and 1 <= self.max_sym_exp <= 4
+
+    def _tsd_one(self, h):
+        if hasattr(self.decoder, "att"):
+            self.decoder.att[0].reset()
+        with torch.no_grad():
+            return self._tsd(h)
+
+    @ops.inference_call
+    def tsd_batch(self, hs_pad, hlens=None):
+        """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
+        -> B n-best lists, each what __call__ returns for hs_pad[b, :hlens[b]] with search_type="tsd": the last B sorted by
+        score / len(yseq) (score with score_norm=False).
+        DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16, max_sym_exp <= 4: the batched pass loop above, one blocking
+        host read per call.  Anything else: a loop over the per-utterance search."""
+        B, T = hs_pad.shape[:2]
+        if not self._tsd_batched_ok():
+            if hlens is None:
+                lens = [T] * B
+            else:
+                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
+            return [self._tsd_one(hs_pad[b, :lens[b]]) for b in range(B)]
+        dev = hs_pad.device
+        W = min(self.beam_size, self.vocab_size)
+        M = int(self.max_sym_exp)
+        with torch.no_grad():
+            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: all T frames run, finished utterances idle
+                frames = [T] * B
+                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
+                      else hlens.to(device=dev, dtype=torch.int32).clamp(max=T))
+            else:
+                frames = [max(0, min(int(v), T)) for v in hlens]
+                hl = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
+            enc = self.decoder.joint_network.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
+            nmax = max(1, self.tsd_max_rows // W)
+            res = []
+            for b0 in range(0, B, nmax):
+                b1 = min(B, b0 + nmax)
+                res.append(self._tsd_rows(enc[b0:b1], hl[b0:b1], W, M, max(frames[b0:b1])))
+            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
+        ycap = 1 + T * (M - 1)
+        out, o = [], 0
+        for _buf, n in res:
+            score = host[o:o + 2 * n * W].copy().view(np.float64).reshape(n, W)
+            o += 2 * n * W
+            count, ulen = host[o:o + n], host[o + n:o + n + n * W].reshape(n, W)
+            o += n + n * W
+            yseq = host[o:o + n * W * ycap].reshape(n, W, ycap)
+            o += n * W * ycap
+            for b in range(n):
+                hyps = [Hypothesis(score=float(score[b, m]), yseq=yseq[b, m, :ulen[b, m] + 1].tolist()) for m in range(count[b])]
+                if self.score_norm:
+                    out.append(sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True))
+                else:
+                    out.append(sorted(hyps, key=lambda x: x.score, reverse=True))
+        return out
+
+    def _tsd_ws(self, n, W, T, M, dev):
+        """the buffers of one pass loop on n utterances x W slots: the M + 1 hypothesis blocks, the frame's A, what eamd_rnnt_tsd_step
+        leaves for the rest of the pass, the stacked prediction-network state with its staging copy and the pass's intermediates"""
+        dec = self.decoder
+        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
+        G = (4 if dec.dtype == "lstm" else 3) * H
+        R = n * W
+        f = dict(device=dev, dtype=torch.float32)
+        i32 = dict(device=dev, dtype=torch.int32)
+        ws = dict(n=R)
+        ws["st"] = (torch.zeros(M + 1, n, W, device=dev, dtype=torch.float64), torch.zeros(M + 1, n, W, **i32),
+                    torch.zeros(M + 1, n, **i32), torch.zeros(M + 1, n, W, 1 + T * (M - 1), **i32))
+        ws["st"][2][0].fill_(1)                               # B of frame 0: slot 0 holds [blank] with score 0
+        ws["A"] = (torch.zeros(n, W * M, device=dev, dtype=torch.float64), torch.zeros(n, W * M, **i32), torch.zeros(n, **i32))
+        ws["par"] = torch.empty(R, **i32)
+        ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
+        ws["live"] = torch.empty(R, device=dev, dtype=torch.uint8)
+        ws["encr"] = torch.empty(R, J, **f)
+        ws["d"] = torch.empty((M + 1) * R, J, **f)
+        ws["h"] = [torch.zeros((M + 1) * R, H, **f) for _ in range(L)]
+        ws["c"] = [torch.zeros((M + 1) * R, H, **f) for _ in range(L)]
+        stage_h, stage_c = [torch.zeros(R, H, **f) for _ in range(L)], [torch.zeros(R, H, **f) for _ in range(L)]
+        gx = [torch.empty(R, G, **f) for _ in range(L)]
+        gates = [torch.empty(R, 4 * H, **f) for _ in range(L)]
+        gh = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        # _pred_step's view of block j: state copy 0 = the staging copy, copy 1 = the block's rows
+        ws["blk"] = [dict(n=R, tok=ws["tok"], gx=gx, gates=gates, gh=gh, d=ws["d"][j * R:(j + 1) * R],
+                          h=[stage_h, [x[j * R:(j + 1) * R] for x in ws["h"]]], c=[stage_c, [x[j * R:(j + 1) * R] for x in ws["c"]]])
+                     for j in range(M + 1)]
+        return ws
+
+    def _tsd_rows(self, enc, hl, W, M, frames):
+        """the pass loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device, `frames` frames
+        -> (result buffer (int32 words: score | count | ulen | yseq of the last B), n), not yet read"""
+        n, T, J = enc.shape
+        dev = enc.device
+        dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
+        k = min(W, V - 1)
+        R = n * W
+        ws = self._tsd_ws(n, W, T, M, dev)
+        enc_rows = enc.reshape(n * T, J)
+        st, blk = ws["st"], ws["blk"]
+        self._pred_step(blk[0], 0, 1, None)                    # the initial step on blank from the zero state, into block 0
+        lstm = dec.dtype == "lstm"
+        p = 0
+        if frames:
+            # encoder row of frame t: b * T + min(t, T_b - 1), the same for all slots of an utterance
+            tt = torch.arange(frames, device=dev, dtype=torch.int32)
+            ft = torch.minimum(tt[:, None], (hl - 1)[None, :]).clamp_(min=0) + (torch.arange(n, device=dev, dtype=torch.int32) * T)
+            ft = ft.repeat_interleave(W, dim=1).contiguous()
+            ops.gather_rows([(ws["encr"], enc_rows, ft[0])])
+        for t in range(frames):
+            for v in range(M):
+                cin = (M if p else 0) if v == 0 else v
+                cout = v + 1 if v < M - 1 else (0 if p else M)
+                rec = ops.transducer_expand_rows_dev(jn.joint_rows_d(ws["encr"], blk[cin]["d"]), k)
+                ops.rnnt_tsd_step(rec, hl, st, ws["A"], ws["par"], ws["tok"], ws["live"], V, T, M, t, v, p)
+                if v < M - 1:
+                    jobs = [(blk[cout]["h"][0][l], ws["h"][l], ws["par"]) for l in range(dec.dlayers)]
+                    if lstm:
+                        jobs += [(blk[cout]["c"][0][l], ws["c"][l], ws["par"]) for l in range(dec.dlayers)]
+                elif t == frames - 1:
+                    break                                      # the last B's prediction state is never read
+                else:
+                    jobs = [(blk[cout]["h"][1][l], ws["h"][l], ws["par"]) for l in range(dec.dlayers)]
+                    if lstm:
+                        jobs += [(blk[cout]["c"][1][l], ws["c"][l], ws["par"]) for l in range(dec.dlayers)]
+                    jobs += [(blk[cout]["d"], ws["d"], ws["par"]), (ws["encr"], enc_rows, ft[t + 1])]
+                for j0 in range(0, len(jobs), 16):
+                    ops.gather_rows(jobs[j0:j0 + 16])
+                if v < M - 1:
+                    self._pred_step(blk[cout], 0, 1, ws["live"])
+            p = 1 - p
+        last = M if p else 0
+        buf = torch.cat([st[0][last].view(torch.int32).reshape(-1), st[2][last], st[1][last].reshape(-1), st[3][last].reshape(-1)])
         return buf, n
 
     # ---- N-step constrained beam search (reference :466-663) -----------------------------------------------------------

@@ -1554,6 +1554,29 @@ def rnnt_alsd_step(rec, hlens, state_in, state_out, fin, par, tok, live, frame, 
                                          stream_ptr()), "eamd_rnnt_alsd_step")
 
 
+def rnnt_tsd_step(rec, hlens, state, A, par, tok, live, V, T, M, t, v, p):
+    """pass (t, v) of the batched tsd transducer search (eamd_rnnt_tsd_step): rec fp32 [n * W, 1 + 2k] of the rows of C, hlens int32
+    [n] or None; state = (score float64 [M + 1, n, W], ulen int32 [M + 1, n, W], count int32 [M + 1, n], yseq int32
+    [M + 1, n, W, 1 + T (M - 1)]) - blocks 0 and M are B's parities, p the one frame t reads, block v the C of pass v; A = (a_score
+    float64 [n, W M], a_src int32 [n, W M], nA int32 [n]); state and A are updated in place, par int32 / tok int64 / live uint8
+    [n * W] are written"""
+    blocks, n, W = state[0].shape
+    k = min(W, V - 1)
+    want = [((M + 1, n, W), torch.float64), ((M + 1, n, W), torch.int32), ((M + 1, n), torch.int32),
+            ((M + 1, n, W, 1 + T * (M - 1)), torch.int32)]
+    ok = blocks == M + 1 and rec.dtype == torch.float32 and rec.is_contiguous() and tuple(rec.shape) == (n * W, 1 + 2 * k)
+    ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(state, want))
+    want_a = [((n, W * M), torch.float64), ((n, W * M), torch.int32), ((n,), torch.int32)]
+    ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(A, want_a))
+    ok = ok and all(x.numel() == n * W and x.dtype == d and x.is_contiguous()
+                    for x, d in ((par, torch.int32), (tok, torch.int64), (live, torch.uint8)))
+    ok = ok and (hlens is None or (hlens.dtype == torch.int32 and hlens.numel() == n and hlens.is_contiguous()))
+    if not ok:
+        raise _lib.EamdError("rnnt_tsd_step: operand types / shapes")
+    check(_lib.lib().eamd_rnnt_tsd_step(ptr(rec), ptr(hlens), *[ptr(x) for x in state], *[ptr(x) for x in A], ptr(par), ptr(tok),
+                                        ptr(live), n, W, V, T, M, t, v, p, stream_ptr()), "eamd_rnnt_tsd_step")
+
+
 def gather_rows(jobs):
     """up to 16 row gathers in one launch (eamd_gather_rows): jobs = [(dst [r, w], src [m, w], idx int32 [r])], contiguous fp32
     matrices on the device: dst[i] = src[idx[i]]"""

@@ -969,6 +969,33 @@ int eamd_rnnt_alsd_step(const float* rec, const int32_t* hlens, const double* sc
                         uint8_t* live, int32_t* frame, int n, int W, int V, int T, int u_max, int i, void* stream);
 int eamd_gather_rows(const float* const* src, float* const* dst, const int32_t* const* idx, const int32_t* nrows, const int32_t* width,
                      const int32_t* src_rows, int njobs, void* stream);
+/* Batched time-synchronous transducer beam search without an LM, the bookkeeping of pass (t, v) - frame t, symbol expansion v of M =
+ * max_sym_exp - for n utterances in one launch (csrc/rnnt_tsd.hip; reference: beam_search_transducer.py:239-347
+ * time_sync_decoding).  One workgroup per utterance, plain stores.  1 <= W <= 16 slots per utterance (the beam, min(beam_size, V)),
+ * W <= V, 1 <= M <= 4, k = min(W, V - 1), blank = 0; anything else: EAMD_EUNSUPPORTED.  v >= M, t < 0, p outside {0, 1}, a NULL
+ * operand other than hlens, or one array passed for two operands: EAMD_EINVAL.
+ *   hypotheses live in M + 1 blocks of n * W rows; block row = block * n * W + b * W + w is slot w of utterance b.  Block 0 and block
+ *     M are the two parities of B (the list carried across frames; p says which one frame t reads), block v (1 <= v < M) is the C of
+ *     pass v.  score double [M + 1, n, W], ulen int32 [M + 1, n, W] = labels without the leading blank, count int32 [M + 1, n] (slots
+ *     0 .. count - 1 are the list, in order), yseq int32 [M + 1, n, W, ycap] with ycap = 1 + T * (M - 1): B's entries come from A,
+ *     A's from the C of passes 0 .. M - 1, and the C of pass v is v labels longer than the frame's B, so a frame appends at most
+ *     M - 1 labels (the expansion of the last pass is never used).
+ *   A of the frame: a_score double [n, W * M], a_src int32 [n, W * M] = the block row an entry was first added from (its labels and
+ *     prediction-network state are read there), nA int32 [n].  Pass v == 0 starts from an empty A.
+ *   rec [n * W][1 + 2k]: eamd_transducer_expand_rows' record of the rows of C (block v; B's parity p when v == 0).
+ *   hlens [n] (may be NULL = T): T_b = min(hlens[b], T).  t >= T_b: par = the utterance's rows of B's parity p, tok = 0, live = 0;
+ *     at v == M - 1 that B (score, ulen, count, labels) is copied into the other parity; nothing else is written.
+ *   otherwise, A: every slot of C, in order, with score + rec[r][0] (a double plus a float) either joins the first entry present
+ *     before this pass that has its labels (length and tokens; logaddexp in double, in C's order) or is appended.
+ *   v < M - 1: D = per slot of C, in order, (score + rec[r][j], labels + token rec[r][k + j]) for j = 1 .. k; block v + 1 = the first
+ *     W of D by score descending, stable, NaN as -inf (sorted(..., reverse=True)[:beam]); per row par int32 = the parent's block row,
+ *     tok int64 = the token, live uint8 = 1 (the mask eamd_lstm_step_fwd / eamd_lstm_cell_fwd / eamd_gru_cell_fwd take).
+ *   v == M - 1: D is not built (the reference never uses it); B's other parity = the first W of A sorted the same way, labels copied
+ *     from a_src's row; par = a_src, tok = 0, live = 0.
+ *   rows beyond the new list's count: par = the row's own row of C's block, tok = 0, live = 0; score, ulen and labels are not written. */
+int eamd_rnnt_tsd_step(const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count, int32_t* yseq,
+                       double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W, int V,
+                       int T, int M, int t, int v, int p, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer on flat fp32 arenas.  reference: transformer/optimizer.py:12-75 (NoamOpt),
