@@ -944,6 +944,16 @@ static int conv_c1_bwd_w(const void* dy, const float* x, float* dw, float* db, f
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
+}  // extern "C"
+// the second stage alone, for partial sums another kernel left in the same [nslab][10][C] layout (gemm.hip:
+// eamd_conv2_bwd_x_conv1_bwd_w); arguments checked by the caller
+int eamd_conv1_bwd_w_reduce(const float* part, int nslab, int C, float* dw, float* db, hipStream_t stream) {
+  hipLaunchKernelGGL(conv1_bwd_w_reduce_kernel, dim3((10 * C + 63) / 64, min(16, (nslab + 31) / 32)), dim3(256), 0, stream, part,
+                     nslab, C, dw, db);
+  EAMD_LAUNCH_CHECK();
+  return EAMD_OK;
+}
+extern "C" {
 /* floats of scratch for eamd_conv1_bwd_w / eamd_conv3x3_c1_bwd_w (stride/pad as in the forward) */
 static int64_t conv_c1_ws(int B, int T, int C, int st, int pad) {
   if (B <= 0 || T + 2 * pad < 3 || C <= 0) return 0;

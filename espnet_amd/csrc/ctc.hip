@@ -242,7 +242,8 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
                                                        const float* __restrict__ beta, const float* __restrict__ nll,
                                                        float* __restrict__ grad, long gst, long gsb, int T, int V,
                                                        int Smax, int blank, float scale, long si = 0, long gsi = 0,
-                                                       int nsp = 1, const long long* __restrict__ perm = nullptr) {
+                                                       int nsp = 1, const long long* __restrict__ perm = nullptr,
+                                                       const float* __restrict__ gscale = nullptr) {
   extern __shared__ float occ[];  // [V]
   const int t = blockIdx.x, b = blockIdx.y;
   const int i = kPit ? (int)blockIdx.z : 0;
@@ -269,7 +270,29 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const float* __restrict__
   __syncthreads();
   const float* xr = x + t * st + b * sb + (kPit ? i * si : 0);
   const float ls = lse[q * T + t];
+  if (gscale) {      // the upstream scalar, read on the device: the value a scale_dev pass over the gradient would leave
+    const float gs = gscale[0];
+    for (int v = threadIdx.x; v < V; v += blockDim.x) gr[v] = ((expf(xr[v] - ls) - occ[v]) * scale) * gs;
+    return;
+  }
   for (int v = threadIdx.x; v < V; v += blockDim.x) gr[v] = (expf(xr[v] - ls) - occ[v]) * scale;
+}
+
+// the pieces of eamd_ctc_loss's workspace (eamd_ctc_workspace_bytes)
+struct CtcWs { int* lab; int* lablen; float* lse; float* lp; float* alpha; float* beta; int Lm; };
+inline CtcWs ctc_ws_carve(void* workspace, int B, int T, int Lmax) {
+  CtcWs r;
+  const int Smax = 2 * Lmax + 1;
+  char* w = (char*)workspace;
+  r.Lm = Lmax > 0 ? Lmax : 1;
+  r.lab = (int*)w; w += (size_t)B * r.Lm * 4;
+  r.lablen = (int*)w; w += (size_t)B * 4;
+  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
+  r.lse = (float*)w; w += (size_t)B * T * 4;
+  r.lp = (float*)w; w += (size_t)B * T * Smax * 4;
+  r.alpha = (float*)w; w += (size_t)B * T * Smax * 4;
+  r.beta = (float*)w;
+  return r;
 }
 
 }  // namespace
@@ -301,15 +324,10 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
   if (threads > 1024) return EAMD_EUNSUPPORTED;
   if (grad && (size_t)V * 4 > 64 * 1024) return EAMD_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  char* w = (char*)workspace;
-  int Lm = Lmax > 0 ? Lmax : 1;
-  int* lab = (int*)w; w += (size_t)B * Lm * 4;
-  int* lablen = (int*)w; w += (size_t)B * 4;
-  w = (char*)(((uintptr_t)w + 15) & ~(uintptr_t)15);
-  float* lse = (float*)w; w += (size_t)B * T * 4;
-  float* lp = (float*)w; w += (size_t)B * T * Smax * 4;
-  float* alpha = (float*)w; w += (size_t)B * T * Smax * 4;
-  float* beta = (float*)w;
+  const CtcWs ws = ctc_ws_carve(workspace, B, T, Lmax);
+  int* lab = ws.lab; int* lablen = ws.lablen;
+  float* lse = ws.lse; float* lp = ws.lp; float* alpha = ws.alpha; float* beta = ws.beta;
+  const int Lm = ws.Lm;
 
   hipLaunchKernelGGL(ctc_prep_kernel, dim3(B), dim3(64), 0, s, (const long long*)ys_pad, Lmax, ignore_id, lab, lablen, B);
   EAMD_LAUNCH_CHECK();
@@ -325,6 +343,25 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
                        (long)gstride_b, T, V, Smax, blank, grad_scale, 0L, 0L, 1, nullptr);
     EAMD_LAUNCH_CHECK();
   }
+  return EAMD_OK;
+}
+
+
+/* gradient pass alone, from the workspace a previous eamd_ctc_loss call (grad = NULL) on the same acts / ilens filled:
+ * lets the caller run it in backward and fold the upstream scalar, read from device memory, into the one pass */
+int eamd_ctc_grad(const float* acts, int64_t stride_t, int64_t stride_b, const int32_t* ilens, const float* nll, float* grad,
+                  int64_t gstride_t, int64_t gstride_b, const void* workspace, int B, int T, int V, int Lmax, int blank,
+                  float grad_scale, const float* gscale_dev, void* stream) {
+  if (!acts || !ilens || !nll || !grad || !workspace || B <= 0 || T <= 0 || V <= 0 || Lmax < 0) return EAMD_EINVAL;
+  const int Smax = 2 * Lmax + 1;
+  if (((Smax + 63) / 64) * 64 > 1024) return EAMD_EUNSUPPORTED;
+  if ((size_t)V * 4 > 64 * 1024) return EAMD_EUNSUPPORTED;
+  const CtcWs ws = ctc_ws_carve((void*)workspace, B, T, Lmax);
+  hipLaunchKernelGGL(ctc_grad_kernel<false>, dim3(T, B), dim3(256), (size_t)V * sizeof(float), (hipStream_t)stream, acts,
+                     (long)stride_t, (long)stride_b, ilens, ws.lab, ws.lablen, ws.Lm, ws.lse, ws.lp, ws.alpha, ws.beta, nll, grad,
+                     (long)gstride_t, (long)gstride_b, T, V, Smax, blank, grad_scale, 0L, 0L, 1, (const long long*)nullptr,
+                     gscale_dev);
+  EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
 

@@ -377,10 +377,12 @@ int eamd_gemm_bf16_dispatch(const eamd_gemm_t& p, int tile, hipStream_t stream);
 int eamd_gemm_f32_dispatch(const eamd_gemm_t& p, int tile, hipStream_t stream);   // gemm_f32.hip
 
 // argument validation and tile choice shared by eamd_gemm and eamd_gemm_multi (normalises p.splitk)
-static int gemm_check(eamd_gemm_t& p, int& tile_out) {
+// no_c: the caller's kernel stores no result (eamd_conv2_bwd_x_conv1_bwd_w), C may be NULL
+static int gemm_check(eamd_gemm_t& p, int& tile_out, const bool no_c = false) {
   const bool stats = p.epilogue == 7;          // row statistics instead of a result (eamd_gemm_t.stats)
+  const bool no_result = stats || no_c;
   const bool rowgrad = p.epilogue == 8;        // softmax-gradient rows from per-row coefficients
-  if (!p.A || !p.B || (!p.C && !p.Cb && !stats)) return EAMD_EINVAL;
+  if (!p.A || !p.B || (!p.C && !p.Cb && !no_result)) return EAMD_EINVAL;
   if (stats && (!p.stats.part || !p.stats.zfix || (p.stats.col && !p.stats.zcol))) return EAMD_EINVAL;
   if (rowgrad && !p.stats.rowc) return EAMD_EINVAL;
   if ((stats || rowgrad) && (p.stats.fix < 0 || p.stats.fix >= p.N || (p.tile != 64 && p.tile != 128) || p.splitk > 1 ||
@@ -389,7 +391,7 @@ static int gemm_check(eamd_gemm_t& p, int& tile_out) {
     return EAMD_EINVAL;
   if (p.in_dtype != 0 && p.in_dtype != 1) return EAMD_EINVAL;
   if (p.in_dtype == 1 && p.precision != 1) return EAMD_EINVAL;
-  if (p.in_dtype == 0 && (p.Cb || p.aux_dtype || (!p.C && !stats))) return EAMD_EUNSUPPORTED;
+  if (p.in_dtype == 0 && (p.Cb || p.aux_dtype || (!p.C && !no_result))) return EAMD_EUNSUPPORTED;
   if (p.M <= 0 || p.N <= 0 || p.K < 0) return EAMD_EINVAL;
   if (p.batch1 <= 0 || p.batch2 <= 0) return EAMD_EINVAL;
   if (p.splitk < 1) p.splitk = 1;
@@ -434,6 +436,10 @@ static int gemm_check(eamd_gemm_t& p, int& tile_out) {
       if (g.C % tile != 0) return EAMD_EINVAL;            // an M-tile must stay inside one tap
     }
   }
+  // colsum with a gather = column sums of B (eamd_gemm_t.colsum): the pipelined fp32 kernel's gathered weight gradient only
+  if (p.colsum && p.gather.enabled &&
+      (!p.transA || !p.transB || p.in_dtype != 0 || p.batch1 * p.batch2 != 1 || p.a_act != EAMD_ACT_NONE || p.b_act != EAMD_ACT_NONE))
+    return EAMD_EUNSUPPORTED;
   if ((p.N + tile - 1) / tile > 65535) return EAMD_EUNSUPPORTED;
   // fused dropout: the bf16-operand kernels (incl. the dual bf16 output Hb) and, for a plain dropped result, the
   // pipelined fp32 kernel (same epilogue code)
@@ -469,10 +475,11 @@ extern "C" int eamd_gemm(const eamd_gemm_t* pp, void* stream_) {
   if (p.precision == 0) {     // reference precision: the pipelined fp32-MFMA kernel wherever its staging conditions hold
     const int rc = eamd_gemm_f32_dispatch(p, tile, stream);
     if (rc != EAMD_EUNSUPPORTED) return rc;
-    // generic kernel: no dropout, staged relu / swish only
+    // generic kernel: no dropout, staged relu / swish only, no column sums of B
     if (p.drop_p != 0.f || p.Hb || p.a_act > EAMD_ACT_SWISH || p.b_act > EAMD_ACT_SWISH) return EAMD_EUNSUPPORTED;
   }
   if (stats || rowgrad) return EAMD_EUNSUPPORTED;       // the generic kernel has neither row epilogue
+  if (p.colsum && p.gather.enabled) return EAMD_EUNSUPPORTED;      // ... nor the column sums of B
   if (tile == 128) {
     return p.precision ? launch<128, 128, 1>(p, stream) : launch<128, 128, 0>(p, stream);
   }
@@ -503,6 +510,26 @@ extern "C" int eamd_gemm_multi(const eamd_gemm_t* descs, int n, void* stream) {
     if (rc != EAMD_OK) return rc;
   }
   return EAMD_OK;
+}
+
+int eamd_gemm_f32_conv1w(const eamd_gemm_t* ps, const int* tiles, int n, const float* x, int T, int F, float* part, int* nslab,
+                         hipStream_t stream);                                                    // gemm_f32.hip
+int eamd_conv1_bwd_w_reduce(const float* part, int nslab, int C, float* dw, float* db, hipStream_t stream);   // convmod.hip
+
+extern "C" int eamd_conv2_bwd_x_conv1_bwd_w(const eamd_gemm_t* descs, int n, const float* x, int T, int F, float* part,
+                                            float* dw, float* db, void* stream) {
+  if (!descs || n < 1 || n > EAMD_GEMM_MULTI_MAX || !x || !part || !dw || !db || T < 3 || F < 3) return EAMD_EINVAL;
+  eamd_gemm_t ps[EAMD_GEMM_MULTI_MAX];
+  int tiles[EAMD_GEMM_MULTI_MAX];
+  for (int i = 0; i < n; ++i) {
+    ps[i] = descs[i];
+    const int chk = gemm_check(ps[i], tiles[i], true);
+    if (chk != EAMD_OK) return chk;                // nothing has been launched yet
+  }
+  int nslab = 0;
+  const int rc = eamd_gemm_f32_conv1w(ps, tiles, n, x, T, F, part, &nslab, (hipStream_t)stream);
+  if (rc != EAMD_OK) return rc;
+  return eamd_conv1_bwd_w_reduce(part, nslab, ps[0].N, dw, db, (hipStream_t)stream);
 }
 
 int eamd_gemm_f32_group_count(const eamd_gemm_t& p);                                            // gemm_f32.hip

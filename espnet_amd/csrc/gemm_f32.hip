@@ -61,10 +61,116 @@ __device__ __forceinline__ float4 mask4(float4 v, int nv) {
   return make_float4(nv > 0 ? v.x : 0.f, nv > 1 ? v.y : 0.f, nv > 2 ? v.z : 0.f, nv > 3 ? v.w : 0.f);
 }
 
+// Operands of the fused conv1 weight-gradient epilogue (eamd_conv2_bwd_x_conv1_bwd_w): the result tile of the second
+// convolution's input gradient is reduced against the first convolution's input patches instead of being stored.
+struct Conv1W {
+  const float* x;                       // [B, T, F] input of the first convolution (3x3, stride 2, no padding)
+  float* part;                          // [slab][10][C] partial sums (k-major: 9 taps, then the bias), one slab per row tile
+  int T, F;
+  int slab0[EAMD_GEMM_MULTI_MAX];       // first slab of every problem of the launch
+};
+
+// The tile epilogue of that launch.  acc -> LDS as in store_c_tile; g = acc * (aux > 0) is the value epilogue 3 would have
+// stored as the gradient of conv1's output at the tile's 128 positions x 128 channels; the workgroup leaves
+// sum_rows g (bias) and sum_rows g * x[b, 2 hi + kh, 2 wi + kw] (9 taps) per channel in its own slab: no atomics, fixed order.
+// `patch`: 128 x 9 floats + 128 ints of LDS behind the staging tile.
+__device__ __forceinline__ void conv1w_tile(const eamd_gemm_t& p, f32x4 (&acc)[4][4], float* cl, float* patch, int m0, int n0,
+                                            const Conv1W& cw, int slab) {
+  constexpr int BM = 128, BN = 128, WM = 64, WN = 64, MT = 4, NTL = 4, LDC = BN + 4;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int fr = lane & 15, fq = lane >> 4;
+  int* rowp = reinterpret_cast<int*>(patch + BM * 9);      // physical row (b, hi, wi) of every tile row, -1 past M
+  // thread r < 128: position of tile row r and its 9 input values (requested here, stored behind the accumulators)
+  float xv[9];
+  int prow = -1;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) xv[k] = 0.f;
+  if (t < BM && m0 + t < p.M) {
+    const int m = m0 + t;
+    const eamd_rowmap_t& c = p.cmap;
+    const int jj = m % c.Wo, tt = m / c.Wo, ii = tt % c.Ho, bb = tt / c.Ho;
+    const int hi = ii * c.sh + c.oh, wi = jj * c.sw + c.ow;
+    prow = (bb * c.Hc + hi) * c.Wc + wi;
+    const float* xp = cw.x + ((long)bb * cw.T + 2 * hi) * cw.F + 2 * wi;      // stride 2, no padding: all 9 in range
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) xv[kh * 3 + kw] = xp[kh * cw.F + kw];
+  }
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NTL; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        cl[(wm * WM + i * 16 + fq * 4 + r) * LDC + wn * WN + j * 16 + fr] = acc[i][j][r];
+  if (t < BM) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) patch[t * 9 + k] = xv[k];
+    rowp[t] = prow;
+  }
+  __syncthreads();
+
+  // a thread owns 4 channels and the rows t / 32 + 8 i (the layout of store_c_tile's row passes, aux requested 4 passes ahead)
+  const int c4 = t & 31, r0 = t >> 5;
+  const int n = n0 + c4 * 4;
+  float db[4] = {0.f, 0.f, 0.f, 0.f}, dw[4][9];
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dw[e][k] = 0.f;
+#pragma unroll 1
+  for (int g0 = 0; g0 < BM / 8; g0 += 4) {
+    float4 a32[4];
+    int pr[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      pr[q] = rowp[r0 + (g0 + q) * 8];
+      a32[q] = *reinterpret_cast<const float4*>(p.aux + (long)max(pr[q], 0) * p.ldaux + n);      // row 0 for rows past M: legal
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int rr = r0 + (g0 + q) * 8;
+      const float4 a4 = *reinterpret_cast<const float4*>(&cl[rr * LDC + c4 * 4]);
+      const bool ok = pr[q] >= 0;
+      const float g[4] = {ok && a32[q].x > 0.f ? a4.x : 0.f, ok && a32[q].y > 0.f ? a4.y : 0.f,
+                          ok && a32[q].z > 0.f ? a4.z : 0.f, ok && a32[q].w > 0.f ? a4.w : 0.f};
+      float xr[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) xr[k] = patch[rr * 9 + k];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        db[e] += g[e];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dw[e][k] += g[e] * xr[k];
+      }
+    }
+  }
+  __syncthreads();          // the staging tile has been consumed: it now takes the 8 row groups' sums, [group][10][BN]
+  float* red = cl;
+#pragma unroll
+  for (int k = 0; k < 9; ++k)
+    *reinterpret_cast<float4*>(&red[(r0 * 10 + k) * BN + c4 * 4]) = make_float4(dw[0][k], dw[1][k], dw[2][k], dw[3][k]);
+  *reinterpret_cast<float4*>(&red[(r0 * 10 + 9) * BN + c4 * 4]) = make_float4(db[0], db[1], db[2], db[3]);
+  __syncthreads();
+  float* out = cw.part + (long)slab * 10 * p.N + n0;
+  for (int idx = t; idx < 10 * BN; idx += NT_) {
+    float v = 0.f;
+#pragma unroll
+    for (int g = 0; g < NT_ / 32; ++g) v += red[g * 10 * BN + idx];
+    out[(long)(idx / BN) * p.N + (idx % BN)] = v;
+  }
+}
+
 // One workgroup's share of a problem: `bid` of `nblk` workgroups (tile x split-K slice), batch index `zb`.
 // gemm_f32_kernel runs it on a launch of its own; gemm_f32_group_kernel looks the problem up in a device table.
-template <int BM, int BN, bool TA, bool TB, bool GAT, int ACT, bool ROWEPI = false, bool NOPAD = false>
-__device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bid, const int nblk, const int zb) {
+// C1W: the tile ends in conv1w_tile instead of a store (its own instantiation, like ROWEPI: the ordinary epilogues do not
+// pay for it).
+template <int BM, int BN, bool TA, bool TB, bool GAT, int ACT, bool ROWEPI = false, bool NOPAD = false, bool C1W = false>
+__device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bid, const int nblk, const int zb,
+                                              const Conv1W* cw = nullptr, const int slab0 = 0) {
   constexpr int WM = BM / 2, WN = BN / 2;
   constexpr int MT = WM / 16, NTL = WN / 16;
   constexpr int NCA = BM / 32, NCB = BN / 32;           // 16-byte chunks per thread per tile
@@ -188,6 +294,9 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
   constexpr int UNROLL = DEPTH % 2 ? 2 * DEPTH : DEPTH;
   float4 ra[DEPTH][NCA], rb[DEPTH][NCB];
   const bool do_colsum = TA && p.colsum != nullptr && !GAT && tile_n == 0;
+  // gathered weight gradient (dW = col^T dY): colsum means the column sums of the B operand, the bias gradient sum_k dY[k, :]
+  // (eamd_gemm_t.colsum); the workgroups of the first row of tiles sum the B chunks they stage over their K-slice
+  const bool do_bsum = TA && TB && GAT && p.colsum != nullptr && tile_m == 0;
   float cs[4] = {0.f, 0.f, 0.f, 0.f};
 
   const int gWo = GAT ? p.gather.Wo : 1, gHo = GAT ? p.gather.Ho : 1, gsh = GAT ? p.gather.sh : 0, gsw = GAT ? p.gather.sw : 0;
@@ -320,6 +429,16 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
       for (int i = 0; i < NCA; ++i) *reinterpret_cast<float4*>(&la[a_r[i] * S::LDA + a_c[i] * 4]) = ra[SET][i];
 #pragma unroll
       for (int i = 0; i < NCB; ++i) *reinterpret_cast<float4*>(&lb[b_r[i] * S::LDB + b_c[i] * 4]) = rb[SET][i];
+      if constexpr (TA && TB && GAT) {
+        // behind the LDS stores: in front of them (a use of the B chunks ahead of the A stores) the launch was 31 us
+        // slower at config 2 (1572 -> 1604 us, all workgroups), here it is not (1561 -> 1554 us)
+        if (do_bsum) {        // a thread's B chunks are k-rows of its 4 fixed columns; rows past K were zeroed above
+#pragma unroll
+          for (int i = 0; i < NCB; ++i) {
+            cs[0] += rb[SET][i].x; cs[1] += rb[SET][i].y; cs[2] += rb[SET][i].z; cs[3] += rb[SET][i].w;
+          }
+        }
+      }
     }
   };
 
@@ -504,8 +623,35 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
     }
     __syncthreads();
   }
+  if constexpr (TA && TB && GAT) {
+    if (p.colsum != nullptr) {   // block-uniform; same reduction as above over the B image's k-row groups
+      float* csl = sm.ab;
+      constexpr int NSLOT = NT_ / CPR_B;
+      static_assert(NSLOT * BN <= S::OPS, "column-sum slots must fit in the operand buffers");
+      if (do_bsum) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) csl[(t / CPR_B) * BN + b_c[0] * 4 + j] = cs[j];
+      }
+      __syncthreads();
+      if (do_bsum) {
+        for (int i = t; i < BN; i += NT_) {
+          const int n = n0 + i;
+          float v = 0.f;
+#pragma unroll 8
+          for (int sl = 0; sl < NSLOT; ++sl) v += csl[sl * BN + i];
+          if (n < p.N) atomicAdd(p.colsum + n, v * p.alpha);
+        }
+      }
+      __syncthreads();
+    }
+  }
 
   // ---- epilogue ----
+  if constexpr (C1W) {
+    static_assert(BM == 128 && BN == 128 && !TA && !ROWEPI, "the conv1 weight-gradient epilogue is written for the 128 tile");
+    conv1w_tile(p, acc, sm.ab, reinterpret_cast<float*>(smem_raw + sizeof(S)), m0, n0, *cw, slab0 + tile_m);
+    return;
+  }
   if (p.splitk > 1) {
     const bool lead = split == 0;
 #pragma unroll
@@ -579,6 +725,19 @@ __global__ __launch_bounds__(NT_, 2) void gemm_f32_multi_kernel(const MultiF m) 
   const eamd_gemm_t p = m.p[cls];          // wave-uniform copy: scalar loads up front, none inside the tile
   gemm_f32_body<BM, BN, TA, TB, GAT, false, false, NOPAD>(p, bid, m.nt[cls], 0);
 }
+
+// eamd_conv2_bwd_x_conv1_bwd_w: the same grid, every tile reduced by conv1w_tile
+template <bool NOPAD>
+__global__ __launch_bounds__(NT_, 2) void gemm_f32_multi_c1w_kernel(const MultiF m, const Conv1W cw) {
+  const int g = (int)blockIdx.x >> 3;
+  const int per = (int)gridDim.x / (8 * m.n);
+  const int cls = g / per;
+  const int bid = (g - cls * per) * 8 + ((int)blockIdx.x & 7);
+  if (bid >= m.nt[cls]) return;
+  const eamd_gemm_t p = m.p[cls];
+  gemm_f32_body<128, 128, false, true, true, 0, false, NOPAD, true>(p, bid, m.nt[cls], 0, &cw, cw.slab0[cls]);
+}
+constexpr size_t C1W_SMEM = sizeof(SmemF<128, 128, false, true>) + (128 * 9 + 128) * sizeof(float);
 
 template <int BM, int BN, bool TA, bool TB, bool GAT, int ACT, bool NOPAD = false>
 int launch_f2(const eamd_gemm_t& p, hipStream_t stream) {
@@ -711,6 +870,63 @@ int eamd_gemm_f32_multi(const eamd_gemm_t* ps, const int* tiles, int n, hipStrea
   m.n = n;
   const int grid = (maxnt + 7) / 8 * 8 * n;
   return nopad ? multi_launch_t<true>(m, grid, stream) : multi_launch_t<false>(m, grid, stream);
+}
+
+// ---- conv2 input gradient reduced to conv1's weight / bias gradient (eamd_conv2_bwd_x_conv1_bwd_w) ----
+// ps[i] have passed eamd_gemm's argument validation (C may be NULL); everything else the kernel relies on is checked here,
+// before the launch.  *nslab receives the number of [10][C] slabs written to part.
+template <bool NOPAD>
+static int c1w_launch_t(const MultiF& m, const Conv1W& cw, int grid, hipStream_t stream) {
+  static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_multi_c1w_kernel<NOPAD>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)C1W_SMEM);
+  if (attr_err != hipSuccess) return (int)attr_err;
+  hipLaunchKernelGGL(gemm_f32_multi_c1w_kernel<NOPAD>, dim3((unsigned)grid), dim3(NT_), C1W_SMEM, stream, m, cw);
+  EAMD_LAUNCH_CHECK();
+  return EAMD_OK;
+}
+
+int eamd_gemm_f32_conv1w(const eamd_gemm_t* ps, const int* tiles, int n, const float* x, int T, int F, float* part, int* nslab,
+                         hipStream_t stream) {
+  if (n < 1 || n > EAMD_GEMM_MULTI_MAX) return EAMD_EUNSUPPORTED;
+  MultiF m;
+  Conv1W cw;
+  cw.x = x; cw.part = part; cw.T = T; cw.F = F;
+  const int H1 = (T - 3) / 2 + 1, W1 = (F - 3) / 2 + 1;
+  int maxnt = 0;
+  bool nopad = true;
+  long slabs = 0, nimg = -1;
+  for (int i = 0; i < n; ++i) {
+    const eamd_gemm_t& p = ps[i];
+    if (tiles[i] != 128 || p.in_dtype != 0 || p.precision != 0) return EAMD_EUNSUPPORTED;
+    if (!p.gather.enabled || p.transA || !p.transB || p.splitk != 1 || p.batch1 * p.batch2 != 1) return EAMD_EUNSUPPORTED;
+    if (p.Cb || p.Hb || p.aux_dtype || p.epilogue != 3 || !p.aux || p.colsum || p.bias || p.R) return EAMD_EUNSUPPORTED;
+    if (p.a_act != EAMD_ACT_NONE || p.b_act != EAMD_ACT_NONE || p.drop_p != 0.f || p.alpha != 1.f || p.beta != 0.f)
+      return EAMD_EUNSUPPORTED;
+    const bool b_ok = aligned16f(p.B) && p.ldb % 4 == 0 && p.ldb >= (p.N + 3) / 4 * 4;
+    if (p.gather.C % FBK != 0 || !aligned16f(p.A) || !b_ok || !gather_taps_small(p.gather)) return EAMD_EUNSUPPORTED;
+    nopad = nopad && gather_nopad(p.gather);
+    if (p.N % 128 != 0 || p.N != ps[0].N || !aligned16f(p.aux) || p.ldaux % 4 != 0 || p.ldaux < p.N) return EAMD_EUNSUPPORTED;
+    // the rows are positions of conv1's output [B, H1, W1]: one stride-parity class of them
+    const eamd_rowmap_t& c = p.cmap;
+    if (!c.enabled || c.Hc != H1 || c.Wc != W1 || c.Ho < 1 || c.Wo < 1 || c.sh < 1 || c.sw < 1 || c.oh < 0 || c.ow < 0 ||
+        (long)(c.Ho - 1) * c.sh + c.oh >= H1 || (long)(c.Wo - 1) * c.sw + c.ow >= W1 || p.M % (c.Ho * c.Wo) != 0)
+      return EAMD_EUNSUPPORTED;
+    const long b = p.M / (c.Ho * c.Wo);
+    if ((nimg >= 0 && b != nimg) || b * H1 * W1 >= (1L << 31)) return EAMD_EUNSUPPORTED;
+    nimg = b;
+    const long rt = (p.M + 127) / 128, nt = rt * (p.N / 128);
+    if (nt > (1L << 24)) return EAMD_EUNSUPPORTED;
+    m.p[i] = p;
+    m.nt[i] = (int)nt;
+    cw.slab0[i] = (int)slabs;
+    slabs += rt;
+    maxnt = nt > maxnt ? (int)nt : maxnt;
+  }
+  for (int i = n; i < EAMD_GEMM_MULTI_MAX; ++i) { m.p[i] = ps[0]; m.nt[i] = 0; cw.slab0[i] = 0; }
+  m.n = n;
+  *nslab = (int)slabs;
+  const int grid = (maxnt + 7) / 8 * 8 * n;
+  return nopad ? c1w_launch_t<true>(m, cw, grid, stream) : c1w_launch_t<false>(m, cw, grid, stream);
 }
 
 // ---- grouped weight-gradient launch (fp32 operands) ----

@@ -1125,12 +1125,17 @@ def _conv3s2_fwd(y_in, w, b, B, Hi, Wi, Cc, adt):
     return y, wd, Ho, Wo
 
 
-def _conv3s2_bwd(dy, y_in, wd, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc, adt):
-    """dy [B*Ho*Wo, Cc] (already multiplied by this stage's ReLU mask) -> gradient w.r.t. y_in, multiplied by the ReLU
-    mask of y_in in the epilogue; weight / bias gradients are accumulated into dw_buf / db_buf"""
+FUSE_CONV1_WGRAD = True   # tests flip this to reach the stored input gradient + ops.conv1_bwd_w
+
+
+def _conv3s2_bwd_w(dy, y_in, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc):
+    """weight / bias gradient of a 3x3 stride-2 stage, accumulated into dw_buf / db_buf"""
     dev = dy.device
     M = B * Ho * Wo
-    ops.colsum(dy, db_buf)
+    # fp32 operands: the bias gradient (column sums of dy) comes out of the weight-gradient GEMM, which stages dy anyway
+    bsum = not ops.fast() and dy.dtype == torch.float32 and y_in.dtype == torch.float32
+    if not bsum:
+        ops.colsum(dy, db_buf)
     # weight gradient: dwf[(tap, ci), co] = sum_pos col[pos, (tap, ci)] * dy[pos, co]
     dwf = torch.zeros(9 * Cc, Cc, device=dev, dtype=torch.float32)
     g = ops.make_gather(Cc, _TAPS_FWD, Ho, Wo, Hi, Wi, 2, 2)
@@ -1142,11 +1147,14 @@ def _conv3s2_bwd(dy, y_in, wd, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc, adt):
     ntile = (9 * Cc // tile) * ((Cc + tile - 1) // tile)
     want = 1024 if ops.fast() else 1008 if f32_big else 2304
     sk = max(2, min(64, (want + ntile - 1) // ntile, max(1, M // 256)))
-    ops.gemm(y_in, dy, dwf, 9 * Cc, Cc, M, 9 * Cc, Cc, Cc, transA=1, transB=1, gather=g, splitk=sk, tile=tile)
+    ops.gemm(y_in, dy, dwf, 9 * Cc, Cc, M, 9 * Cc, Cc, Cc, transA=1, transB=1, gather=g, splitk=sk, tile=tile,
+             colsum=db_buf if bsum else None)
     ops.conv2_weight_grad(dwf, dw_buf, Cc, Cc)
-    # input gradient, one implicit GEMM per stride-parity class; the classes write disjoint rows of dy_in and leave together
-    # (ops.gemm_multi: one launch in fp32 mode)
-    dy_in = torch.empty(y_in.shape, device=dev, dtype=adt)
+
+
+def _conv3s2_dx_classes(dy, y_in, wd, dy_in, B, Hi, Wi, Ho, Wo, Cc, tile=0):
+    """the input gradient as one implicit GEMM per stride-parity class (deferred descriptors); the classes cover disjoint
+    rows of dy_in (None: the caller's kernel stores no result)"""
     q0, classes = 0, []
     for (ph, pw), taps in _CLASSES:
         Hc, Wc = (Hi - ph + 1) // 2, (Wi - pw + 1) // 2
@@ -1155,10 +1163,34 @@ def _conv3s2_bwd(dy, y_in, wd, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc, adt):
             cm = ops.make_rowmap(Hc, Wc, Hi, Wi, 2, ph, 2, pw)
             nt = len(taps)
             ops.gemm(dy, wd, dy_in, B * Hc * Wc, Cc, nt * Cc, nt * Cc, Cc, Cc, transB=1, b_off=q0 * Cc * Cc,
-                     gather=gt, cmap=cm, epilogue=EPI_MUL_RELU_MASK, aux=y_in, ldaux=Cc, defer=classes)
+                     gather=gt, cmap=cm, epilogue=EPI_MUL_RELU_MASK, aux=y_in, ldaux=Cc, defer=classes, tile=tile)
         q0 += len(taps)
-    ops.gemm_multi(classes)
+    return classes
+
+
+def _conv3s2_bwd(dy, y_in, wd, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc, adt):
+    """dy [B*Ho*Wo, Cc] (already multiplied by this stage's ReLU mask) -> gradient w.r.t. y_in, multiplied by the ReLU
+    mask of y_in in the epilogue; weight / bias gradients are accumulated into dw_buf / db_buf"""
+    _conv3s2_bwd_w(dy, y_in, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc)
+    # the classes write disjoint rows of dy_in and leave together (ops.gemm_multi: one launch in fp32 mode)
+    dy_in = torch.empty(y_in.shape, device=dy.device, dtype=adt)
+    ops.gemm_multi(_conv3s2_dx_classes(dy, y_in, wd, dy_in, B, Hi, Wi, Ho, Wo, Cc))
     return dy_in
+
+
+def _conv1w_fusable(y_in, Cc):
+    """the first C -> C stage's input gradient has one reader, conv1's weight gradient, and conv1's input has no gradient: in
+    fp32 mode with 128-channel tiles it is reduced inside the kernel that computes it"""
+    return FUSE_CONV1_WGRAD and not ops.fast() and y_in.dtype == torch.float32 and Cc % 128 == 0
+
+
+def _conv3s2_bwd_conv1w(dy, y_in, wd, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc, x, dw1_buf, db1_buf):
+    """_conv3s2_bwd for the stage behind conv1 (y_in = conv1's output, x [B, T, F] its input): this stage's weight / bias
+    gradients as there; its input gradient is never stored - the launch that computes it leaves conv1's weight / bias
+    gradient, accumulated into dw1_buf / db1_buf (ops.conv2_bwd_x_conv1_bwd_w)"""
+    _conv3s2_bwd_w(dy, y_in, dw_buf, db_buf, B, Hi, Wi, Ho, Wo, Cc)
+    # (the 128 x 128 tile, which the library picks for this product on its own from about 240 tiles on, at every size)
+    ops.conv2_bwd_x_conv1_bwd_w(_conv3s2_dx_classes(dy, y_in, wd, None, B, Hi, Wi, Ho, Wo, Cc, tile=128), x, dw1_buf, db1_buf)
 
 
 def _taps(k):
@@ -1285,6 +1317,10 @@ class Conv2dSubsamplingFn(torch.autograd.Function):
         dy = dy.view(B * Hl * Wl, Cc)
         for i in range(n - 1, -1, -1):
             (Hi, Wi), (Ho, Wo) = dims[i], dims[i + 1]
+            if i == 0 and ctx.ks[i] == 3 and _conv1w_fusable(ys[0], Cc):
+                _conv3s2_bwd_conv1w(dy, ys[0].view(-1, Cc), wds[0], sink.buf(4), sink.buf(5), B, Hi, Wi, Ho, Wo, Cc, x,
+                                    sink.buf(0), sink.buf(1))
+                return (None, None) + sink.results()
             if ctx.ks[i] == 3:
                 dy = _conv3s2_bwd(dy, ys[i].view(-1, Cc), wds[i], sink.buf(4 + 2 * i), sink.buf(5 + 2 * i), B, Hi, Wi, Ho,
                                   Wo, Cc, adt)
@@ -1359,7 +1395,8 @@ class ScaledPosEncFn(torch.autograd.Function):
 
 # =================================================================================================
 # Losses: gradients are produced by the forward kernels; backward only rescales by the upstream
-# scalar, read on the device (no host synchronisation).
+# scalar, read on the device (no host synchronisation).  CTCLossFn's gradient kernel runs in backward
+# instead and multiplies by that scalar itself.
 # =================================================================================================
 class CTCLossFn(torch.autograd.Function):
     """sum_b -log p(y_b | x_b) / B on raw activations [B, T, V].
@@ -1369,16 +1406,22 @@ class CTCLossFn(torch.autograd.Function):
     def forward(ctx, acts, ys_pad, hlens, blank, ignore_id, time_major=False):
         """time_major: acts is (T, B, V) as warp-ctc takes it; read in place (strides), no transposed copy"""
         B = acts.shape[1] if time_major else acts.shape[0]
-        nll, grad = ops.ctc_loss(acts.contiguous(), ys_pad, hlens, blank, ignore_id, 1.0 / B,
-                                 want_grad=acts.requires_grad, time_major=time_major)
-        ctx.save_for_backward(grad)
+        acts = acts.contiguous()
+        # the lattice kernels only: the gradient kernel runs in backward on the kept workspace, where it takes the upstream
+        # scalar from device memory (one pass over [B, T, V] instead of a gradient pass here and a rescaling pass there)
+        nll, _, ws = ops.ctc_loss(acts, ys_pad, hlens, blank, ignore_id, 1.0 / B, want_grad=False, time_major=time_major,
+                                  keep_workspace=True)
+        ctx.save_for_backward(acts, nll, hlens, ws)
         ctx.nll = nll
+        ctx.cfg = (ys_pad.shape[1], blank, 1.0 / B, time_major)
         return ops.reduce_sum(nll, 1.0 / B)
 
     @staticmethod
     def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return ops.scale_dev(grad, g.contiguous(), 1.0, out=grad), None, None, None, None, None
+        acts, nll, hlens, ws = ctx.saved_tensors
+        L, blank, scale, time_major = ctx.cfg
+        grad = ops.ctc_grad(acts, hlens, nll, ws, L, blank, scale, gscale=g.contiguous().view(1), time_major=time_major)
+        return grad, None, None, None, None, None
 
 
 class CTCRowsLossFn(torch.autograd.Function):

@@ -181,8 +181,11 @@ def gemm(A, B, Cm, M, N, K, lda, ldb, ldc, *, transA=0, transB=0, bias=None, aux
     p.aux_dtype = 1 if (aux is not None and aux.dtype == torch.bfloat16) else 0
     p.R = ptr(R, c_off) if R is not None else None
     if colsum is not None:
-        if not transA or gather is not None or colsum.numel() < M * b1 * b2:
-            raise _lib.EamdError("gemm: colsum needs transA, no gather and M outputs")
+        if gather is not None:       # gathered weight gradient: the column sums of B (eamd_gemm_t.colsum)
+            if not (transA and transB) or bf or (b1, b2) != (1, 1) or colsum.numel() < N:
+                raise _lib.EamdError("gemm: colsum with a gather needs transA, transB, float32 operands and N outputs")
+        elif not transA or colsum.numel() < M * b1 * b2:
+            raise _lib.EamdError("gemm: colsum needs transA and M outputs")
         p.colsum = ptr(colsum)
     p.M, p.N, p.K = M, N, K
     p.transA, p.transB = int(transA), int(transB)
@@ -266,6 +269,29 @@ def gemm_multi(items):
                                  (arr, [it[1] for it in part]),
                                  lambda sp, arr=arr, n=n: check(L.eamd_gemm_multi(arr, n, sp), "eamd_gemm_multi")))
         check(L.eamd_gemm_multi(arr, n, stream_ptr()), "eamd_gemm_multi")
+
+
+def conv2_bwd_x_conv1_bwd_w(items, x, dw, db):
+    """the stride-parity classes of Conv2dSubsampling's second-convolution input gradient (collected with
+    gemm(..., Cm=None, defer=items)) in one launch whose tiles are reduced to the FIRST convolution's weight / bias gradient
+    instead of being stored (eamd_conv2_bwd_x_conv1_bwd_w).  x [B, T, F]: conv1's input; dw [C, 9] / db [C]: accumulated into."""
+    L = _lib.lib()
+    n = len(items)
+    Bn, T, F = x.shape
+    H1, W1 = (T - 3) // 2 + 1, (F - 3) // 2 + 1
+    Cc = items[0][0].N
+    assert 1 <= n <= GEMM_MULTI_MAX and x.is_contiguous() and x.dtype == torch.float32
+    assert dw.dtype == torch.float32 and db.dtype == torch.float32 and dw.numel() >= 9 * Cc and db.numel() >= Cc
+    for p_, keep in items:            # rows of every class are (b, i, j) over the same B images; aux covers conv1's output
+        assert p_.M == Bn * p_.cmap.Ho * p_.cmap.Wo and keep[4] is not None and keep[4].numel() >= Bn * H1 * W1 * p_.ldaux
+    arr = (GemmT * n)(*[it[0] for it in items])
+    part = torch.empty(sum((it[0].M + 127) // 128 for it in items) * 10 * Cc, device=x.device, dtype=torch.float32)
+    args = (arr, n, ptr(x), T, F, ptr(part), ptr(dw), ptr(db))
+    if _gemm_record is not None:
+        _gemm_record.append((dict(kind="multi%d_c1w" % n, flop=sum(2.0 * it[0].M * it[0].N * it[0].K for it in items)),
+                             (arr, [it[1] for it in items], x, part, dw, db),
+                             lambda sp, args=args: check(L.eamd_conv2_bwd_x_conv1_bwd_w(*args, sp), "eamd_conv2_bwd_x_conv1_bwd_w")))
+    check(L.eamd_conv2_bwd_x_conv1_bwd_w(*args, stream_ptr()), "eamd_conv2_bwd_x_conv1_bwd_w")
 
 
 # ---- grouped weight-gradient launches ------------------------------------------------------------
@@ -2190,9 +2216,11 @@ def bf_apply_bwd(gy, x, out=None):
 
 
 # ---- CTC -----------------------------------------------------------------------------------------
-def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True, time_major=False):
+def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True, time_major=False,
+             keep_workspace=False):
     """acts [B,T,V] raw activations (time_major: [T,B,V], warp-ctc's layout - read in place through the entry point's
-    (stride_t, stride_b), the gradient comes back in the same layout); ys_pad [B,L] int64; ilens [B] int32 -> nll [B], grad"""
+    (stride_t, stride_b), the gradient comes back in the same layout); ys_pad [B,L] int64; ilens [B] int32 -> nll [B], grad.
+    keep_workspace: -> nll, grad, workspace (what ctc_grad needs to run the gradient pass later)"""
     if time_major:
         T, B, V = acts_btv.shape
         st, sb = B * V, V
@@ -2209,7 +2237,29 @@ def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, wan
     check(_lib.lib().eamd_ctc_loss(ptr(acts_btv), st, sb, ptr(ys_pad), ptr(ilens), ptr(nll),
                                    ptr(grad), st, sb, ptr(ws), B, T, V, L, blank, ignore_id,
                                    grad_scale, stream_ptr()), "eamd_ctc_loss")
+    if keep_workspace:
+        return nll, grad, ws
     return nll, grad
+
+
+def ctc_grad(acts_btv, ilens, nll, ws, L, blank=0, grad_scale=1.0, gscale=None, time_major=False):
+    """the gradient pass of ctc_loss alone, on the workspace `ws` and `nll` that ctc_loss(..., want_grad=False,
+    keep_workspace=True) returned for the same acts / ilens and labels of padded length L.  gscale: optional float32 device
+    scalar, multiplied in last: the result equals scale_dev(ctc_loss(...)[1], gscale), from one pass"""
+    if time_major:
+        T, B, V = acts_btv.shape
+        st, sb = B * V, V
+    else:
+        B, T, V = acts_btv.shape
+        st, sb = V, T * V
+    L_ = _lib.lib()
+    assert acts_btv.is_contiguous() and acts_btv.dtype == torch.float32 and ilens.dtype == torch.int32 and ilens.numel() == B
+    assert nll.dtype == torch.float32 and nll.numel() == B and ws.numel() >= L_.eamd_ctc_workspace_bytes(B, T, L)
+    assert gscale is None or (gscale.dtype == torch.float32 and gscale.numel() == 1)
+    grad = torch.empty_like(acts_btv)
+    check(L_.eamd_ctc_grad(ptr(acts_btv), st, sb, ptr(ilens), ptr(nll), ptr(grad), st, sb, ptr(ws), B, T, V, L, blank,
+                           grad_scale, ptr(gscale), stream_ptr()), "eamd_ctc_grad")
+    return grad
 
 
 def ctc_pit_loss(acts, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True):

@@ -46,7 +46,10 @@ int eamd_abi_version(void);
  *                staged (in_dtype 0) or already bf16 in memory (in_dtype 1, the fast path: 16-byte
  *                staging, BK = 64, ds_read_b64_tr_b16 for the k-strided operand layouts).
  * colsum (transA=1 only): the column sums of A are added there by the same launch, i.e. the bias
- * gradient dB = sum_m dY[m,:] comes for free with dW = dY^T X.
+ * gradient dB = sum_m dY[m,:] comes for free with dW = dY^T X.  With a gather (transA = transB = 1, fp32 operands: the
+ * implicit-convolution weight gradient dW = col^T dY, whose A operand is the gathered activation) colsum instead receives the
+ * column sums of B, colsum[n] += alpha * sum_k B[k,n]: the convolution's bias gradient.  Kernels without that sum refuse
+ * the combination (EAMD_EUNSUPPORTED).
  * Two-level batch (batch1 x batch2) with independent element strides for A/B/C(aux,R share C's).
  * Optional implicit-im2col view of A (`gather`) and strided row map for C (`cmap`) express the
  * Conv2dSubsampling convolutions and their input-gradient without materialising columns.
@@ -71,7 +74,8 @@ typedef struct {
 typedef struct {
   const float* A; const float* B; float* C;
   const float* bias; const float* aux; const float* R;
-  float* colsum;       /* optional, transA only: colsum[m] += alpha * sum_k A[k,m] (bias gradient) */
+  float* colsum;       /* optional, transA only: colsum[m] += alpha * sum_k A[k,m] (bias gradient); with a gather:
+                          colsum[n] += alpha * sum_k B[k,n], see above */
   int32_t M, N, K;
   int32_t transA, transB;
   int64_t lda, ldb, ldc, ldaux, ldr;
@@ -128,6 +132,21 @@ int eamd_gemm(const eamd_gemm_t* p, void* stream);
  * output); any other combination runs as n eamd_gemm calls in order.  Results are those of the separate calls, bit for bit. */
 #define EAMD_GEMM_MULTI_MAX 4
 int eamd_gemm_multi(const eamd_gemm_t* descs, int n, void* stream);
+
+/* The input gradient of Conv2dSubsampling's second convolution (the 1 - EAMD_GEMM_MULTI_MAX stride-parity classes that
+ * eamd_gemm_multi launches together, reference: the autograd of transformer/subsampling.py:28-35), reduced on the spot to the
+ * weight and bias gradient of the FIRST convolution Conv2d(1, C, 3, 2): that gradient's only other reader.  Every result tile,
+ * already multiplied by the ReLU mask (epilogue 3, aux = conv1's output), is contracted in the tile epilogue with the 9 input
+ * values x[b, 2 hi + kh, 2 wi + kw] of its rows; nothing is stored to C (C may be NULL).  x: [B, T, F] fp32, the first
+ * convolution's input; the descriptors' row maps (cmap) place the classes in its output [B, (T-3)/2+1, (F-3)/2+1, C].
+ * part: scratch of sum_i ceil(M_i / 128) * 10 * N floats (one [10][N] slab of partial sums per 128-row tile, written without
+ * atomics and added in a fixed order).  dw [N, 9] and db [N] are accumulated into, as by eamd_conv1_bwd_w.
+ * Every descriptor is validated as eamd_gemm validates it before anything is launched.  EAMD_EUNSUPPORTED for anything but
+ * fp32 operands, precision 0, the 128 x 128 tile with N % 128 == 0, gathered non-transposed A x W^T (padding taps of the
+ * gather read as zero, as in eamd_gemm), epilogue 3 with fp32 aux, alpha 1, beta 0, no bias / residual / colsum / dropout, splitk 1, batch 1, one batch size and
+ * row maps that stay inside conv1's output. */
+int eamd_conv2_bwd_x_conv1_bwd_w(const eamd_gemm_t* descs, int n, const float* x, int T, int F, float* part, float* dw,
+                                 float* db, void* stream);
 
 /* Grouped launch of independent weight-gradient GEMMs (the dW_i += alpha dY_i^T X_i of one backward pass - reference:
  * the autograd of every nn.Linear on the path, e.g. transformer/attention.py:30-33 - each too small to fill the chip on
@@ -610,8 +629,15 @@ int eamd_ctc_loss(const float* acts, int64_t stride_t, int64_t stride_b, const i
                   const int32_t* ilens, float* nll, float* grad, int64_t gstride_t, int64_t gstride_b,
                   void* workspace, int B, int T, int V, int Lmax, int blank, int ignore_id, float grad_scale,
                   void* stream);
+/* The gradient pass of eamd_ctc_loss alone, from the workspace a call with grad = NULL on the same acts, ilens, B, T, V, Lmax
+ * and blank left behind (lse, lp, alpha, beta, labels) and the nll it returned: a training step runs it in backward.
+ * gscale_dev: optional device scalar (the upstream gradient of the summed loss); the stored value is
+ * ((softmax - occupancy) * grad_scale) * gscale_dev[0], i.e. eamd_ctc_loss's gradient followed by eamd_scale_dev, in one pass. */
+int eamd_ctc_grad(const float* acts, int64_t stride_t, int64_t stride_b, const int32_t* ilens, const float* nll, float* grad,
+                  int64_t gstride_t, int64_t gstride_b, const void* workspace, int B, int T, int V, int Lmax, int blank,
+                  float grad_scale, const float* gscale_dev, void* stream);
 
-/* Permutation-invariant CTC of S = 2 or 3 speakers (PIT).  reference: e2e_asr_mix_transformer.py:116-135, e2e_asr_mix.py:48-108.
+/* Permutation-invariant CTC of S = 2 or 3 speakers (PIT). reference: e2e_asr_mix_transformer.py:116-135, e2e_asr_mix.py:48-108.
  * acts [S,B,T,V] fp32 raw activations (speaker-major, V contiguous); ys_pad [B,S,Lmax] int64 padded with ignore_id; ilens [B] int32
  * (shared by the speakers of an utterance).  nll_pair [B,S,S] = -log p of hypothesis i against reference j (+inf if infeasible);
  * perm [B,S] int64 = the reference assigned to hypothesis i by the permutation of least (sum_i (nll_pair[b,i,perm]/B))/S (the
