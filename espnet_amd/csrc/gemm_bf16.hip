@@ -564,7 +564,8 @@ int eamd_gemm_bf16_dispatch(const eamd_gemm_t& p, int tile, hipStream_t stream) 
   if (a_ok && b_ok && tile == 64) {
     constexpr int PERSIST_MIN_TILES = 512;
     const long ntiles = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-    if (ntiles >= PERSIST_MIN_TILES && ntiles < (1L << 30) && p.K % 256 == 0 && p.splitk == 1 &&
+    // K > 0: the persistent ring always requests the first three K-tiles of a tile (K = 0 has none to read)
+    if (ntiles >= PERSIST_MIN_TILES && ntiles < (1L << 30) && p.K > 0 && p.K % 256 == 0 && p.splitk == 1 &&
         p.batch1 * p.batch2 == 1 && !p.colsum && p.a_act == EAMD_ACT_NONE && p.b_act == EAMD_ACT_NONE && !p.cmap.enabled &&
         !p.transB && !p.aux && p.epilogue < 7) {   // measured: the k-strided-B (NN) launches do not gain, aux epilogues want the prefetch
       return eamd_gemm_bf16_persist(p, (int)ntiles, stream);

@@ -406,8 +406,8 @@ __device__ __forceinline__ void gemm_f32_body(const eamd_gemm_t& p, const int bi
 #pragma unroll
       for (int i = 0; i < NCA; ++i) {
         float4 v = ra[SET][i];
+        if (do_colsum) { cs[0] += v.x; cs[1] += v.y; cs[2] += v.z; cs[3] += v.w; }      // of A as stored (eamd_gemm_t.colsum)
         if (p.a_act != EAMD_ACT_NONE) v = act4<ACT>(v, p.a_act);
-        if (do_colsum) { cs[0] += v.x; cs[1] += v.y; cs[2] += v.z; cs[3] += v.w; }
         *reinterpret_cast<float4*>(&la[a_r[i] * S::LDA + a_c[i] * 4]) = v;
         __builtin_amdgcn_sched_barrier(0);
       }

@@ -46,7 +46,8 @@ int eamd_abi_version(void);
  *                staged (in_dtype 0) or already bf16 in memory (in_dtype 1, the fast path: 16-byte
  *                staging, BK = 64, ds_read_b64_tr_b16 for the k-strided operand layouts).
  * colsum (transA=1 only): the column sums of A are added there by the same launch, i.e. the bias
- * gradient dB = sum_m dY[m,:] comes for free with dW = dY^T X.  With a gather (transA = transB = 1, fp32 operands: the
+ * gradient dB = sum_m dY[m,:] comes for free with dW = dY^T X; the sums are of A as stored, before a_act, on every
+ * kernel.  With a gather (transA = transB = 1, fp32 operands: the
  * implicit-convolution weight gradient dW = col^T dY, whose A operand is the gathered activation) colsum instead receives the
  * column sums of B, colsum[n] += alpha * sum_k B[k,n]: the convolution's bias gradient.  Kernels without that sum refuse
  * the combination (EAMD_EUNSUPPORTED).
