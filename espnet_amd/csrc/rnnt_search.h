@@ -1,4 +1,4 @@
-// Shared by the batched transducer search kernels (rnnt_alsd.hip, rnnt_tsd.hip).
+// Shared by the batched transducer search kernels (rnnt_alsd.hip, rnnt_tsd.hip, rnnt_nsc.hip).
 #pragma once
 
 // numpy.logaddexp on doubles (npy_logaddexp)

@@ -30,7 +30,11 @@ computed is this package's own design:
     loop and one at the end;
   * batched tsd (`tsd_batch`): the tsd search of all utterances of a batch pass by pass in lock-step, hypotheses in M + 1 device
     blocks (B's two parities and the C of every pass), the A / C / B bookkeeping of a pass in one launch (eamd_rnnt_tsd_step), no
-    host read inside the pass loop and one at the end.
+    host read inside the pass loop and one at the end;
+  * batched nsc (`nsc_batch`): the nsc search of all utterances of a batch n-step by n-step in lock-step, hypotheses in N + 2 device
+    blocks (kept's two parities and the V of every n-step), prefix rescoring, S, substract and the selections of a call in one
+    launch (eamd_rnnt_nsc_step), the rescoring's pair terms from a device-side pair list, no host read inside the frame loop and
+    one at the end.
 
 Prediction networks take part through one of three protocols: `step(tokens, states)` (batched; DecoderRNNT),
 `batch_step(yseqs)` (DecoderTT: the reference's batch_score, whose outputs depend on the batch a prefix is first computed
@@ -976,3 +980,167 @@ class BeamSearchTransducer:
                         v.score += r[0]
             kept = sorted(S + V, key=lambda x: x.score, reverse=True)[:beam]
         return self._sort_nbest(kept)
+
+    # ---- batched nsc ----------------------------------------------------------------------------------------------------
+    # nsc takes nstep = N expansions per frame (and, when N > 1, one more pass for the blank term of the last V) whatever the
+    # hypotheses are, so the utterances of a batch advance in lock-step here too.  Hypotheses live in N + 2 blocks of R = n * W rows
+    # (W = min(beam_size, V)): block 0 and block N + 1 are the two parities of `kept`, block v is the V of n-step v - 1; the
+    # prediction network's h / c are stacked the same way, [(N + 2) R, .], and lin_dec's d with the history levels of the prefix
+    # rescoring as [N + 2][1 + prefix_alpha][R]: level a of a row is d of its labels without the last a.  One call (t, v) is
+    # joint_rows_d on the frame's encoder rows and the d rows of hyps' block - at v == 0 on all (1 + prefix_alpha) R rows of kept's
+    # block, so that the same eamd_transducer_expand_rows launch leaves the frame's pair terms by the device-side pair list the
+    # previous frame's last call wrote -, eamd_rnnt_nsc_step (prefix rescoring, S, substract and the selection of V or of the next
+    # kept: one workgroup per utterance, it leaves the parent block row, the token, the `live` mask and the history rows of every
+    # slot) and eamd_gather_rows by those rows: h / c into a staging copy, from which the masked _pred_step writes the next block,
+    # and the history levels; at the end of a frame with N > 1 h / c / d / history into kept's other parity; at every frame's end the
+    # next frame's encoder rows.  The host loop only enqueues; the last kept of all utterances comes back in ONE copy and is sorted on
+    # the host as _sort_nbest sorts it.
+    nsc_max_rows = 256                # rows (utterances x W) per frame loop; larger batches go in chunks.  A guess, not a measurement
+
+    def _nsc_batched_ok(self):
+        return (self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16 and 1 <= self.nstep <= 4
+                and 0 <= self.prefix_alpha <= 3)
+
+    def _nsc_one(self, h):
+        if hasattr(self.decoder, "att"):
+            self.decoder.att[0].reset()
+        with torch.no_grad():
+            return self._nsc(h)
+
+    @ops.inference_call
+    def nsc_batch(self, hs_pad, hlens=None):
+        """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
+        -> B n-best lists, each what __call__ returns for hs_pad[b, :hlens[b]] with search_type="nsc": the last kept sorted by
+        score / len(yseq) (score with score_norm=False).
+        DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16, nstep <= 4, prefix_alpha <= 3: the batched frame loop above,
+        one blocking host read per call.  Anything else: a loop over the per-utterance search."""
+        B, T = hs_pad.shape[:2]
+        if not self._nsc_batched_ok():
+            if hlens is None:
+                lens = [T] * B
+            else:
+                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
+            return [self._nsc_one(hs_pad[b, :lens[b]]) for b in range(B)]
+        dev = hs_pad.device
+        W = min(self.beam_size, self.vocab_size)
+        N, alpha = int(self.nstep), int(self.prefix_alpha)
+        with torch.no_grad():
+            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: all T frames run, finished utterances idle
+                frames = [T] * B
+                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
+                      else hlens.to(device=dev, dtype=torch.int32).clamp(max=T))
+            else:
+                frames = [max(0, min(int(v), T)) for v in hlens]
+                hl = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
+            enc = self.decoder.joint_network.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
+            nmax = max(1, self.nsc_max_rows // W)
+            res = []
+            for b0 in range(0, B, nmax):
+                b1 = min(B, b0 + nmax)
+                res.append(self._nsc_rows(enc[b0:b1], hl[b0:b1], W, N, alpha, max(frames[b0:b1])))
+            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
+        ycap = 1 + T * N
+        out, o = [], 0
+        for _buf, n in res:
+            score = host[o:o + 2 * n * W].copy().view(np.float64).reshape(n, W)
+            o += 2 * n * W
+            count, ulen = host[o:o + n], host[o + n:o + n + n * W].reshape(n, W)
+            o += n + n * W
+            yseq = host[o:o + n * W * ycap].reshape(n, W, ycap)
+            o += n * W * ycap
+            for b in range(n):
+                hyps = [Hypothesis(score=float(score[b, m]), yseq=yseq[b, m, :ulen[b, m] + 1].tolist()) for m in range(count[b])]
+                if self.score_norm:
+                    out.append(sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True))
+                else:
+                    out.append(sorted(hyps, key=lambda x: x.score, reverse=True))
+        return out
+
+    def _nsc_ws(self, n, W, T, N, alpha, dev):
+        """the buffers of one frame loop on n utterances x W slots: the N + 2 hypothesis blocks, the frame's S, what eamd_rnnt_nsc_step
+        leaves for the rest of the call, the pair list and its log-probabilities, the stacked prediction-network state with its
+        staging copy, the stacked d / history rows and the call's intermediates"""
+        dec = self.decoder
+        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
+        G = (4 if dec.dtype == "lstm" else 3) * H
+        R, LV = n * W, 1 + alpha
+        f = dict(device=dev, dtype=torch.float32)
+        i32 = dict(device=dev, dtype=torch.int32)
+        ws = dict(n=R)
+        ws["st"] = (torch.zeros(N + 2, n, W, device=dev, dtype=torch.float64), torch.zeros(N + 2, n, W, **i32),
+                    torch.zeros(N + 2, n, **i32), torch.zeros(N + 2, n, W, 1 + T * N, **i32))
+        ws["st"][2][0].fill_(1)                               # kept of frame 0: slot 0 holds [blank] with score 0
+        ws["S"] = (torch.zeros(n, W * N, device=dev, dtype=torch.float64), torch.zeros(n, W * N, **i32), torch.zeros(n, **i32))
+        ws["par"] = torch.empty(R, **i32)
+        ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
+        ws["live"] = torch.empty(R, device=dev, dtype=torch.uint8)
+        ws["hidx"] = torch.zeros(LV, R, **i32)
+        ws["pairs"] = torch.zeros(max(1, R * alpha), 2, **i32)
+        ws["pairs"][:, 0].fill_(-1)                           # frame 0: [blank] has no prefix
+        ws["pair_lp"] = torch.zeros(max(1, R * alpha), **f)
+        ws["encr"] = torch.empty(LV * R, J, **f)
+        ws["hs"] = torch.zeros(N + 2, LV, R, J, **f)          # level 0: d; level a: d of the labels without the last a
+        ws["h"] = [torch.zeros((N + 2) * R, H, **f) for _ in range(L)]
+        ws["c"] = [torch.zeros((N + 2) * R, H, **f) for _ in range(L)]
+        stage_h, stage_c = [torch.zeros(R, H, **f) for _ in range(L)], [torch.zeros(R, H, **f) for _ in range(L)]
+        gx = [torch.empty(R, G, **f) for _ in range(L)]
+        gates = [torch.empty(R, 4 * H, **f) for _ in range(L)]
+        gh = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        # _pred_step's view of block j: state copy 0 = the staging copy, copy 1 = the block's rows
+        ws["blk"] = [dict(n=R, tok=ws["tok"], gx=gx, gates=gates, gh=gh, d=ws["hs"][j, 0],
+                          h=[stage_h, [x[j * R:(j + 1) * R] for x in ws["h"]]], c=[stage_c, [x[j * R:(j + 1) * R] for x in ws["c"]]])
+                     for j in range(N + 2)]
+        return ws
+
+    def _nsc_rows(self, enc, hl, W, N, alpha, frames):
+        """the frame loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device, `frames` frames
+        -> (result buffer (int32 words: score | count | ulen | yseq of the last kept), n), not yet read"""
+        n, T, J = enc.shape
+        dev = enc.device
+        dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
+        k = min(W, V - 1)
+        R, LV = n * W, 1 + alpha
+        ws = self._nsc_ws(n, W, T, N, alpha, dev)
+        enc_rows = enc.reshape(n * T, J)
+        st, blk, hs = ws["st"], ws["blk"], ws["hs"]
+        hs_rows = hs.view((N + 2) * LV * R, J)
+        self._pred_step(blk[0], 0, 1, None)                    # the initial step on blank from the zero state, into block 0
+        lstm = dec.dtype == "lstm"
+        layers = range(dec.dlayers)
+        p = 0
+        if frames:
+            # encoder row of frame t: b * T + min(t, T_b - 1), the same for all slots of an utterance and for every history level
+            tt = torch.arange(frames, device=dev, dtype=torch.int32)
+            ft = torch.minimum(tt[:, None], (hl - 1)[None, :]).clamp_(min=0) + (torch.arange(n, device=dev, dtype=torch.int32) * T)
+            ft = ft.repeat_interleave(W, dim=1).repeat(1, LV).contiguous()
+            ops.gather_rows([(ws["encr"], enc_rows, ft[0])])
+        for t in range(frames):
+            kp, ko = (N + 1, 0) if p else (0, N + 1)
+            for v in range(1 if N == 1 else N + 1):
+                last = N == 1 or v == N
+                if v == 0 and alpha:
+                    rec = ops.transducer_expand_rows_pairs_dev(jn.joint_rows_d(ws["encr"], hs[kp].view(LV * R, J)), k, ws["pairs"],
+                                                               ws["pair_lp"])[:R]
+                else:
+                    rec = ops.transducer_expand_rows_dev(jn.joint_rows_d(ws["encr"][:R], hs[kp if v == 0 else v, 0]), k)
+                ops.rnnt_nsc_step(rec, ws["pair_lp"], hl, st, ws["S"], ws["par"], ws["tok"], ws["live"], ws["hidx"], ws["pairs"],
+                                  V, T, N, alpha, t, v, p)
+                if last and t == frames - 1:
+                    break                                      # the last kept's prediction state is never read
+                cout = ko if last else v + 1
+                step = N == 1 or not last                      # rows of the new block may have appended a token
+                dst = 0 if step else 1
+                jobs = [(blk[cout]["h"][dst][l], ws["h"][l], ws["par"]) for l in layers]
+                if lstm:
+                    jobs += [(blk[cout]["c"][dst][l], ws["c"][l], ws["par"]) for l in layers]
+                jobs += [(hs[cout, a], hs_rows, ws["hidx"][a]) for a in range(1 if step else 0, LV)]
+                if last:
+                    jobs.append((ws["encr"], enc_rows, ft[t + 1]))
+                for j0 in range(0, len(jobs), 16):
+                    ops.gather_rows(jobs[j0:j0 + 16])
+                if step:
+                    self._pred_step(blk[cout], 0, 1, ws["live"])
+            p = 1 - p
+        last = N + 1 if p else 0
+        buf = torch.cat([st[0][last].view(torch.int32).reshape(-1), st[2][last], st[1][last].reshape(-1), st[3][last].reshape(-1)])
+        return buf, n

@@ -221,8 +221,10 @@ class E2E(ASRInterface, torch.nn.Module):
         One padded encoder pass (as in forward: the lengths are the encoder's own output lengths); beam_size <= 1 then takes
         BeamSearchTransducer.greedy_batch - all utterances frame by frame on the device, one host read; beam_size > 1 with
         search_type "alsd" takes BeamSearchTransducer.alsd_batch - all utterances step by step on the device, one host read -,
-        with search_type "tsd" BeamSearchTransducer.tsd_batch - all utterances pass by pass on the device, one host read - and
-        every other search type runs the configured search on each utterance's valid frames."""
+        with search_type "tsd" BeamSearchTransducer.tsd_batch - all utterances pass by pass on the device, one host read -, with
+        search_type "nsc" BeamSearchTransducer.nsc_batch - all utterances n-step by n-step on the device, one host read - and
+        search_type "default" runs the configured search on each utterance's valid frames (its inner loop has a data-dependent
+        length)."""
         from dataclasses import asdict
         self.eval()
         p = next(self.parameters())
@@ -247,5 +249,7 @@ class E2E(ASRInterface, torch.nn.Module):
             return [[asdict(n) for n in nb] for nb in beam_search.alsd_batch(hs_pad, hlens)]
         if beam_search.search_type == "tsd":
             return [[asdict(n) for n in nb] for nb in beam_search.tsd_batch(hs_pad, hlens)]
+        if beam_search.search_type == "nsc":
+            return [[asdict(n) for n in nb] for nb in beam_search.nsc_batch(hs_pad, hlens)]
         hl = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
         return [[asdict(n) for n in beam_search(hs_pad[b, : hl[b]])] for b in range(len(xs))]

@@ -1603,6 +1603,52 @@ def rnnt_tsd_step(rec, hlens, state, A, par, tok, live, V, T, M, t, v, p):
                                         ptr(live), n, W, V, T, M, t, v, p, stream_ptr()), "eamd_rnnt_tsd_step")
 
 
+def transducer_expand_rows_pairs_dev(logits, k, pairs, pair_out):
+    """eamd_transducer_expand_rows without LM, its record and the pair log-probabilities left on the device: logits fp32 [n, V] (unit
+    column stride), pairs int32 [g, 2] on the device (row, token; a row that is no row of logits is skipped), pair_out fp32 [g] ->
+    rec fp32 [n, 1 + 2k]; pair_out[j] = logp[row_j][token_j].  Nothing is read back."""
+    n, V = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise _lib.EamdError("transducer_expand_rows_pairs_dev: float32 [n, V] with unit column stride")
+    g = pair_out.numel()
+    if pairs.dtype != torch.int32 or not pairs.is_contiguous() or pairs.numel() != 2 * g or g < 1 \
+            or pair_out.dtype != torch.float32 or not pair_out.is_contiguous():
+        raise _lib.EamdError("transducer_expand_rows_pairs_dev: pairs int32 [g, 2], pair_out float32 [g], contiguous")
+    rec = torch.empty(n, 1 + 2 * k, device=logits.device, dtype=torch.float32)
+    check(_lib.lib().eamd_transducer_expand_rows(ptr(logits), logits.stride(0), n, V, k, None, None, ptr(pairs), g, ptr(rec),
+                                                 ptr(pair_out), stream_ptr()), "eamd_transducer_expand_rows")
+    return rec
+
+
+def rnnt_nsc_step(rec, pair_lp, hlens, state, S, par, tok, live, hidx, pairs, V, T, N, alpha, t, v, p):
+    """call (t, v) of the batched nsc transducer search (eamd_rnnt_nsc_step): rec fp32 [n * W, 1 + 2k] of the rows of hyps' block,
+    pair_lp fp32 [max(1, n * W * alpha)] of the frame's first pass, hlens int32 [n] or None; state = (score float64 [N + 2, n, W],
+    ulen int32 [N + 2, n, W], count int32 [N + 2, n], yseq int32 [N + 2, n, W, 1 + T N]) - blocks 0 and N + 1 are kept's parities, p
+    the one frame t reads, block v the hyps of n-step v; S = (s_score float64 [n, W N], s_src int32 [n, W N], nS int32 [n]); state
+    and S are updated in place, par int32 / tok int64 / live uint8 [n * W], hidx int32 [1 + alpha, n * W] and, on a frame's last
+    call, pairs int32 [max(1, n * W * alpha), 2] are written"""
+    blocks, n, W = state[0].shape
+    k = min(W, V - 1)
+    g = max(1, n * W * alpha)
+    want = [((N + 2, n, W), torch.float64), ((N + 2, n, W), torch.int32), ((N + 2, n), torch.int32),
+            ((N + 2, n, W, 1 + T * N), torch.int32)]
+    ok = blocks == N + 2 and rec.dtype == torch.float32 and rec.is_contiguous() and tuple(rec.shape) == (n * W, 1 + 2 * k)
+    ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(state, want))
+    want_s = [((n, W * N), torch.float64), ((n, W * N), torch.int32), ((n,), torch.int32)]
+    ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(S, want_s))
+    ok = ok and all(x.numel() == n * W and x.dtype == d and x.is_contiguous()
+                    for x, d in ((par, torch.int32), (tok, torch.int64), (live, torch.uint8)))
+    ok = ok and alpha >= 0 and hidx.dtype == torch.int32 and hidx.is_contiguous() and tuple(hidx.shape) == (1 + alpha, n * W)
+    ok = ok and pairs.dtype == torch.int32 and pairs.is_contiguous() and tuple(pairs.shape) == (g, 2)
+    ok = ok and pair_lp.dtype == torch.float32 and pair_lp.is_contiguous() and pair_lp.numel() == g
+    ok = ok and (hlens is None or (hlens.dtype == torch.int32 and hlens.numel() == n and hlens.is_contiguous()))
+    if not ok:
+        raise _lib.EamdError("rnnt_nsc_step: operand types / shapes")
+    check(_lib.lib().eamd_rnnt_nsc_step(ptr(rec), ptr(pair_lp), ptr(hlens), *[ptr(x) for x in state], *[ptr(x) for x in S], ptr(par),
+                                        ptr(tok), ptr(live), ptr(hidx), ptr(pairs), n, W, V, T, N, alpha, t, v, p, stream_ptr()),
+          "eamd_rnnt_nsc_step")
+
+
 def gather_rows(jobs):
     """up to 16 row gathers in one launch (eamd_gather_rows): jobs = [(dst [r, w], src [m, w], idx int32 [r])], contiguous fp32
     matrices on the device: dst[i] = src[idx[i]]"""

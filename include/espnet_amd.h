@@ -1023,6 +1023,52 @@ int eamd_gather_rows(const float* const* src, float* const* dst, const int32_t* 
 int eamd_rnnt_tsd_step(const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count, int32_t* yseq,
                        double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W, int V,
                        int T, int M, int t, int v, int p, void* stream);
+/* Batched N-step constrained transducer beam search without an LM, the bookkeeping of call (t, v) - frame t, n-step v of N = nstep -
+ * for n utterances in one launch (csrc/rnnt_nsc.hip; reference: beam_search_transducer.py:466-663 nsc_beam_search,
+ * transducer/utils.py:75-93 substract).  One workgroup per utterance, plain stores.  1 <= W <= 16 slots per utterance (the beam,
+ * min(beam_size, V)), W <= V, 1 <= N <= 4, 0 <= alpha = prefix_alpha <= 3, k = min(W, V - 1), blank = 0; anything else:
+ * EAMD_EUNSUPPORTED.  A frame takes the calls v = 0 .. N (v = 0 alone when N == 1).  v beyond that, t < 0, p outside {0, 1}, a NULL
+ * operand other than hlens, or one array passed for two operands: EAMD_EINVAL.
+ *   hypotheses live in N + 2 blocks of R = n * W rows; block row = block * R + b * W + w is slot w of utterance b.  Block 0 and block
+ *     N + 1 are the two parities of `kept` (p says which one frame t reads), block v (1 <= v <= N) is the V of n-step v - 1 = the
+ *     hyps of n-step v.  score double [N + 2, n, W], ulen int32 [N + 2, n, W] = labels without the leading blank, count int32
+ *     [N + 2, n] (slots 0 .. count - 1 are the list, in order), yseq int32 [N + 2, n, W, ycap] with ycap = 1 + T * N: a frame
+ *     appends at most N labels.  A list is never written past ycap.
+ *   S of the frame (the blank continuations of every n-step's hyps): s_score double [n, W * N], s_src int32 [n, W * N] = the block
+ *     row whose labels and prediction-network state the entry carries, nS int32 [n].  Call v == 0 starts from an empty S.
+ *   the lin_dec outputs of the rows are stacked [N + 2][1 + alpha][R] (x joint width): level 0 is the row's own d, level a is
+ *     hist[a] = lin_dec of the prediction output of the row's labels without the last a; hrow(block row q * R + s, level) =
+ *     (q * (1 + alpha) + level) * R + s is a row of that stack.
+ *   rec [n * W][1 + 2k]: eamd_transducer_expand_rows' record of the rows of hyps' block (blank logp, k non-blank logp, their tokens).
+ *   pair_lp [n * W][alpha], read at v == 0: entry (r, a - 1) = logp(joint(enc_t, hist[a] of kept slot r))[y_r[len_r - a]] for
+ *     a <= ulen, as the frame's first eamd_transducer_expand_rows leaves it for the pair list below.
+ *   hlens [n] (may be NULL = T): T_b = min(hlens[b], T).  t >= T_b: par = the utterance's rows of kept's parity p, tok = 0, live = 0,
+ *     hidx[a] = hrow(that row, a); at the frame's last call that kept (score, ulen, count, labels) is copied into the other parity;
+ *     nothing else is written.
+ *   v == 0, first: hyps = kept by length descending, stable.  For every pair j < i of that order where the labels of i are a strictly
+ *     shorter prefix of those of j and delta = len_j - len_i <= alpha: score_j = logaddexp(score_j, score_i + the sum of the terms
+ *     a = delta .. 1 of j's row of pair_lp, added one by one), in ascending i, from the scores of i as they were before this stage.
+ *     Every term is read from j's history rows; the reference's first term, on hyps[i].y[-1], is the same vector.
+ *   v < N: every hypothesis of hyps, in hyps' order, contributes its k extensions (score + rec[r][j], labels + token rec[r][k + j],
+ *     j = 1 .. k) and its blank continuation (score + rec[r][0]), which is appended to S.  V = the first W of the extensions whose
+ *     labels equal no member of hyps, by score descending, stable, NaN as -inf (sorted(..., reverse=True), substract, [:beam]).
+ *     N > 1: V is written to block v + 1; per row par int32 = the parent's block row, tok int64 = the token, live uint8 = 1 (the
+ *     mask eamd_lstm_step_fwd / eamd_lstm_cell_fwd / eamd_gru_cell_fwd take), hidx[0] = hrow(par, 0), hidx[a] = hrow(par, a - 1);
+ *     rows beyond the new count: par = the row's own row of hyps' block, tok = 0, live = 0, hidx[a] = hrow(that row, a); score, ulen
+ *     and labels are not written.
+ *   v == N (N > 1): V = block N with rec[r][0] added to every score (in the selection only: block N is not written).  N == 1: V stays
+ *     in the workgroup, block 1 is never written, and the same call goes on.  The other parity of kept = the first W of S followed
+ *     by V, sorted the same way.  An entry of S, or of V when N > 1, is carried: labels copied from its block row, par = that row,
+ *     tok = 0, live = 0, hidx[a] = hrow(par, a).  An entry of V when N == 1 appends its token: par = the parent's row, tok, live = 1,
+ *     hidx[0] = hrow(par, 0), hidx[a] = hrow(par, a - 1).  Rows beyond the new count as above.
+ *   the same call writes the pair list of frame t + 1, pairs int32 [n * W][alpha][2]: for new slot r and depth a <= its ulen
+ *     (row, token) = (a * R + r, y[len - a]) - the row of hist[a] among the (1 + alpha) R joint rows of the next frame's first pass
+ *     (the slots' own d first, then the levels) - else (-1, 0), which eamd_transducer_expand_rows skips.
+ *   hidx int32 [1 + alpha][R] is written by every call: with it one eamd_gather_rows job per level moves the stack's rows. */
+int eamd_rnnt_nsc_step(const float* rec, const float* pair_lp, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count,
+                       int32_t* yseq, double* s_score, int32_t* s_src, int32_t* nS, int32_t* par, int64_t* tok, uint8_t* live,
+                       int32_t* hidx, int32_t* pairs, int n, int W, int V, int T, int N, int alpha, int t, int v, int p,
+                       void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer on flat fp32 arenas.  reference: transformer/optimizer.py:12-75 (NoamOpt),
