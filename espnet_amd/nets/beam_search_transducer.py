@@ -34,7 +34,13 @@ computed is this package's own design:
   * batched nsc (`nsc_batch`): the nsc search of all utterances of a batch n-step by n-step in lock-step, hypotheses in N + 2 device
     blocks (kept's two parities and the V of every n-step), prefix rescoring, S, substract and the selections of a call in one
     launch (eamd_rnnt_nsc_step), the rescoring's pair terms from a device-side pair list, no host read inside the frame loop and
-    one at the end.
+    one at the end;
+  * batched default (`default_batch`): the default search of all utterances of a batch POP by pop in lock-step, every utterance
+    with its own frame counter on the device; A (sorted, cut to default_max_pops entries) and B in device arrays, the
+    prediction-network states in a pool of two frame-parity regions, labels as a log of (parent, token) records; finishing a pop,
+    ending a frame and selecting the next pop in one launch (eamd_rnnt_default_step); the host reads the done flags after the
+    first beam x frames steps and after every further chunk, then ONE result copy; an utterance whose frame wants more pops than
+    default_max_pops (an untrained, flat model does) overflows and is searched again per utterance.
 
 Prediction networks take part through one of three protocols: `step(tokens, states)` (batched; DecoderRNNT),
 `batch_step(yseqs)` (DecoderTT: the reference's batch_score, whose outputs depend on the batch a prefix is first computed
@@ -454,6 +460,210 @@ class BeamSearchTransducer:
         if self.score_norm:
             return sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True)
         return sorted(hyps, key=lambda x: x.score, reverse=True)
+
+    # ---- batched default ------------------------------------------------------------------------------------------------
+    # The default search pops the best entry of A until W entries of B beat everything left in A: how many pops a frame takes
+    # depends on the data, so a batch cannot advance frame by frame.  It advances POP by pop: every utterance finishes one pop per
+    # step and keeps its own frame counter on the device; a finished one is masked.  Three facts carry the design.  (1) B gains one
+    # entry per pop and a frame needs W of them ahead of A, so an utterance of T_b frames takes at least W T_b pops: the first
+    # W max(T_b) steps are enqueued without asking.  (2) Without an LM a child scores at most its parent, so max(A) never rises
+    # within a frame and an entry with P or more entries ahead of it (score descending, then insertion order) cannot be popped
+    # within the next P pops: with at most P = default_max_pops pops per frame A needs P entries, kept sorted, and the reference's
+    # first maximum is entry 0.  (3) only popped entries reach B, so every prediction-network state the next frame reads was
+    # written by a pop of this frame: the state pool has 2 P rows per utterance, one region per frame parity, and pop i of a frame
+    # writes row i of its region (a pop of a carried entry copies its state forward: its `live` is 0, the masked cells pass h / c
+    # through, and lin_dec is recomputed, so d is stored nowhere).  Labels are not kept on the device: every pop appends one
+    # (parent record, token) pair to the utterance's log and the host rebuilds the sequences after the result copy.
+    # One step on n rows (not n W): eamd_gather_rows (h / c by the parent's pool row, the encoder row by b T + t_b), the masked
+    # _pred_step, eamd_scatter_rows (the new h / c into the pop's pool row), joint_rows_d, eamd_transducer_expand_rows with its
+    # record left on the device, eamd_rnnt_default_step (csrc/rnnt_default.hip: finishes the pop, ends the frame when W entries of B
+    # are ahead, selects the next pop).  The host loop only enqueues; after the first W max(T_b) steps, and after every further
+    # default_chunk_steps, it reads the done / overflow flags in one small copy, and stops when every utterance has stopped or
+    # default_step_budget W max(T_b) steps are spent.  Then ONE result copy.  An utterance whose frame wanted a (P + 1)-th pop, or
+    # that the budget cut off, has overflowed and is searched again by the per-utterance search: the answer is always the exact one.
+    default_max_pops = 256            # P: pops per frame before an utterance overflows (the kernel takes W <= P <= 256).  A guess
+    default_chunk_steps = 64          # steps between two reads of the flags after the first W max(T_b).  A guess
+    default_step_budget = 8           # steps at most, in units of W max(T_b).  A guess
+    default_max_rows = 64             # utterances per step loop; larger batches go in chunks.  A guess, not a measurement
+
+    def _default_batched_ok(self):
+        return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16
+
+    def _default_one(self, h):
+        if hasattr(self.decoder, "att"):
+            self.decoder.att[0].reset()
+        with torch.no_grad():
+            return self._default(h)
+
+    @ops.inference_call
+    def default_batch(self, hs_pad, hlens=None):
+        """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
+        -> B n-best lists, each what __call__ returns for hs_pad[b, :hlens[b]] with search_type="default": the last frame's B sorted
+        by score / len(yseq) (score with score_norm=False); [Hypothesis(0.0, [blank])] for a row without frames.
+        DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16: the batched step loop above.  `passes` is the number of steps
+        enqueued, `host_reads` the blocking reads (flags + the one result copy), `overflowed` the utterances that were searched
+        again per utterance, `pops` per utterance (pops, frames, most pops of one frame) as the device counted them.
+        Anything else: a loop over the per-utterance search."""
+        B, T = hs_pad.shape[:2]
+        self.passes = self.host_reads = 0
+        self.overflowed, self.pops = [], []
+        if not self._default_batched_ok():
+            if hlens is None:
+                lens = [T] * B
+            else:
+                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
+            return [self._default_one(hs_pad[b, :lens[b]]) for b in range(B)]
+        dev = hs_pad.device
+        W = min(self.beam_size, self.vocab_size)
+        P = min(max(int(self.default_max_pops), W), 256)
+        with torch.no_grad():
+            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: the padded T bounds the first chunk
+                frames = [T] * B
+                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
+                      else hlens.to(device=dev, dtype=torch.int32).clamp(min=0, max=T))
+            else:
+                frames = [max(0, min(int(v), T)) for v in hlens]
+                hl = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
+            enc = self.decoder.joint_network.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
+            nmax = max(1, int(self.default_max_rows))
+            res = []
+            for b0 in range(0, B, nmax):
+                b1 = min(B, b0 + nmax)
+                res.append(self._default_rows(enc[b0:b1], hl[b0:b1].contiguous(), W, P, max(frames[b0:b1])))
+            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one result copy
+            self.host_reads += 1
+        out, o = [], 0
+        for _buf, n, used in res:
+            score = host[o:o + 2 * n * P].copy().view(np.float64).reshape(n, P)
+            o += 2 * n * P
+            b_log, ctr = host[o:o + n * P].reshape(n, P), host[o + n * P:o + n * P + 8 * n].reshape(n, 8)
+            o += n * P + 8 * n
+            flags, lens = host[o:o + 2 * n].reshape(2, n), host[o + 2 * n:o + 3 * n]
+            o += 3 * n
+            log = host[o:o + n * used * 2].reshape(n, used, 2)
+            o += n * used * 2
+            for b in range(n):
+                g = len(out)
+                self.pops.append((int(ctr[b, 4]) if lens[b] else 0, int(lens[b]), int(ctr[b, 7])))
+                if flags[1, b] or not flags[0, b]:             # overflowed, or still running when the budget was spent
+                    self.overflowed.append(g)
+                    out.append(self._default_one(hs_pad[g, :int(lens[b])]))
+                    continue
+                labels = {0: [self.blank]}
+                hyps = []
+                for j in range(int(ctr[b, 3])):
+                    node, todo = int(b_log[b, j]), []
+                    while node not in labels:
+                        todo.append(node)
+                        node = int(log[b, node, 0])
+                    for m in reversed(todo):
+                        par, tk = int(log[b, m, 0]), int(log[b, m, 1])
+                        labels[m] = labels[par] + [tk] if tk else labels[par]
+                    hyps.append(Hypothesis(score=float(score[b, j]), yseq=list(labels[int(b_log[b, j])])))
+                if self.score_norm:
+                    out.append(sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True))
+                else:
+                    out.append(sorted(hyps, key=lambda x: x.score, reverse=True))
+        return out
+
+    def _default_ws(self, n, P, log_cap, dev):
+        """the buffers of one step loop on n utterances: A, B, the pending pop, counters, flags and the label log, what
+        eamd_rnnt_default_step leaves for the rest of the step, the state pool of 2 P rows per utterance, and the step's intermediates"""
+        dec = self.decoder
+        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
+        G = (4 if dec.dtype == "lstm" else 3) * H
+        f = dict(device=dev, dtype=torch.float32)
+        i32 = dict(device=dev, dtype=torch.int32)
+        ws = dict(n=n)
+        ws["A"] = (torch.zeros(n, P, device=dev, dtype=torch.float64),) + tuple(torch.zeros(n, P, **i32) for _ in range(4))
+        ws["B"] = (torch.zeros(n, P, device=dev, dtype=torch.float64),) + tuple(torch.zeros(n, P, **i32) for _ in range(2))
+        ws["cur"] = torch.zeros(n, device=dev, dtype=torch.float64)
+        ws["ctr"] = torch.zeros(n, 8, **i32)
+        ws["log"] = torch.empty(n, log_cap, 2, **i32)          # sized to the step budget: only record 0 is filled
+        ws["flags"] = torch.zeros(2, n, **i32)
+        ws["par"] = torch.empty(n, **i32)
+        ws["dst"] = torch.empty(n, **i32)
+        ws["frame"] = torch.empty(n, **i32)
+        ws["tok"] = torch.zeros(n, device=dev, dtype=torch.int64)
+        ws["live"] = torch.zeros(n, device=dev, dtype=torch.uint8)
+        ws["alive"] = torch.empty(n, device=dev, dtype=torch.uint8)
+        ws["encr"] = torch.empty(n, J, **f)
+        ws["d"] = torch.empty(n, J, **f)
+        ws["pool_h"] = [torch.zeros(n * 2 * P, H, **f) for _ in range(L)]
+        ws["pool_c"] = [torch.zeros(n * 2 * P, H, **f) for _ in range(L)]
+        ws["h"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
+        ws["c"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
+        ws["gx"] = [torch.empty(n, G, **f) for _ in range(L)]
+        ws["gates"] = [torch.empty(n, 4 * H, **f) for _ in range(L)]
+        ws["gh"] = [torch.empty(n, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        return ws
+
+    def _default_rows(self, enc, hl, W, P, frames):
+        """the step loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device, `frames` = the most
+        frames an utterance has -> (result buffer (int32 words: b_score | b_log | ctr | flags | hl | the log's used records), n,
+        records per utterance in the buffer); the flags are read here, the buffer is not"""
+        n, T, J = enc.shape
+        dev = enc.device
+        dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
+        k = min(W, V - 1)
+        first = W * frames
+        budget = first * max(1, int(self.default_step_budget))
+        ws = self._default_ws(n, P, budget + 1, dev)
+        enc_rows = enc.reshape(n * T, J)
+        lstm = dec.dtype == "lstm"
+        layers = range(dec.dlayers)
+        # before frame 0: A = [(0.0, [blank])], and that entry is the first pop: record 0, its state in row 0 of the odd region
+        rows = torch.arange(n, device=dev, dtype=torch.int32)
+        run = (hl > 0)
+        ws["flags"][0].copy_(~run)
+        ws["ctr"][:, 1].copy_(run)                             # pops of frame 0: the pending one
+        ws["ctr"][:, 3].copy_(~run)                            # an utterance without frames: B = [(0.0, [blank])]
+        ws["ctr"][:, 4].fill_(1)
+        ws["log"][:, 0, 0].fill_(-1)
+        ws["log"][:, 0, 1].zero_()
+        ws["par"].copy_(rows * (2 * P) + P)
+        ws["dst"].copy_(rows * (2 * P))
+        ws["frame"].copy_(rows * T)
+        ws["alive"].copy_(run)
+        self._pred_step(ws, 0, 1, None)                        # the initial step on blank from the zero state
+        jobs = [(ws["pool_h"][l], ws["h"][1][l], ws["par"], None) for l in layers]
+        if lstm:
+            jobs += [(ws["pool_c"][l], ws["c"][1][l], ws["par"], None) for l in layers]
+        for j0 in range(0, len(jobs), 16):
+            ops.scatter_rows(jobs[j0:j0 + 16])
+        gather = [(ws["encr"], enc_rows, ws["frame"])] + [(ws["h"][0][l], ws["pool_h"][l], ws["par"]) for l in layers]
+        scatter = [(ws["pool_h"][l], ws["h"][1][l], ws["dst"], ws["alive"]) for l in layers]
+        if lstm:
+            gather += [(ws["c"][0][l], ws["pool_c"][l], ws["par"]) for l in layers]
+            scatter += [(ws["pool_c"][l], ws["c"][1][l], ws["dst"], ws["alive"]) for l in layers]
+
+        def step():
+            for j0 in range(0, len(gather), 16):
+                ops.gather_rows(gather[j0:j0 + 16])
+            self._pred_step(ws, 0, 1, ws["live"])
+            for j0 in range(0, len(scatter), 16):
+                ops.scatter_rows(scatter[j0:j0 + 16])
+            rec = ops.transducer_expand_rows_dev(jn.joint_rows_d(ws["encr"], ws["d"]), k)
+            ops.rnnt_default_step(rec, hl, ws["A"], ws["B"], ws["cur"], ws["ctr"], ws["log"], ws["flags"], ws["par"], ws["tok"],
+                                  ws["dst"], ws["live"], ws["frame"], ws["alive"], W, V, T)
+
+        steps = first
+        for _ in range(first):
+            step()
+        while True:
+            flags = ws["flags"].cpu().numpy()                  # one small blocking copy
+            self.host_reads += 1
+            if bool((flags[0] | flags[1]).all()) or steps >= budget:
+                break
+            more = min(max(1, int(self.default_chunk_steps)), budget - steps)
+            for _ in range(more):
+                step()
+            steps += more
+        self.passes += steps
+        used = steps + 1
+        buf = torch.cat([ws["B"][0].view(torch.int32).reshape(-1), ws["B"][2].reshape(-1), ws["ctr"].reshape(-1),
+                         ws["flags"].reshape(-1), hl, ws["log"][:, :used].reshape(-1)])
+        return buf, n, used
 
     # ---- tsd / alsd / nsc: passes --------------------------------------------------------------------------------------
     def _batch_pred(self, nodes):

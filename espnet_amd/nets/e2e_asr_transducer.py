@@ -223,8 +223,10 @@ class E2E(ASRInterface, torch.nn.Module):
         search_type "alsd" takes BeamSearchTransducer.alsd_batch - all utterances step by step on the device, one host read -,
         with search_type "tsd" BeamSearchTransducer.tsd_batch - all utterances pass by pass on the device, one host read -, with
         search_type "nsc" BeamSearchTransducer.nsc_batch - all utterances n-step by n-step on the device, one host read - and
-        search_type "default" runs the configured search on each utterance's valid frames (its inner loop has a data-dependent
-        length)."""
+        with search_type "default" BeamSearchTransducer.default_batch - all utterances pop by pop on the device, each with its
+        own frame counter (the inner loop has a data-dependent length): a read of the done flags after the first
+        beam x frames steps and after every further chunk, one result copy, and the per-utterance search again for an
+        utterance whose frame took more pops than the device keeps."""
         from dataclasses import asdict
         self.eval()
         p = next(self.parameters())
@@ -251,5 +253,7 @@ class E2E(ASRInterface, torch.nn.Module):
             return [[asdict(n) for n in nb] for nb in beam_search.tsd_batch(hs_pad, hlens)]
         if beam_search.search_type == "nsc":
             return [[asdict(n) for n in nb] for nb in beam_search.nsc_batch(hs_pad, hlens)]
+        if beam_search.search_type == "default":
+            return [[asdict(n) for n in nb] for nb in beam_search.default_batch(hs_pad, hlens)]
         hl = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
         return [[asdict(n) for n in beam_search(hs_pad[b, : hl[b]])] for b in range(len(xs))]

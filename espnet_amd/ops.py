@@ -1668,6 +1668,53 @@ def gather_rows(jobs):
     check(_lib.lib().eamd_gather_rows(src, dst, idx, nrows, width, srows, n, stream_ptr()), "eamd_gather_rows")
 
 
+def rnnt_default_step(rec, hlens, A, B, cur_score, ctr, log, flags, par, tok, dst, live, frame, alive, W, V, T):
+    """one pop of the batched default transducer search (eamd_rnnt_default_step): rec fp32 [n, 1 + 2k] of the pending pops' joint
+    rows, hlens int32 [n] or None; A = (a_score float64 [n, P], a_seq, a_row, a_log, a_tok int32 [n, P]), B = (b_score float64 [n, P],
+    b_row, b_log int32 [n, P]), cur_score float64 [n], ctr int32 [n, 8], log int32 [n, log_cap, 2], flags int32 [2, n]: updated in
+    place; par int32 / tok int64 / dst int32 / live uint8 / frame int32 / alive uint8 [n] are written"""
+    n, P = A[0].shape
+    k = min(W, V - 1)
+    want_a = [torch.float64] + [torch.int32] * 4
+    want_b = [torch.float64] + [torch.int32] * 2
+    ok = rec.dtype == torch.float32 and rec.is_contiguous() and tuple(rec.shape) == (n, 1 + 2 * k)
+    ok = ok and len(A) == 5 and len(B) == 3
+    ok = ok and all(tuple(x.shape) == (n, P) and x.dtype == d and x.is_contiguous() for x, d in zip(tuple(A) + tuple(B), want_a + want_b))
+    ok = ok and cur_score.dtype == torch.float64 and cur_score.numel() == n and cur_score.is_contiguous()
+    ok = ok and ctr.dtype == torch.int32 and tuple(ctr.shape) == (n, 8) and ctr.is_contiguous()
+    ok = ok and log.dtype == torch.int32 and log.dim() == 3 and log.shape[0] == n and log.shape[2] == 2 and log.is_contiguous()
+    ok = ok and flags.dtype == torch.int32 and tuple(flags.shape) == (2, n) and flags.is_contiguous()
+    ok = ok and all(x.numel() == n and x.dtype == d and x.is_contiguous()
+                    for x, d in ((par, torch.int32), (tok, torch.int64), (dst, torch.int32), (live, torch.uint8),
+                                 (frame, torch.int32), (alive, torch.uint8)))
+    ok = ok and (hlens is None or (hlens.dtype == torch.int32 and hlens.numel() == n and hlens.is_contiguous()))
+    if not ok:
+        raise _lib.EamdError("rnnt_default_step: operand types / shapes")
+    check(_lib.lib().eamd_rnnt_default_step(ptr(rec), ptr(hlens), *[ptr(x) for x in A], *[ptr(x) for x in B], ptr(cur_score), ptr(ctr),
+                                            ptr(log), ptr(flags), ptr(par), ptr(tok), ptr(dst), ptr(live), ptr(frame), ptr(alive),
+                                            n, W, V, T, P, k, log.shape[1], stream_ptr()), "eamd_rnnt_default_step")
+
+
+def scatter_rows(jobs):
+    """up to 16 masked row scatters in one launch (eamd_scatter_rows): jobs = [(dst [m, w], src [r, w], idx int32 [r], mask uint8 [r]
+    or None)], contiguous fp32 matrices on the device: dst[idx[i]] = src[i] where mask[i] != 0; an index outside dst writes nothing"""
+    n = len(jobs)
+    assert 0 < n <= 16
+    for d, s_, ix, m in jobs:
+        if not (d.dtype == s_.dtype == torch.float32 and d.is_contiguous() and s_.is_contiguous() and d.dim() == s_.dim() == 2
+                and d.shape[1] == s_.shape[1] and ix.dtype == torch.int32 and ix.is_contiguous() and ix.numel() == s_.shape[0]
+                and d.shape[0] >= 1 and (m is None or (m.dtype == torch.uint8 and m.is_contiguous() and m.numel() == s_.shape[0]))):
+            raise _lib.EamdError("scatter_rows: contiguous float32 [rows, width] matrices of one width, int32 indices, uint8 masks")
+    dst = (C.c_void_p * n)(*[d.data_ptr() for d, _, _, _ in jobs])
+    src = (C.c_void_p * n)(*[s_.data_ptr() for _, s_, _, _ in jobs])
+    idx = (C.c_void_p * n)(*[ix.data_ptr() for _, _, ix, _ in jobs])
+    mask = (C.c_void_p * n)(*[ptr(m) for _, _, _, m in jobs])
+    nrows = (C.c_int32 * n)(*[s_.shape[0] for _, s_, _, _ in jobs])
+    width = (C.c_int32 * n)(*[d.shape[1] for d, _, _, _ in jobs])
+    drows = (C.c_int32 * n)(*[d.shape[0] for d, _, _, _ in jobs])
+    check(_lib.lib().eamd_scatter_rows(dst, src, idx, mask, nrows, width, drows, n, stream_ptr()), "eamd_scatter_rows")
+
+
 def linear_into(x, W, b, out):
     """out[M, N] = x W^T + b into a caller-owned buffer (the static buffers a replayed decoding step reads and writes): the
     few-row kernel of linear_fwd where it takes the shape, else the GEMM"""

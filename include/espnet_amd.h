@@ -1069,6 +1069,45 @@ int eamd_rnnt_nsc_step(const float* rec, const float* pair_lp, const int32_t* hl
                        int32_t* yseq, double* s_score, int32_t* s_src, int32_t* nS, int32_t* par, int64_t* tok, uint8_t* live,
                        int32_t* hidx, int32_t* pairs, int n, int W, int V, int T, int N, int alpha, int t, int v, int p,
                        void* stream);
+/* Batched default (Graves A / B) transducer beam search without an LM, the bookkeeping of one POP for n utterances in one launch
+ * (csrc/rnnt_default.hip; reference: beam_search_transducer.py:163-237 default_beam_search).  The pops of a frame depend on the data,
+ * so the utterances advance in lock-step in pops and every utterance keeps its own frame counter.  One workgroup per utterance, plain
+ * stores.  1 <= W <= 16 (the beam, min(beam_size, V)), W <= V, W <= P <= 256 pops per frame at most: anything else
+ * EAMD_EUNSUPPORTED.  k != min(W, V - 1), log_cap < 1, a NULL operand other than hlens: EAMD_EINVAL.  blank = 0.
+ *   A of the frame: a_score double [n, P], a_seq / a_row / a_log / a_tok int32 [n, P], sorted by (score descending, a_seq ascending),
+ *     NaN as -inf: entry 0 is the reference's max(A), the first maximum in list order.  a_seq is the insertion order, a_row the pool
+ *     row (0 .. 2P - 1 of the utterance) the entry's prediction-network state is read from, a_log a log record and a_tok the token a
+ *     child appends to that record's labels (0: an entry carried over from B, whose labels ARE the record's and whose state exists).
+ *   B of the frame: b_score double [n, P], b_row / b_log int32 [n, P], in the order of the pops.
+ *   ctr int32 [n, 8]: 0 frame t, 1 pops selected in this frame, 2 entries of A, 3 entries of B, 4 log records, 5 next a_seq, 6 the
+ *     pending pop's record, 7 the most pops a finished frame took.  cur_score double [n]: the pending pop's score.
+ *   log int32 [n, log_cap, 2]: record = (parent record, token; 0 = the parent's labels); record 0 is [blank].  One record per pop.
+ *   flags int32 [2, n]: done, overflow.  An utterance with either set is not touched; par = dst = its first pool row, tok = 0,
+ *     live = 0, frame = b * T, alive = 0 are written for it.
+ *   pool: 2P rows per utterance, rows [0, P) for even frames and [P, 2P) for odd ones; pop number i of frame t writes row
+ *     (t & 1) P + i.
+ *   The call FINISHES the pending pop (score s, record c, pool row r) from rec [n][1 + 2k], eamd_transducer_expand_rows' record of its
+ *     joint row: appends (s + rec[j], seq++, r, c, token rec[k + j]) for j = 1 .. k to A and (s + rec[0], r, c) to B - double sums of a
+ *     double and a float -, keeps the P best of A (with at most P pops per frame no other entry can be popped), takes bound = A[0]
+ *     and counts the entries of B with score > bound.  With W or more of them the frame ends: they are ranked ascending by score,
+ *     stable, and become the next frame's A with a_seq = rank, a_tok = 0; B is emptied and t advances.  After the last frame,
+ *     t == min(hlens[b], T) (hlens NULL: T), they are written to B in rank order instead - the list the reference sorts into the
+ *     n-best -, ctr[3] is their count and done is set.
+ *   It then SELECTS the next pop: entry 0 leaves A, a record (a_log, a_tok) is appended to the log, and par int32 [n] = the global
+ *     pool row b 2P + a_row to read, tok int64 [n] = a_tok, dst int32 [n] = the global pool row to write, live uint8 [n] = a_tok != 0
+ *     (the mask eamd_lstm_step_fwd / eamd_lstm_cell_fwd / eamd_gru_cell_fwd take), frame int32 [n] = b T + t, alive uint8 [n] = 1
+ *     (eamd_scatter_rows' mask).  The (P + 1)-th pop of a frame, or a pop with the log full, sets overflow instead and stops the
+ *     utterance.
+ * eamd_scatter_rows: up to 16 masked row scatters in one launch, dst_j[idx_j[r], :] = src_j[r, :] for r < nrows[j] with mask_j[r] != 0
+ *   (mask_j NULL: every row; fp32 rows of width[j] elements, float4 moves as in eamd_gather_rows).  dst / src / idx / mask: HOST arrays
+ *   of device pointers, idx_j int32 and mask_j uint8 on the device; an index outside [0, dst_rows[j]) writes nothing.  Rows of one job
+ *   that share an index race. */
+int eamd_rnnt_default_step(const float* rec, const int32_t* hlens, double* a_score, int32_t* a_seq, int32_t* a_row, int32_t* a_log,
+                           int32_t* a_tok, double* b_score, int32_t* b_row, int32_t* b_log, double* cur_score, int32_t* ctr,
+                           int32_t* log, int32_t* flags, int32_t* par, int64_t* tok, int32_t* dst, uint8_t* live, int32_t* frame,
+                           uint8_t* alive, int n, int W, int V, int T, int P, int k, int log_cap, void* stream);
+int eamd_scatter_rows(float* const* dst, const float* const* src, const int32_t* const* idx, const uint8_t* const* mask,
+                      const int32_t* nrows, const int32_t* width, const int32_t* dst_rows, int njobs, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Optimizer on flat fp32 arenas.  reference: transformer/optimizer.py:12-75 (NoamOpt),
