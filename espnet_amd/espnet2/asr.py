@@ -194,6 +194,9 @@ class CTC(torch.nn.Module):
     def prefix_beam_search(self, hs_pad, hlens, **kw):
         return self._ctc[0].prefix_beam_search(hs_pad, hlens, **kw)
 
+    def segment(self, hs_pad, hlens, texts, config, **kw):
+        return self._ctc[0].segment(hs_pad, hlens, texts, config, **kw)
+
 
 class ESPnetASRModel(AbsESPnetModel):
     """reference: espnet2/asr/espnet_model.py:35-290.  frontend = None (fbank features are the input) or

@@ -57,3 +57,12 @@ def ctc_align_batch(model, xs_pad, ilens, ys_pad, blank_id=0):
     the encoder frames (score, states, tokens, start, end; device tensors): one encoder call, one alignment pass"""
     hs_pad, hlens = encode_batch(model, xs_pad, ilens)
     return model.ctc.forced_align_batch(hs_pad, hlens, ys_pad, blank_id)
+
+
+def ctc_segment_recordings(model, xs_pad, ilens, texts, config, **kw):
+    """xs_pad (B,T,idim) features of whole recordings, ilens (B) valid frames, texts[b] the utterances of recording b, config a
+    ctc_segmentation.CtcSegmentationParameters (char_list; subsampling_factor = the encoder's frame rate reduction) -> per
+    recording the list of (start, end, confidence) in seconds (the model side of the reference's bin/asr_align.py, which
+    segments one recording per call): one encoder call, then CTC.segment"""
+    hs_pad, hlens = encode_batch(model, xs_pad, ilens)
+    return model.ctc.segment(hs_pad, hlens, texts, config, **kw)

@@ -1349,6 +1349,17 @@ class CTC(torch.nn.Module):
             return CTCAlignment(*ops.ctc_forced_align(y.contiguous(), hl.contiguous(), ys_pad, blank=blank_id,
                                                        ignore_id=self.ignore_id))
 
+    def segment(self, hs_pad, hlens, texts, config, **kw):
+        """CTC segmentation of whole recordings (nets.ctc_segmentation.ctc_segment_batch; the reference: bin/asr_align.py with the
+        ctc_segmentation package, one recording per call): hs_pad (B,T,D) encoder output; hlens valid frames; texts[b] the
+        utterances of recording b; config a CtcSegmentationParameters with char_list set -> per recording the list of
+        (start, end, confidence) in seconds.  Output layer and log-softmax rows, then the batched trellis"""
+        from .ctc_segmentation import ctc_segment_batch
+        hl = [int(v) for v in (hlens.tolist() if isinstance(hlens, torch.Tensor) else hlens)]
+        with torch.no_grad():
+            lpz = self.log_softmax(hs_pad.to(self.ctc_lo.weight.device).contiguous())
+            return ctc_segment_batch(config, lpz, hl, texts, **kw)
+
     def prefix_beam_search(self, hs_pad, hlens, **kw):
         """time-synchronous CTC prefix beam search of a padded batch (nets.ctc_prefix_beam.CTCPrefixBeamSearch, not in the
         reference): hs_pad (B,T,D) encoder output; hlens valid frames (list / tensor); kw: beam_size, cand_size, nbest, penalty,

@@ -2409,6 +2409,122 @@ def ctc_forced_align(acts, ilens, ys_pad, blank=0, ignore_id=-1, normalized=Fals
     return score, states, tokens, seg_start, seg_end
 
 
+CTC_SEGMENT_MAX_S = 16      # longest token in characters (csrc/ctc_segment.hip kMaxS)
+
+
+def _seg_align(n, a=256):
+    return (n + a - 1) // a * a
+
+
+def ctc_segment_window(window, Tmax):
+    return max(1, min(int(window), int(Tmax)))
+
+
+def ctc_segment_ring_in_lds(S, window, Tmax):
+    """whether the fill kernel keeps its S + 1 columns of values in LDS at this window (else: in the workspace)"""
+    rc = _lib.lib().eamd_ctc_segment_ring_in_lds(S, ctc_segment_window(window, Tmax))
+    if rc < 0:
+        check(rc, "eamd_ctc_segment_ring_in_lds")
+    return bool(rc)
+
+
+def ctc_segment_workspace_layout(nsel, B, Tmax, Lmax, S, window, ring_global=False):
+    """byte offsets of (psum, ring, bp) in the workspace of one window attempt, and its size.  ring is None when it lives in LDS"""
+    Wm = ctc_segment_window(window, Tmax)
+    o_psum, n = 0, _seg_align(B * (Tmax + 1) * 8)
+    o_ring = None
+    if ring_global or not ctc_segment_ring_in_lds(S, window, Tmax):
+        o_ring, n = n, n + _seg_align(nsel * (S + 1) * (Wm + Wm // 32 + 1) * 4)
+    o_bp, n = n, n + _seg_align(nsel * Wm * Lmax)
+    return o_psum, o_ring, o_bp, n
+
+
+def ctc_segment_bytes(nsel, B, Tmax, Lmax, S, Umax, window, ring_global=False):
+    """device bytes one window attempt needs beside its results: backpointers, ring, prefix sums, and the emission rows"""
+    return ctc_segment_workspace_layout(nsel, B, Tmax, Lmax, S, window, ring_global)[3] + B * Umax * Tmax * 4
+
+
+def ctc_segment_emissions(lpz, lens, tok, blank=0, gratis_blank=False):
+    """eamd_ctc_segment_emissions: lpz [B,Tmax,V] fp32 log-probabilities, lens [B] int32, tok [B,Umax] int32 (row 0: blank; -1:
+    unused) -> em [B,Umax,Tmax]: the rows the trellis reads, contiguous in t (frames behind lens[b] are left unwritten)"""
+    B, Tmax, V = lpz.shape
+    assert lpz.dtype == torch.float32 and lpz.is_contiguous() and lens.dtype == torch.int32 and lens.numel() == B
+    assert tok.dtype == torch.int32 and tok.is_contiguous() and tok.shape[0] == B
+    if not 0 <= blank < V:
+        raise ValueError("blank id %d outside the %d outputs" % (blank, V))
+    em = torch.empty(B, tok.shape[1], Tmax, device=lpz.device, dtype=torch.float32)
+    check(_lib.lib().eamd_ctc_segment_emissions(ptr(lpz), ptr(lens), ptr(tok), ptr(em), B, Tmax, V, tok.shape[1], blank,
+                                                bool(gratis_blank), stream_ptr()), "eamd_ctc_segment_emissions")
+    return em
+
+
+def ctc_segment_result_bytes(B, Tmax, Lmax, NU):
+    return B * (NU * 3 * 8 + 4 * 4 + 2 * Lmax * 4 + 2 * Tmax * 4)
+
+
+def ctc_segment_result(B, Tmax, Lmax, NU, device, out=None):
+    """the results of eamd_ctc_segment_run as views of ONE byte buffer, so that the host fetches them in one copy: seg [B,NU,3]
+    f64 and info [B,4] int32 first (res["head"] bytes: all a caller of the segments needs), then offsets / timings [B,Lmax] int32,
+    char_probs [B,Tmax] f32, states [B,Tmax] int32.  out: a byte tensor of res["bytes"] bytes at an 8-byte aligned address"""
+    shapes = (("seg", torch.float64, (B, NU, 3)), ("info", torch.int32, (B, 4)), ("offsets", torch.int32, (B, Lmax)),
+              ("timings", torch.int32, (B, Lmax)), ("char_probs", torch.float32, (B, Tmax)), ("states", torch.int32, (B, Tmax)))
+    total = ctc_segment_result_bytes(B, Tmax, Lmax, NU)
+    if out is None:
+        out = torch.zeros(total, device=device, dtype=torch.uint8)
+    assert out.dtype == torch.uint8 and out.numel() == total and out.is_contiguous() and out.data_ptr() % 8 == 0
+    res, o = {"buf": out, "bytes": total}, 0
+    for name, d, s in shapes:
+        n = math.prod(s) * torch.empty(0, dtype=d).element_size()
+        res[name] = out[o:o + n].view(d).view(s)
+        o += n
+        if name == "info":
+            res["head"] = o
+    return res
+
+
+def ctc_segment_fetch(res, full=False):
+    """ONE device-to-host copy of a result buffer (its head: seg and info, or all of it) -> dict of numpy arrays"""
+    host = (res["buf"] if full else res["buf"][:res["head"]]).cpu()
+    out, o = {}, 0
+    for name in ("seg", "info") + (("offsets", "timings", "char_probs", "states") if full else ()):
+        v = res[name]
+        n = v.numel() * v.element_size()
+        out[name] = host[o:o + n].view(v.dtype).view(v.shape).numpy()
+        o += n
+    return out
+
+
+def ctc_segment_run(em, gtu, tok, lens, llens, sel, utt, nutt, res, window, n_mean, index_duration, ring_global=False,
+                    workspace=None):
+    """eamd_ctc_segment_run: one window attempt (fill, walk back, segments) for the recordings sel (int32 indices) into the views
+    of res (ctc_segment_result); the other recordings keep what res holds.  em [B,Umax,Tmax]; gtu [B,Lmax,S] int32 rows of em
+    (-1: no token); tok [B,Umax]; lens / llens [B] frames / characters; utt [B,NU+1], nutt [B] utterance begin indices.
+    workspace: a byte tensor of ctc_segment_workspace_layout(...)[3] bytes (256-byte aligned), else allocated here"""
+    B, Umax, Tmax = em.shape
+    Lmax, S = gtu.shape[1], gtu.shape[2]
+    NU = utt.shape[1] - 1
+    nsel = sel.numel()
+    for t in (gtu, tok, lens, llens, sel, utt, nutt):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == em.device
+    assert em.dtype == torch.float32 and em.is_contiguous() and gtu.shape[0] == B and tok.shape == (B, Umax)
+    assert lens.numel() == B and llens.numel() == B and nutt.numel() == B and utt.shape[0] == B and 1 <= nsel <= B
+    assert res["seg"].shape == (B, NU, 3) and res["offsets"].shape == (B, Lmax) and res["states"].shape == (B, Tmax)
+    if S > CTC_SEGMENT_MAX_S:
+        raise ValueError("tokens of %d characters: the segmentation kernel takes at most %d" % (S, CTC_SEGMENT_MAX_S))
+    o_psum, o_ring, o_bp, nbytes = ctc_segment_workspace_layout(nsel, B, Tmax, Lmax, S, window, ring_global)
+    if workspace is None:
+        workspace = torch.empty(nbytes, device=em.device, dtype=torch.uint8)
+    assert workspace.dtype == torch.uint8 and workspace.numel() >= nbytes and workspace.data_ptr() % 256 == 0
+    base = workspace.data_ptr()
+    check(_lib.lib().eamd_ctc_segment_run(ptr(em), ptr(gtu), ptr(tok), ptr(lens), ptr(llens), ptr(sel), ptr(utt), ptr(nutt),
+                                          base + o_bp, None if o_ring is None else base + o_ring, base + o_psum,
+                                          ptr(res["info"]), ptr(res["offsets"]), ptr(res["timings"]), ptr(res["char_probs"]),
+                                          ptr(res["states"]), ptr(res["seg"]), nsel, B, Tmax, Lmax, S, Umax, NU, int(window),
+                                          int(n_mean), float(index_duration), bool(ring_global), stream_ptr()),
+          "eamd_ctc_segment_run")
+    return res
+
+
 def maskctc_seed(logits, hlens, thr, K, mask_token, eos, blank=0, Lcap=None):
     """Mask-CTC seed (eamd_maskctc_seed): logits [B,T',V] fp32 CTC output-layer activations, hlens [B] int32 (device) valid
     frames -> dict of device tensors: y_in [B,Lcap] int64 (confident token or mask_token, padded with eos), tok_p [B,Lcap] (max p

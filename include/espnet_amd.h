@@ -664,6 +664,30 @@ int eamd_ctc_forced_align(const float* acts, int64_t stride_t, int64_t stride_b,
                           float* score, int32_t* states, int64_t* tokens, int32_t* seg_start, int32_t* seg_end, void* workspace,
                           int B, int T, int V, int Lmax, int blank, int ignore_id, int normalized, void* stream);
 
+/* CTC segmentation of whole recordings (csrc/ctc_segment.hip; Kuerzinger et al. 2020; the reference calls the external
+ * ctc_segmentation package from espnet/bin/asr_align.py).  Recording b has lens[b] frames and a transcript of llens[b] characters.
+ * eamd_ctc_segment_emissions: lpz [B,Tmax,V] fp32 log-probabilities -> em [B,Umax,Tmax], row 0 = blank (0 everywhere with
+ *   gratis_blank), row u > 0 = token tok[b,u] (tok [B,Umax] int32; -1 = unused row, left unwritten; an id >= V reads as -inf).
+ *   Frames >= lens[b] are neither read nor written.
+ * eamd_ctc_segment_run: one window attempt for the nsel recordings sel[0..nsel) (int32 indices into B; the others keep what
+ *   their buffers hold).  gtu [B,Lmax,S] int32: row of em for the span of s + 1 characters ending at character c, -1 = none.
+ *   utt [B,NU+1] int32 begin index of each utterance and one behind the last, nutt [B] utterances.  W = min(window, lens[b]).
+ *   Outputs per recording: info [B,4] int32 = status (0 ok, 1 no path in this window, 2 bad lengths, 3 broken walk), end row,
+ *   W, last window offset; offsets [B,Lmax] int32 window offset of every column; timings [B,Lmax] int32 frame of every character;
+ *   char_probs [B,Tmax] fp32 and states [B,Tmax] int32 per frame (token id, -1 = stay, -2 and 0.0 = off the path);
+ *   seg [B,NU,3] float64 = start, end (seconds, frame x index_duration) and confidence of every utterance (n_mean frames per
+ *   sliding mean).  Workspaces: bp nsel * min(window, Tmax) * Lmax bytes; psum B * (Tmax + 1) float64; ring (only read when
+ *   eamd_ctc_segment_ring_in_lds(S, min(window, Tmax)) is 0 or ring_global is set, else may be NULL):
+ *   nsel * (S + 1) * (Wm + Wm / 32 + 1) floats, Wm = min(window, Tmax).  S <= 16, else EAMD_EUNSUPPORTED. */
+int eamd_ctc_segment_ring_in_lds(int S, int W);
+int eamd_ctc_segment_emissions(const float* lpz, const int32_t* lens, const int32_t* tok, float* em, int B, int Tmax, int V,
+                               int Umax, int blank, int gratis_blank, void* stream);
+int eamd_ctc_segment_run(const float* em, const int32_t* gtu, const int32_t* tok, const int32_t* lens, const int32_t* llens,
+                         const int32_t* sel, const int32_t* utt, const int32_t* nutt, uint8_t* bp, float* ring, double* psum,
+                         int32_t* info, int32_t* offsets, int32_t* timings, float* char_probs, int32_t* states, double* seg,
+                         int nsel, int B, int Tmax, int Lmax, int S, int Umax, int NU, int window, int n_mean,
+                         double index_duration, int ring_global, void* stream);
+
 /* CTC prefix scores of (hypothesis, candidate) pairs for joint CTC/attention beam search.
  * reference: espnet/nets/ctc_prefix_score.py:224-310, scorers/ctc.py:11-127.
  * logp [T,V]; r_prev [nhyp,T,2]; cand [nhyp,ncand]; last/olen [nhyp]; psi [nhyp,ncand]; r_new [nhyp,ncand,T,2]. */
