@@ -9,11 +9,11 @@
 //                         the state of the other parity, appends the finals, and leaves per row what the rest of the step needs:
 //                         the row whose prediction-network state it continues (par), the appended token (tok), the cell kernels'
 //                         mask (live) and the encoder row of the next step (frame).  Selection is a rank-by-counting sort in LDS
-//                         (stable: equal scores keep A's order); equal label sequences are found by comparing lengths and tokens,
-//                         one wave per pair; the only traffic that grows with T is the copy of W parents' labels.
-//   eamd_gather_rows      up to 16 row gathers dst_j[r, :] = src_j[idx_j[r], :] in one launch: the projected encoder rows by frame
-//                         and h / c of every prediction-network layer by par.
-// Plain stores, no atomics, no scratch buffers: a workgroup owns its utterance's rows of every output.
+//                         (rs_rank: stable, equal scores keep A's order); equal label sequences are found by comparing lengths
+//                         and tokens, one wave per pair (rs_same_labels); the only traffic that grows with T is the copy of W
+//                         parents' labels (rs_copy_labels).
+// The rows the rest of the step needs are moved by eamd_gather_rows (row_moves.hip).  Plain stores, no atomics, no scratch
+// buffers: a workgroup owns its utterance's rows of every output.
 #include "common.h"
 #include "rnnt_search.h"
 #include "../../include/espnet_amd.h"
@@ -82,10 +82,9 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
       frame[r] = b * T + min(max(i + 2 - o_ulen[tid], 0), tmax);
     }
     if (tid == 0) nhyp_out[b] = nh;
-    for (int x = tid; x < nh * ycap; x += AL_THREADS) {
-      const int w = x / ycap, e = x - w * ycap;
-      if (e <= o_ulen[w]) yseq_out[(row0 + w) * ycap + e] = yseq_in[(row0 + w) * ycap + e];
-    }
+    rs_copy_labels<AL_THREADS>(nh, ycap, tid, [&](int w) {
+      return RsLabels{yseq_out + (row0 + w) * ycap, yseq_in + (row0 + w) * ycap, o_ulen[w], o_ulen[w], 0};
+    });
     return;
   }
   // A: per active slot its blank continuation, then its k extensions in the record's order
@@ -98,14 +97,7 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
   __syncthreads();
   // sorted(A, reverse=True)[:W]: position = candidates ahead (larger score, or equal score and earlier in A)
   for (int c = tid; c < C; c += AL_THREADS) {
-    const double v = c_score[c];
-    const double key = v != v ? -INFINITY : v;
-    int cnt = 0;
-    for (int o = 0; o < C; ++o) {
-      const double ov = c_score[o];
-      const double ok = ov != ov ? -INFINITY : ov;
-      cnt += (ok > key || (ok == key && o < c)) ? 1 : 0;
-    }
+    const int cnt = rs_rank(c_score, C, c);
     c_rank[c] = cnt;
     if (cnt < W) s_cand[cnt] = c;
   }
@@ -124,23 +116,10 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
   for (int p = wave; p < nn * nn; p += AL_THREADS / 64) {
     const int m2 = p / nn, m1 = p - m2 * nn;
     if (m1 >= m2) continue;
-    bool eq = n_ulen[m1] == n_ulen[m2];
-    if (eq) {
-      const int w1 = n_src[m1], w2 = n_src[m2], L = n_ulen[m1];
-      const int* y1 = yseq_in + (row0 + w1) * ycap;
-      const int* y2 = yseq_in + (row0 + w2) * ycap;
-      // 64 labels at a time from the end: hypotheses of a beam share their beginnings, a difference shows in the first round
-      for (int hi = min(L, ycap - 1); hi >= 1 && eq; hi -= 64) {
-        const int e = hi - lane;
-        bool same = true;
-        if (e >= 1) {
-          const int t1 = e <= o_ulen[w1] ? y1[e] : n_tok[m1];
-          const int t2 = e <= o_ulen[w2] ? y2[e] : n_tok[m2];
-          same = t1 == t2;
-        }
-        eq = __all(same ? 1 : 0) != 0;
-      }
-    }
+    const int w1 = n_src[m1], w2 = n_src[m2];
+    const bool eq = n_ulen[m1] == n_ulen[m2] &&
+                    rs_same_labels(yseq_in + (row0 + w1) * ycap, o_ulen[w1], n_tok[m1], yseq_in + (row0 + w2) * ycap, o_ulen[w2],
+                                   n_tok[m2], min(n_ulen[m1], ycap - 1), lane);
     if (lane == 0) s_eq[m2][m1] = eq ? 1 : 0;
   }
   __syncthreads();
@@ -192,53 +171,14 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
     }
   }
   if (tid == 0) nhyp_out[b] = nn;
-  for (int x = tid; x < nn * ycap; x += AL_THREADS) {
-    const int m = x / ycap, e = x - m * ycap;
-    if (e > n_ulen[m]) continue;
+  rs_copy_labels<AL_THREADS>(nn, ycap, tid, [&](int m) {
     const int w = n_src[m];
-    yseq_out[(row0 + m) * ycap + e] = e <= o_ulen[w] ? yseq_in[(row0 + w) * ycap + e] : n_tok[m];
-  }
-  const int nq = s_nf;
-  for (int x = tid; x < nq * fw; x += AL_THREADS) {
-    const int q = x / fw, e = x - q * fw;
+    return RsLabels{yseq_out + (row0 + m) * ycap, yseq_in + (row0 + w) * ycap, o_ulen[w], n_ulen[m], n_tok[m]};
+  });
+  rs_copy_labels<AL_THREADS>(s_nf, fw, tid, [&](int q) {
     const int w = f_slot[q];
-    if (e <= o_ulen[w]) fin_yseq[((long)b * fcap + f_pos[q]) * fw + e] = yseq_in[(row0 + w) * ycap + e];
-  }
-}
-
-struct GatherJobs {
-  const float* src[16];
-  float* dst[16];
-  const int* idx[16];
-  int nrows[16], width[16], src_rows[16], vec[16];
-  int n;
-};
-
-__global__ __launch_bounds__(256) void gather_rows_kernel(const GatherJobs j) {
-  const int job = blockIdx.y;
-  if (job >= j.n) return;
-  const float* s = j.src[job];
-  float* d = j.dst[job];
-  const int* idx = j.idx[job];
-  const int width = j.width[job], last = j.src_rows[job] - 1;
-  if (j.vec[job]) {
-    const int wq = width >> 2;
-    const long total = (long)j.nrows[job] * wq;
-    for (long x = (long)blockIdx.x * 256 + threadIdx.x; x < total; x += (long)gridDim.x * 256) {
-      const long r = x / wq;
-      const int c = (int)(x - r * wq);
-      const long sr = min(max(idx[r], 0), last);
-      reinterpret_cast<float4*>(d + r * width)[c] = reinterpret_cast<const float4*>(s + sr * width)[c];
-    }
-  } else {
-    const long total = (long)j.nrows[job] * width;
-    for (long x = (long)blockIdx.x * 256 + threadIdx.x; x < total; x += (long)gridDim.x * 256) {
-      const long r = x / width;
-      const int c = (int)(x - r * width);
-      const long sr = min(max(idx[r], 0), last);
-      d[r * width + c] = s[sr * width + c];
-    }
-  }
+    return RsLabels{fin_yseq + ((long)b * fcap + f_pos[q]) * fw, yseq_in + (row0 + w) * ycap, o_ulen[w], o_ulen[w], 0};
+  });
 }
 
 }  // namespace
@@ -259,34 +199,6 @@ int eamd_rnnt_alsd_step(const float* rec, const int32_t* hlens, const double* sc
   hipLaunchKernelGGL(rnnt_alsd_step_kernel, dim3(n), dim3(AL_THREADS), 0, (hipStream_t)stream, rec, hlens, score_in, ulen_in, nhyp_in,
                      yseq_in, score_out, ulen_out, nhyp_out, yseq_out, fin_score, fin_len, fin_yseq, nfin, par,
                      reinterpret_cast<long long*>(tok), live, frame, W, V, T, u_max, i);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
-}
-
-int eamd_gather_rows(const float* const* src, float* const* dst, const int32_t* const* idx, const int32_t* nrows, const int32_t* width,
-                     const int32_t* src_rows, int njobs, void* stream) {
-  if (!src || !dst || !idx || !nrows || !width || !src_rows || njobs <= 0 || njobs > 16) return EAMD_EINVAL;
-  GatherJobs j;
-  long most = 0;
-  for (int q = 0; q < 16; ++q) {
-    const bool on = q < njobs;
-    j.src[q] = on ? src[q] : nullptr;
-    j.dst[q] = on ? dst[q] : nullptr;
-    j.idx[q] = on ? idx[q] : nullptr;
-    j.nrows[q] = j.width[q] = j.src_rows[q] = j.vec[q] = 0;
-    if (!on) continue;
-    if (!src[q] || !dst[q] || !idx[q] || nrows[q] < 0 || width[q] < 1 || src_rows[q] < 1) return EAMD_EINVAL;
-    if ((((uintptr_t)src[q] | (uintptr_t)dst[q] | (uintptr_t)idx[q]) & 3)) return EAMD_EUNSUPPORTED;
-    j.nrows[q] = nrows[q];
-    j.width[q] = width[q];
-    j.src_rows[q] = src_rows[q];
-    j.vec[q] = width[q] % 4 == 0 && !(((uintptr_t)src[q] | (uintptr_t)dst[q]) & 15);
-    const long work = (long)nrows[q] * (j.vec[q] ? width[q] / 4 : width[q]);
-    most = work > most ? work : most;
-  }
-  j.n = njobs;
-  const unsigned bx = most == 0 ? 1 : (unsigned)((most + 255) / 256 < 64 ? (most + 255) / 256 : 64);
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(bx, njobs), dim3(256), 0, (hipStream_t)stream, j);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }

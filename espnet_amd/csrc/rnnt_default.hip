@@ -10,11 +10,11 @@
 //                            token (tok), the pool row to write (dst), the cell kernels' mask (live), the encoder row (frame) and
 //                            the scatter's mask (alive).  A is kept sorted by (score descending, insertion order ascending): the
 //                            reference's first maximum in list order is entry 0, and cutting A is a cut of the ranks.  Ranks come
-//                            from counting in LDS, as in rnnt_alsd.hip.  Labels are not kept: every pop appends one (parent record,
+//                            from counting in LDS with rs_key's order (A's tie is the insertion order, and B's two orders come
+//                            from one pass, so the loops stay here).  Labels are not kept: every pop appends one (parent record,
 //                            token) pair to the utterance's log, from which the host rebuilds the sequences.
-//   eamd_scatter_rows        up to 16 masked row scatters dst_j[idx_j[r], :] = src_j[r, :] in one launch: the new prediction-network
-//                            state of every layer into the pool rows the step kernel named.
-// Plain stores, no atomics: a workgroup owns its utterance's rows of every array.
+// The new prediction-network state of every layer goes into the pool rows the step kernel named by eamd_scatter_rows
+// (row_moves.hip).  Plain stores, no atomics: a workgroup owns its utterance's rows of every array.
 #include "common.h"
 #include "rnnt_search.h"
 #include "../../include/espnet_amd.h"
@@ -27,8 +27,6 @@ constexpr int DF_A = DF_P + DF_W;              // A before the cut: P kept entri
 constexpr int DF_THREADS = 256;
 // columns of ctr [n][8]
 constexpr int DC_T = 0, DC_POPS = 1, DC_NA = 2, DC_NB = 3, DC_NLOG = 4, DC_SEQ = 5, DC_CUR = 6, DC_MAXPOPS = 7;
-
-__device__ __forceinline__ double df_key(double v) { return v != v ? -INFINITY : v; }
 
 __global__ __launch_bounds__(DF_THREADS) void rnnt_default_step_kernel(
     const float* __restrict__ rec, const int* __restrict__ hlens, double* __restrict__ a_score, int* __restrict__ a_seq,
@@ -103,11 +101,11 @@ __global__ __launch_bounds__(DF_THREADS) void rnnt_default_step_kernel(
   __syncthreads();
   // position in A: entries ahead (larger score, or equal score and earlier insertion); entry 0 is max(A), the first one in list order
   for (int x = tid; x < nA; x += DF_THREADS) {
-    const double key = df_key(sa_score[x]);
+    const double key = rs_key(sa_score[x]);
     const int sq = sa_seq[x];
     int cnt = 0;
     for (int o = 0; o < nA; ++o) {
-      const double ok = df_key(sa_score[o]);
+      const double ok = rs_key(sa_score[o]);
       cnt += (ok > key || (ok == key && sa_seq[o] < sq)) ? 1 : 0;
     }
     sa_pos[x] = cnt;
@@ -115,7 +113,7 @@ __global__ __launch_bounds__(DF_THREADS) void rnnt_default_step_kernel(
   }
   __syncthreads();
   const double bound = s_bound;
-  const bool mine = tid < nB && df_key(sb_score[tid]) > bound;          // nB <= P <= DF_THREADS: one entry of B per thread
+  const bool mine = tid < nB && rs_key(sb_score[tid]) > bound;          // nB <= P <= DF_THREADS: one entry of B per thread
   if (tid < nB) sb_ahead[tid] = mine ? 1 : 0;
   const int nahead = __syncthreads_count(mine ? 1 : 0);
   const bool turn = nahead >= W;                                        // the frame ends
@@ -123,10 +121,10 @@ __global__ __launch_bounds__(DF_THREADS) void rnnt_default_step_kernel(
   if (turn && t1 >= Tb) {
     // the last frame: B = ahead in its stable ascending order, the list the reference sorts into the n-best
     if (mine) {
-      const double key = df_key(sb_score[tid]);
+      const double key = rs_key(sb_score[tid]);
       int rank = 0;
       for (int o = 0; o < nB; ++o) {
-        const double ok = df_key(sb_score[o]);
+        const double ok = rs_key(sb_score[o]);
         rank += (sb_ahead[o] && (ok < key || (ok == key && o < tid))) ? 1 : 0;
       }
       b_score[a0 + rank] = sb_score[tid];
@@ -156,11 +154,11 @@ __global__ __launch_bounds__(DF_THREADS) void rnnt_default_step_kernel(
   const int shift = pop ? 1 : 0;
   if (turn) {
     if (mine) {
-      const double key = df_key(sb_score[tid]);
-      int rank = 0, pos = 0;
+      const double key = rs_key(sb_score[tid]);
+      int rank = 0, pos = 0;                                            // both orders from one pass over B
       for (int o = 0; o < nB; ++o) {
         if (!sb_ahead[o]) continue;
-        const double ok = df_key(sb_score[o]);
+        const double ok = rs_key(sb_score[o]);
         rank += (ok < key || (ok == key && o < tid)) ? 1 : 0;
         pos += (ok > key || (ok == key && o < tid)) ? 1 : 0;
       }
@@ -231,37 +229,6 @@ __global__ __launch_bounds__(DF_THREADS) void rnnt_default_step_kernel(
   }
 }
 
-struct ScatterJobs {
-  const float* src[16];
-  float* dst[16];
-  const int* idx[16];
-  const unsigned char* mask[16];
-  int nrows[16], width[16], dst_rows[16], vec[16];
-  int n;
-};
-
-__global__ __launch_bounds__(256) void scatter_rows_kernel(const ScatterJobs j) {
-  const int job = blockIdx.y;
-  if (job >= j.n) return;
-  const float* s = j.src[job];
-  float* d = j.dst[job];
-  const int* idx = j.idx[job];
-  const unsigned char* mask = j.mask[job];
-  const int width = j.width[job], rows = j.dst_rows[job];
-  const int wq = j.vec[job] ? width >> 2 : width;
-  const long total = (long)j.nrows[job] * wq;
-  for (long x = (long)blockIdx.x * 256 + threadIdx.x; x < total; x += (long)gridDim.x * 256) {
-    const long r = x / wq;
-    const int col = (int)(x - r * wq);
-    const int dr = idx[r];
-    if (dr < 0 || dr >= rows || (mask && !mask[r])) continue;
-    if (j.vec[job])
-      reinterpret_cast<float4*>(d + (long)dr * width)[col] = reinterpret_cast<const float4*>(s + r * width)[col];
-    else
-      d[(long)dr * width + col] = s[r * width + col];
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -280,35 +247,6 @@ int eamd_rnnt_default_step(const float* rec, const int32_t* hlens, double* a_sco
   hipLaunchKernelGGL(rnnt_default_step_kernel, dim3(n), dim3(DF_THREADS), 0, (hipStream_t)stream, rec, hlens, a_score, a_seq, a_row,
                      a_log, a_tok, b_score, b_row, b_log, cur_score, ctr, log, flags, par, reinterpret_cast<long long*>(tok), dst, live,
                      frame, alive, n, W, V, T, P, k, log_cap);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
-}
-
-int eamd_scatter_rows(float* const* dst, const float* const* src, const int32_t* const* idx, const uint8_t* const* mask,
-                      const int32_t* nrows, const int32_t* width, const int32_t* dst_rows, int njobs, void* stream) {
-  if (!dst || !src || !idx || !mask || !nrows || !width || !dst_rows || njobs <= 0 || njobs > 16) return EAMD_EINVAL;
-  ScatterJobs j;
-  long most = 0;
-  for (int q = 0; q < 16; ++q) {
-    const bool on = q < njobs;
-    j.src[q] = on ? src[q] : nullptr;
-    j.dst[q] = on ? dst[q] : nullptr;
-    j.idx[q] = on ? idx[q] : nullptr;
-    j.mask[q] = on ? mask[q] : nullptr;
-    j.nrows[q] = j.width[q] = j.dst_rows[q] = j.vec[q] = 0;
-    if (!on) continue;
-    if (!src[q] || !dst[q] || !idx[q] || nrows[q] < 0 || width[q] < 1 || dst_rows[q] < 1) return EAMD_EINVAL;
-    if ((((uintptr_t)src[q] | (uintptr_t)dst[q] | (uintptr_t)idx[q]) & 3)) return EAMD_EUNSUPPORTED;
-    j.nrows[q] = nrows[q];
-    j.width[q] = width[q];
-    j.dst_rows[q] = dst_rows[q];
-    j.vec[q] = width[q] % 4 == 0 && !(((uintptr_t)src[q] | (uintptr_t)dst[q]) & 15);
-    const long work = (long)nrows[q] * (j.vec[q] ? width[q] / 4 : width[q]);
-    most = work > most ? work : most;
-  }
-  j.n = njobs;
-  const unsigned bx = most == 0 ? 1 : (unsigned)((most + 255) / 256 < 64 ? (most + 255) / 256 : 64);
-  hipLaunchKernelGGL(scatter_rows_kernel, dim3(bx, njobs), dim3(256), 0, (hipStream_t)stream, j);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }

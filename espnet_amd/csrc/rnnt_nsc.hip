@@ -13,8 +13,8 @@
 //                        other parity of `kept` and the pair list of the next frame; and leaves per row what the rest of the pass
 //                        needs: the block row whose prediction-network state it continues (par), the appended token (tok), the
 //                        cell kernels' mask (live) and, per history level, the row of the stacked lin_dec outputs it takes (hidx).
-//                        Selection is a rank-by-counting sort in LDS (stable: equal scores keep the list's order, NaN as -inf);
-//                        prefix tests compare lengths and then tokens, one wave per pair.
+//                        Selection is a rank-by-counting sort in LDS (rs_rank: stable, equal scores keep the list's order, NaN as
+//                        -inf); prefix tests compare lengths and then tokens, one wave per pair (rs_same_labels).
 // Prefix rescoring reads every pair term from the history rows of the LONGER hypothesis j: term a (a = delta .. 1) is
 // logp(joint(enc_t, hist[a] of j))[y_j[len_j - a]], where hist[a] is lin_dec of the prediction output of y_j[:-a].  The reference
 // takes the first term from hyps[i].y[-1]: the prediction output of the same labels, hence the same vector.
@@ -35,8 +35,6 @@ constexpr int NS_A = 3;                        // prefix_alpha at most
 constexpr int NS_D = NS_W * NS_W;              // extensions at most: W slots x k <= W tokens
 constexpr int NS_M = NS_W * NS_N + NS_W;       // entries of S + V at most
 constexpr int NS_THREADS = 256;
-
-__device__ __forceinline__ double ns_key(double v) { return v != v ? -INFINITY : v; }
 
 __global__ __launch_bounds__(NS_THREADS) void rnnt_nsc_step_kernel(
     const float* __restrict__ rec, const float* __restrict__ pair_lp, const int* __restrict__ hlens, double* __restrict__ score,
@@ -73,18 +71,7 @@ __global__ __launch_bounds__(NS_THREADS) void rnnt_nsc_step_kernel(
       live[row0 + tid] = 0;
       for (int a = 0; a < LV; ++a) hidx[a * R + row0 + tid] = hrow(b0 + tid, a);
     }
-    if (last) {
-      const int nb = min(max(count[kp * n + b], 0), W);
-      if (tid == 0) count[ko * n + b] = nb;
-      if (tid < nb) {
-        score[out0 + tid] = score[b0 + tid];
-        ulen[out0 + tid] = ulen[b0 + tid];
-      }
-      for (int x = tid; x < nb * ycap; x += NS_THREADS) {
-        const int w = x / ycap, e = x - w * ycap;
-        if (e <= min(max(ulen[b0 + w], 0), ycap - 1)) yseq[(long)(out0 + w) * ycap + e] = yseq[(long)(b0 + w) * ycap + e];
-      }
-    }
+    if (last) rs_carry_block<NS_THREADS>(score, ulen, count, yseq, ycap, W, kp * n + b, ko * n + b, b0, out0, tid);
     return;
   }
   const int nc = min(max(count[cin * n + b], 0), W);
@@ -100,21 +87,13 @@ __global__ __launch_bounds__(NS_THREADS) void rnnt_nsc_step_kernel(
     }
     if (v == 0 && tid >= 64 && tid < 64 + W * alpha) s_pl[tid - 64] = pair_lp[(long)row0 * alpha + tid - 64];
     __syncthreads();
-    // which slot's labels begin which other slot's: lengths, then tokens, 64 at a time from the end of the shorter one
+    // which slot's labels begin which other slot's: lengths, then the tokens of the shorter one
     const int dmax = v == 0 ? max(alpha, 1) : 1;
     for (int q = wave; q < nc * nc; q += NS_THREADS / 64) {
-      const int i = q / nc, j = q - i * nc;
-      const int dl = h_ulen[j] - h_ulen[i];
-      bool pre = dl >= 1 && dl <= dmax;
-      if (pre) {
-        const int* y1 = yseq + (long)(in0 + i) * ycap;
-        const int* y2 = yseq + (long)(in0 + j) * ycap;
-        for (int hi = h_ulen[i]; hi >= 1 && pre; hi -= 64) {
-          const int x = hi - lane;
-          const bool same = x >= 1 ? y1[x] == y2[x] : true;
-          pre = __all(same ? 1 : 0) != 0;
-        }
-      }
+      const int i = q / nc, j = q - i * nc, L = h_ulen[i];
+      const int dl = h_ulen[j] - L;
+      const bool pre = dl >= 1 && dl <= dmax &&
+                       rs_same_labels(yseq + (long)(in0 + i) * ycap, L, 0, yseq + (long)(in0 + j) * ycap, L, 0, L, lane);
       if (lane == 0) s_pre[i][j] = pre ? dl : 0;
     }
     // hyps: at v == 0 kept by length descending, stable; else the block's own order
@@ -168,12 +147,7 @@ __global__ __launch_bounds__(NS_THREADS) void rnnt_nsc_step_kernel(
     if (tid == 0) nS[b] = ns0 + nc;
     const int nok = __syncthreads_count(ok ? 1 : 0);
     if (ok) {
-      const double key = ns_key(d_score[tid]);
-      int cnt = 0;
-      for (int o = 0; o < nd; ++o) {
-        const double okey = ns_key(d_score[o]);
-        cnt += (d_ok[o] && (okey > key || (okey == key && o < tid))) ? 1 : 0;
-      }
+      const int cnt = rs_rank(d_score, nd, tid, [&](int o) { return d_ok[o] != 0; });
       if (cnt < W) s_sel[cnt] = tid;
     }
     __syncthreads();
@@ -198,13 +172,11 @@ __global__ __launch_bounds__(NS_THREADS) void rnnt_nsc_step_kernel(
           for (int a = 0; a < LV; ++a) hidx[a * R + r] = hrow(in0 + tid, a);
         }
       }
-      for (int x = tid; x < nv * ycap; x += NS_THREADS) {
-        const int m = x / ycap, e = x - m * ycap;
+      rs_copy_labels<NS_THREADS>(nv, ycap, tid, [&](int m) {
         const int c = s_sel[m], w = s_perm[c / k], jx = c % k;
-        if (e > min(h_ulen[w] + 1, ycap - 1)) continue;
-        yseq[(long)(out0 + m) * ycap + e] =
-            e <= h_ulen[w] ? yseq[(long)(in0 + w) * ycap + e] : min(max((int)s_rec[w * RW + 1 + k + jx], 0), V - 1);
-      }
+        return RsLabels{yseq + (long)(out0 + m) * ycap, yseq + (long)(in0 + w) * ycap, h_ulen[w], min(h_ulen[w] + 1, ycap - 1),
+                        min(max((int)s_rec[w * RW + 1 + k + jx], 0), V - 1)};
+      });
       return;
     }
     if (tid < nv) {                            // N == 1: S is this call's blank continuations, V follows
@@ -232,12 +204,7 @@ __global__ __launch_bounds__(NS_THREADS) void rnnt_nsc_step_kernel(
   __syncthreads();
   // the frame's end: the first W of sorted(S + V, reverse=True) are the next kept
   if (tid < nm) {
-    const double key = ns_key(m_score[tid]);
-    int cnt = 0;
-    for (int o = 0; o < nm; ++o) {
-      const double okey = ns_key(m_score[o]);
-      cnt += (okey > key || (okey == key && o < tid)) ? 1 : 0;
-    }
+    const int cnt = rs_rank(m_score, nm, tid);
     if (cnt < W) s_sel[cnt] = tid;             // the extensions' s_sel has been read: m_cand holds it
   }
   __syncthreads();
@@ -285,11 +252,9 @@ __global__ __launch_bounds__(NS_THREADS) void rnnt_nsc_step_kernel(
     }
   }
   __syncthreads();
-  for (int x = tid; x < nn * ycap; x += NS_THREADS) {
-    const int m = x / ycap, e = x - m * ycap;
-    if (e > k_u[m]) continue;
-    yseq[(long)(out0 + m) * ycap + e] = e <= k_pu[m] ? yseq[(long)k_src[m] * ycap + e] : k_tk[m];
-  }
+  rs_copy_labels<NS_THREADS>(nn, ycap, tid, [&](int m) {
+    return RsLabels{yseq + (long)(out0 + m) * ycap, yseq + (long)k_src[m] * ycap, k_pu[m], k_u[m], k_tk[m]};
+  });
 }
 
 }  // namespace
@@ -306,11 +271,8 @@ int eamd_rnnt_nsc_step(const float* rec, const float* pair_lp, const int32_t* hl
   if (N >= 1 && v > (N == 1 ? 0 : N)) return EAMD_EINVAL;
   // one array handed in for two operands: a workgroup's stores would meet its own loads.  (The block a call reads and the block it
   // writes are told apart by (v, p) inside one allocation, so they cannot be the same.)
-  const int32_t* ints[] = {ulen, count, yseq, s_src, nS, par, hidx, pairs};
-  for (int x = 0; x < 8; ++x)
-    for (int y = x + 1; y < 8; ++y)
-      if (ints[x] == ints[y]) return EAMD_EINVAL;
-  if (score == s_score || rec == pair_lp) return EAMD_EINVAL;
+  const void* const ints[] = {ulen, count, yseq, s_src, nS, par, hidx, pairs};
+  if (!rs_distinct(ints) || score == s_score || rec == pair_lp) return EAMD_EINVAL;
   if (W > NS_W || W > V || N < 1 || N > NS_N || alpha < 0 || alpha > NS_A) return EAMD_EUNSUPPORTED;
   if ((int64_t)(N + 2) * (1 + alpha) * n * W > 0x7fffffff || (int64_t)n * T > 0x7fffffff || 1 + (int64_t)T * N > 0x7fffffff / NS_W)
     return EAMD_EUNSUPPORTED;

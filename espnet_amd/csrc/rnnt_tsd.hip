@@ -10,9 +10,9 @@
 //                        frame; updates A; on a pass v < M - 1 writes the block of pass v + 1, at v == M - 1 the other parity of B;
 //                        and leaves per row what the rest of the pass needs: the block row whose prediction-network state it
 //                        continues (par), the appended token (tok) and the cell kernels' mask (live).  Selection is a
-//                        rank-by-counting sort in LDS (stable: equal scores keep the list's order); equal label sequences are found
-//                        by comparing lengths and tokens, one wave per pair; the only traffic that grows with T is the copy of W
-//                        hypotheses' labels.
+//                        rank-by-counting sort in LDS (rs_rank: stable, equal scores keep the list's order); equal label sequences
+//                        are found by comparing lengths and tokens, one wave per pair (rs_same_labels); the only traffic that grows
+//                        with T is the copy of W hypotheses' labels (rs_copy_labels).
 // Hypotheses live in M + 1 blocks of n * W rows: block 0 and block M are the two parities of B, block v (1 <= v < M) is the C of pass
 // v.  Block row = block * n * W + b * W + w.  Plain stores, no atomics, no scratch buffers: a workgroup owns its utterance's rows.
 #include "common.h"
@@ -26,8 +26,6 @@ constexpr int TS_M = 4;                        // passes per frame at most
 constexpr int TS_D = TS_W * TS_W;              // candidates of D at most: W slots x k <= W tokens
 constexpr int TS_A = TS_W * TS_M;              // entries of A at most
 constexpr int TS_THREADS = 256;
-
-__device__ __forceinline__ double ts_key(double v) { return v != v ? -INFINITY : v; }
 
 __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     const float* __restrict__ rec, const int* __restrict__ hlens, double* __restrict__ score, int* __restrict__ ulen,
@@ -59,18 +57,7 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
       tok[row0 + tid] = 0;
       live[row0 + tid] = 0;
     }
-    if (v == M - 1) {
-      const int nb = min(max(count[(p ? M : 0) * n + b], 0), W);
-      if (tid == 0) count[cout * n + b] = nb;
-      if (tid < nb) {
-        score[out0 + tid] = score[b0 + tid];
-        ulen[out0 + tid] = ulen[b0 + tid];
-      }
-      for (int x = tid; x < nb * ycap; x += TS_THREADS) {
-        const int w = x / ycap, e = x - w * ycap;
-        if (e <= min(max(ulen[b0 + w], 0), ycap - 1)) yseq[(long)(out0 + w) * ycap + e] = yseq[(long)(b0 + w) * ycap + e];
-      }
-    }
+    if (v == M - 1) rs_carry_block<TS_THREADS>(score, ulen, count, yseq, ycap, W, (p ? M : 0) * n + b, cout * n + b, b0, out0, tid);
     return;
   }
   // everything the decisions need is fetched here, side by side: the stages below depend on each other, and a global load in each
@@ -92,20 +79,11 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     sa_ulen[e] = min(max(ulen[src], 0), ycap - 1);
   }
   __syncthreads();
-  // which C slot holds the labels of which entry of A: lengths, then tokens, 64 at a time from the end (hypotheses of a beam share
-  // their beginnings, a difference shows in the first round)
+  // which C slot holds the labels of which entry of A: lengths, then tokens
   for (int q = wave; q < nc * na0; q += TS_THREADS / 64) {
-    const int c = q / na0, e = q - c * na0;
-    bool eq = c_ulen[c] == sa_ulen[e];
-    if (eq) {
-      const int* y1 = yseq + (long)(in0 + c) * ycap;
-      const int* y2 = yseq + (long)sa_src[e] * ycap;
-      for (int hi = c_ulen[c]; hi >= 1 && eq; hi -= 64) {
-        const int x = hi - lane;
-        const bool same = x >= 1 ? y1[x] == y2[x] : true;
-        eq = __all(same ? 1 : 0) != 0;
-      }
-    }
+    const int c = q / na0, e = q - c * na0, L = c_ulen[c];
+    const bool eq = L == sa_ulen[e] &&
+                    rs_same_labels(yseq + (long)(in0 + c) * ycap, L, 0, yseq + (long)sa_src[e] * ycap, L, 0, L, lane);
     if (lane == 0) s_eq[c][e] = eq ? 1 : 0;
   }
   __syncthreads();
@@ -152,12 +130,7 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     }
     __syncthreads();
     for (int c = tid; c < nd; c += TS_THREADS) {
-      const double key = ts_key(d_score[c]);
-      int cnt = 0;
-      for (int o = 0; o < nd; ++o) {
-        const double ok = ts_key(d_score[o]);
-        cnt += (ok > key || (ok == key && o < c)) ? 1 : 0;
-      }
+      const int cnt = rs_rank(d_score, nd, c);
       if (cnt < W) s_sel[cnt] = c;
     }
     __syncthreads();
@@ -178,23 +151,16 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
         live[r] = 0;
       }
     }
-    for (int x = tid; x < nn * ycap; x += TS_THREADS) {
-      const int m = x / ycap, e = x - m * ycap;
+    rs_copy_labels<TS_THREADS>(nn, ycap, tid, [&](int m) {
       const int c = s_sel[m], w = c / k, j = c - w * k;
-      if (e > min(c_ulen[w] + 1, ycap - 1)) continue;
-      yseq[(long)(out0 + m) * ycap + e] =
-          e <= c_ulen[w] ? yseq[(long)(in0 + w) * ycap + e] : min(max((int)s_rec[w * RW + 1 + k + j], 0), V - 1);
-    }
+      return RsLabels{yseq + (long)(out0 + m) * ycap, yseq + (long)(in0 + w) * ycap, c_ulen[w], min(c_ulen[w] + 1, ycap - 1),
+                      min(max((int)s_rec[w * RW + 1 + k + j], 0), V - 1)};
+    });
     return;
   }
   // the frame's end: the first W of sorted(A, reverse=True) are the next B
   if (tid < na) {
-    const double key = ts_key(sa_score[tid]);
-    int cnt = 0;
-    for (int o = 0; o < na; ++o) {
-      const double ok = ts_key(sa_score[o]);
-      cnt += (ok > key || (ok == key && o < tid)) ? 1 : 0;
-    }
+    const int cnt = rs_rank(sa_score, na, tid);
     if (cnt < W) s_sel[cnt] = tid;
   }
   __syncthreads();
@@ -213,11 +179,10 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     tok[r] = 0;
     live[r] = 0;
   }
-  for (int x = tid; x < nn * ycap; x += TS_THREADS) {
-    const int m = x / ycap, e = x - m * ycap;
+  rs_copy_labels<TS_THREADS>(nn, ycap, tid, [&](int m) {
     const int a = s_sel[m];
-    if (e <= sa_ulen[a]) yseq[(long)(out0 + m) * ycap + e] = yseq[(long)sa_src[a] * ycap + e];
-  }
+    return RsLabels{yseq + (long)(out0 + m) * ycap, yseq + (long)sa_src[a] * ycap, sa_ulen[a], sa_ulen[a], 0};
+  });
 }
 
 }  // namespace
@@ -231,11 +196,8 @@ int eamd_rnnt_tsd_step(const float* rec, const int32_t* hlens, double* score, in
   if (n < 1 || W < 1 || V < 2 || T < 1 || t < 0 || v < 0 || (M >= 1 && v >= M) || (p != 0 && p != 1)) return EAMD_EINVAL;
   // one array handed in for two operands: a workgroup's stores would meet its own loads.  (The block a pass reads and the block it
   // writes are told apart by (v, p) inside one allocation, so they cannot be the same.)
-  const int32_t* ints[] = {ulen, count, yseq, a_src, nA, par};
-  for (int x = 0; x < 6; ++x)
-    for (int y = x + 1; y < 6; ++y)
-      if (ints[x] == ints[y]) return EAMD_EINVAL;
-  if (score == a_score) return EAMD_EINVAL;
+  const void* const ints[] = {ulen, count, yseq, a_src, nA, par};
+  if (!rs_distinct(ints) || score == a_score) return EAMD_EINVAL;
   if (W > TS_W || W > V || M < 1 || M > TS_M) return EAMD_EUNSUPPORTED;
   if ((int64_t)(M + 1) * n * W > 0x7fffffff || (int64_t)n * T > 0x7fffffff || 1 + (int64_t)T * (M - 1) > 0x7fffffff / TS_W)
     return EAMD_EUNSUPPORTED;

@@ -40,7 +40,13 @@ computed is this package's own design:
     prediction-network states in a pool of two frame-parity regions, labels as a log of (parent, token) records; finishing a pop,
     ending a frame and selecting the next pop in one launch (eamd_rnnt_default_step); the host reads the done flags after the
     first beam x frames steps and after every further chunk, then ONE result copy; an utterance whose frame wants more pops than
-    default_max_pops (an untrained, flat model does) overflows and is searched again per utterance.
+    default_max_pops (an untrained, flat model does) overflows and is searched again per utterance;
+  * what the five batched searches share is written once, above them: the loop over the per-utterance search for a batch the device
+    loops do not take (`_fallback` over `_one`), the lengths (`_lengths`), encoder projection + chunking by *_max_rows + the call's one
+    result copy (`_chunks`), one result layout per search from which the buffer is both built and taken apart (`_pack` / `_unpack`),
+    the n-best order (`_nbest`) and the scratch builders (`_pred_ws`, `_block_ws`, `_frame_rows`); the five step loops differ for
+    real and stay apart.  On the device the same holds for rnnt_search.h (score key, stable rank, label comparison and copy) and
+    row_moves.hip (eamd_gather_rows / eamd_scatter_rows).
 
 Prediction networks take part through one of three protocols: `step(tokens, states)` (batched; DecoderRNNT),
 `batch_step(yseqs)` (DecoderTT: the reference's batch_score, whose outputs depend on the batch a prefix is first computed
@@ -121,6 +127,39 @@ class _Pred:
 
 
 _SEARCHES = {"default": "_default", "tsd": "_tsd", "alsd": "_alsd", "nsc": "_nsc"}
+
+# ---- result layouts -------------------------------------------------------------------------------------------------------
+# A batched search hands its results to the host in ONE int32 buffer.  What is in it is said once, by a layout: an ordered list of
+# (name, shape, numpy dtype) with int32 / float32 fields taking one word per element and float64 fields two.  `_pack` builds the
+# buffer on the device from it, `_unpack` takes the host copy apart by it.
+_TORCH = {np.int32: torch.int32, np.float32: torch.float32, np.float64: torch.float64}
+
+
+def _fields(layout, o=0):
+    """(name, shape, dtype, first word, words) of every field of a layout that starts at word o"""
+    for name, shape, dt in layout:
+        words = int(np.prod(shape, dtype=np.int64)) * (np.dtype(dt).itemsize // 4)
+        yield name, shape, dt, o, words
+        o += words
+
+
+def _pack(layout, tensors):
+    """the layout's fields, given in its order as tensors (float fields contiguous), as one int32 buffer"""
+    parts = []
+    for (name, shape, dt), x in zip(layout, tensors):
+        assert tuple(x.shape) == tuple(shape) and x.dtype == _TORCH[dt], name
+        parts.append((x if dt is np.int32 else x.view(torch.int32)).reshape(-1))
+    return torch.cat(parts)
+
+
+def _unpack(layout, words, o=0):
+    """words: int32 numpy array that holds a packed layout from word o on -> ({name: array}, the first word after it)"""
+    out = {}
+    for name, shape, dt, first, n in _fields(layout, o):
+        a = words[first:first + n]
+        out[name] = (a if dt is np.int32 else a.copy().view(dt)).reshape(shape)      # the copy aligns a float64 field
+        o = first + n
+    return out, o
 
 
 class _Hyp:
@@ -237,6 +276,98 @@ class BeamSearchTransducer:
             t += f + 1                     # at most one symbol per frame (reference greedy_search)
         return Hypothesis(score=score, yseq=self._tree.labels(node))
 
+    # ---- batched searches: what all five share --------------------------------------------------------------------------
+    def _one(self, name, h):
+        """the per-utterance search `name` (looked up on self at call time) on one row of a batch"""
+        if hasattr(self.decoder, "att"):
+            self.decoder.att[0].reset()
+        with torch.no_grad():
+            return getattr(self, name)(h)
+
+    def _fallback(self, name, hs_pad, hlens):
+        """a batch the device loops do not take: a loop over the per-utterance search"""
+        B, T = hs_pad.shape[:2]
+        if hlens is None:
+            lens = [T] * B
+        else:
+            lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
+        return [self._one(name, hs_pad[b, :lens[b]]) for b in range(B)]
+
+    @staticmethod
+    def _lengths(hlens, B, T, dev):
+        """hlens (None / list / tensor) -> (frames per utterance on the host, the same as a device int32 vector), both in [0, T].
+        A device tensor is not read: its host list is [T] * B, the padded length, which only bounds the loops."""
+        # The clamp is every caller's: the kernels take T_b = max(0, min(hlens[b], T)) themselves, the host's (hl - 1).clamp(0, 1)
+        # and minimum(t, hl - 1).clamp_(min=0) give 0 for any length <= 0, and a loop length is a maximum over a chunk of frames,
+        # W * frames or alsd's t + min(u_max, t - 1) (<= -1 for t <= 0, clamped or not): a length <= 0 never sets it.
+        if hlens is None or torch.is_tensor(hlens):
+            frames = [T] * B
+            hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
+                  else hlens.to(device=dev, dtype=torch.int32).clamp(min=0, max=T))
+        else:
+            frames = [max(0, min(int(v), T)) for v in hlens]
+            hl = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
+        return frames, hl
+
+    def _chunks(self, hs_pad, nmax, rows):
+        """projects the encoder, runs rows(enc [B, T, J], b0, b1) -> (result buffer, its layout) on every chunk of nmax
+        utterances and reads all the buffers in the call's ONE blocking copy -> per chunk the layout's {name: host array}"""
+        B, T = hs_pad.shape[:2]
+        enc = self.decoder.joint_network.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
+        res = [rows(enc, b0, min(B, b0 + nmax)) for b0 in range(0, B, nmax)]
+        host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()
+        out, o = [], 0
+        for _buf, layout in res:
+            got, o = _unpack(layout, host, o)
+            out.append(got)
+        return out
+
+    def _nbest(self, hyps, length=lambda x: len(x.yseq)):
+        """the reference's n-best order: score / length descending (score with score_norm=False), equal keys in list order"""
+        if self.score_norm:
+            return sorted(hyps, key=lambda x: x.score / length(x), reverse=True)
+        return sorted(hyps, key=lambda x: x.score, reverse=True)
+
+    def _pred_ws(self, R, dev, copies=2):
+        """what _pred_step needs on R rows besides lin_dec's output `d`: the token and mask vectors (zero: nothing emitted),
+        `copies` copies of the prediction network's state (zero) and the step's intermediates"""
+        dec = self.decoder
+        H, L = dec.dunits, dec.dlayers
+        G = (4 if dec.dtype == "lstm" else 3) * H
+        f = dict(device=dev, dtype=torch.float32)
+        ws = dict(n=R)
+        ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
+        ws["live"] = torch.zeros(R, device=dev, dtype=torch.uint8)
+        ws["h"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(copies)]
+        ws["c"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(copies)]
+        ws["gx"] = [torch.empty(R, G, **f) for _ in range(L)]
+        ws["gates"] = [torch.empty(R, 4 * H, **f) for _ in range(L)]       # lstm: pre-activations / activated gates; gru: acts
+        ws["gh"] = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        return ws
+
+    def _block_ws(self, blocks, R, d, dev):
+        """tsd / nsc: the prediction network's state of `blocks` hypothesis blocks of R rows stacked [blocks * R, H] per layer (a
+        block row indexes it directly), one staging copy, and ws["blk"][j] = _pred_step's view of block j: state copy 0 = the
+        staging copy, copy 1 = the block's rows, d = d[j]"""
+        ws = self._pred_ws(R, dev, copies=1)
+        H = self.decoder.dunits
+        stage_h, stage_c = ws["h"][0], ws["c"][0]
+        ws["h"] = [torch.zeros(blocks * R, H, device=dev, dtype=torch.float32) for _ in stage_h]
+        ws["c"] = [torch.zeros(blocks * R, H, device=dev, dtype=torch.float32) for _ in stage_c]
+        ws["blk"] = [dict(ws, d=d[j], h=[stage_h, [x[j * R:(j + 1) * R] for x in ws["h"]]],
+                          c=[stage_c, [x[j * R:(j + 1) * R] for x in ws["c"]]]) for j in range(blocks)]
+        return ws
+
+    @staticmethod
+    def _frame_rows(hl, T, W, frames, levels=1):
+        """tsd / nsc: [frames, levels * n * W] int32, the encoder row of frame t for every row of a block, b * T + min(t, T_b - 1):
+        the same for all slots of an utterance and for each of `levels` stacked copies of the block"""
+        n, dev = hl.shape[0], hl.device
+        tt = torch.arange(frames, device=dev, dtype=torch.int32)
+        ft = torch.minimum(tt[:, None], (hl - 1)[None, :]).clamp_(min=0) + (torch.arange(n, device=dev, dtype=torch.int32) * T)
+        ft = ft.repeat_interleave(W, dim=1)
+        return (ft.repeat(1, levels) if levels > 1 else ft).contiguous()
+
     # ---- batched greedy ---------------------------------------------------------------------------------------------
     # The reference's greedy search emits at most one symbol per frame, so the utterances of a batch advance through the frames in
     # lock-step: frame t of all rows is one fused joint + argmax launch (eamd_rnnt_greedy_joint: the [B, V] logits are never stored),
@@ -251,12 +382,6 @@ class BeamSearchTransducer:
     graph_max_signatures = 16
     greedy_max_rows = 64              # rows per frame loop (eamd_rnnt_greedy_*, eamd_lstm_step_fwd); larger batches go in chunks
 
-    def _greedy_one(self, h):
-        if hasattr(self.decoder, "att"):
-            self.decoder.att[0].reset()
-        with torch.no_grad():
-            return self._greedy(h)
-
     def _greedy_batched_ok(self):
         from .transducer.rnn_decoder import DecoderRNNT
         dec = self.decoder
@@ -268,62 +393,35 @@ class BeamSearchTransducer:
         -> [Hypothesis(score, yseq)] * B, yseq[0] == blank: what __call__ returns per utterance with beam_size <= 1.
         DecoderRNNT (lstm / gru): the batched frame loop above, one blocking host read per call.  Other prediction networks:
         a loop over the per-utterance search."""
-        B, T = hs_pad.shape[:2]
         if not self._greedy_batched_ok():
-            if hlens is None:
-                lens = [T] * B
-            else:
-                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
-            return [self._greedy_one(hs_pad[b, :lens[b]]) for b in range(B)]
-        dev = hs_pad.device
+            return self._fallback("_greedy", hs_pad, hlens)
+        B, T = hs_pad.shape[:2]
         with torch.no_grad():
-            if hlens is None:
-                hl = torch.full((B,), T, dtype=torch.int32, device=dev)
-            elif torch.is_tensor(hlens):
-                hl = hlens.to(device=dev, dtype=torch.int32).clamp(max=T)
-            else:
-                hl = torch.tensor([min(int(v), T) for v in hlens], dtype=torch.int32).to(dev, non_blocking=True)
-            jn = self.decoder.joint_network
-            enc = jn.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
-            res = []
-            for b0 in range(0, B, self.greedy_max_rows):
-                b1 = min(B, b0 + self.greedy_max_rows)
-                res.append(self._greedy_rows(enc[b0:b1], hl[b0:b1]))
-            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
-        hyps, o = [], 0
-        for _buf, n, ycap in res:
-            yseq = host[o:o + n * ycap].reshape(n, ycap)
-            ylen = host[o + n * ycap:o + n * ycap + n]
-            score = host[o + n * ycap + n:o + n * ycap + 2 * n].view(np.float32)
-            hyps += [Hypothesis(score=float(score[i]), yseq=yseq[i, :ylen[i]].tolist()) for i in range(n)]
-            o += n * ycap + 2 * n
-        return hyps
+            _frames, hl = self._lengths(hlens, B, T, hs_pad.device)
+            res = self._chunks(hs_pad, self.greedy_max_rows, lambda enc, b0, b1: self._greedy_rows(enc[b0:b1], hl[b0:b1]))
+        return [Hypothesis(score=float(r["score"][i]), yseq=r["yseq"][i, :r["ylen"][i]].tolist())
+                for r in res for i in range(len(r["ylen"]))]
+
+    @staticmethod
+    def _greedy_layout(n, ycap):
+        return [("yseq", (n, ycap), np.int32), ("ylen", (n,), np.int32), ("score", (n,), np.float32)]
 
     def _greedy_ws(self, n, Tcap, dev):
-        """the buffers of one frame loop on n rows: results (yseq | ylen | score in one int32 buffer), both copies of the
-        prediction network's state, the step's intermediates and the device frame counter"""
+        """the buffers of one frame loop on n rows: the result buffer with its fields as views, both copies of the prediction
+        network's state, the step's intermediates and the device frame counter"""
         dec = self.decoder
-        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
-        G = (4 if dec.dtype == "lstm" else 3) * H
-        f = dict(device=dev, dtype=torch.float32)
-        ycap = Tcap + 1
-        ws = dict(n=n, Tcap=Tcap, ycap=ycap, graph=None, calls=0)
-        ws["res"] = torch.empty(n * ycap + 2 * n, device=dev, dtype=torch.int32)
-        ws["yseq"] = ws["res"][:n * ycap].view(n, ycap)
-        ws["ylen"] = ws["res"][n * ycap:n * ycap + n]
-        ws["score"] = ws["res"][n * ycap + n:].view(torch.float32)
-        ws["enc"] = torch.zeros(n, Tcap, J, **f)
+        J = dec.joint_dim
+        ws = self._pred_ws(n, dev)
+        ws.update(Tcap=Tcap, layout=self._greedy_layout(n, Tcap + 1), graph=None, calls=0)
+        fields = list(_fields(ws["layout"]))
+        ws["res"] = torch.empty(fields[-1][3] + fields[-1][4], device=dev, dtype=torch.int32)
+        for name, shape, dt, o, words in fields:
+            ws[name] = ws["res"][o:o + words].view(_TORCH[dt]).view(shape)
+        ws["enc"] = torch.zeros(n, Tcap, J, device=dev, dtype=torch.float32)
         ws["hl"] = torch.empty(n, device=dev, dtype=torch.int32)
         ws["t"] = torch.zeros(1, device=dev, dtype=torch.int32)
-        ws["tok"] = torch.empty(n, device=dev, dtype=torch.int64)
-        ws["live"] = torch.empty(n, device=dev, dtype=torch.uint8)
         ws["part"] = ops.rnnt_greedy_part(n, dec.odim, dev)
-        ws["d"] = torch.empty(n, J, **f)
-        ws["h"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
-        ws["c"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
-        ws["gx"] = [torch.empty(n, G, **f) for _ in range(L)]
-        ws["gates"] = [torch.empty(n, 4 * H, **f) for _ in range(L)]       # lstm: pre-activations / activated gates; gru: acts
-        ws["gh"] = [torch.empty(n, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        ws["d"] = torch.empty(n, J, device=dev, dtype=torch.float32)
         return ws
 
     def _pred_step(self, ws, src, dst, live):
@@ -359,7 +457,7 @@ class BeamSearchTransducer:
 
     def _greedy_rows(self, enc, hl):
         """the frame loop on n <= greedy_max_rows rows: enc (n, T, J) projected encoder states, hl (n,) int32 on the device
-        -> (result buffer, n, ycap), not yet read"""
+        -> (result buffer, its layout), not yet read"""
         from .. import graphs
         n, T, _J = enc.shape
         dev = enc.device
@@ -403,7 +501,7 @@ class BeamSearchTransducer:
                 ws["t"].zero_()
                 for _ in range((T + 1) // 2):
                     ws["graph"].replay()
-                return ws["res"].clone(), n, ws["ycap"]
+                return ws["res"].clone(), ws["layout"]
             except Exception as e:  # noqa: BLE001 - a step that cannot be captured: eager frame loops from now on
                 import logging
                 logging.getLogger(__name__).warning("greedy transducer frame graph disabled: %s", str(e)[:200])
@@ -413,7 +511,7 @@ class BeamSearchTransducer:
                 return self._greedy_rows(enc, hl)
         for t in range(T):
             self._frame(ws, t & 1, t, None)
-        return (ws["res"].clone() if self.graph_steps else ws["res"]), n, ws["ycap"]
+        return (ws["res"].clone() if self.graph_steps else ws["res"]), ws["layout"]
 
     # ---- default beam search ----------------------------------------------------------------------------------------
     def _default(self, h):
@@ -489,12 +587,6 @@ class BeamSearchTransducer:
     def _default_batched_ok(self):
         return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16
 
-    def _default_one(self, h):
-        if hasattr(self.decoder, "att"):
-            self.decoder.att[0].reset()
-        with torch.no_grad():
-            return self._default(h)
-
     @ops.inference_call
     def default_batch(self, hs_pad, hlens=None):
         """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
@@ -504,50 +596,27 @@ class BeamSearchTransducer:
         enqueued, `host_reads` the blocking reads (flags + the one result copy), `overflowed` the utterances that were searched
         again per utterance, `pops` per utterance (pops, frames, most pops of one frame) as the device counted them.
         Anything else: a loop over the per-utterance search."""
-        B, T = hs_pad.shape[:2]
         self.passes = self.host_reads = 0
         self.overflowed, self.pops = [], []
         if not self._default_batched_ok():
-            if hlens is None:
-                lens = [T] * B
-            else:
-                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
-            return [self._default_one(hs_pad[b, :lens[b]]) for b in range(B)]
-        dev = hs_pad.device
+            return self._fallback("_default", hs_pad, hlens)
+        B, T = hs_pad.shape[:2]
         W = min(self.beam_size, self.vocab_size)
         P = min(max(int(self.default_max_pops), W), 256)
         with torch.no_grad():
-            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: the padded T bounds the first chunk
-                frames = [T] * B
-                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
-                      else hlens.to(device=dev, dtype=torch.int32).clamp(min=0, max=T))
-            else:
-                frames = [max(0, min(int(v), T)) for v in hlens]
-                hl = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
-            enc = self.decoder.joint_network.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
-            nmax = max(1, int(self.default_max_rows))
-            res = []
-            for b0 in range(0, B, nmax):
-                b1 = min(B, b0 + nmax)
-                res.append(self._default_rows(enc[b0:b1], hl[b0:b1].contiguous(), W, P, max(frames[b0:b1])))
-            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one result copy
-            self.host_reads += 1
-        out, o = [], 0
-        for _buf, n, used in res:
-            score = host[o:o + 2 * n * P].copy().view(np.float64).reshape(n, P)
-            o += 2 * n * P
-            b_log, ctr = host[o:o + n * P].reshape(n, P), host[o + n * P:o + n * P + 8 * n].reshape(n, 8)
-            o += n * P + 8 * n
-            flags, lens = host[o:o + 2 * n].reshape(2, n), host[o + 2 * n:o + 3 * n]
-            o += 3 * n
-            log = host[o:o + n * used * 2].reshape(n, used, 2)
-            o += n * used * 2
-            for b in range(n):
+            frames, hl = self._lengths(hlens, B, T, hs_pad.device)    # a device tensor: the padded T bounds the first chunk
+            res = self._chunks(hs_pad, max(1, int(self.default_max_rows)), lambda enc, b0, b1: self._default_rows(
+                enc[b0:b1], hl[b0:b1].contiguous(), W, P, max(frames[b0:b1])))
+            self.host_reads += 1                                       # the call's one result copy
+        out = []
+        for r in res:
+            score, b_log, ctr, flags, lens, log = (r[name] for name in ("b_score", "b_log", "ctr", "flags", "hl", "log"))
+            for b in range(len(lens)):
                 g = len(out)
                 self.pops.append((int(ctr[b, 4]) if lens[b] else 0, int(lens[b]), int(ctr[b, 7])))
                 if flags[1, b] or not flags[0, b]:             # overflowed, or still running when the budget was spent
                     self.overflowed.append(g)
-                    out.append(self._default_one(hs_pad[g, :int(lens[b])]))
+                    out.append(self._one("_default", hs_pad[g, :int(lens[b])]))
                     continue
                 labels = {0: [self.blank]}
                 hyps = []
@@ -560,21 +629,23 @@ class BeamSearchTransducer:
                         par, tk = int(log[b, m, 0]), int(log[b, m, 1])
                         labels[m] = labels[par] + [tk] if tk else labels[par]
                     hyps.append(Hypothesis(score=float(score[b, j]), yseq=list(labels[int(b_log[b, j])])))
-                if self.score_norm:
-                    out.append(sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True))
-                else:
-                    out.append(sorted(hyps, key=lambda x: x.score, reverse=True))
+                out.append(self._nbest(hyps))
         return out
+
+    @staticmethod
+    def _default_layout(n, P, used):
+        """B's scores and records, the counters, the flags, the lengths and the `used` filled records per utterance of the log"""
+        return [("b_score", (n, P), np.float64), ("b_log", (n, P), np.int32), ("ctr", (n, 8), np.int32), ("flags", (2, n), np.int32),
+                ("hl", (n,), np.int32), ("log", (n, used, 2), np.int32)]
 
     def _default_ws(self, n, P, log_cap, dev):
         """the buffers of one step loop on n utterances: A, B, the pending pop, counters, flags and the label log, what
         eamd_rnnt_default_step leaves for the rest of the step, the state pool of 2 P rows per utterance, and the step's intermediates"""
         dec = self.decoder
         H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
-        G = (4 if dec.dtype == "lstm" else 3) * H
         f = dict(device=dev, dtype=torch.float32)
         i32 = dict(device=dev, dtype=torch.int32)
-        ws = dict(n=n)
+        ws = self._pred_ws(n, dev)                             # `live` starts at 0: the first step's pop is a carried entry
         ws["A"] = (torch.zeros(n, P, device=dev, dtype=torch.float64),) + tuple(torch.zeros(n, P, **i32) for _ in range(4))
         ws["B"] = (torch.zeros(n, P, device=dev, dtype=torch.float64),) + tuple(torch.zeros(n, P, **i32) for _ in range(2))
         ws["cur"] = torch.zeros(n, device=dev, dtype=torch.float64)
@@ -584,24 +655,16 @@ class BeamSearchTransducer:
         ws["par"] = torch.empty(n, **i32)
         ws["dst"] = torch.empty(n, **i32)
         ws["frame"] = torch.empty(n, **i32)
-        ws["tok"] = torch.zeros(n, device=dev, dtype=torch.int64)
-        ws["live"] = torch.zeros(n, device=dev, dtype=torch.uint8)
         ws["alive"] = torch.empty(n, device=dev, dtype=torch.uint8)
         ws["encr"] = torch.empty(n, J, **f)
         ws["d"] = torch.empty(n, J, **f)
         ws["pool_h"] = [torch.zeros(n * 2 * P, H, **f) for _ in range(L)]
         ws["pool_c"] = [torch.zeros(n * 2 * P, H, **f) for _ in range(L)]
-        ws["h"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
-        ws["c"] = [[torch.zeros(n, H, **f) for _ in range(L)] for _ in range(2)]
-        ws["gx"] = [torch.empty(n, G, **f) for _ in range(L)]
-        ws["gates"] = [torch.empty(n, 4 * H, **f) for _ in range(L)]
-        ws["gh"] = [torch.empty(n, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
         return ws
 
     def _default_rows(self, enc, hl, W, P, frames):
         """the step loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device, `frames` = the most
-        frames an utterance has -> (result buffer (int32 words: b_score | b_log | ctr | flags | hl | the log's used records), n,
-        records per utterance in the buffer); the flags are read here, the buffer is not"""
+        frames an utterance has -> (result buffer, its layout (_default_layout)); the flags are read here, the buffer is not"""
         n, T, J = enc.shape
         dev = enc.device
         dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
@@ -629,8 +692,7 @@ class BeamSearchTransducer:
         jobs = [(ws["pool_h"][l], ws["h"][1][l], ws["par"], None) for l in layers]
         if lstm:
             jobs += [(ws["pool_c"][l], ws["c"][1][l], ws["par"], None) for l in layers]
-        for j0 in range(0, len(jobs), 16):
-            ops.scatter_rows(jobs[j0:j0 + 16])
+        ops.scatter_rows(jobs)
         gather = [(ws["encr"], enc_rows, ws["frame"])] + [(ws["h"][0][l], ws["pool_h"][l], ws["par"]) for l in layers]
         scatter = [(ws["pool_h"][l], ws["h"][1][l], ws["dst"], ws["alive"]) for l in layers]
         if lstm:
@@ -638,11 +700,9 @@ class BeamSearchTransducer:
             scatter += [(ws["pool_c"][l], ws["c"][1][l], ws["dst"], ws["alive"]) for l in layers]
 
         def step():
-            for j0 in range(0, len(gather), 16):
-                ops.gather_rows(gather[j0:j0 + 16])
+            ops.gather_rows(gather)
             self._pred_step(ws, 0, 1, ws["live"])
-            for j0 in range(0, len(scatter), 16):
-                ops.scatter_rows(scatter[j0:j0 + 16])
+            ops.scatter_rows(scatter)
             rec = ops.transducer_expand_rows_dev(jn.joint_rows_d(ws["encr"], ws["d"]), k)
             ops.rnnt_default_step(rec, hl, ws["A"], ws["B"], ws["cur"], ws["ctr"], ws["log"], ws["flags"], ws["par"], ws["tok"],
                                   ws["dst"], ws["live"], ws["frame"], ws["alive"], W, V, T)
@@ -660,10 +720,8 @@ class BeamSearchTransducer:
                 step()
             steps += more
         self.passes += steps
-        used = steps + 1
-        buf = torch.cat([ws["B"][0].view(torch.int32).reshape(-1), ws["B"][2].reshape(-1), ws["ctr"].reshape(-1),
-                         ws["flags"].reshape(-1), hl, ws["log"][:, :used].reshape(-1)])
-        return buf, n, used
+        layout = self._default_layout(n, P, steps + 1)
+        return _pack(layout, [ws["B"][0], ws["B"][2], ws["ctr"], ws["flags"], hl, ws["log"][:, :steps + 1]]), layout
 
     # ---- tsd / alsd / nsc: passes --------------------------------------------------------------------------------------
     def _batch_pred(self, nodes):
@@ -719,11 +777,7 @@ class BeamSearchTransducer:
         return self.lm_weight * torch.tensor(lm_lp, dtype=torch.float32)
 
     def _sort_nbest(self, hyps):
-        if self.score_norm:
-            hyps = sorted(hyps, key=lambda x: x.score / len(self._tree.labels(x.node)), reverse=True)
-        else:
-            hyps = sorted(hyps, key=lambda x: x.score, reverse=True)
-        return self._result(hyps)
+        return self._result(self._nbest(hyps, lambda x: len(self._tree.labels(x.node))))
 
     def _result(self, hyps):
         return [Hypothesis(score=float(x.score), yseq=self._tree.labels(x.node)) for x in hyps]
@@ -826,12 +880,6 @@ class BeamSearchTransducer:
     def _alsd_batched_ok(self):
         return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16
 
-    def _alsd_one(self, h):
-        if hasattr(self.decoder, "att"):
-            self.decoder.att[0].reset()
-        with torch.no_grad():
-            return self._alsd(h)
-
     @ops.inference_call
     def alsd_batch(self, hs_pad, hlens=None):
         """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
@@ -839,90 +887,58 @@ class BeamSearchTransducer:
         by score / len(yseq) (score with score_norm=False), or B in slot order when no hypothesis reached the last frame.
         DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16: the batched step loop above, one blocking host read per call.
         Anything else: a loop over the per-utterance search."""
-        B, T = hs_pad.shape[:2]
         if not self._alsd_batched_ok():
-            if hlens is None:
-                lens = [T] * B
-            else:
-                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
-            return [self._alsd_one(hs_pad[b, :lens[b]]) for b in range(B)]
-        dev = hs_pad.device
+            return self._fallback("_alsd", hs_pad, hlens)
+        B, T = hs_pad.shape[:2]
         W = min(self.beam_size, self.vocab_size)
         u_max = int(self.u_max)
         with torch.no_grad():
-            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: the padded T bounds every utterance
-                steps = [T + min(u_max, T - 1)] * B
-                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
-                      else hlens.to(device=dev, dtype=torch.int32).clamp(max=T))
-            else:
-                lens = [min(int(v), T) for v in hlens]
-                steps = [t + min(u_max, t - 1) for t in lens]
-                hl = torch.tensor(lens, dtype=torch.int32).to(dev, non_blocking=True)
-            jn = self.decoder.joint_network
-            enc = jn.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
-            nmax = max(1, self.alsd_max_rows // W)
-            res = []
-            for b0 in range(0, B, nmax):
-                b1 = min(B, b0 + nmax)
-                res.append(self._alsd_rows(enc[b0:b1], hl[b0:b1], W, u_max, max(steps[b0:b1])))
-            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
-        ycap, fw, fcap = T + u_max + 1, u_max + 2, W * (u_max + 2)
-        out, o = [], 0
-
-        def take(count, shape, f64=False):
-            nonlocal o
-            a = host[o:o + count * (2 if f64 else 1)]
-            o += a.size
-            return (a.copy().view(np.float64) if f64 else a).reshape(shape)
-
-        for _buf, n in res:
-            fin_score, score = take(n * fcap, (n, fcap), True), take(n * W, (n, W), True)
-            nfin, fin_len, fin_yseq = take(n, (n,)), take(n * fcap, (n, fcap)), take(n * fcap * fw, (n, fcap, fw))
-            nhyp, ulen, yseq = take(n, (n,)), take(n * W, (n, W)), take(n * W * ycap, (n, W, ycap))
-            for b in range(n):
-                if nfin[b]:
-                    hyps = [Hypothesis(score=float(fin_score[b, j]), yseq=fin_yseq[b, j, :fin_len[b, j]].tolist())
-                            for j in range(nfin[b])]
-                    if self.score_norm:
-                        hyps = sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True)
-                    else:
-                        hyps = sorted(hyps, key=lambda x: x.score, reverse=True)
+            frames, hl = self._lengths(hlens, B, T, hs_pad.device)    # a device tensor: the padded T bounds every utterance
+            steps = [t + min(u_max, t - 1) for t in frames]
+            res = self._chunks(hs_pad, max(1, self.alsd_max_rows // W), lambda enc, b0, b1: self._alsd_rows(
+                enc[b0:b1], hl[b0:b1], W, u_max, max(steps[b0:b1])))
+        out = []
+        for r in res:
+            for b in range(len(r["nfin"])):
+                if r["nfin"][b]:
+                    out.append(self._nbest([Hypothesis(score=float(r["fin_score"][b, j]),
+                                                       yseq=r["fin_yseq"][b, j, :r["fin_len"][b, j]].tolist())
+                                            for j in range(r["nfin"][b])]))
                 else:
-                    hyps = [Hypothesis(score=float(score[b, m]), yseq=yseq[b, m, :ulen[b, m] + 1].tolist()) for m in range(nhyp[b])]
-                out.append(hyps)
+                    out.append([Hypothesis(score=float(r["score"][b, m]), yseq=r["yseq"][b, m, :r["ulen"][b, m] + 1].tolist())
+                                for m in range(r["nhyp"][b])])
         return out
+
+    @staticmethod
+    def _alsd_layout(n, W, T, u_max):
+        """the finals (fcap = W (u_max + 2) of them at most, u_max + 2 labels each) and the last B"""
+        fw, fcap = u_max + 2, W * (u_max + 2)
+        return [("fin_score", (n, fcap), np.float64), ("score", (n, W), np.float64), ("nfin", (n,), np.int32),
+                ("fin_len", (n, fcap), np.int32), ("fin_yseq", (n, fcap, fw), np.int32), ("nhyp", (n,), np.int32),
+                ("ulen", (n, W), np.int32), ("yseq", (n, W, T + u_max + 1), np.int32)]
 
     def _alsd_ws(self, n, W, T, u_max, dev):
         """the buffers of one step loop on n utterances x W slots: both parities of the search state, the finals, what
         eamd_rnnt_alsd_step leaves for the rest of the step, both copies of the prediction network's state and the step's intermediates"""
-        dec = self.decoder
-        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
-        G = (4 if dec.dtype == "lstm" else 3) * H
+        J = self.decoder.joint_dim
         R = n * W
         fw, fcap = u_max + 2, W * (u_max + 2)
         f = dict(device=dev, dtype=torch.float32)
         i32 = dict(device=dev, dtype=torch.int32)
-        ws = dict(n=R)
+        ws = self._pred_ws(R, dev)
         ws["st"] = [(torch.zeros(n, W, device=dev, dtype=torch.float64), torch.zeros(n, W, **i32), torch.ones(n, **i32),
                      torch.zeros(n, W, T + u_max + 1, **i32)) for _ in range(2)]
         ws["fin"] = (torch.zeros(n, fcap, device=dev, dtype=torch.float64), torch.zeros(n, fcap, **i32),
                      torch.zeros(n, fcap, fw, **i32), torch.zeros(n, **i32))
         ws["par"] = torch.empty(R, **i32)
         ws["frame"] = torch.empty(R, **i32)
-        ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
-        ws["live"] = torch.empty(R, device=dev, dtype=torch.uint8)
         ws["encr"] = torch.empty(R, J, **f)
         ws["d"] = torch.empty(R, J, **f)
-        ws["h"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(2)]
-        ws["c"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(2)]
-        ws["gx"] = [torch.empty(R, G, **f) for _ in range(L)]
-        ws["gates"] = [torch.empty(R, 4 * H, **f) for _ in range(L)]
-        ws["gh"] = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
         return ws
 
     def _alsd_rows(self, enc, hl, W, u_max, steps):
         """the step loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device
-        -> (result buffer (int32 words: fin_score | score | nfin | fin_len | fin_yseq | nhyp | ulen | yseq), n), not yet read"""
+        -> (result buffer, its layout (_alsd_layout)), not yet read"""
         n, T, J = enc.shape
         dev = enc.device
         dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
@@ -948,14 +964,12 @@ class BeamSearchTransducer:
                 jobs.append((ws["h"][0][l], ws["h"][1][l], ws["par"]))
                 if lstm:
                     jobs.append((ws["c"][0][l], ws["c"][1][l], ws["par"]))
-            for j0 in range(0, len(jobs), 16):
-                ops.gather_rows(jobs[j0:j0 + 16])
+            ops.gather_rows(jobs)
             self._pred_step(ws, 0, 1, ws["live"])
         score, ulen, nhyp, yseq = ws["st"][p]
         fin_score, fin_len, fin_yseq, nfin = ws["fin"]
-        buf = torch.cat([fin_score.view(torch.int32).reshape(-1), score.view(torch.int32).reshape(-1), nfin, fin_len.reshape(-1),
-                         fin_yseq.reshape(-1), nhyp, ulen.reshape(-1), yseq.reshape(-1)])
-        return buf, n
+        layout = self._alsd_layout(n, W, T, u_max)
+        return _pack(layout, [fin_score, score, nfin, fin_len, fin_yseq, nhyp, ulen, yseq]), layout
 
     # ---- batched tsd ----------------------------------------------------------------------------------------------------
     # tsd takes max_sym_exp = M passes per frame whatever the hypotheses are, so the utterances of a batch advance in lock-step here
@@ -973,12 +987,6 @@ class BeamSearchTransducer:
     def _tsd_batched_ok(self):
         return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16 and 1 <= self.max_sym_exp <= 4
 
-    def _tsd_one(self, h):
-        if hasattr(self.decoder, "att"):
-            self.decoder.att[0].reset()
-        with torch.no_grad():
-            return self._tsd(h)
-
     @ops.inference_call
     def tsd_batch(self, hs_pad, hlens=None):
         """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
@@ -986,82 +994,48 @@ class BeamSearchTransducer:
         score / len(yseq) (score with score_norm=False).
         DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16, max_sym_exp <= 4: the batched pass loop above, one blocking
         host read per call.  Anything else: a loop over the per-utterance search."""
-        B, T = hs_pad.shape[:2]
         if not self._tsd_batched_ok():
-            if hlens is None:
-                lens = [T] * B
-            else:
-                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
-            return [self._tsd_one(hs_pad[b, :lens[b]]) for b in range(B)]
-        dev = hs_pad.device
+            return self._fallback("_tsd", hs_pad, hlens)
+        B, T = hs_pad.shape[:2]
         W = min(self.beam_size, self.vocab_size)
         M = int(self.max_sym_exp)
         with torch.no_grad():
-            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: all T frames run, finished utterances idle
-                frames = [T] * B
-                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
-                      else hlens.to(device=dev, dtype=torch.int32).clamp(max=T))
-            else:
-                frames = [max(0, min(int(v), T)) for v in hlens]
-                hl = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
-            enc = self.decoder.joint_network.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
-            nmax = max(1, self.tsd_max_rows // W)
-            res = []
-            for b0 in range(0, B, nmax):
-                b1 = min(B, b0 + nmax)
-                res.append(self._tsd_rows(enc[b0:b1], hl[b0:b1], W, M, max(frames[b0:b1])))
-            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
-        ycap = 1 + T * (M - 1)
-        out, o = [], 0
-        for _buf, n in res:
-            score = host[o:o + 2 * n * W].copy().view(np.float64).reshape(n, W)
-            o += 2 * n * W
-            count, ulen = host[o:o + n], host[o + n:o + n + n * W].reshape(n, W)
-            o += n + n * W
-            yseq = host[o:o + n * W * ycap].reshape(n, W, ycap)
-            o += n * W * ycap
-            for b in range(n):
-                hyps = [Hypothesis(score=float(score[b, m]), yseq=yseq[b, m, :ulen[b, m] + 1].tolist()) for m in range(count[b])]
-                if self.score_norm:
-                    out.append(sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True))
-                else:
-                    out.append(sorted(hyps, key=lambda x: x.score, reverse=True))
-        return out
+            frames, hl = self._lengths(hlens, B, T, hs_pad.device)    # a device tensor: all T frames run, finished utterances idle
+            res = self._chunks(hs_pad, max(1, self.tsd_max_rows // W), lambda enc, b0, b1: self._tsd_rows(
+                enc[b0:b1], hl[b0:b1], W, M, max(frames[b0:b1])))
+        return [hyps for r in res for hyps in self._block_nbest(r)]
+
+    @staticmethod
+    def _block_layout(n, W, ycap):
+        """tsd / nsc: one hypothesis block, the last B / kept"""
+        return [("score", (n, W), np.float64), ("count", (n,), np.int32), ("ulen", (n, W), np.int32), ("yseq", (n, W, ycap), np.int32)]
+
+    def _block_nbest(self, r):
+        """the n-best list of every utterance of an unpacked _block_layout"""
+        return [self._nbest([Hypothesis(score=float(r["score"][b, m]), yseq=r["yseq"][b, m, :r["ulen"][b, m] + 1].tolist())
+                             for m in range(r["count"][b])]) for b in range(len(r["count"]))]
 
     def _tsd_ws(self, n, W, T, M, dev):
         """the buffers of one pass loop on n utterances x W slots: the M + 1 hypothesis blocks, the frame's A, what eamd_rnnt_tsd_step
         leaves for the rest of the pass, the stacked prediction-network state with its staging copy and the pass's intermediates"""
-        dec = self.decoder
-        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
-        G = (4 if dec.dtype == "lstm" else 3) * H
+        J = self.decoder.joint_dim
         R = n * W
         f = dict(device=dev, dtype=torch.float32)
         i32 = dict(device=dev, dtype=torch.int32)
-        ws = dict(n=R)
+        d = torch.empty((M + 1) * R, J, **f)
+        ws = self._block_ws(M + 1, R, [d[j * R:(j + 1) * R] for j in range(M + 1)], dev)
+        ws["d"] = d
         ws["st"] = (torch.zeros(M + 1, n, W, device=dev, dtype=torch.float64), torch.zeros(M + 1, n, W, **i32),
                     torch.zeros(M + 1, n, **i32), torch.zeros(M + 1, n, W, 1 + T * (M - 1), **i32))
         ws["st"][2][0].fill_(1)                               # B of frame 0: slot 0 holds [blank] with score 0
         ws["A"] = (torch.zeros(n, W * M, device=dev, dtype=torch.float64), torch.zeros(n, W * M, **i32), torch.zeros(n, **i32))
         ws["par"] = torch.empty(R, **i32)
-        ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
-        ws["live"] = torch.empty(R, device=dev, dtype=torch.uint8)
         ws["encr"] = torch.empty(R, J, **f)
-        ws["d"] = torch.empty((M + 1) * R, J, **f)
-        ws["h"] = [torch.zeros((M + 1) * R, H, **f) for _ in range(L)]
-        ws["c"] = [torch.zeros((M + 1) * R, H, **f) for _ in range(L)]
-        stage_h, stage_c = [torch.zeros(R, H, **f) for _ in range(L)], [torch.zeros(R, H, **f) for _ in range(L)]
-        gx = [torch.empty(R, G, **f) for _ in range(L)]
-        gates = [torch.empty(R, 4 * H, **f) for _ in range(L)]
-        gh = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
-        # _pred_step's view of block j: state copy 0 = the staging copy, copy 1 = the block's rows
-        ws["blk"] = [dict(n=R, tok=ws["tok"], gx=gx, gates=gates, gh=gh, d=ws["d"][j * R:(j + 1) * R],
-                          h=[stage_h, [x[j * R:(j + 1) * R] for x in ws["h"]]], c=[stage_c, [x[j * R:(j + 1) * R] for x in ws["c"]]])
-                     for j in range(M + 1)]
         return ws
 
     def _tsd_rows(self, enc, hl, W, M, frames):
         """the pass loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device, `frames` frames
-        -> (result buffer (int32 words: score | count | ulen | yseq of the last B), n), not yet read"""
+        -> (result buffer, its layout (_block_layout of the last B)), not yet read"""
         n, T, J = enc.shape
         dev = enc.device
         dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
@@ -1074,10 +1048,7 @@ class BeamSearchTransducer:
         lstm = dec.dtype == "lstm"
         p = 0
         if frames:
-            # encoder row of frame t: b * T + min(t, T_b - 1), the same for all slots of an utterance
-            tt = torch.arange(frames, device=dev, dtype=torch.int32)
-            ft = torch.minimum(tt[:, None], (hl - 1)[None, :]).clamp_(min=0) + (torch.arange(n, device=dev, dtype=torch.int32) * T)
-            ft = ft.repeat_interleave(W, dim=1).contiguous()
+            ft = self._frame_rows(hl, T, W, frames)
             ops.gather_rows([(ws["encr"], enc_rows, ft[0])])
         for t in range(frames):
             for v in range(M):
@@ -1096,14 +1067,13 @@ class BeamSearchTransducer:
                     if lstm:
                         jobs += [(blk[cout]["c"][1][l], ws["c"][l], ws["par"]) for l in range(dec.dlayers)]
                     jobs += [(blk[cout]["d"], ws["d"], ws["par"]), (ws["encr"], enc_rows, ft[t + 1])]
-                for j0 in range(0, len(jobs), 16):
-                    ops.gather_rows(jobs[j0:j0 + 16])
+                ops.gather_rows(jobs)
                 if v < M - 1:
                     self._pred_step(blk[cout], 0, 1, ws["live"])
             p = 1 - p
         last = M if p else 0
-        buf = torch.cat([st[0][last].view(torch.int32).reshape(-1), st[2][last], st[1][last].reshape(-1), st[3][last].reshape(-1)])
-        return buf, n
+        layout = self._block_layout(n, W, 1 + T * (M - 1))
+        return _pack(layout, [st[0][last], st[2][last], st[1][last], st[3][last]]), layout
 
     # ---- N-step constrained beam search (reference :466-663) -----------------------------------------------------------
     def _nsc(self, h):
@@ -1211,12 +1181,6 @@ class BeamSearchTransducer:
         return (self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16 and 1 <= self.nstep <= 4
                 and 0 <= self.prefix_alpha <= 3)
 
-    def _nsc_one(self, h):
-        if hasattr(self.decoder, "att"):
-            self.decoder.att[0].reset()
-        with torch.no_grad():
-            return self._nsc(h)
-
     @ops.inference_call
     def nsc_batch(self, hs_pad, hlens=None):
         """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
@@ -1224,87 +1188,43 @@ class BeamSearchTransducer:
         score / len(yseq) (score with score_norm=False).
         DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16, nstep <= 4, prefix_alpha <= 3: the batched frame loop above,
         one blocking host read per call.  Anything else: a loop over the per-utterance search."""
-        B, T = hs_pad.shape[:2]
         if not self._nsc_batched_ok():
-            if hlens is None:
-                lens = [T] * B
-            else:
-                lens = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
-            return [self._nsc_one(hs_pad[b, :lens[b]]) for b in range(B)]
-        dev = hs_pad.device
+            return self._fallback("_nsc", hs_pad, hlens)
+        B, T = hs_pad.shape[:2]
         W = min(self.beam_size, self.vocab_size)
         N, alpha = int(self.nstep), int(self.prefix_alpha)
         with torch.no_grad():
-            if hlens is None or torch.is_tensor(hlens):       # a device tensor is not read: all T frames run, finished utterances idle
-                frames = [T] * B
-                hl = (torch.full((B,), T, dtype=torch.int32, device=dev) if hlens is None
-                      else hlens.to(device=dev, dtype=torch.int32).clamp(max=T))
-            else:
-                frames = [max(0, min(int(v), T)) for v in hlens]
-                hl = torch.tensor(frames, dtype=torch.int32).to(dev, non_blocking=True)
-            enc = self.decoder.joint_network.project_enc(hs_pad.reshape(B * T, -1)).view(B, T, -1)
-            nmax = max(1, self.nsc_max_rows // W)
-            res = []
-            for b0 in range(0, B, nmax):
-                b1 = min(B, b0 + nmax)
-                res.append(self._nsc_rows(enc[b0:b1], hl[b0:b1], W, N, alpha, max(frames[b0:b1])))
-            host = (res[0][0] if len(res) == 1 else torch.cat([r[0] for r in res])).cpu().numpy()     # the call's one host read
-        ycap = 1 + T * N
-        out, o = [], 0
-        for _buf, n in res:
-            score = host[o:o + 2 * n * W].copy().view(np.float64).reshape(n, W)
-            o += 2 * n * W
-            count, ulen = host[o:o + n], host[o + n:o + n + n * W].reshape(n, W)
-            o += n + n * W
-            yseq = host[o:o + n * W * ycap].reshape(n, W, ycap)
-            o += n * W * ycap
-            for b in range(n):
-                hyps = [Hypothesis(score=float(score[b, m]), yseq=yseq[b, m, :ulen[b, m] + 1].tolist()) for m in range(count[b])]
-                if self.score_norm:
-                    out.append(sorted(hyps, key=lambda x: x.score / len(x.yseq), reverse=True))
-                else:
-                    out.append(sorted(hyps, key=lambda x: x.score, reverse=True))
-        return out
+            frames, hl = self._lengths(hlens, B, T, hs_pad.device)    # a device tensor: all T frames run, finished utterances idle
+            res = self._chunks(hs_pad, max(1, self.nsc_max_rows // W), lambda enc, b0, b1: self._nsc_rows(
+                enc[b0:b1], hl[b0:b1], W, N, alpha, max(frames[b0:b1])))
+        return [hyps for r in res for hyps in self._block_nbest(r)]
 
     def _nsc_ws(self, n, W, T, N, alpha, dev):
         """the buffers of one frame loop on n utterances x W slots: the N + 2 hypothesis blocks, the frame's S, what eamd_rnnt_nsc_step
         leaves for the rest of the call, the pair list and its log-probabilities, the stacked prediction-network state with its
         staging copy, the stacked d / history rows and the call's intermediates"""
-        dec = self.decoder
-        H, L, J = dec.dunits, dec.dlayers, dec.joint_dim
-        G = (4 if dec.dtype == "lstm" else 3) * H
+        J = self.decoder.joint_dim
         R, LV = n * W, 1 + alpha
         f = dict(device=dev, dtype=torch.float32)
         i32 = dict(device=dev, dtype=torch.int32)
-        ws = dict(n=R)
+        hs = torch.zeros(N + 2, LV, R, J, **f)                # level 0: d; level a: d of the labels without the last a
+        ws = self._block_ws(N + 2, R, [hs[j, 0] for j in range(N + 2)], dev)
+        ws["hs"] = hs
         ws["st"] = (torch.zeros(N + 2, n, W, device=dev, dtype=torch.float64), torch.zeros(N + 2, n, W, **i32),
                     torch.zeros(N + 2, n, **i32), torch.zeros(N + 2, n, W, 1 + T * N, **i32))
         ws["st"][2][0].fill_(1)                               # kept of frame 0: slot 0 holds [blank] with score 0
         ws["S"] = (torch.zeros(n, W * N, device=dev, dtype=torch.float64), torch.zeros(n, W * N, **i32), torch.zeros(n, **i32))
         ws["par"] = torch.empty(R, **i32)
-        ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
-        ws["live"] = torch.empty(R, device=dev, dtype=torch.uint8)
         ws["hidx"] = torch.zeros(LV, R, **i32)
         ws["pairs"] = torch.zeros(max(1, R * alpha), 2, **i32)
         ws["pairs"][:, 0].fill_(-1)                           # frame 0: [blank] has no prefix
         ws["pair_lp"] = torch.zeros(max(1, R * alpha), **f)
         ws["encr"] = torch.empty(LV * R, J, **f)
-        ws["hs"] = torch.zeros(N + 2, LV, R, J, **f)          # level 0: d; level a: d of the labels without the last a
-        ws["h"] = [torch.zeros((N + 2) * R, H, **f) for _ in range(L)]
-        ws["c"] = [torch.zeros((N + 2) * R, H, **f) for _ in range(L)]
-        stage_h, stage_c = [torch.zeros(R, H, **f) for _ in range(L)], [torch.zeros(R, H, **f) for _ in range(L)]
-        gx = [torch.empty(R, G, **f) for _ in range(L)]
-        gates = [torch.empty(R, 4 * H, **f) for _ in range(L)]
-        gh = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
-        # _pred_step's view of block j: state copy 0 = the staging copy, copy 1 = the block's rows
-        ws["blk"] = [dict(n=R, tok=ws["tok"], gx=gx, gates=gates, gh=gh, d=ws["hs"][j, 0],
-                          h=[stage_h, [x[j * R:(j + 1) * R] for x in ws["h"]]], c=[stage_c, [x[j * R:(j + 1) * R] for x in ws["c"]]])
-                     for j in range(N + 2)]
         return ws
 
     def _nsc_rows(self, enc, hl, W, N, alpha, frames):
         """the frame loop on n utterances: enc (n, T, J) projected encoder states, hl (n,) int32 on the device, `frames` frames
-        -> (result buffer (int32 words: score | count | ulen | yseq of the last kept), n), not yet read"""
+        -> (result buffer, its layout (_block_layout of the last kept)), not yet read"""
         n, T, J = enc.shape
         dev = enc.device
         dec, jn, V = self.decoder, self.decoder.joint_network, self.vocab_size
@@ -1319,10 +1239,7 @@ class BeamSearchTransducer:
         layers = range(dec.dlayers)
         p = 0
         if frames:
-            # encoder row of frame t: b * T + min(t, T_b - 1), the same for all slots of an utterance and for every history level
-            tt = torch.arange(frames, device=dev, dtype=torch.int32)
-            ft = torch.minimum(tt[:, None], (hl - 1)[None, :]).clamp_(min=0) + (torch.arange(n, device=dev, dtype=torch.int32) * T)
-            ft = ft.repeat_interleave(W, dim=1).repeat(1, LV).contiguous()
+            ft = self._frame_rows(hl, T, W, frames, levels=LV)          # the same rows for every history level
             ops.gather_rows([(ws["encr"], enc_rows, ft[0])])
         for t in range(frames):
             kp, ko = (N + 1, 0) if p else (0, N + 1)
@@ -1346,11 +1263,10 @@ class BeamSearchTransducer:
                 jobs += [(hs[cout, a], hs_rows, ws["hidx"][a]) for a in range(1 if step else 0, LV)]
                 if last:
                     jobs.append((ws["encr"], enc_rows, ft[t + 1]))
-                for j0 in range(0, len(jobs), 16):
-                    ops.gather_rows(jobs[j0:j0 + 16])
+                ops.gather_rows(jobs)
                 if step:
                     self._pred_step(blk[cout], 0, 1, ws["live"])
             p = 1 - p
         last = N + 1 if p else 0
-        buf = torch.cat([st[0][last].view(torch.int32).reshape(-1), st[2][last], st[1][last].reshape(-1), st[3][last].reshape(-1)])
-        return buf, n
+        layout = self._block_layout(n, W, 1 + T * N)
+        return _pack(layout, [st[0][last], st[2][last], st[1][last], st[3][last]]), layout

@@ -247,13 +247,8 @@ class E2E(ASRInterface, torch.nn.Module):
                 hlens = subsampled_lengths(il, xs_pad.shape[1])
         if beam_search.beam_size <= 1:
             return [asdict(h) for h in beam_search.greedy_batch(hs_pad, hlens)]
-        if beam_search.search_type == "alsd":
-            return [[asdict(n) for n in nb] for nb in beam_search.alsd_batch(hs_pad, hlens)]
-        if beam_search.search_type == "tsd":
-            return [[asdict(n) for n in nb] for nb in beam_search.tsd_batch(hs_pad, hlens)]
-        if beam_search.search_type == "nsc":
-            return [[asdict(n) for n in nb] for nb in beam_search.nsc_batch(hs_pad, hlens)]
-        if beam_search.search_type == "default":
-            return [[asdict(n) for n in nb] for nb in beam_search.default_batch(hs_pad, hlens)]
+        if beam_search.search_type in ("alsd", "tsd", "nsc", "default"):
+            batch = getattr(beam_search, beam_search.search_type + "_batch")
+            return [[asdict(n) for n in nb] for nb in batch(hs_pad, hlens)]
         hl = [int(v) for v in (hlens.tolist() if torch.is_tensor(hlens) else hlens)]
         return [[asdict(n) for n in beam_search(hs_pad[b, : hl[b]])] for b in range(len(xs))]

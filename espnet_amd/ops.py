@@ -1650,22 +1650,24 @@ def rnnt_nsc_step(rec, pair_lp, hlens, state, S, par, tok, live, hidx, pairs, V,
 
 
 def gather_rows(jobs):
-    """up to 16 row gathers in one launch (eamd_gather_rows): jobs = [(dst [r, w], src [m, w], idx int32 [r])], contiguous fp32
-    matrices on the device: dst[i] = src[idx[i]]"""
-    n = len(jobs)
-    assert 0 < n <= 16
+    """row gathers, sixteen per launch (eamd_gather_rows): jobs = [(dst [r, w], src [m, w], idx int32 [r])], any positive number of
+    them, contiguous fp32 matrices on the device: dst[i] = src[idx[i]]"""
+    assert len(jobs) > 0
     for d, s_, ix in jobs:
         if not (d.dtype == s_.dtype == torch.float32 and d.is_contiguous() and s_.is_contiguous() and d.dim() == s_.dim() == 2
                 and d.shape[1] == s_.shape[1] and ix.dtype == torch.int32 and ix.is_contiguous() and ix.numel() == d.shape[0]
                 and s_.shape[0] >= 1):
             raise _lib.EamdError("gather_rows: contiguous float32 [rows, width] matrices of one width, int32 indices")
-    src = (C.c_void_p * n)(*[s_.data_ptr() for _, s_, _ in jobs])
-    dst = (C.c_void_p * n)(*[d.data_ptr() for d, _, _ in jobs])
-    idx = (C.c_void_p * n)(*[ix.data_ptr() for _, _, ix in jobs])
-    nrows = (C.c_int32 * n)(*[d.shape[0] for d, _, _ in jobs])
-    width = (C.c_int32 * n)(*[d.shape[1] for d, _, _ in jobs])
-    srows = (C.c_int32 * n)(*[s_.shape[0] for _, s_, _ in jobs])
-    check(_lib.lib().eamd_gather_rows(src, dst, idx, nrows, width, srows, n, stream_ptr()), "eamd_gather_rows")
+    for j0 in range(0, len(jobs), 16):
+        part = jobs[j0:j0 + 16]
+        n = len(part)
+        src = (C.c_void_p * n)(*[s_.data_ptr() for _, s_, _ in part])
+        dst = (C.c_void_p * n)(*[d.data_ptr() for d, _, _ in part])
+        idx = (C.c_void_p * n)(*[ix.data_ptr() for _, _, ix in part])
+        nrows = (C.c_int32 * n)(*[d.shape[0] for d, _, _ in part])
+        width = (C.c_int32 * n)(*[d.shape[1] for d, _, _ in part])
+        srows = (C.c_int32 * n)(*[s_.shape[0] for _, s_, _ in part])
+        check(_lib.lib().eamd_gather_rows(src, dst, idx, nrows, width, srows, n, stream_ptr()), "eamd_gather_rows")
 
 
 def rnnt_default_step(rec, hlens, A, B, cur_score, ctr, log, flags, par, tok, dst, live, frame, alive, W, V, T):
@@ -1696,23 +1698,26 @@ def rnnt_default_step(rec, hlens, A, B, cur_score, ctr, log, flags, par, tok, ds
 
 
 def scatter_rows(jobs):
-    """up to 16 masked row scatters in one launch (eamd_scatter_rows): jobs = [(dst [m, w], src [r, w], idx int32 [r], mask uint8 [r]
-    or None)], contiguous fp32 matrices on the device: dst[idx[i]] = src[i] where mask[i] != 0; an index outside dst writes nothing"""
-    n = len(jobs)
-    assert 0 < n <= 16
+    """masked row scatters, sixteen per launch (eamd_scatter_rows): jobs = [(dst [m, w], src [r, w], idx int32 [r], mask uint8 [r]
+    or None)], any positive number of them, contiguous fp32 matrices on the device: dst[idx[i]] = src[i] where mask[i] != 0; an
+    index outside dst writes nothing"""
+    assert len(jobs) > 0
     for d, s_, ix, m in jobs:
         if not (d.dtype == s_.dtype == torch.float32 and d.is_contiguous() and s_.is_contiguous() and d.dim() == s_.dim() == 2
                 and d.shape[1] == s_.shape[1] and ix.dtype == torch.int32 and ix.is_contiguous() and ix.numel() == s_.shape[0]
                 and d.shape[0] >= 1 and (m is None or (m.dtype == torch.uint8 and m.is_contiguous() and m.numel() == s_.shape[0]))):
             raise _lib.EamdError("scatter_rows: contiguous float32 [rows, width] matrices of one width, int32 indices, uint8 masks")
-    dst = (C.c_void_p * n)(*[d.data_ptr() for d, _, _, _ in jobs])
-    src = (C.c_void_p * n)(*[s_.data_ptr() for _, s_, _, _ in jobs])
-    idx = (C.c_void_p * n)(*[ix.data_ptr() for _, _, ix, _ in jobs])
-    mask = (C.c_void_p * n)(*[ptr(m) for _, _, _, m in jobs])
-    nrows = (C.c_int32 * n)(*[s_.shape[0] for _, s_, _, _ in jobs])
-    width = (C.c_int32 * n)(*[d.shape[1] for d, _, _, _ in jobs])
-    drows = (C.c_int32 * n)(*[d.shape[0] for d, _, _, _ in jobs])
-    check(_lib.lib().eamd_scatter_rows(dst, src, idx, mask, nrows, width, drows, n, stream_ptr()), "eamd_scatter_rows")
+    for j0 in range(0, len(jobs), 16):
+        part = jobs[j0:j0 + 16]
+        n = len(part)
+        dst = (C.c_void_p * n)(*[d.data_ptr() for d, _, _, _ in part])
+        src = (C.c_void_p * n)(*[s_.data_ptr() for _, s_, _, _ in part])
+        idx = (C.c_void_p * n)(*[ix.data_ptr() for _, _, ix, _ in part])
+        mask = (C.c_void_p * n)(*[ptr(m) for _, _, _, m in part])
+        nrows = (C.c_int32 * n)(*[s_.shape[0] for _, s_, _, _ in part])
+        width = (C.c_int32 * n)(*[d.shape[1] for d, _, _, _ in part])
+        drows = (C.c_int32 * n)(*[d.shape[0] for d, _, _, _ in part])
+        check(_lib.lib().eamd_scatter_rows(dst, src, idx, mask, nrows, width, drows, n, stream_ptr()), "eamd_scatter_rows")
 
 
 def linear_into(x, W, b, out):

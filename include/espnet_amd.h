@@ -1010,7 +1010,7 @@ int eamd_rnnt_greedy_pick(const float* part, const int32_t* hlens, int32_t* yseq
  *     tok int64 = the appended token or blank, live uint8 = 1 only for a slot that appended a token (the mask eamd_lstm_step_fwd /
  *     eamd_lstm_cell_fwd / eamd_gru_cell_fwd take), frame int32 = b * T + clamp((i + 1) - ulen' + 1, 0, T_b - 1): the encoder row the
  *     slot reads in step i + 1.
- * eamd_gather_rows: up to 16 row gathers in one launch, dst_j[r, :] = src_j[idx_j[r], :] for r < nrows[j] (fp32 rows of width[j]
+ * eamd_gather_rows (csrc/row_moves.hip): up to 16 row gathers in one launch, dst_j[r, :] = src_j[idx_j[r], :] for r < nrows[j] (fp32 rows of width[j]
  *   elements; float4 moves when the width is a multiple of 4 and the rows are 16-byte aligned).  src / dst / idx: HOST arrays of device
  *   pointers as eamd_copy_jobs takes them, idx_j int32 on the device; nrows / width / src_rows: host arrays; an index outside
  *   [0, src_rows[j]) reads the nearest valid row. */
@@ -1122,7 +1122,7 @@ int eamd_rnnt_nsc_step(const float* rec, const float* pair_lp, const int32_t* hl
  *     (the mask eamd_lstm_step_fwd / eamd_lstm_cell_fwd / eamd_gru_cell_fwd take), frame int32 [n] = b T + t, alive uint8 [n] = 1
  *     (eamd_scatter_rows' mask).  The (P + 1)-th pop of a frame, or a pop with the log full, sets overflow instead and stops the
  *     utterance.
- * eamd_scatter_rows: up to 16 masked row scatters in one launch, dst_j[idx_j[r], :] = src_j[r, :] for r < nrows[j] with mask_j[r] != 0
+ * eamd_scatter_rows (csrc/row_moves.hip): up to 16 masked row scatters in one launch, dst_j[idx_j[r], :] = src_j[r, :] for r < nrows[j] with mask_j[r] != 0
  *   (mask_j NULL: every row; fp32 rows of width[j] elements, float4 moves as in eamd_gather_rows).  dst / src / idx / mask: HOST arrays
  *   of device pointers, idx_j int32 and mask_j uint8 on the device; an index outside [0, dst_rows[j]) writes nothing.  Rows of one job
  *   that share an index race. */

@@ -192,3 +192,78 @@ def test_beam_step_log_replay_on_the_host():
     assert [h.yseq.tolist() for h in log.ended[0]] == [[9, 9], [9, 3, 5, 6, 9]] and log.stopped == [True, True]
     res = log.results()
     assert [h.yseq.tolist() for h in res[0]] == [[9, 9], [9, 3, 5, 6, 9]] and len(res[1]) == 1                    # best first
+
+
+def test_transducer_result_layout_round_trip():
+    """beam_search_transducer._pack / _unpack: float64 and int32 fields of odd sizes, an empty field, two chunks in one buffer"""
+    from espnet_amd.nets.beam_search_transducer import _fields, _pack, _unpack
+
+    def chunk(n, seed):
+        g = torch.Generator().manual_seed(seed)
+        layout = [("score", (n, 3), np.float64), ("count", (n,), np.int32), ("none", (n, 0), np.float64),
+                  ("yseq", (n, 2, 5), np.int32), ("tail", (7,), np.float64), ("f32", (n,), np.float32)]
+        vals = [torch.randn(n, 3, generator=g, dtype=torch.float64), torch.randint(-9, 9, (n,), generator=g, dtype=torch.int32),
+                torch.empty(n, 0, dtype=torch.float64), torch.randint(0, 99, (n, 2, 5), generator=g, dtype=torch.int32),
+                torch.randn(7, generator=g, dtype=torch.float64), torch.randn(n, generator=g)]
+        return layout, vals
+
+    chunks = [chunk(3, 0), chunk(1, 1)]                      # 18 + 3 + 30 words before `tail`: a float64 field that starts at an odd word
+    bufs = [_pack(layout, vals) for layout, vals in chunks]
+    for buf, (layout, _vals) in zip(bufs, chunks):
+        last = list(_fields(layout))[-1]
+        assert buf.dtype == torch.int32 and buf.dim() == 1 and buf.numel() == last[3] + last[4]
+    assert [f[3] for f in _fields(chunks[0][0])][4] % 2 == 1
+    host = torch.cat(bufs).numpy()
+    o = 0
+    for layout, vals in chunks:
+        got, o = _unpack(layout, host, o)
+        assert list(got) == [name for name, _s, _d in layout]
+        for (name, shape, dt), v in zip(layout, vals):
+            assert got[name].dtype == dt and got[name].shape == tuple(shape)
+            assert np.array_equal(got[name], v.numpy())      # bit-exact: the words are only viewed
+    assert o == host.size
+    with pytest.raises(AssertionError):
+        _pack(chunks[0][0], chunks[1][1])                    # a field that does not have the layout's shape
+
+
+@pytest.mark.parametrize("njobs", [1, 16, 17, 33])
+def test_row_moves_slice_jobs_into_launches_of_16(monkeypatch, njobs):
+    """ops.gather_rows / ops.scatter_rows take any positive number of jobs and hand eamd_gather_rows / eamd_scatter_rows at
+    most 16 at a time, in order, every job exactly once"""
+    from espnet_amd import _lib, ops
+
+    class Fake:
+        def __init__(self):
+            self.calls = []
+
+        def eamd_gather_rows(self, src, dst, idx, nrows, width, srows, n, stream):
+            assert len(src) == len(dst) == len(idx) == len(nrows) == len(width) == len(srows) == n
+            self.calls.append(("gather", n, list(dst), list(src), list(idx), list(nrows), list(width), list(srows)))
+            return 0
+
+        def eamd_scatter_rows(self, dst, src, idx, mask, nrows, width, drows, n, stream):
+            assert len(src) == len(dst) == len(idx) == len(mask) == len(nrows) == len(width) == len(drows) == n
+            self.calls.append(("scatter", n, list(dst), list(src), list(idx), list(nrows), list(width), list(drows)))
+            return 0
+
+    fake = Fake()
+    monkeypatch.setattr(_lib, "lib", lambda: fake)
+    monkeypatch.setattr(ops, "stream_ptr", lambda: None)
+    small = [torch.zeros(2 + j % 3, 4) for j in range(njobs)]           # the side with one row per index
+    big = [torch.zeros(5 + j % 2, 4) for j in range(njobs)]             # the indexed side
+    idx = [torch.zeros(2 + j % 3, dtype=torch.int32) for j in range(njobs)]
+    ops.gather_rows([(small[j], big[j], idx[j]) for j in range(njobs)])
+    ops.scatter_rows([(big[j], small[j], idx[j], None) for j in range(njobs)])
+    want = [min(16, njobs - j0) for j0 in range(0, njobs, 16)]
+    for kind, dst, src in (("gather", small, big), ("scatter", big, small)):
+        calls = [c for c in fake.calls if c[0] == kind]
+        assert [c[1] for c in calls] == want
+        assert [p for c in calls for p in c[2]] == [x.data_ptr() for x in dst]
+        assert [p for c in calls for p in c[3]] == [x.data_ptr() for x in src]
+        assert [p for c in calls for p in c[4]] == [x.data_ptr() for x in idx]
+        assert [v for c in calls for v in c[5]] == [x.shape[0] for x in small]
+        assert [v for c in calls for v in c[6]] == [4] * njobs
+        assert [v for c in calls for v in c[7]] == [x.shape[0] for x in big]
+    assert [c[0] for c in fake.calls] == ["gather"] * len(want) + ["scatter"] * len(want)
+    with pytest.raises(AssertionError):
+        ops.gather_rows([])
