@@ -12,6 +12,10 @@
 //                         (rs_rank: stable, equal scores keep A's order); equal label sequences are found by comparing lengths
 //                         and tokens, one wave per pair (rs_same_labels); the only traffic that grows with T is the copy of W
 //                         parents' labels (rs_copy_labels).
+//   eamd_rnnt_alsd_step_lm  the same step with RNNLM shallow fusion: the record of width 1 + 3k that eamd_transducer_expand_rows
+//                         writes with an LM (the raw LM log-probability of each chosen token behind the token ids) and lm_weight;
+//                         the score sums follow the reference's float32 arithmetic (rnnt_search.h: rs_add / rs_ext / rs_merge).
+//                         One kernel text, templated on LM.
 // The rows the rest of the step needs are moved by eamd_gather_rows (row_moves.hip).  Plain stores, no atomics, no scratch
 // buffers: a workgroup owns its utterance's rows of every output.
 #include "common.h"
@@ -24,12 +28,15 @@ constexpr int AL_W = 16;                       // slots per utterance at most
 constexpr int AL_C = AL_W * (AL_W + 1);        // candidates per utterance at most: W active slots x (blank + k <= W tokens)
 constexpr int AL_THREADS = 256;
 
+// LM: the record carries the k raw LM log-probabilities of the chosen tokens behind the token ids, and the score sums follow the
+// float32 rule of rnnt_search.h (rs_add / rs_ext / rs_merge) with wf = (float)lm_weight; LM = false ignores wf
+template <bool LM>
 __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
     const float* __restrict__ rec, const int* __restrict__ hlens, const double* __restrict__ score_in, const int* __restrict__ ulen_in,
     const int* __restrict__ nhyp_in, const int* __restrict__ yseq_in, double* __restrict__ score_out, int* __restrict__ ulen_out,
     int* __restrict__ nhyp_out, int* __restrict__ yseq_out, double* __restrict__ fin_score, int* __restrict__ fin_len,
     int* __restrict__ fin_yseq, int* __restrict__ nfin, int* __restrict__ par, long long* __restrict__ tok,
-    unsigned char* __restrict__ live, int* __restrict__ frame, int W, int V, int T, int u_max, int i) {
+    unsigned char* __restrict__ live, int* __restrict__ frame, int W, int V, int T, int u_max, int i, float wf) {
   __shared__ double c_score[AL_C];             // candidates of A, raw scores
   __shared__ double s_score[AL_W];             // the new B: scores (first occurrences grow in the recombination)
   __shared__ int c_rank[AL_C];
@@ -39,11 +46,11 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
   __shared__ int n_ulen[AL_W], n_src[AL_W], n_tok[AL_W], n_live[AL_W];
   __shared__ int f_slot[AL_W], f_pos[AL_W];    // finals of this step: old slot, position in the final list
   __shared__ unsigned char s_eq[AL_W][AL_W];
-  __shared__ float s_rec[AL_W * (1 + 2 * AL_W)];             // the utterance's rows of the record
+  __shared__ float s_rec[AL_W * (1 + (LM ? 3 : 2) * AL_W)];             // the utterance's rows of the record
   __shared__ double o_score[AL_W];
   __shared__ int s_nact, s_nf, s_nfin0;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = min(W, V - 1), RW = 1 + 2 * k, K1 = k + 1;
+  const int k = min(W, V - 1), RW = 1 + (LM ? 3 : 2) * k, K1 = k + 1;
   const int ycap = T + u_max + 1, fw = u_max + 2, fcap = W * fw;
   const int Tb = max(0, hlens ? min(hlens[b], T) : T);
   const int umb = min(u_max, Tb - 1);
@@ -92,7 +99,8 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
   for (int c = tid; c < C; c += AL_THREADS) {
     const int a = c / K1, j = c - a * K1;
     const int w = a_slot[a];
-    c_score[c] = o_score[w] + (double)s_rec[w * RW + j];
+    c_score[c] = j == 0 ? rs_add<LM>(o_score[w], o_ulen[w], s_rec[w * RW])
+                        : rs_ext<LM>(o_score[w], o_ulen[w], s_rec[w * RW + j], LM ? s_rec[w * RW + 2 * k + j] : 0.f, wf);
   }
   __syncthreads();
   // sorted(A, reverse=True)[:W]: position = candidates ahead (larger score, or equal score and earlier in A)
@@ -130,7 +138,7 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
       for (int m1 = 0; m1 < m; ++m1)
         if (s_eq[m][m1]) { f = m1; break; }
       s_first[m] = f;
-      if (f != m) s_score[f] = al_logaddexp(s_score[f], s_score[m]);
+      if (f != m) s_score[f] = rs_merge<LM>(s_score[f], s_score[m], n_ulen[m]);
     }
     // finals: the blank continuations of the slots on the last frame, in slot order
     int nf = min(max(s_nfin0, 0), fcap), q = 0;
@@ -181,6 +189,26 @@ __global__ __launch_bounds__(AL_THREADS) void rnnt_alsd_step_kernel(
   });
 }
 
+int alsd_launch(bool lm, float lm_weight, const float* rec, const int32_t* hlens, const double* score_in, const int32_t* ulen_in,
+                const int32_t* nhyp_in, const int32_t* yseq_in, double* score_out, int32_t* ulen_out, int32_t* nhyp_out,
+                int32_t* yseq_out, double* fin_score, int32_t* fin_len, int32_t* fin_yseq, int32_t* nfin, int32_t* par, int64_t* tok,
+                uint8_t* live, int32_t* frame, int n, int W, int V, int T, int u_max, int i, void* stream) {
+  if (!rec || !score_in || !ulen_in || !nhyp_in || !yseq_in || !score_out || !ulen_out || !nhyp_out || !yseq_out || !fin_score ||
+      !fin_len || !fin_yseq || !nfin || !par || !tok || !live || !frame)
+    return EAMD_EINVAL;
+  if (n < 1 || W < 1 || V < 2 || T < 1 || u_max < 0 || i < 0) return EAMD_EINVAL;
+  if (lm_weight != lm_weight || lm_weight - lm_weight != 0.f) return EAMD_EINVAL;            // NaN or infinite
+  if (score_in == score_out || ulen_in == ulen_out || nhyp_in == nhyp_out || yseq_in == yseq_out) return EAMD_EINVAL;
+  if (W > AL_W || W > V) return EAMD_EUNSUPPORTED;
+  if ((int64_t)n * T > 0x7fffffff || (int64_t)T + u_max + 1 > 0x7fffffff / AL_W || (int64_t)n * W > 0x7fffffff) return EAMD_EUNSUPPORTED;
+  const auto kernel = lm ? rnnt_alsd_step_kernel<true> : rnnt_alsd_step_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(n), dim3(AL_THREADS), 0, (hipStream_t)stream, rec, hlens, score_in, ulen_in, nhyp_in, yseq_in,
+                     score_out, ulen_out, nhyp_out, yseq_out, fin_score, fin_len, fin_yseq, nfin, par,
+                     reinterpret_cast<long long*>(tok), live, frame, W, V, T, u_max, i, lm_weight);
+  EAMD_LAUNCH_CHECK();
+  return EAMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -189,18 +217,17 @@ int eamd_rnnt_alsd_step(const float* rec, const int32_t* hlens, const double* sc
                         const int32_t* yseq_in, double* score_out, int32_t* ulen_out, int32_t* nhyp_out, int32_t* yseq_out,
                         double* fin_score, int32_t* fin_len, int32_t* fin_yseq, int32_t* nfin, int32_t* par, int64_t* tok,
                         uint8_t* live, int32_t* frame, int n, int W, int V, int T, int u_max, int i, void* stream) {
-  if (!rec || !score_in || !ulen_in || !nhyp_in || !yseq_in || !score_out || !ulen_out || !nhyp_out || !yseq_out || !fin_score ||
-      !fin_len || !fin_yseq || !nfin || !par || !tok || !live || !frame)
-    return EAMD_EINVAL;
-  if (n < 1 || W < 1 || V < 2 || T < 1 || u_max < 0 || i < 0) return EAMD_EINVAL;
-  if (score_in == score_out || ulen_in == ulen_out || nhyp_in == nhyp_out || yseq_in == yseq_out) return EAMD_EINVAL;
-  if (W > AL_W || W > V) return EAMD_EUNSUPPORTED;
-  if ((int64_t)n * T > 0x7fffffff || (int64_t)T + u_max + 1 > 0x7fffffff / AL_W || (int64_t)n * W > 0x7fffffff) return EAMD_EUNSUPPORTED;
-  hipLaunchKernelGGL(rnnt_alsd_step_kernel, dim3(n), dim3(AL_THREADS), 0, (hipStream_t)stream, rec, hlens, score_in, ulen_in, nhyp_in,
-                     yseq_in, score_out, ulen_out, nhyp_out, yseq_out, fin_score, fin_len, fin_yseq, nfin, par,
-                     reinterpret_cast<long long*>(tok), live, frame, W, V, T, u_max, i);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
+  return alsd_launch(false, 0.f, rec, hlens, score_in, ulen_in, nhyp_in, yseq_in, score_out, ulen_out, nhyp_out, yseq_out, fin_score,
+                     fin_len, fin_yseq, nfin, par, tok, live, frame, n, W, V, T, u_max, i, stream);
+}
+
+int eamd_rnnt_alsd_step_lm(const float* rec, const int32_t* hlens, const double* score_in, const int32_t* ulen_in,
+                           const int32_t* nhyp_in, const int32_t* yseq_in, double* score_out, int32_t* ulen_out, int32_t* nhyp_out,
+                           int32_t* yseq_out, double* fin_score, int32_t* fin_len, int32_t* fin_yseq, int32_t* nfin, int32_t* par,
+                           int64_t* tok, uint8_t* live, int32_t* frame, int n, int W, int V, int T, int u_max, int i, float lm_weight,
+                           void* stream) {
+  return alsd_launch(true, lm_weight, rec, hlens, score_in, ulen_in, nhyp_in, yseq_in, score_out, ulen_out, nhyp_out, yseq_out,
+                     fin_score, fin_len, fin_yseq, nfin, par, tok, live, frame, n, W, V, T, u_max, i, stream);
 }
 
 }  // extern "C"

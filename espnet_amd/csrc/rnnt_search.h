@@ -12,6 +12,46 @@ __device__ __forceinline__ double al_logaddexp(double a, double b) {
   return d;                                    // NaN
 }
 
+// numpy.logaddexp on floats (npy_logaddexpf)
+__device__ __forceinline__ float al_logaddexpf(float a, float b) {
+#pragma clang fp contract(off)
+  if (a == b) return a + 0.693147180559945309417232121458176568f;
+  const float d = a - b;
+  if (d > 0) return a + log1pf(expf(-d));
+  if (d <= 0) return b + log1pf(expf(d));
+  return d;                                    // NaN
+}
+
+// Score sums of alsd / tsd.  Without an LM (LM = false) every sum is a double plus a float.  With RNNLM shallow fusion the reference
+// adds lm_weight * torch.tensor(q, dtype=float32) to an extension's score, which turns the score into a float32 0-d tensor: from
+// the first label on every later sum, and the logaddexp of a merge, runs in float32; only [blank] (u == 0 labels) and its chain of
+// blank continuations stay double.  A score is still STORED as a double; with LM = true one with u > 0 holds a float32 value.  The
+// float sums and the product are single IEEE operations: contraction is switched off in these functions (device code is compiled
+// with -ffp-contract=fast, and HIP's __fmul_rn / __fadd_rn are plain operators that the compiler fuses into one multiply-add after
+// inlining), so that wf * q is rounded to float32 before it is added, as torch rounds it.
+//   rs_add    parent score S with u labels + a joint log-probability: a blank continuation, or the first half of an extension
+//   rs_ext    an extension: rs_add, then + (float)lm_weight * q, the product rounded to float32 before the sum
+//   rs_merge  the score of two equal label sequences of u labels
+template <bool LM>
+__device__ __forceinline__ double rs_add(double S, int u, float lp) {
+#pragma clang fp contract(off)
+  if (!LM || u == 0) return S + (double)lp;
+  return (double)((float)S + lp);
+}
+template <bool LM>
+__device__ __forceinline__ double rs_ext(double S, int u, float lp, float q, float wf) {
+#pragma clang fp contract(off)
+  if (!LM) return S + (double)lp;
+  const float m = wf * q;                      // rounded to float32 before the sum
+  const float s = (float)rs_add<true>(S, u, lp);
+  return (double)(s + m);
+}
+template <bool LM>
+__device__ __forceinline__ double rs_merge(double a, double b, int u) {
+  if (!LM || u == 0) return al_logaddexp(a, b);
+  return (double)al_logaddexpf((float)a, (float)b);
+}
+
 // how a score ranks: NaN counts as -inf
 __device__ __forceinline__ double rs_key(double v) { return v != v ? -INFINITY : v; }
 

@@ -13,6 +13,10 @@
 //                        rank-by-counting sort in LDS (rs_rank: stable, equal scores keep the list's order); equal label sequences
 //                        are found by comparing lengths and tokens, one wave per pair (rs_same_labels); the only traffic that grows
 //                        with T is the copy of W hypotheses' labels (rs_copy_labels).
+//   eamd_rnnt_tsd_step_lm  the same pass with RNNLM shallow fusion: the record of width 1 + 3k that eamd_transducer_expand_rows
+//                        writes with an LM (the raw LM log-probability of each chosen token behind the token ids) and lm_weight;
+//                        the score sums follow the reference's float32 arithmetic (rnnt_search.h: rs_add / rs_ext / rs_merge).
+//                        One kernel text, templated on LM.
 // Hypotheses live in M + 1 blocks of n * W rows: block 0 and block M are the two parities of B, block v (1 <= v < M) is the C of pass
 // v.  Block row = block * n * W + b * W + w.  Plain stores, no atomics, no scratch buffers: a workgroup owns its utterance's rows.
 #include "common.h"
@@ -27,22 +31,25 @@ constexpr int TS_D = TS_W * TS_W;              // candidates of D at most: W slo
 constexpr int TS_A = TS_W * TS_M;              // entries of A at most
 constexpr int TS_THREADS = 256;
 
+// LM: the record carries the k raw LM log-probabilities of the chosen tokens behind the token ids, and the score sums follow the
+// float32 rule of rnnt_search.h (rs_add / rs_ext / rs_merge) with wf = (float)lm_weight; LM = false ignores wf
+template <bool LM>
 __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     const float* __restrict__ rec, const int* __restrict__ hlens, double* __restrict__ score, int* __restrict__ ulen,
     int* __restrict__ count, int* __restrict__ yseq, double* __restrict__ a_score, int* __restrict__ a_src, int* __restrict__ nA,
     int* __restrict__ par, long long* __restrict__ tok, unsigned char* __restrict__ live, int n, int W, int V, int T, int M, int t,
-    int v, int p) {
+    int v, int p, float wf) {
   __shared__ double d_score[TS_D];             // candidates of D
   __shared__ double sa_score[TS_A];            // A: scores, block rows, lengths
   __shared__ double c_score[TS_W];             // C: scores, lengths
-  __shared__ float s_rec[TS_W * (1 + 2 * TS_W)];
+  __shared__ float s_rec[TS_W * (1 + (LM ? 3 : 2) * TS_W)];
   __shared__ int sa_src[TS_A], sa_ulen[TS_A];
   __shared__ int c_ulen[TS_W];
   __shared__ int c_new[TS_W];                  // C slot -> 1 when no entry of A holds its labels
   __shared__ int s_sel[TS_W];                  // new slot -> its candidate of D, or its entry of A
   __shared__ unsigned char s_eq[TS_W][TS_A];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int k = min(W, V - 1), RW = 1 + 2 * k;
+  const int k = min(W, V - 1), RW = 1 + (LM ? 3 : 2) * k;
   const int ycap = 1 + T * (M - 1), AM = W * M;
   const int R = n * W, rows = (M + 1) * R;
   const int cin = v == 0 ? (p ? M : 0) : v;    // the block that holds C, the block this pass writes
@@ -100,7 +107,7 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     for (int c = 0; c < nc; ++c) {
       bool mine = s_eq[c][tid] != 0;
       for (int e = 0; e < tid && mine; ++e) mine = !s_eq[c][e];
-      if (mine) s = al_logaddexp(s, c_score[c] + (double)s_rec[c * RW]);
+      if (mine) s = rs_merge<LM>(s, rs_add<LM>(c_score[c], c_ulen[c], s_rec[c * RW]), c_ulen[c]);
     }
     sa_score[tid] = s;
   } else if (tid >= 64 && tid < 64 + nc) {
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     if (c_new[c]) {
       int pos = na0;
       for (int o = 0; o < c; ++o) pos += c_new[o];
-      sa_score[pos] = c_score[c] + (double)s_rec[c * RW];
+      sa_score[pos] = rs_add<LM>(c_score[c], c_ulen[c], s_rec[c * RW]);
       sa_src[pos] = in0 + c;
       sa_ulen[pos] = c_ulen[c];
     }
@@ -126,7 +133,7 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
     const int nd = nc * k;
     for (int c = tid; c < nd; c += TS_THREADS) {
       const int w = c / k, j = c - w * k;
-      d_score[c] = c_score[w] + (double)s_rec[w * RW + 1 + j];
+      d_score[c] = rs_ext<LM>(c_score[w], c_ulen[w], s_rec[w * RW + 1 + j], LM ? s_rec[w * RW + 1 + 2 * k + j] : 0.f, wf);
     }
     __syncthreads();
     for (int c = tid; c < nd; c += TS_THREADS) {
@@ -185,15 +192,12 @@ __global__ __launch_bounds__(TS_THREADS) void rnnt_tsd_step_kernel(
   });
 }
 
-}  // namespace
-
-extern "C" {
-
-int eamd_rnnt_tsd_step(const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count, int32_t* yseq,
-                       double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W, int V,
-                       int T, int M, int t, int v, int p, void* stream) {
+int tsd_launch(bool lm, float lm_weight, const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count,
+               int32_t* yseq, double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W,
+               int V, int T, int M, int t, int v, int p, void* stream) {
   if (!rec || !score || !ulen || !count || !yseq || !a_score || !a_src || !nA || !par || !tok || !live) return EAMD_EINVAL;
   if (n < 1 || W < 1 || V < 2 || T < 1 || t < 0 || v < 0 || (M >= 1 && v >= M) || (p != 0 && p != 1)) return EAMD_EINVAL;
+  if (lm_weight != lm_weight || lm_weight - lm_weight != 0.f) return EAMD_EINVAL;            // NaN or infinite
   // one array handed in for two operands: a workgroup's stores would meet its own loads.  (The block a pass reads and the block it
   // writes are told apart by (v, p) inside one allocation, so they cannot be the same.)
   const void* const ints[] = {ulen, count, yseq, a_src, nA, par};
@@ -201,10 +205,29 @@ int eamd_rnnt_tsd_step(const float* rec, const int32_t* hlens, double* score, in
   if (W > TS_W || W > V || M < 1 || M > TS_M) return EAMD_EUNSUPPORTED;
   if ((int64_t)(M + 1) * n * W > 0x7fffffff || (int64_t)n * T > 0x7fffffff || 1 + (int64_t)T * (M - 1) > 0x7fffffff / TS_W)
     return EAMD_EUNSUPPORTED;
-  hipLaunchKernelGGL(rnnt_tsd_step_kernel, dim3(n), dim3(TS_THREADS), 0, (hipStream_t)stream, rec, hlens, score, ulen, count, yseq,
-                     a_score, a_src, nA, par, reinterpret_cast<long long*>(tok), live, n, W, V, T, M, t, v, p);
+  const auto kernel = lm ? rnnt_tsd_step_kernel<true> : rnnt_tsd_step_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(n), dim3(TS_THREADS), 0, (hipStream_t)stream, rec, hlens, score, ulen, count, yseq, a_score, a_src,
+                     nA, par, reinterpret_cast<long long*>(tok), live, n, W, V, T, M, t, v, p, lm_weight);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eamd_rnnt_tsd_step(const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count, int32_t* yseq,
+                       double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W, int V,
+                       int T, int M, int t, int v, int p, void* stream) {
+  return tsd_launch(false, 0.f, rec, hlens, score, ulen, count, yseq, a_score, a_src, nA, par, tok, live, n, W, V, T, M, t, v, p,
+                    stream);
+}
+
+int eamd_rnnt_tsd_step_lm(const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count, int32_t* yseq,
+                          double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W, int V,
+                          int T, int M, int t, int v, int p, float lm_weight, void* stream) {
+  return tsd_launch(true, lm_weight, rec, hlens, score, ulen, count, yseq, a_score, a_src, nA, par, tok, live, n, W, V, T, M, t, v, p,
+                    stream);
 }
 
 }  // extern "C"

@@ -31,6 +31,15 @@ computed is this package's own design:
   * batched tsd (`tsd_batch`): the tsd search of all utterances of a batch pass by pass in lock-step, hypotheses in M + 1 device
     blocks (B's two parities and the C of every pass), the A / C / B bookkeeping of a pass in one launch (eamd_rnnt_tsd_step), no
     host read inside the pass loop and one at the end;
+  * RNN LM shallow fusion in alsd_batch / tsd_batch (lm=ClassifierWithState(RNNLM), lm_batched=True; `_lm_batched_ok`.  The switch
+    is off by default: with an LM both calls looped over the per-utterance search before, and they keep doing so unless asked):
+    in these two searches the LM
+    advances exactly when the prediction network does, so its h / c ride in the same state copies / blocks, move in the same
+    eamd_gather_rows launch and step through the same masked cell kernels (`_stack_step`); its log-probabilities of all rows of a
+    pass come from the top layer's h (lo + log-softmax), eamd_transducer_expand_rows picks the chosen tokens' terms into its
+    record on the device, and eamd_rnnt_alsd_step_lm / eamd_rnnt_tsd_step_lm add them with the reference's float32 arithmetic
+    (below).  nsc_batch and default_batch keep looping over the per-utterance search when an LM is given: there the LM's scores
+    travel with the hypothesis (nsc) or the LM steps at pop time (default), which takes other loops;
   * batched nsc (`nsc_batch`): the nsc search of all utterances of a batch n-step by n-step in lock-step, hypotheses in N + 2 device
     blocks (kept's two parities and the V of every n-step), prefix rescoring, S, substract and the selections of a call in one
     launch (eamd_rnnt_nsc_step), the rescoring's pair terms from a device-side pair list, no host read inside the frame loop and
@@ -44,7 +53,8 @@ computed is this package's own design:
   * what the five batched searches share is written once, above them: the loop over the per-utterance search for a batch the device
     loops do not take (`_fallback` over `_one`), the lengths (`_lengths`), encoder projection + chunking by *_max_rows + the call's one
     result copy (`_chunks`), one result layout per search from which the buffer is both built and taken apart (`_pack` / `_unpack`),
-    the n-best order (`_nbest`) and the scratch builders (`_pred_ws`, `_block_ws`, `_frame_rows`); the five step loops differ for
+    the n-best order (`_nbest`), the masked cell-stack step the prediction network and the RNN LM both run (`_stack_step`) and the
+    scratch builders (`_pred_ws`, `_block_ws`, `_lm_ws`, `_frame_rows`); the five step loops differ for
     real and stay apart.  On the device the same holds for rnnt_search.h (score key, stable rank, label comparison and copy) and
     row_moves.hip (eamd_gather_rows / eamd_scatter_rows).
 
@@ -58,8 +68,11 @@ still scores and expands (`v < max_sym_exp` always holds); alsd never scores fra
 (duplicates stay, the first occurrence's score grows in place) and B is returned unsorted when no hypothesis reached the
 last frame; nsc's prefix rescoring mutates scores in length order and adds the last step's blank only when nstep != 1.
 Once an LM term is added, tsd / alsd scores are float32 0-d tensors in the reference (score + lm_weight * tensor): they are
-carried the same way here.  One reference behaviour is NOT copied: its prediction / LM caches are keyed by
-"".join(str(x) for x in yseq), which collides once V > 10 ([1, 23] and [12, 3]); the trie's node ids do not."""
+carried the same way here, by the per-utterance searches as tensors and by the device loops as doubles that hold float32 values
+(every sum, the LM product and the logaddexp of a merge rounded to float32 from the first label on; [blank] and its blank
+continuations stay double; the n-best sort divides in float32).  One reference behaviour is NOT copied: its prediction / LM
+caches are keyed by "".join(str(x) for x in yseq), which collides once V > 10 ([1, 23] and [12, 3]); the trie's node ids do not."""
+import math
 from dataclasses import dataclass, field
 from typing import Any, List
 
@@ -173,7 +186,7 @@ class _Hyp:
 
 class BeamSearchTransducer:
     def __init__(self, decoder, beam_size, lm=None, lm_weight=0.1, search_type="default", max_sym_exp=2, u_max=50,
-                 nstep=1, prefix_alpha=1, score_norm=True, frame_chunk=32):
+                 nstep=1, prefix_alpha=1, score_norm=True, frame_chunk=32, lm_batched=False):
         self.decoder = decoder
         self.beam_size = beam_size
         self.vocab_size = decoder.odim
@@ -188,6 +201,7 @@ class BeamSearchTransducer:
                                       % search_type)
         self.search_type = search_type
         self.lm, self.lm_weight = lm, lm_weight
+        self.lm_batched = lm_batched           # alsd_batch / tsd_batch take an RNN LM into their device loops (_lm_batched_ok)
         self.max_sym_exp, self.u_max, self.nstep, self.prefix_alpha = max_sym_exp, u_max, nstep, prefix_alpha
         self.score_norm = score_norm
         self.frame_chunk = frame_chunk
@@ -332,17 +346,51 @@ class BeamSearchTransducer:
         """what _pred_step needs on R rows besides lin_dec's output `d`: the token and mask vectors (zero: nothing emitted),
         `copies` copies of the prediction network's state (zero) and the step's intermediates"""
         dec = self.decoder
-        H, L = dec.dunits, dec.dlayers
-        G = (4 if dec.dtype == "lstm" else 3) * H
-        f = dict(device=dev, dtype=torch.float32)
         ws = dict(n=R)
         ws["tok"] = torch.zeros(R, device=dev, dtype=torch.int64)
         ws["live"] = torch.zeros(R, device=dev, dtype=torch.uint8)
+        ws.update(self._stack_ws(R, dec.dunits, dec.dlayers, dec.dtype, dev, copies))
+        return ws
+
+    @staticmethod
+    def _stack_ws(R, H, L, typ, dev, copies):
+        """what _stack_step needs on R rows of an L-layer cell stack of H units besides the token and mask vectors: `copies` copies
+        of its state (zero) and the step's intermediates"""
+        G = (4 if typ == "lstm" else 3) * H
+        f = dict(device=dev, dtype=torch.float32)
+        ws = {}
         ws["h"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(copies)]
         ws["c"] = [[torch.zeros(R, H, **f) for _ in range(L)] for _ in range(copies)]
         ws["gx"] = [torch.empty(R, G, **f) for _ in range(L)]
         ws["gates"] = [torch.empty(R, 4 * H, **f) for _ in range(L)]       # lstm: pre-activations / activated gates; gru: acts
-        ws["gh"] = [torch.empty(R, G, **f) for _ in range(L)] if dec.dtype == "gru" else None
+        ws["gh"] = [torch.empty(R, G, **f) for _ in range(L)] if typ == "gru" else None
+        return ws
+
+    @staticmethod
+    def _stack_blocks(ws, blocks, R, H, dev, **extra):
+        """ws (one state copy) -> the state of `blocks` blocks of R rows stacked [blocks * R, H] per layer in ws["h"] / ws["c"], the
+        copy ws had as the staging copy, and the list of per-block views: state copy 0 = the staging copy, copy 1 = the block's
+        rows, plus extra[name][j] under `name`"""
+        stage_h, stage_c = ws["h"][0], ws["c"][0]
+        ws["h"] = [torch.zeros(blocks * R, H, device=dev, dtype=torch.float32) for _ in stage_h]
+        ws["c"] = [torch.zeros(blocks * R, H, device=dev, dtype=torch.float32) for _ in stage_c]
+        return [dict(ws, h=[stage_h, [x[j * R:(j + 1) * R] for x in ws["h"]]],
+                     c=[stage_c, [x[j * R:(j + 1) * R] for x in ws["c"]]], **{name: v[j] for name, v in extra.items()})
+                for j in range(blocks)]
+
+    def _lm_ws(self, R, tok, dev, blocks=0):
+        """the LM's side of a device loop on R rows: the state of its cell stack as _pred_ws keeps the prediction network's (two
+        copies, or with `blocks` the stacked blocks and a staging copy of _block_ws, views under "blk"), the step's intermediates, the
+        loop's token vector `tok`, the [R, V] buffers of the LM's output rows ("z": logits; "logp": the log-probabilities of the
+        last pass that computed them, zero before) and the device iota eamd_transducer_expand_rows takes as lm_row"""
+        net = self.lm.predictor
+        ws = dict(n=R, tok=tok)
+        ws.update(self._stack_ws(R, net.n_units, net.n_layers, net.typ, dev, 1 if blocks else 2))
+        ws["z"] = torch.empty(R, self.vocab_size, device=dev, dtype=torch.float32)
+        ws["logp"] = torch.zeros(R, self.vocab_size, device=dev, dtype=torch.float32)
+        ws["iota"] = torch.arange(R, device=dev, dtype=torch.int32)
+        if blocks:
+            ws["blk"] = self._stack_blocks(ws, blocks, R, net.n_units, dev)
         return ws
 
     def _block_ws(self, blocks, R, d, dev):
@@ -350,12 +398,7 @@ class BeamSearchTransducer:
         block row indexes it directly), one staging copy, and ws["blk"][j] = _pred_step's view of block j: state copy 0 = the
         staging copy, copy 1 = the block's rows, d = d[j]"""
         ws = self._pred_ws(R, dev, copies=1)
-        H = self.decoder.dunits
-        stage_h, stage_c = ws["h"][0], ws["c"][0]
-        ws["h"] = [torch.zeros(blocks * R, H, device=dev, dtype=torch.float32) for _ in stage_h]
-        ws["c"] = [torch.zeros(blocks * R, H, device=dev, dtype=torch.float32) for _ in stage_c]
-        ws["blk"] = [dict(ws, d=d[j], h=[stage_h, [x[j * R:(j + 1) * R] for x in ws["h"]]],
-                          c=[stage_c, [x[j * R:(j + 1) * R] for x in ws["c"]]]) for j in range(blocks)]
+        ws["blk"] = self._stack_blocks(ws, blocks, R, self.decoder.dunits, dev, d=d)
         return ws
 
     @staticmethod
@@ -424,16 +467,17 @@ class BeamSearchTransducer:
         ws["d"] = torch.empty(n, J, device=dev, dtype=torch.float32)
         return ws
 
-    def _pred_step(self, ws, src, dst, live):
-        """prediction network on ws.tok from state copy `src` into copy `dst` (live: uint8 [n] or None = every row), then lin_dec"""
+    @staticmethod
+    def _stack_step(embed, cells, typ, H, ws, src, dst, live):
+        """an embedding + LSTMCell / GRUCell stack (the prediction network's, the RNN LM's) on ws.tok from state copy `src` into
+        copy `dst` (live: uint8 [n] or None = every row; a masked row keeps h / c) -> the top layer's new h"""
         from .. import rnn_functional as R_
-        dec, n = self.decoder, ws["n"]
-        H = dec.dunits
-        x = ops.embed_pe(ws["tok"], dec.embed.weight, None, 1, 1.0)
-        for l, cell in enumerate(dec.decoder):
+        n = ws["n"]
+        x = ops.embed_pe(ws["tok"], embed, None, 1, 1.0)
+        for l, cell in enumerate(cells):
             hp, hn, gx = ws["h"][src][l], ws["h"][dst][l], ws["gx"][l]
             ops.linear_into(x, cell.weight_ih, cell.bias_ih, gx)
-            if dec.dtype == "lstm":
+            if typ == "lstm":
                 cp, cn, gates = ws["c"][src][l], ws["c"][dst][l], ws["gates"][l]
                 if ops.lstm_step_ok(n, H):
                     ops.lstm_step_fwd(gx, cell.weight_hh, cell.bias_hh, hp, cp, live, hn, cn, None, gates)
@@ -445,7 +489,58 @@ class BeamSearchTransducer:
                 R_._rec_gemm(hp, cell.weight_hh, gh, n, 3 * H, H, H, H, 3 * H, bias=cell.bias_hh)
                 ops.gru_cell_fwd(gx, gh, hp, live, hn, None, ws["gates"][l])
             x = hn
+        return x
+
+    def _pred_step(self, ws, src, dst, live):
+        """prediction network on ws.tok from state copy `src` into copy `dst` (live: uint8 [n] or None = every row), then lin_dec"""
+        dec = self.decoder
+        x = self._stack_step(dec.embed.weight, dec.decoder, dec.dtype, dec.dunits, ws, src, dst, live)
         ops.linear_into(x, dec.joint_network.lin_dec.weight, None, ws["d"])
+
+    # ---- RNN LM shallow fusion in the alsd / tsd device loops ------------------------------------------------------------
+    # In alsd and tsd the LM advances exactly when the prediction network does: a hypothesis that appends a token steps both, one
+    # that appends nothing keeps both states.  ClassifierWithState(RNNLM) is an embedding + LSTMCell / GRUCell stack + Linear, so
+    # its state rides in the same copies / blocks as the prediction network's (_lm_ws), moves in the same eamd_gather_rows launch by
+    # the same parent rows and steps through the same masked kernels (_stack_step).  Its log-probabilities are computed for all R
+    # rows of a pass from the top layer's h (lo + eamd_log_softmax_rows; row r belongs to slot r, so lm_row is an iota and nothing
+    # [R, V]-sized is ever gathered); eamd_transducer_expand_rows picks the chosen tokens' terms into its record and the *_step_lm
+    # kernels add them by the reference's float32 arithmetic (csrc/rnnt_search.h).
+    def _lm_batched_ok(self):
+        """does the device loop take self.lm?  Asked for (lm_batched), ClassifierWithState(RNNLM) itself (lstm / gru), fp32
+        parameters on the prediction network's device, no dropout at work, a finite weight"""
+        from .lm import ClassifierWithState, RNNLM
+        lm = self.lm
+        if not self.lm_batched:
+            return False
+        if type(lm) is not ClassifierWithState or type(lm.predictor) is not RNNLM:
+            return False
+        net = lm.predictor
+        dev = self.decoder.embed.weight.device
+        try:
+            finite = math.isfinite(float(self.lm_weight))
+        except (TypeError, ValueError):
+            return False
+        return (finite and net.typ in ("lstm", "gru")
+                and all(q.dtype == torch.float32 and q.device == dev for q in net.parameters())
+                and not (net.training and any(d.p > 0 for d in net.dropout)))
+
+    def _lm_stack_step(self, ws, src, dst, live):
+        """the LM's cell stack on ws.tok from state copy `src` into copy `dst`, masked by `live`"""
+        net = self.lm.predictor
+        self._stack_step(net.embed.weight, net.rnn, net.typ, net.n_units, ws, src, dst, live)
+
+    def _lm_rows(self, ws, h_top):
+        """the LM log-probabilities of all rows from the top layer's h -> ws["logp"] [R, V]"""
+        net = self.lm.predictor
+        ops.linear_into(h_top, net.lo.weight, net.lo.bias, ws["z"])
+        return ops.log_softmax_rows(ws["z"], out=ws["logp"])
+
+    def _nbest_lm(self, hyps):
+        """_nbest for scores carried by the float32 rule: a hypothesis with labels divides score / len in float32"""
+        if not self.score_norm:
+            return self._nbest(hyps)
+        return sorted(hyps, key=lambda x: x.score / len(x.yseq) if len(x.yseq) <= 1
+                      else float(np.float32(x.score) / np.float32(len(x.yseq))), reverse=True)
 
     def _frame(self, ws, parity, t, t_dev):
         """one frame: joint + argmax, bookkeeping, masked prediction step (state copy 1 - parity -> copy parity)"""
@@ -878,15 +973,19 @@ class BeamSearchTransducer:
     alsd_max_rows = 256               # rows (utterances x W) per step loop; larger batches go in chunks.  A guess, not a measurement
 
     def _alsd_batched_ok(self):
-        return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16
+        return self._greedy_batched_ok() and (self.lm is None or self._lm_batched_ok()) and self.beam_size <= 16
 
     @ops.inference_call
     def alsd_batch(self, hs_pad, hlens=None):
         """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
         -> B n-best lists, each what __call__ returns for hs_pad[b, :hlens[b]] with search_type="alsd": the final hypotheses sorted
         by score / len(yseq) (score with score_norm=False), or B in slot order when no hypothesis reached the last frame.
-        DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16: the batched step loop above, one blocking host read per call.
-        Anything else: a loop over the per-utterance search."""
+        DecoderRNNT (lstm / gru), fp32, beam_size <= 16, without an LM or - with lm_batched=True - with ClassifierWithState(RNNLM)
+        (_lm_batched_ok): the batched step loop above, one blocking host read per call.  With an LM the scores of hypotheses with
+        labels hold float32 values, as
+        the per-utterance search carries them, and the n-best sort divides in float32.
+        Anything else (an LM without lm_batched, nsc / default with an LM, a TransformerLM, an LM with dropout at work): a loop
+        over the per-utterance search."""
         if not self._alsd_batched_ok():
             return self._fallback("_alsd", hs_pad, hlens)
         B, T = hs_pad.shape[:2]
@@ -897,11 +996,12 @@ class BeamSearchTransducer:
             steps = [t + min(u_max, t - 1) for t in frames]
             res = self._chunks(hs_pad, max(1, self.alsd_max_rows // W), lambda enc, b0, b1: self._alsd_rows(
                 enc[b0:b1], hl[b0:b1], W, u_max, max(steps[b0:b1])))
+        nbest = self._nbest if self.lm is None else self._nbest_lm
         out = []
         for r in res:
             for b in range(len(r["nfin"])):
                 if r["nfin"][b]:
-                    out.append(self._nbest([Hypothesis(score=float(r["fin_score"][b, j]),
+                    out.append(nbest([Hypothesis(score=float(r["fin_score"][b, j]),
                                                        yseq=r["fin_yseq"][b, j, :r["fin_len"][b, j]].tolist())
                                             for j in range(r["nfin"][b])]))
                 else:
@@ -946,6 +1046,11 @@ class BeamSearchTransducer:
         ws = self._alsd_ws(n, W, T, u_max, dev)
         enc_rows = enc.reshape(n * T, J)
         self._pred_step(ws, 0, 1, None)                        # the initial step on blank from the zero state, into copy 1
+        lm = None
+        if self.lm is not None:                                # the LM's step on blank from its zero state, as _ensure_lm's for the root
+            lm = self._lm_ws(n * W, ws["tok"], dev)
+            self._lm_stack_step(lm, 0, 1, None)
+            wf = float(self.lm_weight)
         # step 0 scores slot 0 on frame 1 (t = i - u + 1: frame 0 is never scored), or frame 0 of a one-frame utterance
         first = torch.arange(n, device=dev, dtype=torch.int32) * T + (hl - 1).clamp(0, 1)
         ws["frame"].copy_(first.repeat_interleave(W))
@@ -953,9 +1058,15 @@ class BeamSearchTransducer:
         lstm = dec.dtype == "lstm"
         p = 0
         for i in range(steps):
-            rec = ops.transducer_expand_rows_dev(jn.joint_rows_d(ws["encr"], ws["d"]), k)
-            ops.rnnt_alsd_step(rec, hl, ws["st"][p], ws["st"][1 - p], ws["fin"], ws["par"], ws["tok"], ws["live"], ws["frame"],
-                               V, T, u_max, i)
+            logits = jn.joint_rows_d(ws["encr"], ws["d"])
+            if lm is None:
+                rec = ops.transducer_expand_rows_dev(logits, k)
+                ops.rnnt_alsd_step(rec, hl, ws["st"][p], ws["st"][1 - p], ws["fin"], ws["par"], ws["tok"], ws["live"], ws["frame"],
+                                   V, T, u_max, i)
+            else:
+                rec = ops.transducer_expand_rows_lm_dev(logits, k, self._lm_rows(lm, lm["h"][1][-1]), lm["iota"], in_range=True)
+                ops.rnnt_alsd_step_lm(rec, hl, ws["st"][p], ws["st"][1 - p], ws["fin"], ws["par"], ws["tok"], ws["live"],
+                                      ws["frame"], V, T, u_max, i, wf)
             p = 1 - p
             if i == steps - 1:
                 break
@@ -964,8 +1075,15 @@ class BeamSearchTransducer:
                 jobs.append((ws["h"][0][l], ws["h"][1][l], ws["par"]))
                 if lstm:
                     jobs.append((ws["c"][0][l], ws["c"][1][l], ws["par"]))
+            if lm is not None:
+                for l in range(self.lm.predictor.n_layers):
+                    jobs.append((lm["h"][0][l], lm["h"][1][l], ws["par"]))
+                    if self.lm.predictor.typ == "lstm":
+                        jobs.append((lm["c"][0][l], lm["c"][1][l], ws["par"]))
             ops.gather_rows(jobs)
             self._pred_step(ws, 0, 1, ws["live"])
+            if lm is not None:
+                self._lm_stack_step(lm, 0, 1, ws["live"])
         score, ulen, nhyp, yseq = ws["st"][p]
         fin_score, fin_len, fin_yseq, nfin = ws["fin"]
         layout = self._alsd_layout(n, W, T, u_max)
@@ -985,15 +1103,21 @@ class BeamSearchTransducer:
     tsd_max_rows = 256                # rows (utterances x W) per pass loop; larger batches go in chunks.  A guess, not a measurement
 
     def _tsd_batched_ok(self):
-        return self._greedy_batched_ok() and self.lm is None and self.beam_size <= 16 and 1 <= self.max_sym_exp <= 4
+        return (self._greedy_batched_ok() and (self.lm is None or self._lm_batched_ok()) and self.beam_size <= 16
+                and 1 <= self.max_sym_exp <= 4)
 
     @ops.inference_call
     def tsd_batch(self, hs_pad, hlens=None):
         """hs_pad (B, T, D_enc) encoder states on the device, hlens (list / tensor / None = every row runs all T frames)
         -> B n-best lists, each what __call__ returns for hs_pad[b, :hlens[b]] with search_type="tsd": the last B sorted by
         score / len(yseq) (score with score_norm=False).
-        DecoderRNNT (lstm / gru) without an LM, fp32, beam_size <= 16, max_sym_exp <= 4: the batched pass loop above, one blocking
-        host read per call.  Anything else: a loop over the per-utterance search."""
+        DecoderRNNT (lstm / gru), fp32, beam_size <= 16, max_sym_exp <= 4, without an LM or - with lm_batched=True - with
+        ClassifierWithState(RNNLM) (_lm_batched_ok): the batched pass loop above, one blocking host read per call.  With an LM the
+        scores of hypotheses with
+        labels hold float32 values, as the per-utterance search carries them, and the n-best sort divides in float32.  The last pass
+        of a frame discards D: it computes no LM rows (its record's LM terms come from the buffer of the pass before and are never
+        read), but its A update follows the float32 arithmetic like every other.
+        Anything else: a loop over the per-utterance search."""
         if not self._tsd_batched_ok():
             return self._fallback("_tsd", hs_pad, hlens)
         B, T = hs_pad.shape[:2]
@@ -1003,16 +1127,16 @@ class BeamSearchTransducer:
             frames, hl = self._lengths(hlens, B, T, hs_pad.device)    # a device tensor: all T frames run, finished utterances idle
             res = self._chunks(hs_pad, max(1, self.tsd_max_rows // W), lambda enc, b0, b1: self._tsd_rows(
                 enc[b0:b1], hl[b0:b1], W, M, max(frames[b0:b1])))
-        return [hyps for r in res for hyps in self._block_nbest(r)]
+        return [hyps for r in res for hyps in self._block_nbest(r, self._nbest if self.lm is None else self._nbest_lm)]
 
     @staticmethod
     def _block_layout(n, W, ycap):
         """tsd / nsc: one hypothesis block, the last B / kept"""
         return [("score", (n, W), np.float64), ("count", (n,), np.int32), ("ulen", (n, W), np.int32), ("yseq", (n, W, ycap), np.int32)]
 
-    def _block_nbest(self, r):
+    def _block_nbest(self, r, nbest=None):
         """the n-best list of every utterance of an unpacked _block_layout"""
-        return [self._nbest([Hypothesis(score=float(r["score"][b, m]), yseq=r["yseq"][b, m, :r["ulen"][b, m] + 1].tolist())
+        return [(nbest or self._nbest)([Hypothesis(score=float(r["score"][b, m]), yseq=r["yseq"][b, m, :r["ulen"][b, m] + 1].tolist())
                              for m in range(r["count"][b])]) for b in range(len(r["count"]))]
 
     def _tsd_ws(self, n, W, T, M, dev):
@@ -1046,6 +1170,14 @@ class BeamSearchTransducer:
         st, blk = ws["st"], ws["blk"]
         self._pred_step(blk[0], 0, 1, None)                    # the initial step on blank from the zero state, into block 0
         lstm = dec.dtype == "lstm"
+        lm = None
+        if self.lm is not None:                                # the LM's step on blank from its zero state, into block 0
+            lm = self._lm_ws(R, ws["tok"], dev, blocks=M + 1)
+            lblk = lm["blk"]
+            self._lm_stack_step(lblk[0], 0, 1, None)
+            wf = float(self.lm_weight)
+            lm_layers = range(self.lm.predictor.n_layers)
+            lm_lstm = self.lm.predictor.typ == "lstm"
         p = 0
         if frames:
             ft = self._frame_rows(hl, T, W, frames)
@@ -1054,12 +1186,23 @@ class BeamSearchTransducer:
             for v in range(M):
                 cin = (M if p else 0) if v == 0 else v
                 cout = v + 1 if v < M - 1 else (0 if p else M)
-                rec = ops.transducer_expand_rows_dev(jn.joint_rows_d(ws["encr"], blk[cin]["d"]), k)
-                ops.rnnt_tsd_step(rec, hl, st, ws["A"], ws["par"], ws["tok"], ws["live"], V, T, M, t, v, p)
+                logits = jn.joint_rows_d(ws["encr"], blk[cin]["d"])
+                if lm is None:
+                    rec = ops.transducer_expand_rows_dev(logits, k)
+                    ops.rnnt_tsd_step(rec, hl, st, ws["A"], ws["par"], ws["tok"], ws["live"], V, T, M, t, v, p)
+                else:
+                    # the last pass builds no D: its LM terms are never read, so the buffer of the pass before stands in for them
+                    logp = self._lm_rows(lm, lblk[cin]["h"][1][-1]) if v < M - 1 else lm["logp"]
+                    rec = ops.transducer_expand_rows_lm_dev(logits, k, logp, lm["iota"], in_range=True)
+                    ops.rnnt_tsd_step_lm(rec, hl, st, ws["A"], ws["par"], ws["tok"], ws["live"], V, T, M, t, v, p, wf)
                 if v < M - 1:
                     jobs = [(blk[cout]["h"][0][l], ws["h"][l], ws["par"]) for l in range(dec.dlayers)]
                     if lstm:
                         jobs += [(blk[cout]["c"][0][l], ws["c"][l], ws["par"]) for l in range(dec.dlayers)]
+                    if lm is not None:
+                        jobs += [(lblk[cout]["h"][0][l], lm["h"][l], ws["par"]) for l in lm_layers]
+                        if lm_lstm:
+                            jobs += [(lblk[cout]["c"][0][l], lm["c"][l], ws["par"]) for l in lm_layers]
                 elif t == frames - 1:
                     break                                      # the last B's prediction state is never read
                 else:
@@ -1067,9 +1210,15 @@ class BeamSearchTransducer:
                     if lstm:
                         jobs += [(blk[cout]["c"][1][l], ws["c"][l], ws["par"]) for l in range(dec.dlayers)]
                     jobs += [(blk[cout]["d"], ws["d"], ws["par"]), (ws["encr"], enc_rows, ft[t + 1])]
+                    if lm is not None:
+                        jobs += [(lblk[cout]["h"][1][l], lm["h"][l], ws["par"]) for l in lm_layers]
+                        if lm_lstm:
+                            jobs += [(lblk[cout]["c"][1][l], lm["c"][l], ws["par"]) for l in lm_layers]
                 ops.gather_rows(jobs)
                 if v < M - 1:
                     self._pred_step(blk[cout], 0, 1, ws["live"])
+                    if lm is not None:
+                        self._lm_stack_step(lblk[cout], 0, 1, ws["live"])
             p = 1 - p
         last = M if p else 0
         layout = self._block_layout(n, W, 1 + T * (M - 1))

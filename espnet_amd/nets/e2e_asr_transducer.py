@@ -226,7 +226,9 @@ class E2E(ASRInterface, torch.nn.Module):
         with search_type "default" BeamSearchTransducer.default_batch - all utterances pop by pop on the device, each with its
         own frame counter (the inner loop has a data-dependent length): a read of the done flags after the first
         beam x frames steps and after every further chunk, one result copy, and the per-utterance search again for an
-        utterance whose frame took more pops than the device keeps."""
+        utterance whose frame took more pops than the device keeps.  With RNNLM shallow fusion (lm=ClassifierWithState(RNNLM),
+        lm_batched=True) alsd and tsd still take their device loops, the LM's state riding beside the prediction network's;
+        without the switch, for nsc and default with an LM, and for any other LM, the per-utterance search is looped over."""
         from dataclasses import asdict
         self.eval()
         p = next(self.parameters())

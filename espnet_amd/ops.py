@@ -1463,9 +1463,15 @@ def beam_finish(top_s, top_i, beam, V, L, step, eos, maxlen, sc_in, logps, c_loc
     return sc_out, yseq_out, hyp_out, hyp_i, tok_i, pos, rec
 
 
-def log_softmax_rows(x):
+def log_softmax_rows(x, out=None):
+    """log-softmax of the rows of x fp32 [rows, V]; out: a contiguous fp32 [rows, V] buffer other than x to write into"""
     rows, V = x.shape
-    y = torch.empty_like(x)
+    if out is None:
+        y = torch.empty_like(x)
+    else:
+        if out.dtype != x.dtype or tuple(out.shape) != (rows, V) or not out.is_contiguous() or out.data_ptr() == x.data_ptr():
+            raise _lib.EamdError("log_softmax_rows: out contiguous [rows, V] of x's dtype, not x itself")
+        y = out
     check(_lib.lib().eamd_log_softmax_rows(ptr(x), ptr(y), rows, V, stream_ptr()), "eamd_log_softmax_rows")
     return y
 
@@ -1556,16 +1562,38 @@ def transducer_expand_rows_dev(logits, k):
     return rec
 
 
-def rnnt_alsd_step(rec, hlens, state_in, state_out, fin, par, tok, live, frame, V, T, u_max, i):
+def transducer_expand_rows_lm_dev(logits, k, lm, lm_row, in_range=False):
+    """eamd_transducer_expand_rows with an LM, its record left on the device: logits fp32 [n, V] (unit column stride), lm fp32
+    [n_lm, V] contiguous, lm_row int32 [n] on the device -> rec fp32 [n, 1 + 3k] = (logp[r][0], the k best non-blank
+    log-probabilities, their token ids as floats, lm[lm_row[r]][token] of each).  The kernel of transducer_expand_rows; nothing is
+    read back, so lm_row cannot be checked on the host: it is clamped to lm's rows on the device first (one small launch), unless
+    the caller built it itself and says in_range=True (the search loops' iota)."""
+    n, V = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise _lib.EamdError("transducer_expand_rows_lm_dev: float32 [n, V] with unit column stride")
+    if lm.dtype != torch.float32 or lm.dim() != 2 or not lm.is_contiguous() or lm.shape[1] != V or lm.shape[0] < 1 \
+            or lm.device != logits.device or lm_row.dtype != torch.int32 or lm_row.numel() != n or not lm_row.is_contiguous() \
+            or lm_row.device != logits.device:
+        raise _lib.EamdError("transducer_expand_rows_lm_dev: lm contiguous float32 [n_lm, V], lm_row int32 [n], on the logits' device")
+    if not in_range:
+        lm_row = lm_row.clamp(0, lm.shape[0] - 1)
+    rec = torch.empty(n, 1 + 3 * k, device=logits.device, dtype=torch.float32)
+    check(_lib.lib().eamd_transducer_expand_rows(ptr(logits), logits.stride(0), n, V, k, ptr(lm), ptr(lm_row), None, 0, ptr(rec), None,
+                                                 stream_ptr()), "eamd_transducer_expand_rows")
+    return rec
+
+
+def rnnt_alsd_step(rec, hlens, state_in, state_out, fin, par, tok, live, frame, V, T, u_max, i, lm_weight=None):
     """step i of the batched alsd transducer search (eamd_rnnt_alsd_step): rec fp32 [n * W, 1 + 2k] of this step's rows, hlens int32
     [n] or None; state_in / state_out = (score float64 [n, W], ulen int32 [n, W], nhyp int32 [n], yseq int32 [n, W, T + u_max + 1])
     of the two parities; fin = (fin_score float64 [n, fcap], fin_len int32 [n, fcap], fin_yseq int32 [n, fcap, u_max + 2], nfin
-    int32 [n]) with fcap = W (u_max + 2), appended in place; par int32 / tok int64 / live uint8 / frame int32 [n * W] are written"""
+    int32 [n]) with fcap = W (u_max + 2), appended in place; par int32 / tok int64 / live uint8 / frame int32 [n * W] are written.
+    lm_weight (rnnt_alsd_step_lm): eamd_rnnt_alsd_step_lm on the record of width 1 + 3k"""
     n, W = state_in[0].shape
     k = min(W, V - 1)
     fcap = W * (u_max + 2)
     want = [((n, W), torch.float64), ((n, W), torch.int32), ((n,), torch.int32), ((n, W, T + u_max + 1), torch.int32)]
-    ok = rec.dtype == torch.float32 and rec.is_contiguous() and tuple(rec.shape) == (n * W, 1 + 2 * k)
+    ok = rec.dtype == torch.float32 and rec.is_contiguous() and tuple(rec.shape) == (n * W, 1 + (2 if lm_weight is None else 3) * k)
     for st in (state_in, state_out):
         ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(st, want))
     want_f = [((n, fcap), torch.float64), ((n, fcap), torch.int32), ((n, fcap, u_max + 2), torch.int32), ((n,), torch.int32)]
@@ -1575,22 +1603,34 @@ def rnnt_alsd_step(rec, hlens, state_in, state_out, fin, par, tok, live, frame, 
     ok = ok and (hlens is None or (hlens.dtype == torch.int32 and hlens.numel() == n and hlens.is_contiguous()))
     if not ok:
         raise _lib.EamdError("rnnt_alsd_step: operand types / shapes")
-    check(_lib.lib().eamd_rnnt_alsd_step(ptr(rec), ptr(hlens), *[ptr(x) for x in state_in], *[ptr(x) for x in state_out],
-                                         *[ptr(x) for x in fin], ptr(par), ptr(tok), ptr(live), ptr(frame), n, W, V, T, u_max, i,
-                                         stream_ptr()), "eamd_rnnt_alsd_step")
+    if lm_weight is None:
+        check(_lib.lib().eamd_rnnt_alsd_step(ptr(rec), ptr(hlens), *[ptr(x) for x in state_in], *[ptr(x) for x in state_out],
+                                             *[ptr(x) for x in fin], ptr(par), ptr(tok), ptr(live), ptr(frame), n, W, V, T, u_max, i,
+                                             stream_ptr()), "eamd_rnnt_alsd_step")
+    else:
+        check(_lib.lib().eamd_rnnt_alsd_step_lm(ptr(rec), ptr(hlens), *[ptr(x) for x in state_in], *[ptr(x) for x in state_out],
+                                                *[ptr(x) for x in fin], ptr(par), ptr(tok), ptr(live), ptr(frame), n, W, V, T, u_max,
+                                                i, float(lm_weight), stream_ptr()), "eamd_rnnt_alsd_step_lm")
 
 
-def rnnt_tsd_step(rec, hlens, state, A, par, tok, live, V, T, M, t, v, p):
+def rnnt_alsd_step_lm(rec, hlens, state_in, state_out, fin, par, tok, live, frame, V, T, u_max, i, lm_weight):
+    """rnnt_alsd_step with RNNLM shallow fusion (eamd_rnnt_alsd_step_lm): rec fp32 [n * W, 1 + 3k] as transducer_expand_rows_lm_dev
+    leaves it, lm_weight a finite number; the operands and their checks are rnnt_alsd_step's"""
+    rnnt_alsd_step(rec, hlens, state_in, state_out, fin, par, tok, live, frame, V, T, u_max, i, float(lm_weight))
+
+
+def rnnt_tsd_step(rec, hlens, state, A, par, tok, live, V, T, M, t, v, p, lm_weight=None):
     """pass (t, v) of the batched tsd transducer search (eamd_rnnt_tsd_step): rec fp32 [n * W, 1 + 2k] of the rows of C, hlens int32
     [n] or None; state = (score float64 [M + 1, n, W], ulen int32 [M + 1, n, W], count int32 [M + 1, n], yseq int32
     [M + 1, n, W, 1 + T (M - 1)]) - blocks 0 and M are B's parities, p the one frame t reads, block v the C of pass v; A = (a_score
     float64 [n, W M], a_src int32 [n, W M], nA int32 [n]); state and A are updated in place, par int32 / tok int64 / live uint8
-    [n * W] are written"""
+    [n * W] are written.  lm_weight (rnnt_tsd_step_lm): eamd_rnnt_tsd_step_lm on the record of width 1 + 3k"""
     blocks, n, W = state[0].shape
     k = min(W, V - 1)
     want = [((M + 1, n, W), torch.float64), ((M + 1, n, W), torch.int32), ((M + 1, n), torch.int32),
             ((M + 1, n, W, 1 + T * (M - 1)), torch.int32)]
-    ok = blocks == M + 1 and rec.dtype == torch.float32 and rec.is_contiguous() and tuple(rec.shape) == (n * W, 1 + 2 * k)
+    ok = blocks == M + 1 and rec.dtype == torch.float32 and rec.is_contiguous() \
+        and tuple(rec.shape) == (n * W, 1 + (2 if lm_weight is None else 3) * k)
     ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(state, want))
     want_a = [((n, W * M), torch.float64), ((n, W * M), torch.int32), ((n,), torch.int32)]
     ok = ok and all(tuple(x.shape) == s and x.dtype == d and x.is_contiguous() for x, (s, d) in zip(A, want_a))
@@ -1599,8 +1639,19 @@ def rnnt_tsd_step(rec, hlens, state, A, par, tok, live, V, T, M, t, v, p):
     ok = ok and (hlens is None or (hlens.dtype == torch.int32 and hlens.numel() == n and hlens.is_contiguous()))
     if not ok:
         raise _lib.EamdError("rnnt_tsd_step: operand types / shapes")
-    check(_lib.lib().eamd_rnnt_tsd_step(ptr(rec), ptr(hlens), *[ptr(x) for x in state], *[ptr(x) for x in A], ptr(par), ptr(tok),
-                                        ptr(live), n, W, V, T, M, t, v, p, stream_ptr()), "eamd_rnnt_tsd_step")
+    if lm_weight is None:
+        check(_lib.lib().eamd_rnnt_tsd_step(ptr(rec), ptr(hlens), *[ptr(x) for x in state], *[ptr(x) for x in A], ptr(par), ptr(tok),
+                                            ptr(live), n, W, V, T, M, t, v, p, stream_ptr()), "eamd_rnnt_tsd_step")
+    else:
+        check(_lib.lib().eamd_rnnt_tsd_step_lm(ptr(rec), ptr(hlens), *[ptr(x) for x in state], *[ptr(x) for x in A], ptr(par),
+                                               ptr(tok), ptr(live), n, W, V, T, M, t, v, p, float(lm_weight), stream_ptr()),
+              "eamd_rnnt_tsd_step_lm")
+
+
+def rnnt_tsd_step_lm(rec, hlens, state, A, par, tok, live, V, T, M, t, v, p, lm_weight):
+    """rnnt_tsd_step with RNNLM shallow fusion (eamd_rnnt_tsd_step_lm): rec fp32 [n * W, 1 + 3k] as transducer_expand_rows_lm_dev
+    leaves it, lm_weight a finite number; the operands and their checks are rnnt_tsd_step's"""
+    rnnt_tsd_step(rec, hlens, state, A, par, tok, live, V, T, M, t, v, p, float(lm_weight))
 
 
 def transducer_expand_rows_pairs_dev(logits, k, pairs, pair_out):

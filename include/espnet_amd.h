@@ -1018,6 +1018,20 @@ int eamd_rnnt_alsd_step(const float* rec, const int32_t* hlens, const double* sc
                         const int32_t* yseq_in, double* score_out, int32_t* ulen_out, int32_t* nhyp_out, int32_t* yseq_out,
                         double* fin_score, int32_t* fin_len, int32_t* fin_yseq, int32_t* nfin, int32_t* par, int64_t* tok,
                         uint8_t* live, int32_t* frame, int n, int W, int V, int T, int u_max, int i, void* stream);
+/* eamd_rnnt_alsd_step with RNNLM shallow fusion: the same step on the record eamd_transducer_expand_rows writes with an LM.
+ *   rec [n * W][1 + 3k]: blank logp, k non-blank logp, their tokens, the raw LM log-probability q of each of those tokens.
+ *   lm_weight: finite, else EAMD_EINVAL; wf = (float)lm_weight.
+ *   Score sums follow the reference's arithmetic, in which lm_weight * torch.tensor(q, dtype=float32) turns a score into a float32
+ *   tensor from the first label on.  With S the parent's score and u its labels: add(S, u, lp) = S + (double)lp when u == 0, else
+ *   (double)((float)S + lp); a blank continuation is add(S, u, rec[r][0]); an extension is (double)((float)add(S, u, lp) + wf * q),
+ *   the product rounded to float32 before the sum (no fused multiply-add); the recombination of two equal sequences of u > 0 labels
+ *   is numpy's float32 logaddexp, of u == 0 labels the double one.  Scores stay stored as doubles and are ranked as doubles.
+ *   Everything else - operands, checks, clamps, finals, par / tok / live / frame - is eamd_rnnt_alsd_step's. */
+int eamd_rnnt_alsd_step_lm(const float* rec, const int32_t* hlens, const double* score_in, const int32_t* ulen_in,
+                           const int32_t* nhyp_in, const int32_t* yseq_in, double* score_out, int32_t* ulen_out, int32_t* nhyp_out,
+                           int32_t* yseq_out, double* fin_score, int32_t* fin_len, int32_t* fin_yseq, int32_t* nfin, int32_t* par,
+                           int64_t* tok, uint8_t* live, int32_t* frame, int n, int W, int V, int T, int u_max, int i, float lm_weight,
+                           void* stream);
 int eamd_gather_rows(const float* const* src, float* const* dst, const int32_t* const* idx, const int32_t* nrows, const int32_t* width,
                      const int32_t* src_rows, int njobs, void* stream);
 /* Batched time-synchronous transducer beam search without an LM, the bookkeeping of pass (t, v) - frame t, symbol expansion v of M =
@@ -1047,6 +1061,14 @@ int eamd_gather_rows(const float* const* src, float* const* dst, const int32_t* 
 int eamd_rnnt_tsd_step(const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count, int32_t* yseq,
                        double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W, int V,
                        int T, int M, int t, int v, int p, void* stream);
+/* eamd_rnnt_tsd_step with RNNLM shallow fusion: the same pass on the record eamd_transducer_expand_rows writes with an LM, rec
+ * [n * W][1 + 3k] (the raw LM log-probability of each chosen token behind the token ids), and a finite lm_weight (else
+ * EAMD_EINVAL).  A's appends and merges and D's extensions follow the float32 arithmetic described at eamd_rnnt_alsd_step_lm (a
+ * merge of sequences with u > 0 labels is numpy's float32 logaddexp); the last pass of a frame builds no D and reads no LM term.
+ * Everything else is eamd_rnnt_tsd_step's. */
+int eamd_rnnt_tsd_step_lm(const float* rec, const int32_t* hlens, double* score, int32_t* ulen, int32_t* count, int32_t* yseq,
+                          double* a_score, int32_t* a_src, int32_t* nA, int32_t* par, int64_t* tok, uint8_t* live, int n, int W, int V,
+                          int T, int M, int t, int v, int p, float lm_weight, void* stream);
 /* Batched N-step constrained transducer beam search without an LM, the bookkeeping of call (t, v) - frame t, n-step v of N = nstep -
  * for n utterances in one launch (csrc/rnnt_nsc.hip; reference: beam_search_transducer.py:466-663 nsc_beam_search,
  * transducer/utils.py:75-93 substract).  One workgroup per utterance, plain stores.  1 <= W <= 16 slots per utterance (the beam,
