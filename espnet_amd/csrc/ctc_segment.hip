@@ -13,6 +13,7 @@
 // Unreachable cells are -inf.  Every loop is bounded by T, L, W or S; workgroups never wait for each other.
 #include <limits.h>
 #include "common.h"
+#include "select.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -54,11 +55,6 @@ __device__ __forceinline__ void load_rows(const float* __restrict__ row, int t0,
 #pragma unroll
     for (int j = 0; j < kRpt; ++j) e[j] = row[min(t0 + j, W - 1)];
   }
-}
-
-// first maximum: the larger value, of equal values the smaller row
-__device__ __forceinline__ void first_max(float& v, int& r, float v2, int r2) {
-  if (v2 > v || (v2 == v && r2 < r)) { v = v2; r = r2; }
 }
 
 template <bool kLds>
@@ -196,13 +192,8 @@ __global__ __launch_bounds__(kMaxThreads) void seg_fill_kernel(
           if (t0 + j < W) bp_c[t0 + j] = (unsigned char)(word >> (8 * j));
       }
     }
-    // the column's first maximum over the visited rows
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const float v2 = __shfl_xor(mv, d, 64);
-      const int r2 = __shfl_xor(mr, d, 64);
-      first_max(mv, mr, v2, r2);
-    }
+    // the column's first maximum over the visited rows (select.h: the larger value, of equal values the smaller row)
+    wave_first_max<64>(mv, mr);
     if (lane == 0) { am_v[wv] = mv; am_r[wv] = mr; }
     __syncthreads();                                            // also: this column's ring values are written
     float cv = am_v[0];

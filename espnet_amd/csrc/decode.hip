@@ -14,6 +14,7 @@
 //   eamd_beam_slots_dyn       the slot table behind a beam step's selection
 #include <stdlib.h>
 #include "common.h"
+#include "select.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -347,8 +348,6 @@ __global__ __launch_bounds__(256) void weighted_sum_kernel(const float* __restri
   }
 }
 
-__device__ __forceinline__ bool sel_before(float va, long ia, float vb, long ib) { return va > vb || (va == vb && ia < ib); }
-
 __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ pre, const long long* __restrict__ ids,
                                                           const float* __restrict__ psi, const float* __restrict__ c_s,
                                                           const float* __restrict__ hyp, float w_ctc, int beam, int P, int V,
@@ -390,21 +389,15 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
     long bi = 0x7fffffffffffffffL;
 #pragma unroll
     for (int q = 0; q < RMAX; ++q)
-      if (t + 256 * q < C && sel_before(pv, pi, val[q], key[q]) && sel_before(val[q], key[q], bv, bi)) { bv = val[q]; bi = key[q]; }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const float ov = __shfl_xor(bv, m);
-      const long oi = __shfl_xor(bi, m);
-      if (sel_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
+      if (t + 256 * q < C && ranks_before(pv, pi, val[q], key[q])) first_max(bv, bi, val[q], key[q]);
+    wave_first_max<64>(bv, bi);
     if (lane == 0) { sv[w] = bv; si[w] = bi; }
     __syncthreads();
     if (t == 0) {
       float fv = sv[0];
       long fi = si[0];
 #pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (sel_before(sv[q], si[q], fv, fi)) { fv = sv[q]; fi = si[q]; }
+      for (int q = 1; q < 4; ++q) first_max(fv, fi, sv[q], si[q]);
       if (fi == 0x7fffffffffffffffL) { fv = -INFINITY; fi = 0; }     // fewer candidates than `beam`: a dead slot
       wv = fv; wi = fi;
       top_s[(long)u * beam + r] = fv;
@@ -436,11 +429,6 @@ struct BeamStepArgs {
   // slot_out[s][t] = slot_in[hypothesis of s][t] for t < step, the hypothesis's slot itself at t = step
   const int* slot_in; int* slot_out; int Lcap;
 };
-__device__ __forceinline__ unsigned sel_bits(float v) {      // order-preserving bits (NaN was made -inf; -0 ranks as +0)
-  if (v == 0.f) v = 0.f;
-  const unsigned b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
   // (locals, not fields of the by-value argument struct: writing to `a` moved it to private memory - 7.5 -> 12.4 us)
   const int step_ = a.step_dev ? min(max(a.step_dev[0], 0), a.W - 2) : a.step;
@@ -479,7 +467,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
       v = v + a.hyp[h];
       val[q] = (v != v || none) ? -INFINITY : v;
       // (its index lies beyond the utterance's beam x V continuations: distinct from every real key, a dead slot if it ever wins)
-      key[q] = ((unsigned long long)sel_bits(val[q]) << 32) | (0xFFFFFFFFu - (unsigned)(none ? beam * V + c : slot * V + (int)tok));
+      key[q] = order_key(order_bits(val[q]), (unsigned)(none ? beam * V + c : slot * V + (int)tok));
       ckey[c] = key[q];
     }
   }
@@ -494,7 +482,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
         const ulonglong2 o = *reinterpret_cast<const ulonglong2*>(&ckey[j]);
         r += (o.x > key[q]) + (o.y > key[q]);
       }
-      if (r < beam) { win_s[r] = val[q]; win_i[r] = (long)(0xFFFFFFFFu - (unsigned)key[q]); }
+      if (r < beam) { win_s[r] = val[q]; win_i[r] = (long)key_index(key[q]); }
     }
   }
   __syncthreads();

@@ -16,6 +16,7 @@
 //                   block scan and two barriers.  The two DP rows live in LDS up to kEdLdsCols entries, else in the
 //                   caller's workspace.
 #include "common.h"
+#include "select.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -24,30 +25,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / EAMD_WAVE;
 constexpr int kEdLdsCols = 4096;       // DP rows of up to this many entries (n + 1) stay in LDS: 2 rows x 16 KiB
 constexpr int kEdInf = 1 << 29;
-
-// exclusive prefix sum of v over the workgroup's threads; *total = the sum.  s_w: kWaves ints of LDS.  Two barriers: every
-// thread must call it, and s_w may be reused right after.
-__device__ __forceinline__ int block_excl_sum(int v, int* s_w, int* total) {
-  const int lane = threadIdx.x & (EAMD_WAVE - 1), w = threadIdx.x / EAMD_WAVE;
-  int inc = v;
-#pragma unroll
-  for (int d = 1; d < EAMD_WAVE; d <<= 1) {
-    const int o = __shfl_up(inc, d, EAMD_WAVE);
-    if (lane >= d) inc += o;
-  }
-  if (lane == EAMD_WAVE - 1) s_w[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    const int s = s_w[k];
-    if (k < w) base += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
 
 // exclusive prefix min over the workgroup's threads (kEdInf for thread 0).  One barrier: s_w must not be rewritten before the
 // caller's next barrier.
@@ -155,7 +132,7 @@ __global__ __launch_bounds__(kThreads) void text_units_kernel(const int* __restr
       }
     }
     int tot;
-    const int pos = n + block_excl_sum(len, s_w, &tot);
+    const int pos = n + block_excl_sum<kThreads>(len, s_w, &tot);
     for (int k = 0; k < len && pos + k < cap; ++k) s[pos + k] = tok_cp[off + k];
     n += tot;
   }
@@ -171,7 +148,7 @@ __global__ __launch_bounds__(kThreads) void text_units_kernel(const int* __restr
       flag = words ? (cp != 0x20 && (q == 0 || s[q - 1] == 0x20)) : (cp != drop_cp);
     }
     int tot;
-    const int pos = cnt + block_excl_sum(flag, s_w, &tot);
+    const int pos = cnt + block_excl_sum<kThreads>(flag, s_w, &tot);
     if (flag) o[pos] = words ? (long long)word_hash(s, q, n) : (long long)cp;
     cnt += tot;
   }

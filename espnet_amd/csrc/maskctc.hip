@@ -11,6 +11,7 @@
 //   phase 2 (one workgroup per utterance): pass < niter-1: the kper masked positions with the largest scores get their argmax
 //     (equal scores: the lower position first); pass == niter-1: every masked position gets its argmax; later passes: frozen.
 #include "common.h"
+#include "select.h"
 #include "../../include/espnet_amd.h"
 
 #include <float.h>
@@ -21,30 +22,11 @@ constexpr int kRowThreads = 256;
 constexpr int kSeqThreads = 1024;
 constexpr int kSeqPer = EAMD_MASKCTC_MAX_FRAMES / kSeqThreads;   // frames (or positions) per thread in phase 2
 
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
+// the six-step butterfly, not common.h's wave_sum: another order of the additions changes the last bits of p, and p is compared
+// with a threshold
+__device__ __forceinline__ float butterfly_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-// (value, index) with the larger value winning and, on equal values, the lower index
-__device__ __forceinline__ void arg_merge(float& v, int& i, float v2, int i2) {
-  if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-}
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-  for (int o = 32; o > 0; o >>= 1) arg_merge(v, i, __shfl_xor(v, o, 64), __shfl_xor(i, o, 64));
-}
-// block-wide (value, index) argmax over kRowThreads threads; every thread gets the result
-__device__ void block_argmax(float& v, int& i, float* sv, int* si) {
-  wave_argmax(v, i);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sv[w] = v; si[w] = i; }
-  __syncthreads();
-  v = sv[0]; i = si[0];
-  for (int k = 1; k < kRowThreads / 64; ++k) arg_merge(v, i, sv[k], si[k]);
-  __syncthreads();
 }
 
 // ---- seed, phase 1 ---------------------------------------------------------------------------------------------------
@@ -63,7 +45,7 @@ __global__ __launch_bounds__(kRowThreads) void maskctc_frame_kernel(const float*
     if (xv > m) { s = s * expf(m - xv) + 1.f; m = xv; } else { s += expf(xv - m); }
   }
   const float mw = wave_max(m);
-  s = wave_sum(s * expf(m - mw));
+  s = butterfly_sum(s * expf(m - mw));
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) { sv[w] = mw; ss[w] = s; }
   __syncthreads();
@@ -76,32 +58,12 @@ __global__ __launch_bounds__(kRowThreads) void maskctc_frame_kernel(const float*
   // p = exp(log-softmax) and its first-index argmax
   float pb = -1.f;
   int ib = 0x7fffffff;
-  for (int v = threadIdx.x; v < V; v += kRowThreads) arg_merge(pb, ib, expf((x[v] - mb) - lse), v);
-  block_argmax(pb, ib, sv, si);
+  for (int v = threadIdx.x; v < V; v += kRowThreads) first_max(pb, ib, expf((x[v] - mb) - lse), v);
+  block_first_max(pb, ib, sv, si, kRowThreads / 64);
   if (threadIdx.x == 0) {
     fid[(long)b * T + t] = ib;
     fp[(long)b * T + t] = pb;
   }
-}
-
-// exclusive prefix sum over the kSeqThreads threads of a block; *total gets the sum
-__device__ int block_exclusive_scan(int c, int* sw, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) sw[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int k = 0; k < kSeqThreads / 64; ++k) {
-    if (k < w) base += sw[k];
-    tot += sw[k];
-  }
-  __syncthreads();
-  *total = tot;
-  return base + inc - c;
 }
 
 // ---- seed, phase 2 ---------------------------------------------------------------------------------------------------
@@ -123,7 +85,7 @@ __global__ __launch_bounds__(kSeqThreads) void maskctc_collapse_kernel(
     if (t < Tb && id[t] != blank && (t == 0 || id[t] != id[t - 1])) ++c;
   }
   int n;
-  int k = block_exclusive_scan(c, sw, &n) - 1;     // token index of the run the thread's first frame belongs to
+  int k = block_excl_sum<kSeqThreads>(c, sw, &n) - 1;     // token index of the run the thread's first frame belongs to
   for (int i = threadIdx.x; i < n; i += kSeqThreads) sp[i] = 0u;
   __syncthreads();
   for (int j = 0; j < kSeqPer; ++j) {
@@ -153,7 +115,7 @@ __global__ __launch_bounds__(kSeqThreads) void maskctc_collapse_kernel(
     }
   }
   int M;
-  block_exclusive_scan(m, sw, &M);
+  block_excl_sum<kSeqThreads>(m, sw, &M);
   if (threadIdx.x == 0) {
     const int it = (M >= K && K > 0) ? K : M;
     len[b] = min(n, Lcap);
@@ -175,8 +137,8 @@ __global__ __launch_bounds__(kRowThreads) void maskctc_row_argmax_kernel(
   __shared__ int si[kRowThreads / 64];
   float vb = -INFINITY;
   int ib = 0x7fffffff;
-  for (int v = threadIdx.x; v < V; v += kRowThreads) arg_merge(vb, ib, x[v], v);
-  block_argmax(vb, ib, sv, si);
+  for (int v = threadIdx.x; v < V; v += kRowThreads) first_max(vb, ib, x[v], v);
+  block_first_max(vb, ib, sv, si, kRowThreads / 64);
   if (threadIdx.x == 0) {
     score[(long)b * L + l] = vb;
     arg[(long)b * L + l] = ib < V ? ib : 0;      // (a row of NaN: no value compares greater; class 0)
@@ -215,7 +177,7 @@ __global__ __launch_bounds__(kSeqThreads) void maskctc_select_kernel(
     if (!sm[i]) continue;
     const float si = ss[i];
     int r = 0;
-    for (int j = 0; j < n && r < k; ++j) r += (sm[j] && (ss[j] > si || (ss[j] == si && j < i))) ? 1 : 0;
+    for (int j = 0; j < n && r < k; ++j) r += (sm[j] && ranks_before(ss[j], j, si, i)) ? 1 : 0;
     if (r < k) y[i] = a[i];
   }
 }

@@ -4,6 +4,7 @@
 // reference: torch.nn.LSTM / LSTMCell as used by rnn/encoders.py:15-162, rnn/decoders.py:88-101,120-134,
 //            transducer/rnn_decoder.py:47-57,106-138  (gate order i, f, g, o).
 #include "common.h"
+#include "select.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -594,10 +595,7 @@ __global__ __launch_bounds__(256) void attloc_convmax_fwd_kernel(const float* __
     if (acc > best) { best = acc; bi = t; }
   }
   // wave arg-max, ties to the earliest frame (what max_pool2d's backward picks)
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ob = __shfl_xor(best, off); const int oi = __shfl_xor(bi, off);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
+  wave_first_max<64>(best, bi);
   if (lane == 0) { pooled[row] = fmaxf(best, 0.f); idx[row] = bi; }
 }
 // backward: only the arg-max frame of each (b,c) carries gradient, and only where the ReLU was active

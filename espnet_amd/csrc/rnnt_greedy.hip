@@ -17,6 +17,7 @@
 // Both read the frame index as t, or *t_dev + t (eamd_decode_self_attn_dyn's pos_dev convention): one captured graph serves every
 // frame; pick advances *t_dev after every row has read it.
 #include "common.h"
+#include "select.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -24,16 +25,6 @@ namespace {
 constexpr int RG_TILE = 16;            // columns per tile record (one workgroup)
 constexpr int RG_WAVES = 4;            // waves per workgroup: each takes every fourth 16-k round of the reduction
 constexpr int RG_REC = 4;              // floats per record: maximum, token id (bits), sum of exp, unused
-
-// first maximum of the 16 lanes that share fq (one accumulator row): equal values keep the lower id
-__device__ __forceinline__ void rg_max16(float& v, int& id) {
-#pragma unroll
-  for (int off = 1; off < 16; off <<= 1) {
-    const float ov = __shfl_xor(v, off, 64);
-    const int oi = __shfl_xor(id, off, 64);
-    if (ov > v || (ov == v && oi < id)) { v = ov; id = oi; }
-  }
-}
 
 template <int MT, bool VEC>
 __global__ __launch_bounds__(64 * RG_WAVES) void rnnt_greedy_joint_kernel(const float* __restrict__ enc, const float* __restrict__ d,
@@ -118,7 +109,7 @@ __global__ __launch_bounds__(64 * RG_WAVES) void rnnt_greedy_joint_kernel(const 
       const float v = n < V ? a + bv : -INFINITY;              // columns past V never win and add exp(-inf) = 0
       float mx = v;
       int id = n;
-      rg_max16(mx, id);
+      wave_first_max<16>(mx, id);                              // the 16 lanes that share fq (one accumulator row)
       float s = n < V ? __expf(v - mx) : 0.f;
 #pragma unroll
       for (int off = 1; off < 16; off <<= 1) s += __shfl_xor(s, off, 64);
@@ -143,15 +134,9 @@ __global__ __launch_bounds__(1024) void rnnt_greedy_pick_kernel(const float* __r
     int id = 0x7fffffff;
     for (int j = lane; j < ntile; j += 64) {                   // tiles in ascending order: a later equal maximum does not replace
       const float4 rec = *reinterpret_cast<const float4*>(pr + (long)j * RG_REC);
-      const int ri = __float_as_int(rec.y);
-      if (rec.x > mx || (rec.x == mx && ri < id)) { mx = rec.x; id = ri; }
+      first_max(mx, id, rec.x, __float_as_int(rec.y));
     }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const float ov = __shfl_xor(mx, off, 64);
-      const int oi = __shfl_xor(id, off, 64);
-      if (ov > mx || (ov == mx && oi < id)) { mx = ov; id = oi; }
-    }
+    wave_first_max<64>(mx, id);
     float s = 0.f;
     for (int j = lane; j < ntile; j += 64) {
       const float4 rec = *reinterpret_cast<const float4*>(pr + (long)j * RG_REC);

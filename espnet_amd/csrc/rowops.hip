@@ -3,6 +3,7 @@
 // unless stated; rows are staged in registers / LDS so each element is read from HBM once.
 #include <stdlib.h>
 #include "common.h"
+#include "select.h"
 #include "../../include/espnet_amd.h"
 
 namespace {
@@ -562,18 +563,7 @@ __global__ __launch_bounds__(256) void lsm_loss_reg_kernel(const float* __restri
     if (v[i].z > mx) { mx = v[i].z; am = base + 2; }
     if (v[i].w > mx) { mx = v[i].w; am = base + 3; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float om = __shfl_xor(mx, o, 64); int oi = __shfl_xor(am, o, 64);
-    if (om > mx || (om == mx && oi < am)) { mx = om; am = oi; }
-  }
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  if (l == 0) { red[w] = mx; redi[w] = am; }
-  __syncthreads();
-  mx = red[0]; am = redi[0];
-  for (int k = 1; k < 4; ++k)
-    if (red[k] > mx || (red[k] == mx && redi[k] < am)) { mx = red[k]; am = redi[k]; }
-  __syncthreads();
+  block_first_max(mx, am, red, redi, 4);
   float se = 0.f, sx = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -636,19 +626,8 @@ __global__ __launch_bounds__(256) void lsm_loss_kernel(const float* __restrict__
     float a = xr[v];
     if (a > mx) { mx = a; am = v; }
   }
-  // wave reduce (value, index) with lowest-index tie-break (torch.argmax semantics)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float om = __shfl_xor(mx, o, 64); int oi = __shfl_xor(am, o, 64);
-    if (om > mx || (om == mx && oi < am)) { mx = om; am = oi; }
-  }
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  if (l == 0) { red[w] = mx; redi[w] = am; }
-  __syncthreads();
-  mx = red[0]; am = redi[0];
-  for (int k = 1; k < (blockDim.x >> 6); ++k)
-    if (red[k] > mx || (red[k] == mx && redi[k] < am)) { mx = red[k]; am = redi[k]; }
-  __syncthreads();
+  // lowest-index tie-break (torch.argmax semantics)
+  block_first_max(mx, am, red, redi, blockDim.x >> 6);
   float se = 0.f, sx = 0.f;
   for (int v = threadIdx.x; v < V; v += blockDim.x) { float a = xr[v]; se += __expf(a - mx); sx += a; }
   se = block_sum(se, red);
@@ -682,22 +661,14 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   __shared__ int redi[16];
   const float* xr = x + (long)blockIdx.x * ld;
   float mx = -INFINITY; int am = 0x7fffffff;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) {
-    float a = xr[v];
-    if (a > mx || (a == mx && v < am)) { mx = a; am = v; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    float om = __shfl_xor(mx, o, 64); int oi = __shfl_xor(am, o, 64);
-    if (om > mx || (om == mx && oi < am)) { mx = om; am = oi; }
-  }
+  for (int v = threadIdx.x; v < V; v += blockDim.x) first_max(mx, am, xr[v], v);
+  wave_first_max<64>(mx, am);
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   if (l == 0) { red[w] = mx; redi[w] = am; }
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0) {                 // (thread 0 finishes alone: one barrier)
     mx = red[0]; am = redi[0];
-    for (int k = 1; k < (blockDim.x >> 6); ++k)
-      if (red[k] > mx || (red[k] == mx && redi[k] < am)) { mx = red[k]; am = redi[k]; }
+    for (int k = 1; k < (blockDim.x >> 6); ++k) first_max(mx, am, red[k], redi[k]);
     out[blockIdx.x] = am == 0x7fffffff ? 0 : am;
   }
 }
@@ -1107,24 +1078,13 @@ __global__ __launch_bounds__(256) void linear_mfma16_ksplit_f32_kernel(const flo
 
 // k largest of every row, sorted: value descending, equal values by ascending index (a total order: the selection is the same
 // whatever the grid or the replay).  NaN counts as -inf, -0 as +0.  One workgroup per row; an element is the 64-bit key
-// (order-preserving bits of the value, ~index): "ranks before" is one unsigned compare.
+// (order-preserving bits of the value, ~index): "ranks before" is one unsigned compare (select.h: order_key, block_topk).
 // For the beam search's selections (beam_search.py:143-176: top-k over V and over beam x V per utterance, k <= 1.5 beam):
-// n = 5000 .. 50000, k = 10 .. 15.  Rows of up to 6144 elements stay in registers (24 per thread) and are cut down first: every
-// element of the answer is >= the k-th largest of the 256 per-thread maxima (those k maxima alone are k elements that large), so
-// the elements above that threshold - a few dozen in general - are gathered in LDS and ranked by counting (35 us as k rounds of
-// "largest element below the previous winner" over the whole row, which remains the path for longer rows and for rows with more
-// than TOPK_CAP elements at the threshold).
+// n = 5000 .. 50000, k = 10 .. 15.  Rows of up to 6144 elements stay in registers (24 per thread) and are ranked by counting
+// among the few dozen elements above a threshold (35 us as k rounds of "largest element below the previous winner" over the
+// whole row, which remains the path for longer rows and for rows with more than TOPK_CAP elements at the threshold).
 // torch.topk's multi-block path for these sizes (6 launches + a sort) is also what faults under hipGraph replay on this ROCm.
 namespace {
-constexpr int TOPK_CAP = 1024;
-__device__ __forceinline__ unsigned topk_bits(float v) {
-  v = (v != v) ? -INFINITY : v;
-  if (v == 0.f) v = 0.f;
-  const unsigned b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float topk_value(unsigned b) { return __uint_as_float((b & 0x80000000u) ? (b ^ 0x80000000u) : ~b); }
-__device__ __forceinline__ unsigned long long topk_key(unsigned bits, unsigned i) { return ((unsigned long long)bits << 32) | (0xFFFFFFFFu - i); }
 
 // FUSED: the row is the weighted sum of up to four rows (the scorers' log-probabilities of a beam step, weighted_sum_kernel's
 // arithmetic: separately rounded products and sums), formed while it is read and written out as `pre` for the selection.
@@ -1135,7 +1095,7 @@ template <bool FUSED>
 __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict__ x, long ld, int n, int k,
                                                         float* __restrict__ vals, int64_t* __restrict__ idx, int32_t* __restrict__ idx32,
                                                         const TopkSum ws) {
-  auto element = [&](long i) -> float {
+  auto element = [&, ws](long i) -> float {      // (ws by value: through a reference its weights were re-read per element)
     if constexpr (!FUSED) return x[(long)blockIdx.x * ld + i];
     const long e = (long)blockIdx.x * n + i;
     float v = ws.w[0] * ws.l[0][e];
@@ -1156,111 +1116,33 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
   __shared__ unsigned long long wk;
   __shared__ unsigned tau;
   __shared__ int cnt;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int t = threadIdx.x;
   const int ko = k + (ws.extra >= 0 ? 1 : 0);    // output row stride
   if (t == 0 && ws.extra >= 0) {
     idx[(long)blockIdx.x * ko + k] = ws.extra;
     if (idx32) idx32[(long)blockIdx.x * ko + k] = ws.extra;
     vals[(long)blockIdx.x * ko + k] = 0.f;
   }
-  constexpr int RMAX = 24;                       // register-resident elements per thread (n <= 6144); longer rows re-read memory
-  unsigned reg[RMAX];                            // order-preserving bits; 0 (below every real element) past the end of the row
-  const bool inreg = n <= RMAX * 256;
+  const bool inreg = n <= TOPK_RMAX * 256;       // longer rows re-read memory
   const float* xr = FUSED ? ws.pre + (long)blockIdx.x * n : x + (long)blockIdx.x * ld;      // what the re-reading rounds walk
   if (FUSED && !inreg) {                         // a long row: formed once, then read back like any other
     for (long i = t; i < n; i += 256) element(i);
     __syncthreads();
   }
-  if (inreg) {
-    unsigned tm = 0;
-#pragma unroll
-    for (int q = 0; q < RMAX; ++q) {
-      const int i = t + 256 * q;
-      reg[q] = i < n ? topk_bits(element(i)) : 0u;
-      tm = max(tm, reg[q]);
-    }
-    tmax[t] = tm;
-    if (t == 0) { tau = 0xFFFFFFFFu; cnt = 0; }
-    __syncthreads();
-    int above = 0;                               // thread maxima strictly above mine
-#pragma unroll 8
-    for (int j = 0; j < 256; j += 4) {
-      const uint4 v = *reinterpret_cast<const uint4*>(&tmax[j]);
-      above += (v.x > tm) + (v.y > tm) + (v.z > tm) + (v.w > tm);
-    }
-    if (above < k && tm != 0u) atomicMin(&tau, tm);
-    __syncthreads();
-    const unsigned th = tau;
-#pragma unroll
-    for (int q = 0; q < RMAX; ++q) {
-      if (reg[q] >= th && reg[q] != 0u) {
-        const int p = atomicAdd(&cnt, 1);
-        if (p < TOPK_CAP) cand[p] = topk_key(reg[q], (unsigned)(t + 256 * q));
-      }
-    }
-    __syncthreads();
-    const int c = cnt;
-    if (c <= TOPK_CAP) {
-      for (int j = t; j < c; j += 256) {
-        const unsigned long long my = cand[j];
-        int r = 0;
-        for (int q = 0; q < c; ++q) r += cand[q] > my;
-        if (r < k) {
-          const long o = (long)blockIdx.x * ko + r;
-          const unsigned i = 0xFFFFFFFFu - (unsigned)my;
-          vals[o] = topk_value((unsigned)(my >> 32));
-          idx[o] = (int64_t)i;
-          if (idx32) idx32[o] = (int32_t)i;
-          if ((int)i == ws.extra) {              // (after the barriers above: ordered behind thread 0's store)
-            idx[(long)blockIdx.x * ko + k] = -1;
-            if (idx32) idx32[(long)blockIdx.x * ko + k] = -1;
-          }
-        }
-      }
-      return;
-    }
-    __syncthreads();
-  }
-  unsigned long long prev = 0xFFFFFFFFFFFFFFFFull;      // previous winner: every element ranks after it
-  for (int r = 0; r < k; ++r) {
-    unsigned long long best = 0;
-    if (inreg) {
-#pragma unroll
-      for (int q = 0; q < RMAX; ++q) {
-        const unsigned long long key = topk_key(reg[q], (unsigned)(t + 256 * q));
-        if (reg[q] != 0u && key < prev && key > best) best = key;
-      }
-    } else {
-      for (long i = t; i < n; i += 256) {
-        const unsigned long long key = topk_key(topk_bits(xr[i]), (unsigned)i);
-        if (key < prev && key > best) best = key;
-      }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const unsigned long long o = __shfl_xor(best, m);
-      best = o > best ? o : best;
-    }
-    if (lane == 0) sk[w] = best;
-    __syncthreads();
-    if (t == 0) {
-      unsigned long long f = sk[0];
-#pragma unroll
-      for (int q = 1; q < 4; ++q) f = sk[q] > f ? sk[q] : f;
-      wk = f;
-      const long o = (long)blockIdx.x * ko + r;
-      const unsigned i = 0xFFFFFFFFu - (unsigned)f;
-      vals[o] = topk_value((unsigned)(f >> 32));
-      idx[o] = (int64_t)i;
-      if (idx32) idx32[o] = (int32_t)i;
-      if ((int)i == ws.extra) {
-        idx[(long)blockIdx.x * ko + k] = -1;
-        if (idx32) idx32[(long)blockIdx.x * ko + k] = -1;
-      }
-    }
-    __syncthreads();
-    prev = wk;
-  }
+  block_topk(0, n, k, TopkLds{tmax, cand, sk, &wk, &tau, &cnt},
+             [&](int q) { return t + 256 * q < n ? order_bits(element(t + 256 * q)) : 0u; },
+             [&](long i) { return order_key(order_bits(xr[i]), (unsigned)i); },
+             [&](int r, unsigned long long key) {
+               const long o = (long)blockIdx.x * ko + r;
+               const unsigned i = key_index(key);
+               vals[o] = order_value((unsigned)(key >> 32));
+               idx[o] = (int64_t)i;
+               if (idx32) idx32[o] = (int32_t)i;
+               if ((int)i == ws.extra) {              // (after block_topk's barriers: ordered behind thread 0's store)
+                 idx[(long)blockIdx.x * ko + k] = -1;
+                 if (idx32) idx32[(long)blockIdx.x * ko + k] = -1;
+               }
+             });
 }
 
 // Everything one pass of a transducer search needs from the joint network's logits, in one launch (reference:
@@ -1281,31 +1163,30 @@ __global__ __launch_bounds__(256) void transducer_expand_rows_kernel(const float
   __shared__ unsigned long long wk;
   __shared__ unsigned tau;
   __shared__ int cnt;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int t = threadIdx.x;
   const int row = blockIdx.x;
   const float* xr = x + (long)row * ld;
   const int W = 1 + 2 * k + (lm ? k : 0);
   float* out = rec + (long)row * W;
   const float* lmr = lm ? lm + (long)lm_row[row] * V : nullptr;
-  constexpr int RMAX = 24;
+  constexpr int RMAX = TOPK_RMAX;
   const bool inreg = V <= RMAX * 256;
   // ---- log-sum-exp: log_softmax_rows_kernel's two paths
-  unsigned reg[RMAX];
+  float reg[RMAX];
   float lse;
   if (inreg) {
     float mx = -INFINITY;
 #pragma unroll
     for (int q = 0; q < RMAX; ++q) {
       const int v = t + 256 * q;
-      const float e = v < V ? xr[v] : -INFINITY;
-      reg[q] = __float_as_uint(e);
-      mx = fmaxf(mx, e);
+      reg[q] = v < V ? xr[v] : -INFINITY;
+      mx = fmaxf(mx, reg[q]);
     }
     mx = block_max(mx, red);
     float se = 0.f;
 #pragma unroll
     for (int q = 0; q < RMAX; ++q)
-      if (t + 256 * q < V) se += __expf(__uint_as_float(reg[q]) - mx);
+      if (t + 256 * q < V) se += __expf(reg[q] - mx);
     se = block_sum(se, red);
     lse = mx + __logf(se);
   } else {
@@ -1324,85 +1205,16 @@ __global__ __launch_bounds__(256) void transducer_expand_rows_kernel(const float
       pair_out[j] = (tok >= 0 && tok < V) ? xr[tok] - lse : __int_as_float(0x7fc00000);
     }
   }
-  auto emit = [&](int r, unsigned long long key) {        // rank r of the selection
-    const int v = (int)(0xFFFFFFFFu - (unsigned)key);
-    out[1 + r] = topk_value((unsigned)(key >> 32));
-    out[1 + k + r] = (float)v;
-    if (lmr) out[1 + 2 * k + r] = lmr[v];
-  };
-  // ---- top-k of logp[1:V): topk_rows_kernel's selection, the row register-resident as order-preserving bits (0 = no element)
-  if (inreg) {
-    unsigned tm = 0;
-#pragma unroll
-    for (int q = 0; q < RMAX; ++q) {
-      const int v = t + 256 * q;
-      reg[q] = (v >= 1 && v < V) ? topk_bits(__uint_as_float(reg[q]) - lse) : 0u;
-      tm = max(tm, reg[q]);
-    }
-    tmax[t] = tm;
-    if (t == 0) { tau = 0xFFFFFFFFu; cnt = 0; }
-    __syncthreads();
-    int above = 0;
-#pragma unroll 8
-    for (int j = 0; j < 256; j += 4) {
-      const uint4 v = *reinterpret_cast<const uint4*>(&tmax[j]);
-      above += (v.x > tm) + (v.y > tm) + (v.z > tm) + (v.w > tm);
-    }
-    if (above < k && tm != 0u) atomicMin(&tau, tm);
-    __syncthreads();
-    const unsigned th = tau;
-#pragma unroll
-    for (int q = 0; q < RMAX; ++q) {
-      if (reg[q] >= th && reg[q] != 0u) {
-        const int p = atomicAdd(&cnt, 1);
-        if (p < TOPK_CAP) cand[p] = topk_key(reg[q], (unsigned)(t + 256 * q));
-      }
-    }
-    __syncthreads();
-    const int c = cnt;
-    if (c <= TOPK_CAP) {
-      for (int j = t; j < c; j += 256) {
-        const unsigned long long my = cand[j];
-        int r = 0;
-        for (int q = 0; q < c; ++q) r += cand[q] > my;
-        if (r < k) emit(r, my);
-      }
-      return;
-    }
-    __syncthreads();
-  }
-  unsigned long long prev = 0xFFFFFFFFFFFFFFFFull;
-  for (int r = 0; r < k; ++r) {
-    unsigned long long best = 0;
-    if (inreg) {
-#pragma unroll
-      for (int q = 0; q < RMAX; ++q) {
-        const unsigned long long key = topk_key(reg[q], (unsigned)(t + 256 * q));
-        if (reg[q] != 0u && key < prev && key > best) best = key;
-      }
-    } else {
-      for (int v = t + 1; v < V; v += 256) {       // the re-reading rounds of topk_rows_kernel, starting at token 1
-        const unsigned long long key = topk_key(topk_bits(xr[v] - lse), (unsigned)v);
-        if (key < prev && key > best) best = key;
-      }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const unsigned long long o = __shfl_xor(best, m);
-      best = o > best ? o : best;
-    }
-    if (lane == 0) sk[w] = best;
-    __syncthreads();
-    if (t == 0) {
-      unsigned long long f = sk[0];
-#pragma unroll
-      for (int q = 1; q < 4; ++q) f = sk[q] > f ? sk[q] : f;
-      wk = f;
-      emit(r, f);
-    }
-    __syncthreads();
-    prev = wk;
-  }
+  // ---- top-k of logp[1:V): topk_rows_kernel's selection, on the registers of the pass above where the row is resident
+  block_topk(1, V, k, TopkLds{tmax, cand, sk, &wk, &tau, &cnt},
+             [&](int q) { return (t + 256 * q >= 1 && t + 256 * q < V) ? order_bits(reg[q] - lse) : 0u; },
+             [&](long v) { return order_key(order_bits(xr[v] - lse), (unsigned)v); },
+             [&](int r, unsigned long long key) {        // rank r of the selection
+               const int v = (int)key_index(key);
+               out[1 + r] = order_value((unsigned)(key >> 32));
+               out[1 + k + r] = (float)v;
+               if (lmr) out[1 + 2 * k + r] = lmr[v];
+             });
 }
 }  // namespace
 

@@ -428,6 +428,39 @@ def test_argmax_rows_bit_exact(ops, lib, V):
         assert torch.equal(ops.argmax_rows(xd), out)
 
 
+@pytest.mark.parametrize("V", [7, 300, 6145])
+def test_selection_kernels_agree_on_the_first_maximum(ops, V):
+    """argmax_rows, topk_rows(k = 1) and transducer_expand_rows (top-1 over tokens 1..V of a row with a column 0 in
+    front) name the same element: the larger value and, of equal values, the lower index (csrc/select.h).  NaN-free rows
+    only: argmax_rows skips a NaN, the top-k kernels rank it as -inf."""
+    g = torch.Generator().manual_seed(V)
+
+    def distinct():
+        # distinct multiples of 1/8: x - lse (|.| < 1024, ulp <= 6.1e-5) keeps them distinct, so the subtraction of
+        # transducer_expand_rows cannot turn two neighbours into a tie the other two kernels do not see
+        return torch.randperm(V, generator=g).float() / 8
+
+    x = torch.empty(6, V)
+    x[0] = 0.75                                             # constant: index 0
+    x[1] = -INF                                             # -inf only: index 0
+    x[2] = distinct()                                       # a tie at the top, far apart: the lower index
+    x[2, 1] = x[2, V - 2] = V
+    x[3] = -1 - distinct()                                  # -0 in front of +0 at the top of a negative row
+    x[3, 2], x[3, V - 1] = -0.0, 0.0
+    x[4] = -1 - distinct()                                  # +0 in front of -0
+    x[4, 2], x[4, V - 1] = 0.0, -0.0
+    x[5] = distinct() - V / 16
+    want = torch.tensor([0, 0, 1, 2, 2, int(x[5].argmax())])
+    xd = x.to(DEV)
+    am = ops.argmax_rows(xd).cpu().long()
+    tk = ops.topk_rows(xd, 1)[1].cpu().reshape(-1)
+    rows, _ = ops.transducer_expand_rows(torch.cat([torch.zeros(6, 1), x], 1).to(DEV), 1)
+    ex = torch.tensor([r[1][0][1] - 1 for r in rows])
+    assert torch.equal(am, want), f"argmax_rows {am.tolist()} != {want.tolist()}"
+    assert torch.equal(tk, am), f"topk_rows {tk.tolist()} != argmax_rows {am.tolist()}"
+    assert torch.equal(ex, am), f"transducer_expand_rows {ex.tolist()} != argmax_rows {am.tolist()}"
+
+
 # ---------------------------------------------------------------------------------------------
 # LayerNorm
 # ---------------------------------------------------------------------------------------------
