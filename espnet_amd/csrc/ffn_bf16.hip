@@ -18,27 +18,28 @@
 //     out[32 rows, 32 columns w*32..] += h_chunk W2[:, chunk]^T (16 MFMAs, A fragments from LDS).
 // Backward runs the SAME kernel on the packed images of the transposed weights (eamd_ffn_pack_bf16 makes all four images
 // of a layer in one launch); its epilogue is dz = alpha * acc * f with f staged through LDS.
+// Geometry, LayerNorm staging and the output piece are rowblock.h's, shared with ffn_f32.hip and rowproj_f32.hip.
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "../../include/espnet_amd.h"
-#include "ffn_ln.h"
+#include "rowblock.h"
 
 namespace {
 
 typedef unsigned short bf16_t;
-constexpr int BBM = 32, BD = 256, BHC = 128, BNT = 512;
-constexpr int HLD = BHC + 8;                   // bf16 elements per LDS row of a chunk image (272 bytes: 16-byte aligned rows)
-constexpr int HSZ = BBM * HLD;                 // elements per chunk image
-constexpr int YLD = BD + 4;                    // fp32 staging of the output rows
-constexpr int XLDB = BD + 8;                   // bf16 elements per LDS row of the input image
-constexpr size_t B_CHUNKS = (size_t)4 * HSZ * 2, B_XS = (size_t)BBM * XLDB * 2;
-constexpr size_t B_SMEM = (B_CHUNKS + B_XS) > (size_t)BBM * YLD * 4 ? (B_CHUNKS + B_XS) : (size_t)BBM * YLD * 4;
+constexpr int BHC = 128;                       // hidden units per chunk
+constexpr int HLD = rb_ld(BHC);                  // bf16 elements per LDS row of a chunk image (272 bytes: 16-byte aligned rows)
+constexpr int HSZ = RB_M * HLD;                 // elements per chunk image
+constexpr int YLD = RB_D + 4;                    // fp32 staging of the output rows
+constexpr int XLDB = rb_ld(RB_D);                 // bf16 elements per LDS row of the input image
+constexpr size_t B_CHUNKS = (size_t)4 * HSZ * 2, B_XS = (size_t)RB_M * XLDB * 2;
+constexpr size_t B_SMEM = (B_CHUNKS + B_XS) > (size_t)RB_M * YLD * 4 ? (B_CHUNKS + B_XS) : (size_t)RB_M * YLD * 4;
 
 __device__ __forceinline__ float bf2f_(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
 
 template <bool BWD, int ACT>
-__global__ __launch_bounds__(BNT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) {
+__global__ __launch_bounds__(RB_NT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   bf16_t* const hs = reinterpret_cast<bf16_t*>(smem_raw);          // [2][32][HLD]: h (forward) / dz (backward)
   bf16_t* const fs = hs + 2 * HSZ;                                  // [2][32][HLD]: f (forward: out; backward: in)
@@ -46,10 +47,10 @@ __global__ __launch_bounds__(BNT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) {
   const int t = threadIdx.x;
   const int lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int fr = lane & 15, fq = lane >> 4;
-  const int m0 = blockIdx.x * BBM;
+  const int m0 = blockIdx.x * RB_M;
   const int F = p.F;
   const int nch = F / BHC;
-  const bool full_rows = m0 + BBM <= p.M;
+  const bool full_rows = m0 + RB_M <= p.M;
   const bf16_t* __restrict__ X = reinterpret_cast<const bf16_t*>(p.x);
   const bf16_t* __restrict__ Wa = reinterpret_cast<const bf16_t*>(p.w1);      // [F][256]: rows = hidden units
   const bf16_t* __restrict__ Wb = reinterpret_cast<const bf16_t*>(p.w2);      // [256][F]: rows = outputs
@@ -58,19 +59,20 @@ __global__ __launch_bounds__(BNT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) {
 
   // ---- the 32 input rows: LDS image, A fragments (lane = row fr of row tile i, k-group fq: 8 consecutive k) read per k-step
   // (held in registers they cost 64 VGPRs - the room the one-chunk-ahead prefetch of BOTH weight sets needs) ----
-  if (!BWD && p.ln_x) {        // LayerNorm in front: normalise the fp32 rows on their way into the bf16 LDS image (ffn_ln.h)
-    ffn_ln_stage(p, m0, t, [&](int row, int col, float4 y) __attribute__((always_inline)) {
-      uint2 hh;
-      hh.x = eamd_f2bf(y.x) | ((unsigned)eamd_f2bf(y.y) << 16);
-      hh.y = eamd_f2bf(y.z) | ((unsigned)eamd_f2bf(y.w) << 16);
-      *reinterpret_cast<uint2*>(&xs[row * XLDB + col]) = hh;
-    });
+  if (!BWD && p.ln_x) {        // LayerNorm in front: normalise the fp32 rows on their way into the bf16 LDS image; p.x receives them
+    rb_stage_ln(p, m0, t,
+                [&](int row, int col, float4 y) __attribute__((always_inline)) {
+                  *reinterpret_cast<uint2*>(&xs[row * XLDB + col]) = rb_pack_bf16x4(y);
+                },
+                [&](long gr, int col, float4 y) __attribute__((always_inline)) {
+                  *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(const_cast<float*>(p.x)) + gr * RB_D + col) = rb_pack_bf16x4(y);
+                });
   } else {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const int idx = t + BNT * k, row = idx >> 5, c8 = idx & 31;          // 32 rows x 32 pieces of 8 elements
+      const int idx = t + RB_NT * k, row = idx >> 5, c8 = idx & 31;          // 32 rows x 32 pieces of 8 elements
       *reinterpret_cast<uint4*>(&xs[row * XLDB + c8 * 8]) =
-          *reinterpret_cast<const uint4*>(X + (long)min(m0 + row, p.M - 1) * BD + c8 * 8);
+          *reinterpret_cast<const uint4*>(X + (long)min(m0 + row, p.M - 1) * RB_D + c8 * 8);
     }
   }
   // ---- weight fragments, from the PACKED images eamd_ffn_pack_bf16 makes (fragment order: one wave-instruction reads 1 KB of
@@ -199,33 +201,17 @@ __global__ __launch_bounds__(BNT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) ys[(i * 16 + fq * 4 + r) * YLD + w * 32 + j * 16 + fr] = yacc[i][j][r];
   __syncthreads();
-  const unsigned thr_out = eamd_drop_thr16(p.p_out);
-  const float inv_out = eamd_drop_inv(thr_out);
-  const unsigned seed_out = (!BWD && p.p_out > 0.f) ? eamd_drop_seed((const unsigned long long*)p.drop_step, p.salt_out) : 0u;
+  const RbDrop dro = rb_drop_setup(BWD ? 0.f : p.p_out, p.salt_out, p.drop_step);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int idx = t + BNT * i, lr = idx >> 6, c4 = idx & 63;
+    const int idx = t + RB_NT * i, lr = idx >> 6, c4 = idx & 63;
     const int row = m0 + lr;
     if (row >= p.M) continue;
-    const float4 a4 = *reinterpret_cast<const float4*>(&ys[lr * YLD + c4 * 4]);
-    float v[4] = {a4.x, a4.y, a4.z, a4.w};
-    const long gi = (long)row * BD + c4 * 4;
-    if constexpr (!BWD) {
-      if (p.b2) {
-        const float4 b4 = *reinterpret_cast<const float4*>(p.b2 + c4 * 4);
-        v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
-      }
-      if (p.p_out > 0.f) {
-        bool keep[4];
-        eamd_drop_keep4(seed_out, (unsigned long long)gi, thr_out, keep);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = keep[e] ? v[e] * inv_out : 0.f;
-      }
-      float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.R) r4 = *reinterpret_cast<const float4*>(p.R + gi);
-      v[0] = v[0] * p.alpha + r4.x; v[1] = v[1] * p.alpha + r4.y; v[2] = v[2] * p.alpha + r4.z; v[3] = v[3] * p.alpha + r4.w;
-    }
-    *reinterpret_cast<float4*>(p.out + gi) = make_float4(v[0], v[1], v[2], v[3]);
+    float4 v = *reinterpret_cast<const float4*>(&ys[lr * YLD + c4 * 4]);
+    const long gi = (long)row * RB_D + c4 * 4;
+    if constexpr (!BWD)
+      v = rb_out4(v, p.b2, c4 * 4, dro, (unsigned long long)gi, p.alpha, p.R, gi);
+    *reinterpret_cast<float4*>(p.out + gi) = v;
   }
 }
 
@@ -247,7 +233,7 @@ __global__ __launch_bounds__(256) void ffn_pack_bf16_kernel(const bf16_t* __rest
   if (which == 0 || which == 2) {
     const int n = c * BHC + w * 16 + fr, k0 = slot * 32 + fq * 8;     // slot = ks
     if (which == 0) {
-      const uint4 u = *reinterpret_cast<const uint4*>(w1 + (long)n * BD + k0);
+      const uint4 u = *reinterpret_cast<const uint4*>(w1 + (long)n * RB_D + k0);
       *reinterpret_cast<uint4*>(p0 + piece * 8) = u;
       return;
     }
@@ -265,7 +251,7 @@ __global__ __launch_bounds__(256) void ffn_pack_bf16_kernel(const bf16_t* __rest
       return;
     }
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = w1[(long)(k0 + e) * BD + n];
+    for (int e = 0; e < 8; ++e) v[e] = w1[(long)(k0 + e) * RB_D + n];
     uint4 u;
     u.x = v[0] | ((unsigned)v[1] << 16); u.y = v[2] | ((unsigned)v[3] << 16); u.z = v[4] | ((unsigned)v[5] << 16); u.w = v[6] | ((unsigned)v[7] << 16);
     *reinterpret_cast<uint4*>(p3 + piece * 8) = u;
@@ -274,8 +260,8 @@ __global__ __launch_bounds__(256) void ffn_pack_bf16_kernel(const bf16_t* __rest
 
 template <bool BWD, int ACT>
 int launch_b(const eamd_ffn_t& p, hipStream_t stream) {
-  const int nblk = (p.M + BBM - 1) / BBM;
-  hipLaunchKernelGGL((ffn_bf16_kernel<BWD, ACT>), dim3(nblk), dim3(BNT), B_SMEM, stream, p);
+  const int nblk = (p.M + RB_M - 1) / RB_M;
+  hipLaunchKernelGGL((ffn_bf16_kernel<BWD, ACT>), dim3(nblk), dim3(RB_NT), B_SMEM, stream, p);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
@@ -283,8 +269,8 @@ int launch_b(const eamd_ffn_t& p, hipStream_t stream) {
 }  // namespace
 
 bool eamd_ffn_bf16_ok(const eamd_ffn_t* p) {
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return p->D == BD && p->F % 256 == 0 && p->F >= 256 && (long)p->M * p->F < (1L << 31) && al(p->x) && al(p->w1) && al(p->w2) &&
+  auto al = rb_al16;
+  return p->D == RB_D && p->F % 256 == 0 && p->F >= 256 && (long)p->M * p->F < (1L << 31) && al(p->x) && al(p->w1) && al(p->w2) &&
          al(p->out) && (!p->R || al(p->R)) && (!p->b2 || al(p->b2)) && (!p->f || al(p->f)) && (!p->h || al(p->h));
 }
 int eamd_ffn_bf16_launch(const eamd_ffn_t* p, int bwd, void* stream) {
@@ -296,9 +282,9 @@ int eamd_ffn_bf16_launch(const eamd_ffn_t* p, int bwd, void* stream) {
 extern "C" int eamd_ffn_pack_bf16(const void* w1, const void* w2, void* fwd_first, void* fwd_second, void* bwd_first,
                                   void* bwd_second, int D, int F, void* stream) {
   if (!w1 || !w2 || !fwd_first || !fwd_second || !bwd_first || !bwd_second || F <= 0) return EAMD_EINVAL;
-  if (D != BD || F % 256 != 0) return EAMD_EUNSUPPORTED;
+  if (D != RB_D || F % 256 != 0) return EAMD_EUNSUPPORTED;
   for (const void* q : {w1, w2, (const void*)fwd_first, (const void*)fwd_second, (const void*)bwd_first, (const void*)bwd_second})
-    if (reinterpret_cast<uintptr_t>(q) & 15) return EAMD_EUNSUPPORTED;
+    if (!rb_al16(q)) return EAMD_EUNSUPPORTED;
   const long npiece = (long)(F / BHC) * 8 * 8 * 64;
   hipLaunchKernelGGL(ffn_pack_bf16_kernel, dim3((unsigned)((npiece + 255) / 256), 4), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)w1, (const bf16_t*)w2, (bf16_t*)fwd_first, (bf16_t*)fwd_second, (bf16_t*)bwd_first,

@@ -25,26 +25,24 @@
 //   + h / f copies stored from LDS by the down waves                                    156 / 145 us
 // What s_memtime stamps of a diagnostic build showed is left (DESIGN_HISTORY.md §B): the up waves carry all of the
 // epilogue arithmetic, so the down waves wait for them at the chunk barrier.
+// Geometry, LayerNorm staging, the weight ring, the up waves' 32 x 32 tile and the output piece are rowblock.h's, shared with
+// ffn_bf16.hip and rowproj_f32.hip.
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "../../include/espnet_amd.h"
-#include "ffn_ln.h"
-#include "ln_bwd_rows.h"
+#include "rowblock.h"
 
 bool eamd_ffn_bf16_ok(const eamd_ffn_t* p);                      // ffn_bf16.hip
 int eamd_ffn_bf16_launch(const eamd_ffn_t* p, int bwd, void* stream);
 
 namespace {
 
-constexpr int FBM = 32;          // rows per workgroup
-constexpr int FD = 256;          // model width (template constant of this kernel)
 constexpr int FHC = 128;         // hidden units per chunk
-constexpr int FNT = 512;
-constexpr int XS_LD = 264;       // [32][256 + 8]: ds_read_b128 conflict-free (row stride = 2 mod 16 chunks)
-constexpr int HS_LD = 136;       // [32][128 + 8]
-constexpr int XS_SZ = FBM * XS_LD;                 // 8448 floats
-constexpr int HS_SZ = FBM * HS_LD;                 // 4352
+constexpr int XS_LD = rb_ld(RB_D);      // input rows [32][256 + 8] (rowblock.h)
+constexpr int HS_LD = rb_ld(FHC);       // hidden-unit chunk [32][128 + 8]
+constexpr int XS_SZ = RB_M * XS_LD;                // 8448 floats
+constexpr int HS_SZ = RB_M * HS_LD;                // 4352
 
 // ------------------------------------------------------------------------------------------------------------------
 // Weights straight from global memory into MFMA operand registers.
@@ -61,7 +59,7 @@ constexpr int HS_SZ = FBM * HS_LD;                 // 4352
 constexpr int D_SMEM_FLOATS = XS_SZ + 4 * HS_SZ;      // input rows + 2 hidden-unit chunks + (forward) 2 factor chunks
 
 template <bool BWD, int ACT>
-__global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t p) {
+__global__ __launch_bounds__(RB_NT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* const xs = sm;
   float* const hs = xs + XS_SZ;
@@ -71,34 +69,39 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
   const bool up = wave < 4;
   const int wq = wave & 3;
   const int fr = lane & 15, fq = lane >> 4;
-  const int m0 = blockIdx.x * FBM;
+  const int m0 = blockIdx.x * RB_M;
   const int F = p.F;
   // hidden split (eamd_ffn_t.hsplit = gridDim.y > 1, few rows): this workgroup takes hidden units hid0 .. hid0 + nch * 128 - 1 of
   // its 32 rows and ADDS its share of the second product to `out` (zeroed by the caller; slice 0 also brings bias / residual)
   const int nch = F / FHC / (int)gridDim.y;
   const int hid0 = (int)blockIdx.y * nch * FHC;
   const int nsteps = 8 * nch;
-  const bool full_rows = m0 + FBM <= p.M;
+  const bool full_rows = m0 + RB_M <= p.M;
   using T_ = std::true_type;
   using F_ = std::false_type;
 
-  if (!BWD && p.ln_x) {        // LayerNorm in front: normalise the rows on their way into LDS (ffn_ln.h)
-    ffn_ln_stage(p, m0, t, [&](int row, int col, float4 y) __attribute__((always_inline)) {
-      *reinterpret_cast<f32x4*>(&xs[row * XS_LD + col]) = (f32x4){y.x, y.y, y.z, y.w};
-    });
+  if (!BWD && p.ln_x) {        // LayerNorm in front: normalise the rows on their way into LDS; p.x receives them for backward
+    rb_stage_ln(p, m0, t,
+                [&](int row, int col, float4 y) __attribute__((always_inline)) {
+                  *reinterpret_cast<f32x4*>(&xs[row * XS_LD + col]) = (f32x4){y.x, y.y, y.z, y.w};
+                },
+                [&](long gr, int col, float4 y) __attribute__((always_inline)) {
+                  *reinterpret_cast<float4*>(const_cast<float*>(p.x) + gr * RB_D + col) = y;
+                });
   } else {
+    // local form of rowblock.h's rb_stage_rows: with K a constant the shared loop compiles to other code here
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int idx = t + FNT * i, row = idx >> 6, c4 = idx & 63;
+      const int idx = t + RB_NT * i, row = idx >> 6, c4 = idx & 63;
       *reinterpret_cast<f32x4*>(&xs[row * XS_LD + c4 * 4]) =
-          *reinterpret_cast<const f32x4*>(p.x + (long)min(m0 + row, p.M - 1) * FD + c4 * 4);
+          *reinterpret_cast<const f32x4*>(p.x + (long)min(m0 + row, p.M - 1) * RB_D + c4 * 4);
     }
   }
   __syncthreads();
 
   if (up) {
     // =============================== up waves ===============================
-    const float* __restrict__ W = p.w1 + (long)hid0 * FD;      // packed image of the first product (forward: W1; backward: W2 read along its rows), chunk-major
+    const float* __restrict__ W = p.w1 + (long)hid0 * RB_D;      // packed image of the first product (forward: W1; backward: W2 read along its rows), chunk-major
     // column of accumulator tile j inside the chunk: forward j*16 + fr; backward (float2 fragments along n) 2*fr + j
     // both directions interleave the two column tiles (tile j holds columns 2 fr + j): a lane's (j = 0, 1) elements of one
     // row are neighbours - one dropout hash (an element PAIR), one 8-byte LDS store
@@ -120,31 +123,14 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
     // operand fragments from the PACKED image of this product (eamd_ffn_pack_f32: fragment order, a wave-instruction reads
     // 1 KB of consecutive bytes; from the nn.Linear layout it touched 16 rows x 64 bytes): image[step g][wave][v][lane]
     auto load_b = [&](auto set_c, int g) __attribute__((always_inline)) {
-      constexpr int SET = decltype(set_c)::value;
-      const char* base = reinterpret_cast<const char*>(W) + ((long)min(g, nsteps - 1) * 4 + wq) * 4096 + lane * 16;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) bs[SET][v] = *reinterpret_cast<const f32x4*>(base + v * 1024);
+      rb_load_b<decltype(set_c)::value>(bs, reinterpret_cast<const char*>(W) + ((long)min(g, nsteps - 1) * 4 + wq) * 4096 + lane * 16);
     };
     float fA[2][2][4];
     auto read_a = [&](auto s_c, auto half_c) __attribute__((always_inline)) {
-      constexpr int s = decltype(s_c)::value, hh = decltype(half_c)::value;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float4 v = *reinterpret_cast<const float4*>(&xs[(i * 16 + fr) * XS_LD + s * 32 + hh * 16 + fq * 4]);
-        fA[hh][i][0] = v.x; fA[hh][i][1] = v.y; fA[hh][i][2] = v.z; fA[hh][i][3] = v.w;
-      }
+      rb_read_a<decltype(half_c)::value>(fA, xs, XS_LD, fr, decltype(s_c)::value * 32 + fq * 4);
     };
     auto mfma_half = [&](auto set_c, auto half_c) __attribute__((always_inline)) {
-      constexpr int SET = decltype(set_c)::value, q = decltype(half_c)::value;
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const float b = BWD ? bs[SET][q * 2 + (e >> 1)][(e & 1) * 2 + j] : bs[SET][q * 2 + j][e];
-            zacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fA[q][i][e], b, zacc[i][j], 0, 0, 0);
-          }
+      rb_mfma_half<decltype(set_c)::value, decltype(half_c)::value, BWD>(zacc, fA, bs);
     };
     // epilogue of rows i*16 + fq*4 + rr*2 + (0, 1) x both column tiles of chunk c: quarter (i, rr)
     auto epi_quarter = [&](auto i_c, auto rr_c, int c) __attribute__((always_inline)) {
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
     period(F_{}, F_{}, nch + 1);
   } else {
     // =============================== down waves ===============================
-    const float* __restrict__ W = p.w2 + (long)hid0 * FD;      // packed image of the second product, chunk-major
+    const float* __restrict__ W = p.w2 + (long)hid0 * RB_D;      // packed image of the second product, chunk-major
     f32x4 bs[4][4];            // forward: [set][j] = 4 k-elements of column tile j;  backward: [set][e] = column tiles 0..3 at k = fq*4 + e
     f32x4 yacc[2][4];
 #pragma unroll
@@ -240,10 +226,7 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
 #pragma unroll
       for (int j = 0; j < 4; ++j) yacc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto load_b = [&](auto set_c, int gd) __attribute__((always_inline)) {
-      constexpr int SET = decltype(set_c)::value;
-      const char* base = reinterpret_cast<const char*>(W) + ((long)min(max(gd, 0), nsteps - 1) * 4 + wq) * 4096 + lane * 16;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) bs[SET][v] = *reinterpret_cast<const f32x4*>(base + v * 1024);
+      rb_load_b<decltype(set_c)::value>(bs, reinterpret_cast<const char*>(W) + ((long)min(max(gd, 0), nsteps - 1) * 4 + wq) * 4096 + lane * 16);
     };
     float fA[2][2][4];         // [step parity][row tile][4 k-elements]
     auto read_a = [&](auto par_c, int sd, int hbuf) __attribute__((always_inline)) {
@@ -330,44 +313,25 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
   __syncthreads();
   if constexpr (BWD) {
     if (p.lnb_x) {       // LayerNorm backward over the finished dx rows (ln_bwd_rows.h); scratch = the hidden-unit chunk buffers
-      const EamdLnbArgs la{p.lnb_x, p.lnb_gamma, p.lnb_mean, p.lnb_rstd, p.lnb_dres, p.lnb_ws, p.lnb_drop_out, p.lnb_drop_p,
-                           (unsigned long long)p.lnb_drop_salt, p.drop_step, p.out, (long)FD, p.M};
-      eamd_ln_bwd_rows32<XS_LD>(la, xs, hs, hs + FBM * FD, m0, t, (int)blockIdx.x);
+      eamd_ln_bwd_rows32<XS_LD>(rb_lnb_args(p, p.out, (long)RB_D), xs, hs, hs + RB_M * RB_D, m0, t, (int)blockIdx.x);
       return;
     }
   }
-  const unsigned thr_out = eamd_drop_thr16(p.p_out);
-  const float inv_out = eamd_drop_inv(thr_out);
-  const unsigned seed_out = (!BWD && p.p_out > 0.f) ? eamd_drop_seed((const unsigned long long*)p.drop_step, p.salt_out) : 0u;
+  const RbDrop dro = rb_drop_setup(BWD ? 0.f : p.p_out, p.salt_out, p.drop_step);
+  const bool first = blockIdx.y == 0;           // hidden split: bias and residual come with slice 0
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int idx = t + FNT * i, lr = idx >> 6, c4 = idx & 63;
+    const int idx = t + RB_NT * i, lr = idx >> 6, c4 = idx & 63;
     const int row = m0 + lr;
     if (row >= p.M) continue;
-    const float4 a4 = *reinterpret_cast<const float4*>(&xs[lr * XS_LD + c4 * 4]);
-    float v[4] = {a4.x, a4.y, a4.z, a4.w};
-    const long gi = (long)row * FD + c4 * 4;
-    const bool first = blockIdx.y == 0;         // hidden split: bias and residual come with slice 0
-    if constexpr (!BWD) {
-      if (p.b2 && first) {
-        const float4 b4 = *reinterpret_cast<const float4*>(p.b2 + c4 * 4);
-        v[0] += b4.x; v[1] += b4.y; v[2] += b4.z; v[3] += b4.w;
-      }
-      if (p.p_out > 0.f) {
-        bool keep[4];
-        eamd_drop_keep4(seed_out, (unsigned long long)gi, thr_out, keep);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = keep[e] ? v[e] * inv_out : 0.f;
-      }
-      float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.R && first) r4 = *reinterpret_cast<const float4*>(p.R + gi);
-      v[0] = v[0] * p.alpha + r4.x; v[1] = v[1] * p.alpha + r4.y; v[2] = v[2] * p.alpha + r4.z; v[3] = v[3] * p.alpha + r4.w;
-    }
+    float4 v = *reinterpret_cast<const float4*>(&xs[lr * XS_LD + c4 * 4]);
+    const long gi = (long)row * RB_D + c4 * 4;
+    if constexpr (!BWD)
+      v = rb_out4(v, first ? p.b2 : nullptr, c4 * 4, dro, (unsigned long long)gi, p.alpha, first ? p.R : nullptr, gi);
     if (gridDim.y > 1) {       // two addends onto zeros: the sum does not depend on their order
-#pragma unroll
-      for (int e = 0; e < 4; ++e) atomicAdd(p.out + gi + e, v[e]);
+      atomicAdd(p.out + gi, v.x); atomicAdd(p.out + gi + 1, v.y); atomicAdd(p.out + gi + 2, v.z); atomicAdd(p.out + gi + 3, v.w);
     } else {
-      *reinterpret_cast<float4*>(p.out + gi) = make_float4(v[0], v[1], v[2], v[3]);
+      *reinterpret_cast<float4*>(p.out + gi) = v;
     }
   }
 }
@@ -377,68 +341,58 @@ __global__ __launch_bounds__(FNT, 2) void ffn_f32_direct_kernel(const eamd_ffn_t
 //   which 1 forward second : v = j        <- W2[wq*64 + j*16 + fr][c*128 + s*16 + fq*4 + (0..3)]
 //   which 2 backward first : v = q*2 + e/2, component (e%2)*2 + j  <- W2[s*32 + q*16 + fq*4 + e][c*128 + wq*32 + 2 fr + j]
 //   which 3 backward second: v = e        <- W1[c*128 + s*16 + fq*4 + e][wq*64 + 4 fr + (0..3)]
-__global__ __launch_bounds__(256) void ffn_pack_f32_kernel(const float* __restrict__ w1, const float* __restrict__ w2,
-                                                           float* __restrict__ p0, float* __restrict__ p1,
-                                                           float* __restrict__ p2, float* __restrict__ p3, int F) {
-  const int which = blockIdx.y;
-  const long piece = (long)blockIdx.x * 256 + threadIdx.x;           // ((g*4 + wq)*4 + v)*64 + lane
-  const long npiece = (long)(F / FHC) * 8 * 4 * 4 * 64;
-  if (piece >= npiece) return;
+// piece = ((g*4 + wq)*4 + v)*64 + lane of image `which`: the source element(s) -> the image.  A branch per image, each with its own
+// 16-byte load(s) and store (returned as a value, the compiler merges the four tails and splits the loads).
+struct FfnPackJob { const float* w1; const float* w2; float* p0; float* p1; float* p2; float* p3; int F; int pad; };
+__device__ __forceinline__ void ffn_pack_piece(const FfnPackJob& jb, const int which, const long piece) {
+  const int F = jb.F;
   const int lane = piece & 63, v = (piece >> 6) & 3, wq = (piece >> 8) & 3;
   const int g = (int)(piece >> 10), c = g >> 3, s = g & 7;
   const int fr = lane & 15, fq = lane >> 4;
-  float4 o;
   if (which == 0) {
     const int q = v >> 1, j = v & 1;
-    o = *reinterpret_cast<const float4*>(w1 + (long)(c * FHC + wq * 32 + 2 * fr + j) * FD + s * 32 + q * 16 + fq * 4);
-    *reinterpret_cast<float4*>(p0 + piece * 4) = o;
+    *reinterpret_cast<float4*>(jb.p0 + piece * 4) =
+        *reinterpret_cast<const float4*>(jb.w1 + (long)(c * FHC + wq * 32 + 2 * fr + j) * RB_D + s * 32 + q * 16 + fq * 4);
   } else if (which == 1) {
-    o = *reinterpret_cast<const float4*>(w2 + (long)(wq * 64 + v * 16 + fr) * F + c * FHC + s * 16 + fq * 4);
-    *reinterpret_cast<float4*>(p1 + piece * 4) = o;
+    *reinterpret_cast<float4*>(jb.p1 + piece * 4) =
+        *reinterpret_cast<const float4*>(jb.w2 + (long)(wq * 64 + v * 16 + fr) * F + c * FHC + s * 16 + fq * 4);
   } else if (which == 2) {
     const int q = v >> 1, e0 = (v & 1) * 2;
-    const float* r0 = w2 + (long)(s * 32 + q * 16 + fq * 4 + e0) * F + c * FHC + wq * 32 + 2 * fr;
+    const float* r0 = jb.w2 + (long)(s * 32 + q * 16 + fq * 4 + e0) * F + c * FHC + wq * 32 + 2 * fr;
     const float2 a = *reinterpret_cast<const float2*>(r0), b = *reinterpret_cast<const float2*>(r0 + F);
-    *reinterpret_cast<float4*>(p2 + piece * 4) = make_float4(a.x, a.y, b.x, b.y);
+    *reinterpret_cast<float4*>(jb.p2 + piece * 4) = make_float4(a.x, a.y, b.x, b.y);
   } else {
-    o = *reinterpret_cast<const float4*>(w1 + (long)(c * FHC + s * 16 + fq * 4 + v) * FD + wq * 64 + 4 * fr);
-    *reinterpret_cast<float4*>(p3 + piece * 4) = o;
+    *reinterpret_cast<float4*>(jb.p3 + piece * 4) =
+        *reinterpret_cast<const float4*>(jb.w1 + (long)(c * FHC + s * 16 + fq * 4 + v) * RB_D + wq * 64 + 4 * fr);
   }
+}
+__host__ __device__ constexpr long ffn_pack_pieces(int F) { return (long)(F / FHC) * 8 * 4 * 4 * 64; }      // float4 pieces per image
+
+__global__ __launch_bounds__(256) void ffn_pack_f32_kernel(const float* __restrict__ w1, const float* __restrict__ w2,
+                                                           float* __restrict__ p0, float* __restrict__ p1,
+                                                           float* __restrict__ p2, float* __restrict__ p3, int F) {
+  const long piece = (long)blockIdx.x * 256 + threadIdx.x;
+  if (piece < ffn_pack_pieces(F)) ffn_pack_piece(FfnPackJob{w1, w2, p0, p1, p2, p3, F, 0}, blockIdx.y, piece);
 }
 
 // the same packing for MANY layers in one launch (a table of jobs in the kernel arguments; blockIdx.z = job): a 12-layer macaron
 // Conformer packs 24 feed-forward blocks per step - 24 launches of 5.7 us with their gaps, or one launch of all of them
 constexpr int FFN_PACK_JOBS = 32;
-struct FfnPackJob { const float* w1; const float* w2; float* p0; float* p1; float* p2; float* p3; int F; int pad; };
 struct FfnPackTable { FfnPackJob j[FFN_PACK_JOBS]; };
 __global__ __launch_bounds__(256) void ffn_pack_f32_multi_kernel(const FfnPackTable tab) {
   const FfnPackJob jb = tab.j[blockIdx.z];
-  const int which = blockIdx.y, F = jb.F;
-  const long npiece = (long)(F / FHC) * 8 * 4 * 4 * 64;
-  for (long piece = (long)blockIdx.x * 256 + threadIdx.x; piece < npiece; piece += (long)gridDim.x * 256) {
-    const int lane = piece & 63, v = (piece >> 6) & 3, wq = (piece >> 8) & 3;
-    const int g = (int)(piece >> 10), c = g >> 3, s = g & 7;
-    const int fr = lane & 15, fq = lane >> 4;
-    if (which == 0) {
-      const int q = v >> 1, j = v & 1;
-      *reinterpret_cast<float4*>(jb.p0 + piece * 4) =
-          *reinterpret_cast<const float4*>(jb.w1 + (long)(c * FHC + wq * 32 + 2 * fr + j) * FD + s * 32 + q * 16 + fq * 4);
-    } else if (which == 1) {
-      *reinterpret_cast<float4*>(jb.p1 + piece * 4) =
-          *reinterpret_cast<const float4*>(jb.w2 + (long)(wq * 64 + v * 16 + fr) * F + c * FHC + s * 16 + fq * 4);
-    } else if (which == 2) {
-      const int q = v >> 1, e0 = (v & 1) * 2;
-      const float* r0 = jb.w2 + (long)(s * 32 + q * 16 + fq * 4 + e0) * F + c * FHC + wq * 32 + 2 * fr;
-      const float2 a = *reinterpret_cast<const float2*>(r0), b = *reinterpret_cast<const float2*>(r0 + F);
-      *reinterpret_cast<float4*>(jb.p2 + piece * 4) = make_float4(a.x, a.y, b.x, b.y);
-    } else {
-      *reinterpret_cast<float4*>(jb.p3 + piece * 4) =
-          *reinterpret_cast<const float4*>(jb.w1 + (long)(c * FHC + s * 16 + fq * 4 + v) * FD + wq * 64 + 4 * fr);
-    }
-  }
+  for (long piece = (long)blockIdx.x * 256 + threadIdx.x; piece < ffn_pack_pieces(jb.F); piece += (long)gridDim.x * 256)
+    ffn_pack_piece(jb, blockIdx.y, piece);
 }
 
-bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+// what both pack entry points ask of one FFN's six pointers and its shape
+int check_ffn_pack(const float* w1, const float* w2, float* p0, float* p1, float* p2, float* p3, int D, int F) {
+  if (!w1 || !w2 || !p0 || !p1 || !p2 || !p3 || F <= 0) return EAMD_EINVAL;
+  if (D != RB_D || F % FHC != 0 || F < 2 * FHC) return EAMD_EUNSUPPORTED;
+  for (const void* q : {(const void*)w1, (const void*)w2, (const void*)p0, (const void*)p1, (const void*)p2, (const void*)p3})
+    if (!rb_al16(q)) return EAMD_EUNSUPPORTED;
+  return EAMD_OK;
+}
 
 template <bool BWD, int ACT>
 int launch_ffn(const eamd_ffn_t& p, hipStream_t stream) {
@@ -446,8 +400,8 @@ int launch_ffn(const eamd_ffn_t& p, hipStream_t stream) {
   static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_f32_direct_kernel<BWD, ACT>),
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (attr_err != hipSuccess) return (int)attr_err;
-  const int nblk = (p.M + FBM - 1) / FBM;
-  hipLaunchKernelGGL((ffn_f32_direct_kernel<BWD, ACT>), dim3(nblk, p.hsplit > 1 ? p.hsplit : 1), dim3(FNT), smem, stream, p);
+  const int nblk = (p.M + RB_M - 1) / RB_M;
+  hipLaunchKernelGGL((ffn_f32_direct_kernel<BWD, ACT>), dim3(nblk, p.hsplit > 1 ? p.hsplit : 1), dim3(RB_NT), smem, stream, p);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
@@ -457,8 +411,8 @@ int check_ffn(const eamd_ffn_t* p, bool bwd) {
   if (p->M <= 0 || p->D <= 0 || p->F <= 0) return EAMD_EINVAL;
   if (p->dtype != 0 && p->dtype != 1) return EAMD_EINVAL;
   if (p->ln_x) {      // LayerNorm in front (forward only): x is written, not read
-    if (bwd || !p->ln_w || !p->ln_b || !p->ln_mean || !p->ln_rstd) return EAMD_EINVAL;
-    if (!al16(p->ln_x) || !al16(p->ln_w) || !al16(p->ln_b)) return EAMD_EUNSUPPORTED;
+    if (bwd) return EAMD_EINVAL;
+    if (const int rc = rb_check_ln(*p)) return rc;
   }
   if (p->hsplit < 0) return EAMD_EINVAL;
   if (p->dtype == 1) {                                               // bf16 operands: ffn_bf16.hip
@@ -468,16 +422,14 @@ int check_ffn(const eamd_ffn_t* p, bool bwd) {
     if ((p->p_in > 0.f || p->p_out > 0.f) && !p->drop_step) return EAMD_EINVAL;
     return (p->act == EAMD_ACT_RELU || p->act == EAMD_ACT_SWISH) ? EAMD_OK : EAMD_EUNSUPPORTED;
   }
-  if (p->D != FD || p->F % FHC != 0 || p->F < 2 * FHC) return EAMD_EUNSUPPORTED;
+  if (p->D != RB_D || p->F % FHC != 0 || p->F < 2 * FHC) return EAMD_EUNSUPPORTED;
   if (p->hsplit > 1 && (p->hsplit != 2 || (p->F / FHC) % 2 != 0 || p->F < 4 * FHC)) return EAMD_EUNSUPPORTED;
   if ((long)p->M * p->F >= (1L << 31)) return EAMD_EUNSUPPORTED;     // 32-bit dropout pair index space
-  if (!al16(p->x) || !al16(p->w1) || !al16(p->w2) || !al16(p->out) || (p->R && !al16(p->R)) || (p->b2 && !al16(p->b2)))
+  if (!rb_al16(p->x) || !rb_al16(p->w1) || !rb_al16(p->w2) || !rb_al16(p->out) || (p->R && !rb_al16(p->R)) || (p->b2 && !rb_al16(p->b2)))
     return EAMD_EUNSUPPORTED;
   if (p->lnb_x) {
-    if (!bwd || p->hsplit > 1 || !p->lnb_gamma || !p->lnb_mean || !p->lnb_rstd || !p->lnb_ws) return EAMD_EINVAL;
-    if (p->lnb_drop_out && (!p->drop_step || p->lnb_drop_p < 0.f || p->lnb_drop_p >= 1.f)) return EAMD_EINVAL;
-    if (!al16(p->lnb_x) || !al16(p->lnb_gamma) || (p->lnb_dres && !al16(p->lnb_dres)) || (p->lnb_drop_out && !al16(p->lnb_drop_out)))
-      return EAMD_EUNSUPPORTED;
+    if (!bwd || p->hsplit > 1) return EAMD_EINVAL;
+    if (const int rc = rb_check_lnb(*p)) return rc;
   }
   if (bwd) {
     if (!p->f) return EAMD_EINVAL;
@@ -493,12 +445,8 @@ int check_ffn(const eamd_ffn_t* p, bool bwd) {
 
 extern "C" int eamd_ffn_pack_f32(const float* w1, const float* w2, float* fwd_first, float* fwd_second, float* bwd_first,
                                  float* bwd_second, int D, int F, void* stream) {
-  if (!w1 || !w2 || !fwd_first || !fwd_second || !bwd_first || !bwd_second || F <= 0) return EAMD_EINVAL;
-  if (D != FD || F % FHC != 0 || F < 2 * FHC) return EAMD_EUNSUPPORTED;
-  for (const void* q : {(const void*)w1, (const void*)w2, (const void*)fwd_first, (const void*)fwd_second, (const void*)bwd_first,
-                        (const void*)bwd_second})
-    if (!al16(q)) return EAMD_EUNSUPPORTED;
-  const long npiece = (long)(F / FHC) * 8 * 4 * 4 * 64;
+  if (const int rc = check_ffn_pack(w1, w2, fwd_first, fwd_second, bwd_first, bwd_second, D, F)) return rc;
+  const long npiece = ffn_pack_pieces(F);
   hipLaunchKernelGGL(ffn_pack_f32_kernel, dim3((unsigned)((npiece + 255) / 256), 4), dim3(256), 0, (hipStream_t)stream, w1, w2,
                      fwd_first, fwd_second, bwd_first, bwd_second, F);
   EAMD_LAUNCH_CHECK();
@@ -509,11 +457,7 @@ extern "C" int eamd_ffn_pack_f32_multi(const eamd_ffn_pack_t* jobs, int njobs, v
   if (!jobs || njobs <= 0) return EAMD_EINVAL;
   for (int i = 0; i < njobs; ++i) {
     const eamd_ffn_pack_t& q = jobs[i];
-    if (!q.w1 || !q.w2 || !q.fwd_first || !q.fwd_second || !q.bwd_first || !q.bwd_second || q.F <= 0) return EAMD_EINVAL;
-    if (q.D != FD || q.F % FHC != 0 || q.F < 2 * FHC) return EAMD_EUNSUPPORTED;
-    for (const void* a : {(const void*)q.w1, (const void*)q.w2, (const void*)q.fwd_first, (const void*)q.fwd_second,
-                          (const void*)q.bwd_first, (const void*)q.bwd_second})
-      if (!al16(a)) return EAMD_EUNSUPPORTED;
+    if (const int rc = check_ffn_pack(q.w1, q.w2, q.fwd_first, q.fwd_second, q.bwd_first, q.bwd_second, q.D, q.F)) return rc;
   }
   for (int i0 = 0; i0 < njobs; i0 += FFN_PACK_JOBS) {
     const int n = njobs - i0 < FFN_PACK_JOBS ? njobs - i0 : FFN_PACK_JOBS;
@@ -524,7 +468,7 @@ extern "C" int eamd_ffn_pack_f32_multi(const eamd_ffn_pack_t* jobs, int njobs, v
       tab.j[i] = FfnPackJob{q.w1, q.w2, q.fwd_first, q.fwd_second, q.bwd_first, q.bwd_second, q.F, 0};
       fmax = q.F > fmax ? q.F : fmax;
     }
-    const long npiece = (long)(fmax / FHC) * 8 * 4 * 4 * 64;
+    const long npiece = ffn_pack_pieces(fmax);
     const unsigned bx = (unsigned)((npiece + 255) / 256 < 128 ? (npiece + 255) / 256 : 128);
     hipLaunchKernelGGL(ffn_pack_f32_multi_kernel, dim3(bx, 4, n), dim3(256), 0, (hipStream_t)stream, tab);
     EAMD_LAUNCH_CHECK();

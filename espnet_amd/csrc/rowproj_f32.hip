@@ -10,7 +10,7 @@
 // every tile are exposed (53 - 86 TFLOP/s at config 2), and every LayerNorm is one more pass over the rows.  They are local
 // to a block of ROWS, like the feed-forward pair (ffn_f32.hip), so the same structure serves them: one workgroup takes 32 rows
 // through the whole product,
-//   * the rows are staged ONCE in LDS (optionally normalised on the way: LayerNorm in front, as ffn_ln.h),
+//   * the rows are staged ONCE in LDS (optionally normalised on the way: LayerNorm in front, rowblock.h's rb_stage_ln),
 //   * the weights come from a PACKED image in MFMA fragment order straight into operand registers (a wave-instruction
 //     reads 1 KB of consecutive bytes; ring of four fragment sets, three K-steps ahead),
 //   * wave w owns output columns 32 w .. 32 w + 31 of every 256-column chunk (wave tile 32 x 32, K-steps of 32),
@@ -19,72 +19,27 @@
 //     LayerNorm backward itself (dx, the residual gradient added, the dropped copy the previous block's products read, and
 //     the per-workgroup partial sums of d gamma / d beta for the batched second stage of rowops.hip).
 // No barrier inside the K loop (every wave reads the shared rows, nobody writes them).
+// Staging, the weight ring, the wave tile and the output piece are rowblock.h's, shared with the feed-forward kernels.
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "../../include/espnet_amd.h"
-#include "ln_bwd_rows.h"
+#include "rowblock.h"
 
 namespace {
 
-constexpr int RBM = 32;          // rows per workgroup
-constexpr int RNT = 512;         // 8 waves
 constexpr int RCH = 256;         // output columns per chunk: 8 waves x 32
 constexpr int ST_LD = 36;        // wave-private result tile [32][32 + 4]
-constexpr int ST_SZ = RBM * ST_LD;
-constexpr int TL_LD = 264;       // [32][256 + 8] whole-row tile of the LayerNorm-backward epilogue
-
-__device__ __forceinline__ int xs_ld(int K) { return K + 8; }      // ds_read_b128 conflict-free (row stride = 2 mod 16 chunks)
-
-// LayerNorm of the 32 input rows while they are staged (K = 256): thread t owns row t >> 4, columns 4 (l + 16 j) .. + 3
-// (ffn_ln.h's arithmetic: mean, centred sum of squares of the register-resident values, rsqrt(var + eps)); the normalised rows
-// also go to p.a (backward's weight gradient reads them), mean / rstd to ln_mean / ln_rstd.
-__device__ __forceinline__ void stage_ln(const eamd_rowproj_t& p, const int m0, const int t, float* xs, const int LD) {
-  constexpr int D = 256;
-  const int row = t >> 4, l = t & 15;
-  const bool live = m0 + row < p.M;
-  const long gr = (long)min(m0 + row, p.M - 1);
-  const float4* __restrict__ xr = reinterpret_cast<const float4*>(p.ln_x + gr * D);
-  float4 v[4];
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { v[j] = xr[l + 16 * j]; s += v[j].x + v[j].y + v[j].z + v[j].w; }
-#pragma unroll
-  for (int m = 1; m < 16; m <<= 1) s += __shfl_xor(s, m);
-  const float mean = s / D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = v[j].x - mean, b = v[j].y - mean, c = v[j].z - mean, d = v[j].w - mean;
-    q += a * a + b * b + c * c + d * d;
-  }
-#pragma unroll
-  for (int m = 1; m < 16; m <<= 1) q += __shfl_xor(q, m);
-  const float rstd = rsqrtf(q / D + p.ln_eps);
-  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(p.ln_w);
-  const float4* __restrict__ b4 = reinterpret_cast<const float4*>(p.ln_b);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float4 g = g4[l + 16 * j], b = b4[l + 16 * j];
-    float4 o;
-    o.x = (v[j].x - mean) * rstd * g.x + b.x;
-    o.y = (v[j].y - mean) * rstd * g.y + b.y;
-    o.z = (v[j].z - mean) * rstd * g.z + b.z;
-    o.w = (v[j].w - mean) * rstd * g.w + b.w;
-    const int col = (l + 16 * j) * 4;
-    *reinterpret_cast<float4*>(&xs[row * LD + col]) = o;
-    if (live) *reinterpret_cast<float4*>(const_cast<float*>(p.a) + gr * D + col) = o;
-  }
-  if (live && l == 0) { p.ln_mean[gr] = mean; p.ln_rstd[gr] = rstd; }
-}
+constexpr int ST_SZ = RB_M * ST_LD;
+constexpr int TL_LD = rb_ld(RB_D);      // whole-row tile of the LayerNorm-backward epilogue
 
 // Per-column affine + activation of the staged rows (K = 256): a' = act(a * scale[k] + shift[k]) - the BatchNorm apply + Swish
 // in front of pointwise_conv2 (convolution.py:73-76).  a' also goes to p.a_out (the weight gradient's operand).
 __device__ __forceinline__ void stage_affine(const eamd_rowproj_t& p, const int m0, const int t, float* xs, const int LD) {
-  constexpr int D = 256;
+  constexpr int D = RB_D;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int idx = t + RNT * i, row = idx >> 6, c4 = idx & 63;
+    const int idx = t + RB_NT * i, row = idx >> 6, c4 = idx & 63;
     const long gr = (long)min(m0 + row, p.M - 1);
     const float4 v = *reinterpret_cast<const float4*>(p.a + gr * p.lda + c4 * 4);
     const float4 sc = *reinterpret_cast<const float4*>(p.a_scale + c4 * 4), sh = *reinterpret_cast<const float4*>(p.a_shift + c4 * 4);
@@ -97,63 +52,47 @@ __device__ __forceinline__ void stage_affine(const eamd_rowproj_t& p, const int 
 }
 
 template <bool LNB>
-__global__ __launch_bounds__(RNT, 2) void rowproj_f32_kernel(const eamd_rowproj_t p) {
+__global__ __launch_bounds__(RB_NT, 2) void rowproj_f32_kernel(const eamd_rowproj_t p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int K = p.K, N = p.N;
-  const int LD = xs_ld(K);
+  const int LD = rb_ld(K);
   float* const xs = sm;
   const int t = threadIdx.x;
   const int lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int fr = lane & 15, fq = lane >> 4;
-  const int m0 = blockIdx.x * RBM;
+  const int m0 = blockIdx.x * RB_M;
   const int S = K >> 5;                 // K-steps of 32 per chunk
   const int nchunk = N / RCH;
   const int nsteps = S * nchunk;
   // wave-private result tile (LNB: the whole-row tile lives over the input rows instead)
-  float* const st = sm + RBM * LD + wave * ST_SZ;
+  float* const st = sm + RB_M * LD + wave * ST_SZ;
 
   // ---- the 32 input rows -> LDS ----
-  if (p.ln_x) {
-    stage_ln(p, m0, t, xs, LD);
+  if (p.ln_x) {                         // LayerNorm in front (K = 256); p.a receives the normalised rows for backward
+    rb_stage_ln(p, m0, t,
+                [&](int row, int col, float4 y) __attribute__((always_inline)) { *reinterpret_cast<float4*>(&xs[row * LD + col]) = y; },
+                [&](long gr, int col, float4 y) __attribute__((always_inline)) {
+                  *reinterpret_cast<float4*>(const_cast<float*>(p.a) + gr * RB_D + col) = y;
+                });
   } else if (p.a_scale) {
     stage_affine(p, m0, t, xs, LD);
   } else {
-    const int c4n = K >> 2;             // 16-byte pieces per row
-    for (int idx = t; idx < RBM * c4n; idx += RNT) {
-      const int row = idx / c4n, c4 = idx - row * c4n;
-      *reinterpret_cast<f32x4*>(&xs[row * LD + c4 * 4]) =
-          *reinterpret_cast<const f32x4*>(p.a + (long)min(m0 + row, p.M - 1) * p.lda + c4 * 4);
-    }
+    rb_stage_rows(xs, LD, p.a, p.lda, K, m0, p.M, t);
   }
 
   // ---- weights: packed image[step g][wave][v = q*2 + j][lane] (float4 over 4 k), ring of four sets ----
   const char* __restrict__ Wb = reinterpret_cast<const char*>(p.w) + (long)wave * 4096 + lane * 16;
   f32x4 bs[4][4];
   auto load_b = [&](auto set_c, int g) __attribute__((always_inline)) {
-    constexpr int SET = decltype(set_c)::value;
-    const char* base = Wb + (long)min(g, nsteps - 1) * (8 * 4096);
-#pragma unroll
-    for (int v = 0; v < 4; ++v) bs[SET][v] = *reinterpret_cast<const f32x4*>(base + v * 1024);
+    rb_load_b<decltype(set_c)::value>(bs, Wb + (long)min(g, nsteps - 1) * (8 * 4096));
   };
   float fA[2][2][4];
   auto read_a = [&](int kcol, auto half_c) __attribute__((always_inline)) {
-    constexpr int hh = decltype(half_c)::value;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const float4 v = *reinterpret_cast<const float4*>(&xs[(i * 16 + fr) * LD + kcol + hh * 16 + fq * 4]);
-      fA[hh][i][0] = v.x; fA[hh][i][1] = v.y; fA[hh][i][2] = v.z; fA[hh][i][3] = v.w;
-    }
+    rb_read_a<decltype(half_c)::value>(fA, xs, LD, fr, kcol + fq * 4);
   };
   f32x4 acc[2][2];
   auto mfma_half = [&](auto set_c, auto half_c) __attribute__((always_inline)) {
-    constexpr int SET = decltype(set_c)::value, q = decltype(half_c)::value;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fA[q][i][e], bs[SET][q * 2 + j][e], acc[i][j], 0, 0, 0);
+    rb_mfma_half<decltype(set_c)::value, decltype(half_c)::value, false>(acc, fA, bs);
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -175,9 +114,7 @@ __global__ __launch_bounds__(RNT, 2) void rowproj_f32_kernel(const eamd_rowproj_
   __syncthreads();                      // the staged rows are complete
   read_a(0, I0{});
 
-  const unsigned thr_out = eamd_drop_thr16(p.p_out);
-  const float inv_out = eamd_drop_inv(thr_out);
-  const unsigned seed_out = p.p_out > 0.f ? eamd_drop_seed((const unsigned long long*)p.drop_step, p.salt_out) : 0u;
+  const RbDrop dro = rb_drop_setup(p.p_out, p.salt_out, p.drop_step);
 
   int g = 0;
   for (int c = 0; c < nchunk; ++c) {
@@ -211,20 +148,9 @@ __global__ __launch_bounds__(RNT, 2) void rowproj_f32_kernel(const eamd_rowproj_
         const int lr = it * 8 + (lane >> 3);
         const int row = m0 + lr;
         const float4 a4 = *reinterpret_cast<const float4*>(&st[lr * ST_LD + (lane & 7) * 4]);
-        if (row < p.M) {
-          float v[4] = {a4.x + b4.x, a4.y + b4.y, a4.z + b4.z, a4.w + b4.w};
-          const long gi = (long)row * N + col0;
-          if (p.p_out > 0.f) {
-            bool keep[4];
-            eamd_drop_keep4(seed_out, (unsigned long long)gi, thr_out, keep);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = keep[e] ? v[e] * inv_out : 0.f;
-          }
-          float4 r4 = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (p.R) r4 = *reinterpret_cast<const float4*>(p.R + (long)row * p.ldr + col0);
+        if (row < p.M)
           *reinterpret_cast<float4*>(p.out + (long)row * p.ldo + col0) =
-              make_float4(v[0] * p.alpha + r4.x, v[1] * p.alpha + r4.y, v[2] * p.alpha + r4.z, v[3] * p.alpha + r4.w);
-        }
+              rb_out4(a4, &b4.x, 0, dro, (unsigned long long)((long)row * N + col0), p.alpha, p.R, (long)row * p.ldr + col0);
       }
       __builtin_amdgcn_wave_barrier();     // the tile is free again before the next chunk's accumulators land in it
     }
@@ -232,10 +158,10 @@ __global__ __launch_bounds__(RNT, 2) void rowproj_f32_kernel(const eamd_rowproj_
 
   if constexpr (LNB) {
     // ---- LayerNorm backward over the finished rows (N = 256: one chunk).  reference: transformer/layer_norm.py:12-38 ----
-    constexpr int D = 256;
+    constexpr int D = RB_D;
     float* const tl = sm;                             // whole-row tile over the input rows (nobody reads those any more)
-    float* const gs = sm + RBM * TL_LD;               // [32][256] d gamma contributions, then [32][256] d beta contributions
-    float* const bsum = gs + RBM * D;
+    float* const gs = sm + RB_M * TL_LD;               // [32][256] d gamma contributions, then [32][256] d beta contributions
+    float* const bsum = gs + RB_M * D;
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -243,9 +169,7 @@ __global__ __launch_bounds__(RNT, 2) void rowproj_f32_kernel(const eamd_rowproj_
       for (int r = 0; r < 4; ++r)
         *reinterpret_cast<float2*>(&tl[(i * 16 + fq * 4 + r) * TL_LD + wave * 32 + 2 * fr]) = make_float2(acc[i][0][r], acc[i][1][r]);
     __syncthreads();
-    const EamdLnbArgs la{p.lnb_x, p.lnb_gamma, p.lnb_mean, p.lnb_rstd, p.lnb_dres, p.lnb_ws, p.lnb_drop_out, p.lnb_drop_p,
-                         (unsigned long long)p.lnb_drop_salt, p.drop_step, p.out, (long)p.ldo, p.M};
-    eamd_ln_bwd_rows32<TL_LD>(la, tl, gs, bsum, m0, t, (int)blockIdx.x);
+    eamd_ln_bwd_rows32<TL_LD>(rb_lnb_args(p, p.out, (long)p.ldo), tl, gs, bsum, m0, t, (int)blockIdx.x);
   }
 }
 
@@ -275,12 +199,10 @@ __global__ __launch_bounds__(256) void rowproj_pack_kernel(const PackTable tab) 
   }
 }
 
-bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 size_t smem_bytes(int K, bool lnb) {
-  size_t rows = (size_t)RBM * (K + 8);
+  size_t rows = (size_t)RB_M * rb_ld(K);
   if (lnb) {
-    const size_t need = (size_t)RBM * TL_LD + 2 * (size_t)RBM * 256;
+    const size_t need = (size_t)RB_M * TL_LD + 2 * (size_t)RB_M * 256;
     return (rows > need ? rows : need) * sizeof(float);
   }
   return (rows + 8 * (size_t)ST_SZ) * sizeof(float);
@@ -292,22 +214,20 @@ int check_rowproj(const eamd_rowproj_t* p) {
   if (p->K % 256 != 0 || p->N % RCH != 0 || p->K > 768) return EAMD_EUNSUPPORTED;
   if (p->lda < p->K || p->ldo < p->N || (p->R && p->ldr < p->N)) return EAMD_EINVAL;
   if (p->lda % 4 != 0 || p->ldo % 4 != 0 || (p->R && p->ldr % 4 != 0)) return EAMD_EUNSUPPORTED;
-  if (!al16(p->a) || !al16(p->w) || !al16(p->out) || (p->R && !al16(p->R)) || (p->bias && !al16(p->bias))) return EAMD_EUNSUPPORTED;
+  if (!rb_al16(p->a) || !rb_al16(p->w) || !rb_al16(p->out) || (p->R && !rb_al16(p->R)) || (p->bias && !rb_al16(p->bias))) return EAMD_EUNSUPPORTED;
   if (p->p_out < 0.f || p->p_out >= 1.f) return EAMD_EINVAL;
   if (p->p_out > 0.f && (!p->drop_step || p->ldo != p->N)) return EAMD_EINVAL;       // the mask is that of the contiguous [M, N] tensor
   if (p->ln_x) {
-    if (p->K != 256 || p->a_scale || !p->ln_w || !p->ln_b || !p->ln_mean || !p->ln_rstd || p->lda != 256) return EAMD_EINVAL;
-    if (!al16(p->ln_x) || !al16(p->ln_w) || !al16(p->ln_b)) return EAMD_EUNSUPPORTED;
+    if (p->K != 256 || p->a_scale || p->lda != 256) return EAMD_EINVAL;
+    if (const int rc = rb_check_ln(*p)) return rc;
   }
   if (p->a_scale) {
     if (p->K != 256 || !p->a_shift) return EAMD_EINVAL;
-    if (!al16(p->a_scale) || !al16(p->a_shift) || (p->a_out && !al16(p->a_out))) return EAMD_EUNSUPPORTED;
+    if (!rb_al16(p->a_scale) || !rb_al16(p->a_shift) || (p->a_out && !rb_al16(p->a_out))) return EAMD_EUNSUPPORTED;
   }
   if (p->lnb_x) {
-    if (p->N != 256 || !p->lnb_gamma || !p->lnb_mean || !p->lnb_rstd || !p->lnb_ws || p->R || p->p_out > 0.f) return EAMD_EINVAL;
-    if (p->lnb_drop_out && (!p->drop_step || p->lnb_drop_p < 0.f || p->lnb_drop_p >= 1.f)) return EAMD_EINVAL;
-    if (!al16(p->lnb_x) || !al16(p->lnb_gamma) || (p->lnb_dres && !al16(p->lnb_dres)) || (p->lnb_drop_out && !al16(p->lnb_drop_out)))
-      return EAMD_EUNSUPPORTED;
+    if (p->N != 256 || p->R || p->p_out > 0.f) return EAMD_EINVAL;
+    if (const int rc = rb_check_lnb(*p)) return rc;
   }
   return EAMD_OK;
 }
@@ -322,14 +242,14 @@ int launch_rowproj(const eamd_rowproj_t& p, hipStream_t stream) {
     if (e != hipSuccess) return (int)e;
     attr_done = 1;
   }
-  hipLaunchKernelGGL((rowproj_f32_kernel<LNB>), dim3((p.M + RBM - 1) / RBM), dim3(RNT), smem, stream, p);
+  hipLaunchKernelGGL((rowproj_f32_kernel<LNB>), dim3((p.M + RB_M - 1) / RB_M), dim3(RB_NT), smem, stream, p);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
 
 }  // namespace
 
-extern "C" int64_t eamd_rowproj_lnb_workspace(int M) { return (int64_t)((M + RBM - 1) / RBM) * 2 * 256; }
+extern "C" int64_t eamd_rowproj_lnb_workspace(int M) { return (int64_t)((M + RB_M - 1) / RB_M) * 2 * 256; }
 
 extern "C" int eamd_rowproj(const eamd_rowproj_t* p, void* stream) {
   const int rc = check_rowproj(p);
@@ -346,8 +266,8 @@ extern "C" int eamd_rowproj_pack_f32(const eamd_rowproj_pack_t* jobs, int njobs,
     for (int i = 0; i < n; ++i) {
       const eamd_rowproj_pack_t& q = jobs[i0 + i];
       if (!q.w || !q.image || q.K <= 0 || q.N <= 0 || q.ldw <= 0) return EAMD_EINVAL;
-      if (q.K % 256 != 0 || q.N % RCH != 0 || !al16(q.image)) return EAMD_EUNSUPPORTED;
-      if (!q.trans && (!al16(q.w) || q.ldw % 4 != 0)) return EAMD_EUNSUPPORTED;
+      if (q.K % 256 != 0 || q.N % RCH != 0 || !rb_al16(q.image)) return EAMD_EUNSUPPORTED;
+      if (!q.trans && (!rb_al16(q.w) || q.ldw % 4 != 0)) return EAMD_EUNSUPPORTED;
       if (q.ldw < (q.trans ? q.N : q.K)) return EAMD_EINVAL;
       tab.j[i] = PackJob{q.w, q.image, q.K, q.N, q.ldw, q.trans, (long)q.K * q.N / 4};
       if (tab.j[i].npiece > most) most = tab.j[i].npiece;

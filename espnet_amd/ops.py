@@ -690,6 +690,28 @@ def _ffn_call(name, p, keep):
 FFN_LN_FUSED = True      # the LayerNorm in front of a fused FFN runs inside its kernel
 
 
+def _set_ln(p, ln, M):
+    """fill the ln_* fields of an FfnT / RowProjT (the LayerNorm in front of a row-block kernel) from
+    ln = (x_raw fp32 [M, 256], gamma, beta, eps, mean [M], rstd [M])"""
+    xr, g, b, eps, mean, rstd = ln
+    for t_ in (xr, g, b, mean, rstd):
+        if t_.dtype != torch.float32 or not t_.is_contiguous():
+            raise _lib.EamdError("LayerNorm operands are contiguous float32 tensors")
+    D = 256         # the width these kernels normalise (csrc/rowblock.h: RB_D)
+    if tuple(xr.shape) != (M, D) or g.numel() != D or b.numel() != D or mean.numel() < M or rstd.numel() < M:
+        raise _lib.EamdError("LayerNorm operand shapes")
+    p.ln_x, p.ln_w, p.ln_b, p.ln_mean, p.ln_rstd, p.ln_eps = ptr(xr), ptr(g), ptr(b), ptr(mean), ptr(rstd), float(eps)
+
+
+def _set_lnb(p, lnb, device):
+    """fill the lnb_* fields of an FfnT / RowProjT (the LayerNorm backward behind a row-block kernel) from
+    lnb = (x_block_input, gamma, mean, rstd, dres or None, ws, drop_out or None, (p, salt) or None)"""
+    xb, g, mean, rstd, dres, ws, d_out, d_ps = lnb
+    p.lnb_x, p.lnb_gamma, p.lnb_mean, p.lnb_rstd, p.lnb_dres, p.lnb_ws = ptr(xb), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(ws)
+    if d_out is not None:
+        p.lnb_drop_out, p.lnb_drop_p, p.lnb_drop_salt, p.drop_step = ptr(d_out), float(d_ps[0]), int(d_ps[1]), ptr(rng_state(device))
+
+
 def ffn_fwd(x, w1, b1, w2, b2, *, act, alpha=1.0, R=None, drop=(0.0, 0, 0.0, 0), save=True, packed=None, ln=None):
     """out = R + alpha * drop_out(drop_in(act(x W1^T + b1)) W2^T + b2) in ONE launch; with save also the two tensors
     backward needs: h = drop_in(act(z)) and f = mask / (1 - p) * act'(z).  -> (out fp32, f, h); x / w1 / w2 all fp32 or all
@@ -715,15 +737,19 @@ def ffn_fwd(x, w1, b1, w2, b2, *, act, alpha=1.0, R=None, drop=(0.0, 0, 0.0, 0),
     p = _ffn_desc(x, packed[0], b1, packed[1], b2, R, out, f, h, act, alpha, drop, F=F)
     p.hsplit = hs
     if ln is not None:
-        xr, g, b, eps, mean, rstd = ln
-        for t_ in (xr, g, b, mean, rstd):
-            if t_.dtype != torch.float32 or not t_.is_contiguous():
-                raise _lib.EamdError("ffn_fwd: LayerNorm operands are contiguous float32 tensors")
-        if tuple(xr.shape) != (M, D) or g.numel() != D or b.numel() != D or mean.numel() < M or rstd.numel() < M:
-            raise _lib.EamdError("ffn_fwd: LayerNorm operand shapes")
-        p.ln_x, p.ln_w, p.ln_b, p.ln_mean, p.ln_rstd, p.ln_eps = ptr(xr), ptr(g), ptr(b), ptr(mean), ptr(rstd), float(eps)
+        _set_ln(p, ln, M)
     _ffn_call("eamd_ffn_fwd", p, (x, packed, b1, b2, R, out, f, h, ln))
     return out, f, h
+
+
+def _ffn_pack_buf(w1, device, dt):
+    """the [4, F * D] buffer of one FFN's packed images, cached on w1 -> (buffer, whether it was there already)"""
+    F, D = w1.shape
+    buf = getattr(w1, "_eamd_ffn_pack", None)
+    if buf is not None and buf.numel() == 4 * F * D and buf.device == device and buf.dtype == dt:
+        return buf, True
+    buf = w1._eamd_ffn_pack = torch.empty(4, F * D, device=device, dtype=dt)
+    return buf, False
 
 
 def ffn_pack(w1, w2):
@@ -735,11 +761,8 @@ def ffn_pack(w1, w2):
     bf = fast() or w1.dtype == torch.bfloat16
     s1, s2 = (wshadow(w1), wshadow(w2)) if w1.dtype != torch.bfloat16 else (w1, w2)
     dt = torch.bfloat16 if bf else torch.float32
-    buf = getattr(w1, "_eamd_ffn_pack", None)
-    if buf is None or buf.numel() != 4 * F * D or buf.device != s1.device or buf.dtype != dt:
-        buf = torch.empty(4, F * D, device=s1.device, dtype=dt)
-        w1._eamd_ffn_pack = buf
-    elif _rp["active"] and getattr(w1, "_eamd_ffn_pack_epoch", -1) == _rp["epoch"]:
+    buf, cached = _ffn_pack_buf(w1, s1.device, dt)
+    if cached and _rp["active"] and getattr(w1, "_eamd_ffn_pack_epoch", -1) == _rp["epoch"]:
         return buf[0], buf[1], buf[2], buf[3]         # packed by this pass's ffn_prepack (one launch for all blocks)
     name = "eamd_ffn_pack_bf16" if bf else "eamd_ffn_pack_f32"
     check(getattr(_lib.lib(), name)(ptr(s1), ptr(s2), ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(buf[3]), D, F, stream_ptr()), name)
@@ -757,10 +780,7 @@ def ffn_prepack(pairs):
         F, D = w1.shape
         if D != 256 or F % 128 != 0 or F < 256 or w1.dtype != torch.float32:
             continue
-        buf = getattr(w1, "_eamd_ffn_pack", None)
-        if buf is None or buf.numel() != 4 * F * D or buf.device != w1.device or buf.dtype != torch.float32:
-            buf = torch.empty(4, F * D, device=w1.device, dtype=torch.float32)
-            w1._eamd_ffn_pack = buf
+        buf = _ffn_pack_buf(w1, w1.device, torch.float32)[0]
         q = arr[n]
         q.w1, q.w2, q.fwd_first, q.fwd_second, q.bwd_first, q.bwd_second = ptr(w1), ptr(w2), ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(buf[3])
         q.D, q.F = D, F
@@ -793,10 +813,7 @@ def ffn_bwd(dy, w1, w2, f, *, alpha=1.0, packed=None, lnb=None):
     p = _ffn_desc(dy, packed[0], None, packed[1], None, None, dx, f, dz, ACT_NONE, alpha, (0.0, 0, 0.0, 0), F=F)
     p.hsplit = hs
     if lnb is not None:
-        xb, g, mean, rstd, dres, ws, d_out, d_ps = lnb
-        p.lnb_x, p.lnb_gamma, p.lnb_mean, p.lnb_rstd, p.lnb_dres, p.lnb_ws = ptr(xb), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(ws)
-        if d_out is not None:
-            p.lnb_drop_out, p.lnb_drop_p, p.lnb_drop_salt, p.drop_step = ptr(d_out), float(d_ps[0]), int(d_ps[1]), ptr(rng_state(dy.device))
+        _set_lnb(p, lnb, dy.device)
     _ffn_call("eamd_ffn_bwd", p, (dy, packed, f, dz, dx, lnb))
     return dz, dx
 
@@ -887,16 +904,12 @@ def rowproj(a, img, N, *, bias=None, R=None, alpha=1.0, drop=None, ln=None, affi
     if drop is not None and drop[0] > 0.0:
         p.p_out, p.salt_out, p.drop_step = float(drop[0]), int(drop[1]), ptr(rng_state(dev))
     if ln is not None:
-        xr, g, b, eps, mean, rstd = ln
-        p.ln_x, p.ln_w, p.ln_b, p.ln_mean, p.ln_rstd, p.ln_eps = ptr(xr), ptr(g), ptr(b), ptr(mean), ptr(rstd), float(eps)
+        _set_ln(p, ln, M)
     if affine is not None:
         sc, sh, act, a_out = affine
         p.a_scale, p.a_shift, p.a_act, p.a_out = ptr(sc), ptr(sh), int(act), ptr(a_out)
     if lnb is not None:
-        xb, g, mean, rstd, dres, ws, d_out, d_ps = lnb
-        p.lnb_x, p.lnb_gamma, p.lnb_mean, p.lnb_rstd, p.lnb_dres, p.lnb_ws = ptr(xb), ptr(g), ptr(mean), ptr(rstd), ptr(dres), ptr(ws)
-        if d_out is not None:
-            p.lnb_drop_out, p.lnb_drop_p, p.lnb_drop_salt, p.drop_step = ptr(d_out), float(d_ps[0]), int(d_ps[1]), ptr(rng_state(dev))
+        _set_lnb(p, lnb, dev)
     fn = _lib.lib().eamd_rowproj
     keep = (a, img, bias, R, out, ln, affine, lnb)
     if _gemm_record is not None:

@@ -1565,6 +1565,106 @@ def test_ffn_layernorm_in_front(ops, prec, M, F, act):
         espnet_amd.set_precision("fp32")
 
 
+@pytest.mark.parametrize("M", [33, 100])
+def test_rowblock_kernels_share_one_layernorm_staging(ops, M):
+    """The LayerNorm in front is ONE piece of code (csrc/rowblock.h: rb_stage_ln) for the three row-block kernels: the fp32
+    feed-forward and the row projection leave bit-equal normalised rows, mean and rstd; the bf16 feed-forward the same mean and
+    rstd, and as rows the project's bf16 rounding (eamd_cast_bf16: eamd_f2bf, as the kernel's store) of the fp32 rows.
+    M = 33, 100: more than one 32-row block and a ragged last one."""
+    import espnet_amd
+    g = torch.Generator().manual_seed(11)
+    D = F = 256
+    x = (torch.randn(M, D, generator=g) * 3.0 + 0.5).to(DEV)
+    gam, bet = (1.0 + 0.1 * torch.randn(D, generator=g)).to(DEV), (0.1 * torch.randn(D, generator=g)).to(DEV)
+    w1 = (torch.randn(F, D, generator=g) / 16.0).to(DEV)
+    w2 = (torch.randn(D, F, generator=g) / 16.0).to(DEV)
+    eps = 1e-12
+
+    def bufs(dt):
+        nan = float("nan")
+        return torch.full((M, D), nan, device=DEV).to(dt), torch.full((M,), nan, device=DEV), torch.full((M,), nan, device=DEV)
+    xn_f, mean_f, rstd_f = bufs(torch.float32)
+    ops.ffn_fwd(xn_f, w1, None, w2, None, act=ops.ACT_SWISH, ln=(x, gam, bet, eps, mean_f, rstd_f))
+    xn_r, mean_r, rstd_r = bufs(torch.float32)
+    img, = ops.rowproj_pack([(w1, False)])
+    ops.rowproj(xn_r, img, 256, ln=(x, gam, bet, eps, mean_r, rstd_r))
+    torch.cuda.synchronize()
+    assert torch.isfinite(xn_f).all() and torch.isfinite(mean_f).all() and torch.isfinite(rstd_f).all()
+    assert torch.equal(xn_f, xn_r) and torch.equal(mean_f, mean_r) and torch.equal(rstd_f, rstd_r)
+    espnet_amd.set_precision("bf16")
+    try:
+        xn_b, mean_b, rstd_b = bufs(torch.bfloat16)
+        ops.ffn_fwd(xn_b, w1.to(torch.bfloat16), None, w2.to(torch.bfloat16), None, act=ops.ACT_SWISH,
+                    ln=(x, gam, bet, eps, mean_b, rstd_b))
+        torch.cuda.synchronize()
+    finally:
+        espnet_amd.set_precision("fp32")
+    assert torch.equal(mean_b, mean_f) and torch.equal(rstd_b, rstd_f)
+    assert torch.equal(xn_b.view(torch.int16), ops.cast_bf16(xn_f).view(torch.int16))
+
+
+@pytest.mark.parametrize("F", [256, 384])
+def test_ffn_pack_entry_points_share_one_mapping(ops, F):
+    """eamd_ffn_pack_f32 (one FFN per launch) and eamd_ffn_pack_f32_multi (a table of FFNs) write the same four images, and
+    every element of every image is the weight element that the layout comment of csrc/ffn_f32.hip names:
+    image[chunk c][step s][wave wq][v][lane = fq * 16 + fr] = float4."""
+    g = torch.Generator().manual_seed(F)
+    D = 256
+    w1, w2 = torch.randn(F, D, generator=g), torch.randn(D, F, generator=g)
+    w1a, w2a, w1b, w2b = w1.to(DEV), w2.to(DEV), w1.to(DEV), w2.to(DEV)
+    single = [t.clone() for t in ops.ffn_pack(w1a, w2a)]
+    ops.rowproj_prepack([])               # opens a prepack epoch: ffn_pack then hands out what ffn_prepack made
+    try:
+        ops.ffn_prepack([(w1b, w2b)])
+        w1b.add_(1.0)                     # a repack by ffn_pack would now give other images
+        multi = [t.clone() for t in ops.ffn_pack(w1b, w2b)]
+    finally:
+        ops.rowproj_prepack_end()
+    torch.cuda.synchronize()
+    for a, b in zip(single, multi):
+        assert a.numel() == F * D and torch.equal(a, b)
+    c, s, wq, v, lane, e = torch.meshgrid(torch.arange(F // 128), torch.arange(8), torch.arange(4), torch.arange(4),
+                                          torch.arange(64), torch.arange(4), indexing="ij")
+    fr, fq, q, j = lane % 16, lane // 16, v // 2, v % 2
+    want = [w1[c * 128 + wq * 32 + 2 * fr + j, s * 32 + q * 16 + fq * 4 + e],                 # forward first: v = q*2 + j
+            w2[wq * 64 + v * 16 + fr, c * 128 + s * 16 + fq * 4 + e],                         # forward second: v = j
+            w2[s * 32 + q * 16 + fq * 4 + (v % 2) * 2 + e // 2, c * 128 + wq * 32 + 2 * fr + e % 2],     # backward first
+            w1[c * 128 + s * 16 + fq * 4 + v, wq * 64 + 4 * fr + e]]                          # backward second: v = e
+    for which in range(4):
+        assert torch.equal(single[which].cpu().view(want[which].shape), want[which]), "image %d" % which
+
+
+def test_rowproj_validates_its_layernorm_operands(ops, monkeypatch):
+    """ops.rowproj checks dtype, contiguity and shape of the `ln` operands as ops.ffn_fwd does (one helper fills the ln_* fields
+    of both): a bad operand raises EamdError and the library is never called.  (ops takes device tensors only, so this runs here.)"""
+    from espnet_amd import _lib
+
+    def no_launch():
+        raise AssertionError("the library was reached")
+    monkeypatch.setattr(_lib, "lib", no_launch)
+    M = 40
+    dev = dict(device=DEV)
+    a, img = torch.empty(M, 256, **dev), torch.empty(256 * 256, **dev)
+    x, gam, bet = torch.zeros(M, 256, **dev), torch.ones(256, **dev), torch.zeros(256, **dev)
+    mean, rstd = torch.empty(M, **dev), torch.empty(M, **dev)
+    bad = dict(noncontiguous_rows=(torch.zeros(M, 512, **dev)[:, ::2], gam, bet, 1e-12, mean, rstd),
+               noncontiguous_gamma=(x, torch.ones(512, **dev)[::2], bet, 1e-12, mean, rstd),
+               wrong_rows=(torch.zeros(M - 1, 256, **dev), gam, bet, 1e-12, mean, rstd),
+               wrong_width=(torch.zeros(M, 128, **dev), gam, bet, 1e-12, mean, rstd),
+               short_beta=(x, gam, torch.zeros(255, **dev), 1e-12, mean, rstd),
+               short_mean=(x, gam, bet, 1e-12, torch.empty(M - 1, **dev), rstd),
+               short_rstd=(x, gam, bet, 1e-12, mean, torch.empty(M - 1, **dev)),
+               double_rows=(x.double(), gam, bet, 1e-12, mean, rstd))
+    for name, ln in bad.items():
+        with pytest.raises(_lib.EamdError):
+            ops.rowproj(a, img, 256, ln=ln)
+        with pytest.raises(_lib.EamdError):      # the same helper in front of the feed-forward launch
+            ops.ffn_fwd(a, torch.empty(256, 256, **dev), None, torch.empty(256, 256, **dev), None, act=ops.ACT_SWISH, save=False,
+                        packed=(img, img), ln=ln)
+    with pytest.raises(AssertionError, match="the library was reached"):      # valid operands go on to the launch
+        ops.rowproj(a, img, 256, ln=(x, gam, bet, 1e-12, mean, rstd))
+
+
 @pytest.mark.parametrize("rows,n,k", [(10, 5000, 15), (1, 50000, 10), (320, 5000, 10), (32, 50000, 10), (3, 7, 7), (5, 6144, 64), (4, 6145, 3),
                                       (6, 100, 10), (3, 300, 64), (2, 1, 1)])
 def test_topk_rows(ops, rows, n, k):
