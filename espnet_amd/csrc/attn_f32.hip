@@ -26,34 +26,15 @@
 //     "keys 16 t + 4 fq + r, fq = 0..3".  V comes from a panel staged over X once the scores are in registers
 //     ([key][68] floats: the four fq groups of a ds_read_b32 fall into disjoint banks; its global loads are issued
 //     before the softmax).  C^T leaves four adjacent channels per lane (16-byte stores).
-#include "common.h"
+// Shared with attn_fused.hip through attn_common.h: the argument structs, the decoding of a workgroup, the rel_shift length, the
+// inverse rel_shift scatter (long backward), mask word and masked score (long forward), the dropout set-up and keep bits, the
+// 16-lane-group reductions, and on the host the argument checks and the launch.  Softmax, the forward's shifted stores and the
+// short kernels' mask / score code are written out per kernel ("What the attention kernels share", says why).
+#include "attn_common.h"
 
 namespace {
 
-constexpr int ATT_DK = 64;
-constexpr int ATT_MAXK = 512;                 // keys per row: 8 / 16 key tiles of 16 at two workgroups per CU, 32 at one (LDS)
-constexpr int PLD = 68;                       // row stride (floats) of the V / K panel in LDS
-
-struct AttnF32Args {
-  const float* qu; const float* qv; const float* k; const float* v; const float* pos;
-  const unsigned char* mask;
-  float* P; float* ctx;
-  long ldq, ldqv, ldk, ldv, ldpos, ldc, ldp, mb, mi;
-  int B, H, T1, T2, nqb;
-  float scale;
-  // attention dropout (attention.py:91): Pd = dropout(P) feeds the context; mask index = element index in P
-  float* Pd; float drop_p; const unsigned long long* drop_step; unsigned long long drop_salt;
-  const int* tshift;     // device scalar: length the legacy rel_shift works on (NULL: T2) - see eamd_attn_fwd
-};
-
-__device__ __forceinline__ float xmax16_32(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16));
-  return fmaxf(v, __shfl_xor(v, 32));
-}
-__device__ __forceinline__ float xsum16_32(float v) {
-  v += __shfl_xor(v, 16);
-  return v + __shfl_xor(v, 32);
-}
+constexpr int PLD = ATT_PLD;                  // row stride (floats) of the V / K panel in LDS
 
 // this lane's share of a 64-channel row: chunks 4 j + fq
 __device__ __forceinline__ void load_frag(const float* row, int fq, float4 (&f)[4]) {
@@ -136,33 +117,26 @@ __device__ __forceinline__ void score_tiles(const float* keys, long ldk, int T2,
 // NKT = key tiles of 16 the instantiation covers (T2 <= 16 NKT).  Loops over tiles are fully unrolled and free of
 // branches: rows past T2 / T1 are clamped re-reads whose scores are masked / never stored.
 template <bool REL, int NKT>
-__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(const AttnF32Args a) {
+__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(const AttnArgs<float> a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   constexpr int XLD = NKT * 16 + 4;
   constexpr int TPW = NKT / 4;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  // (batch, head) pairs are dealt to the XCDs in contiguous runs: the query blocks of one pair share an L2
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nqb) * 8 + xcd;            // z = h * B + b, as the score tensors are laid out
-  const bool live = z < a.B * a.H;                 // whole workgroup; dead ones only keep the barriers company
-  const int zz = live ? z : 0;
-  const int h = zz / a.B, b = zz % a.B;
+  const AttnGeom g = attn_geom(blockIdx.x, a.nqb, a.B, a.H, a.T1, 64);
+  const bool live = g.live;
+  const int zz = g.zz, h = g.h, b = g.b, r0w = g.r0w, nq = g.nq;
   const int T1 = a.T1, T2 = a.T2;
-  const int r0w = min((jb % a.nqb) * 64, T1 - 1);  // first query of the workgroup
-  const int nq = T1 - r0w;                         // its queries (up to 64)
   const int r0 = r0w + wave * 16;                  // first query this wave owns in the softmax / context phases
   const bool active = live && r0 < T1;
   const int qi = min(r0 + fr, T1 - 1);             // this lane's query (clamped lanes are never stored)
 
   float* X = reinterpret_cast<float*>(smem_raw);
-  // Ts: the length the legacy rel_shift is taken over.  A batch padded beyond its own longest utterance (shape-bucketed
-  // graphs) passes that utterance's length here: the shift then maps bd exactly as the reference's T' x T' matrix does;
-  // keys from Ts on are masked by the caller's mask, and the score matrix is cleared first so that the rows / columns the
-  // shift no longer reaches hold zeros instead of stale LDS.
+  // (the rel_shift part keeps its written-out form: as calls into attn_common.h - shift length, map, next-row dot products - it
+  // changed the scalar-register spills of the 8- and 16-tile instantiations)
   const int Ts = (REL && a.tshift) ? min(max(a.tshift[0], 1), T2) : T2;
   if (REL) {
-    if (Ts < T2) {
+    if (Ts < T2) {                                   // what the shorter shift no longer reaches holds zeros, not stale LDS
       for (int e = t; e < 64 * XLD; e += 256) X[e] = 0.f;
       __syncthreads();
     }
@@ -218,8 +192,8 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(con
   // ---- scale, mask, softmax over the keys of query (r0 + fr) ----
   f32x4 S[NKT];
   if (active) {
-    // mask bytes of this lane's keys: unconditional clamped loads, all in flight together; keys past T2 are masked
-    // by index below
+    // (mask, scores and softmax stay written out here: as a function shared with attn_fused.hip the 16- and 32-tile instantiations
+    // allocated other registers)
     unsigned mk[NKT];
     if (a.mask) {
       const unsigned char* mr = a.mask + (long)b * a.mb + (long)qi * a.mi;
@@ -249,7 +223,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(con
         mx = fmaxf(mx, x);
       }
     }
-    mx = xmax16_32(mx);
+    mx = attn_max16_32(mx);
     const bool dead = mx == -INFINITY;              // every key masked: softmax(min, ...) = uniform, then masked_fill(0)
     float sum = 0.f;
 #pragma unroll
@@ -260,7 +234,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(con
         S[kt][r] = e;
         sum += e;
       }
-    sum = xsum16_32(sum);
+    sum = attn_sum16_32(sum);
     const float inv = dead ? 0.f : 1.f / sum;
     const bool qok = r0 + fr < T1;
     const long pro = ((long)zz * T1 + qi) * a.ldp;
@@ -269,21 +243,18 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(con
     for (int kt = 0; kt < NKT; ++kt) {
       S[kt] *= inv;
       const int j0 = kt * 16 + fq * 4;
-      if (qok && j0 < a.ldp)                         // pad columns receive zeros
-        *reinterpret_cast<float4*>(prow + j0) = make_float4(S[kt][0], S[kt][1], S[kt][2], S[kt][3]);
+      if (qok && j0 < a.ldp) st4(prow + j0, f4(S[kt]));           // pad columns receive zeros
     }
     if (a.drop_p > 0.f) {                            // wave-uniform: the dropped probabilities go on to the context product
-      const unsigned seed = eamd_drop_seed(a.drop_step, a.drop_salt), thr = eamd_drop_thr16(a.drop_p);
-      const float dinv = eamd_drop_inv(thr);
+      const AttnDrop drop = attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt);
 #pragma unroll
       for (int kt = 0; kt < NKT; ++kt) {
         const int j0 = kt * 16 + fq * 4;
         bool kp[4];
-        eamd_drop_keep4(seed, (unsigned long long)(pro + min(j0, (int)a.ldp - 4)), thr, kp);
+        attn_keep4(drop, pro, j0, a.ldp, kp);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) S[kt][r] = kp[r] ? S[kt][r] * dinv : 0.f;
-        if (qok && j0 < a.ldp)
-          *reinterpret_cast<float4*>(a.Pd + pro + j0) = make_float4(S[kt][0], S[kt][1], S[kt][2], S[kt][3]);
+        for (int r = 0; r < 4; ++r) S[kt][r] = kp[r] ? S[kt][r] * drop.dinv : 0.f;
+        if (qok && j0 < a.ldp) st4(a.Pd + pro + j0, f4(S[kt]));
       }
     }
   } else {
@@ -303,8 +274,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(con
   if (r0 + fr < T1) {
     float* crow = a.ctx + ((long)b * T1 + r0 + fr) * a.ldc + h * ATT_DK;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-      *reinterpret_cast<float4*>(crow + dt * 16 + fq * 4) = make_float4(C[dt][0], C[dt][1], C[dt][2], C[dt][3]);
+    for (int dt = 0; dt < 4; ++dt) st4(crow + dt * 16 + fq * 4, f4(C[dt]));
   }
 }
 
@@ -314,31 +284,17 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_fwd_kernel(con
 // the key-side GEMMs (dK = dS^T q, and with relative positions dqv / dpos from the inverse rel_shift scatter dbd,
 // written here element by element exactly as eamd_softmax_bwd does) and dq^T = K^T dS^T from a K panel staged over X -
 // the context product of the forward with K in place of V.  reference: autograd of attention.py:63-114, :141-206.
-struct AttnF32BwdArgs {
-  const float* dctx; const float* k; const float* v; const float* P;
-  float* dS; float* dbd; float* dq;
-  long ldd, ldk, ldv, ldp, ldo;
-  int B, H, T1, T2, nqb;
-  float scale;
-  float drop_p; const unsigned long long* drop_step; unsigned long long drop_salt;   // the forward's attention dropout
-  const int* tshift;
-};
-
 template <int NKT>
-__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(const AttnF32BwdArgs a) {
+__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(const AttnBwdArgs<float> a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   constexpr int XLD = NKT * 16 + 4;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nqb) * 8 + xcd;
-  const bool live = z < a.B * a.H;
-  const int zz = live ? z : 0;
-  const int h = zz / a.B, b = zz % a.B;
+  const AttnGeom g = attn_geom(blockIdx.x, a.nqb, a.B, a.H, a.T1, 64);
+  const bool live = g.live;
+  const int zz = g.zz, h = g.h, b = g.b, r0w = g.r0w, nq = g.nq;
   const int T1 = a.T1, T2 = a.T2;
-  const int Ts = (a.dbd && a.tshift) ? min(max(a.tshift[0], 1), T2) : T2;      // rel_shift length (see the forward kernel)
-  const int r0w = min((jb % a.nqb) * 64, T1 - 1);
-  const int nq = T1 - r0w;
+  const int Ts = a.dbd ? attn_shift_len(a.tshift, T2) : T2;
   const int r0 = r0w + wave * 16;
   const bool active = live && r0 < T1;
   const int qi = min(r0 + fr, T1 - 1);
@@ -361,9 +317,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(c
   f32x4 S[NKT];                                     // dP^T, then dS^T
   if (active) {
     const float* xrow = &X[(wave * 16 + fr) * XLD + 4 * fq];
-    const bool drop = a.drop_p > 0.f;                // wave-uniform
-    const unsigned seed = drop ? eamd_drop_seed(a.drop_step, a.drop_salt) : 0u, thr = eamd_drop_thr16(a.drop_p);
-    const float dinv = eamd_drop_inv(thr);
+    const AttnDrop drop = attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt);
     const long pro = ((long)zz * T1 + qi) * a.ldp;
     float s = 0.f;
 #pragma unroll
@@ -371,17 +325,17 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(c
       const int j0 = kt * 16 + fq * 4;
       const float4 xv = *reinterpret_cast<const float4*>(xrow + kt * 16);
       S[kt] = (f32x4){xv.x, xv.y, xv.z, xv.w};
-      if (drop) {                                    // gradient of the dropped probabilities -> gradient of P
+      if (drop.on) {                                 // gradient of the dropped probabilities -> gradient of P
         bool kp[4];
-        eamd_drop_keep4(seed, (unsigned long long)(pro + min(j0, (int)a.ldp - 4)), thr, kp);
+        attn_keep4(drop, pro, j0, a.ldp, kp);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) S[kt][r] = kp[r] ? S[kt][r] * dinv : 0.f;
+        for (int r = 0; r < 4; ++r) S[kt][r] = kp[r] ? S[kt][r] * drop.dinv : 0.f;
       }
       const float pr[4] = {Pr[kt].x, Pr[kt].y, Pr[kt].z, Pr[kt].w};
 #pragma unroll
       for (int r = 0; r < 4; ++r) if (j0 + r < T2) s += pr[r] * S[kt][r];
     }
-    s = xsum16_32(s);
+    s = attn_sum16_32(s);
     const long zo = (long)zz * T1 * a.ldp;
     float* srow = a.dS + zo + (long)qi * a.ldp;
     const int i = r0 + fr;
@@ -395,8 +349,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(c
         const float g = j < T2 ? pr[r] * (S[kt][r] - s) * a.scale : 0.f;
         S[kt][r] = g;
         if (a.dbd && qok) {
-          // inverse rel_shift for T1 == T2 = T (Ts when the shift is shorter than the padded matrix: everything outside the
-          // Ts x Ts square is zero): padded index T + i T + j lands in row i (j <= i) or row i + 1
+          // inverse rel_shift, attn_dbd_put written out (as the call the 32-tile instantiation takes 35 more AGPRs)
           if (j < Ts && i < Ts) {
             const int R = j <= i ? i : i + 1, c = j <= i ? Ts + j - i : j - i - 1;
             if (c != 0) a.dbd[zo + (long)R * a.ldp + (c - 1)] = g;
@@ -407,8 +360,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(c
       }
       if (qok && j0 < (int)a.ldp) *reinterpret_cast<float4*>(srow + j0) = make_float4(S[kt][0], S[kt][1], S[kt][2], S[kt][3]);
     }
-    if (a.dbd && r0 == 0)                            // the head of row 0 the scatter never reaches
-      for (int f = 1 + lane; f < Ts; f += 64) a.dbd[zo + (f - 1)] = 0.f;
+    if (a.dbd && r0 == 0) attn_dbd_zero_head(a.dbd, zo, Ts, lane, 64);
   } else {
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) S[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -426,7 +378,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(c
   for (int dt = 0; dt < 4; ++dt) C[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   panel_product<NKT>(Ks, S, fr, fq, C);
   if (qok) {
-    float* orow = a.dq + ((long)b * T1 + r0 + fr) * a.ldo + h * ATT_DK;
+    float* orow = reinterpret_cast<float*>(a.dq) + ((long)b * T1 + r0 + fr) * a.ldo + h * ATT_DK;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt)
       *reinterpret_cast<float4*>(orow + dt * 16 + fq * 4) = make_float4(C[dt][0], C[dt][1], C[dt][2], C[dt][3]);
@@ -446,28 +398,8 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_f32_bwd_q_kernel(c
 // softmax walks X three times (max, exp + sum, normalise) instead of holding the row in registers.
 // Per workgroup K, V and the positions are read once (768 KB at 1024 keys) for 16 queries: four times the L2 traffic of
 // the 64-query kernels per query, which is what the LDS budget allows.
-constexpr int ATT_LONG_MAXK = 4096;                         // (LQ, the queries per workgroup, is a template parameter: 16, or 8 beyond 2048 keys)
-
-// element access for the two storage types of the long-row kernels: float (fp32 mode) and bf16 bits (bf16-operand mode:
-// same kernels, operands widened on load, fp32 MFMA; P / dS / dbd / ctx rounded to bf16 on store)
-typedef unsigned short bfbits;
-__device__ __forceinline__ float bf2f_(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 ld4(const bfbits* p) {
-  const uint2 u = *reinterpret_cast<const uint2*>(p);
-  return make_float4(bf2f_(u.x & 0xffffu), bf2f_(u.x >> 16), bf2f_(u.y & 0xffffu), bf2f_(u.y >> 16));
-}
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ void st4(bfbits* p, float4 v) {
-  uint2 u;
-  u.x = (unsigned)eamd_f2bf(v.x) | ((unsigned)eamd_f2bf(v.y) << 16);
-  u.y = (unsigned)eamd_f2bf(v.z) | ((unsigned)eamd_f2bf(v.w) << 16);
-  *reinterpret_cast<uint2*>(p) = u;
-}
-__device__ __forceinline__ void st1(float* p, float v) { *p = v; }
-__device__ __forceinline__ void st1(bfbits* p, float v) { *p = eamd_f2bf(v); }
-__device__ __forceinline__ float rnd(const float*, float v) { return v; }                      // value as the storage type keeps it
-__device__ __forceinline__ float rnd(const bfbits*, float v) { return bf2f_(eamd_f2bf(v)); }
+// (LQ, the queries per workgroup, is a template parameter: 16, or 8 beyond 2048 keys.)  The storage type T is float (fp32 mode)
+// or bf16_t (bf16-operand mode: same kernels, operands widened on load, fp32 MFMA; P / dS / dbd / ctx rounded to bf16 on store).
 template <typename T>
 __device__ __forceinline__ void load_frag_t(const T* row, int fq, float4 (&f)[4]) {
 #pragma unroll
@@ -524,25 +456,17 @@ __device__ __forceinline__ void reduce_store_ct(const f32x4 (&C)[4], float* scr,
 }
 
 template <typename T, bool REL, int LQ, int NW>
-__global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Args a, const int nkt) {
-  constexpr int QT = LQ >= 16 ? LQ / 16 : 1;
-  constexpr int NT = 64 * NW;                          // NW waves split the key tiles (4, or 8 where only one workgroup fits a CU)           // 16-query tiles of the workgroup: every key / value / position fragment a wave
-  const T* const a_qu = reinterpret_cast<const T*>(a.qu); const T* const a_qv = reinterpret_cast<const T*>(a.qv);      // loads serves all of them
-  const T* const a_k = reinterpret_cast<const T*>(a.k); const T* const a_v = reinterpret_cast<const T*>(a.v);
-  const T* const a_pos = reinterpret_cast<const T*>(a.pos);
-  T* const a_P = reinterpret_cast<T*>(a.P); T* const a_Pd = reinterpret_cast<T*>(a.Pd); T* const a_ctx = reinterpret_cast<T*>(a.ctx);
+__global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnArgs<T> a, const int nkt) {
+  constexpr int QT = LQ >= 16 ? LQ / 16 : 1;           // 16-query tiles of the workgroup: every key / value / position fragment a wave loads serves all of them
+  constexpr int NT = 64 * NW;                          // NW waves split the key tiles (4, or 8 where only one workgroup fits a CU)
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int XLD = nkt * 16 + 4;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nqb) * 8 + xcd;
-  const bool live = z < a.B * a.H;
-  const int zz = live ? z : 0;
-  const int h = zz / a.B, b = zz % a.B;
+  const AttnGeom g = attn_geom(blockIdx.x, a.nqb, a.B, a.H, a.T1, LQ);
+  const bool live = g.live;
+  const int zz = g.zz, h = g.h, b = g.b, r0w = g.r0w, nq = min(LQ, g.nq);
   const int T1 = a.T1, T2 = a.T2;
-  const int r0w = min((jb % a.nqb) * LQ, T1 - 1);
-  const int nq = min(LQ, T1 - r0w);
   // per query tile: the row of X / red this lane works on (LQ = 8: lanes of the tile's upper half repeat query LQ - 1 - same values,
   // same addresses, one instruction), the query row it loads (clamped), the query whose mask / probability row it serves
   int rowx[QT], qrow[QT], qi[QT];
@@ -557,7 +481,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
   float* X = reinterpret_cast<float*>(smem_raw);
   float* Tw = X + LQ * XLD + wave * 16 * PLD;           // this wave's tile buffer
   float* red = X + LQ * XLD + NW * 16 * PLD;            // [2][NW][LQ]
-  const int Ts = (REL && a.tshift) ? min(max(a.tshift[0], 1), T2) : T2;
+  const int Ts = REL ? attn_shift_len(a.tshift, T2) : T2;
   if (REL) {
     if (Ts < T2) {
       for (int e = t; e < LQ * XLD; e += NT) X[e] = 0.f;
@@ -565,14 +489,14 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
     }
     float4 qf[QT][4];
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) load_frag_t(a_qv + ((long)b * T1 + qrow[qt]) * a.ldqv + h * ATT_DK, fq, qf[qt]);
+    for (int qt = 0; qt < QT; ++qt) load_frag_t(a.qv + ((long)b * T1 + qrow[qt]) * a.ldqv + h * ATT_DK, fq, qf[qt]);
     if (t < LQ && r0w + t + 1 < T2) X[t * XLD + r0w + t + 1] = 0.f;
     // (the next tile's fragment is requested before this tile's products: with one or two workgroups of 4 - 8 waves per CU nothing
     // else hides the round trip of these row-strided loads)
     float4 pf[4], pfn[4];
-    if (wave < nkt) load_frag_t(a_pos + (long)min(wave * 16 + fr, T2 - 1) * a.ldpos + h * ATT_DK, fq, pf);
+    if (wave < nkt) load_frag_t(a.pos + (long)min(wave * 16 + fr, T2 - 1) * a.ldpos + h * ATT_DK, fq, pf);
     for (int mt = wave; mt < nkt; mt += NW) {
-      if (mt + NW < nkt) load_frag_t(a_pos + (long)min((mt + NW) * 16 + fr, T2 - 1) * a.ldpos + h * ATT_DK, fq, pfn);
+      if (mt + NW < nkt) load_frag_t(a.pos + (long)min((mt + NW) * 16 + fr, T2 - 1) * a.ldpos + h * ATT_DK, fq, pfn);
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) {
         const f32x4 c = dot_tile(pf, qf[qt], (f32x4){0.f, 0.f, 0.f, 0.f});     // c[r] = bd[query 16 qt + fr][m = 16 mt + 4 fq + r]
@@ -590,9 +514,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
     }
     const int i16 = r0w + LQ;                         // first query of the next workgroup: its low positions feed query r0w + LQ - 1
     if (live && i16 < Ts) {
-      const T* qr = a_qv + ((long)b * T1 + i16) * a.ldqv + h * ATT_DK;
+      const T* qr = a.qv + ((long)b * T1 + i16) * a.ldqv + h * ATT_DK;
       for (int m = t; m <= Ts - 2 - i16; m += NT) {
-        const T* pr = a_pos + (long)m * a.ldpos + h * ATT_DK;
+        const T* pr = a.pos + (long)m * a.ldpos + h * ATT_DK;
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -613,9 +537,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
     for (int qt = 0; qt < QT; ++qt) {
       mr[qt] = a.mask ? a.mask + (long)b * a.mb + (long)qi[qt] * a.mi : nullptr;
       mx[qt] = -INFINITY;
-      load_frag_t(a_qu + ((long)b * T1 + qrow[qt]) * a.ldq + h * ATT_DK, fq, qf[qt]);
+      load_frag_t(a.qu + ((long)b * T1 + qrow[qt]) * a.ldq + h * ATT_DK, fq, qf[qt]);
     }
-    const T* keys = a_k + (long)b * T2 * a.ldk + h * ATT_DK;
+    const T* keys = a.k + (long)b * T2 * a.ldk + h * ATT_DK;
     float4 kf[4], kfn[4];
     if (wave < nkt) load_frag_t(keys + (long)min(wave * 16 + fr, T2 - 1) * a.ldk, fq, kf);
     for (int kt = wave; kt < nkt; kt += NW) {
@@ -628,16 +552,13 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
         if (REL) { const float4 o = *xp; c = (f32x4){o.x, o.y, o.z, o.w}; }
         c = dot_tile(kf, qf[qt], c);                    // c[r]: key 16 kt + 4 fq + r, query 16 qt + fr
         unsigned mk = 0x01010101u;
-        if (mr[qt]) mk = mr[qt][min(j0, T2 - 1)] | (mr[qt][min(j0 + 1, T2 - 1)] << 8) | (mr[qt][min(j0 + 2, T2 - 1)] << 16) |
-                         (mr[qt][min(j0 + 3, T2 - 1)] << 24);
+        if (mr[qt]) mk = attn_mask4(mr[qt], j0, T2);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float x = c[r] * a.scale;
-          if (j0 + r >= T2 || ((mk >> (8 * r)) & 0xffu) == 0u) x = -INFINITY;
-          c[r] = x;
-          mx[qt] = fmaxf(mx[qt], x);
+          c[r] = attn_score(c[r], a.scale, j0 + r, T2, mk, r);
+          mx[qt] = fmaxf(mx[qt], c[r]);
         }
-        *xp = make_float4(c[0], c[1], c[2], c[3]);
+        *xp = f4(c);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) kf[j] = kfn[j];
@@ -645,7 +566,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
   }
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    mx[qt] = xmax16_32(mx[qt]);
+    mx[qt] = attn_max16_32(mx[qt]);
     if (fq == 0) red[wave * LQ + rowx[qt]] = mx[qt];
   }
   __syncthreads();
@@ -674,7 +595,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
   }
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    sum[qt] = xsum16_32(sum[qt]);
+    sum[qt] = attn_sum16_32(sum[qt]);
     if (fq == 0) red[NW * LQ + wave * LQ + rowx[qt]] = sum[qt];
   }
   __syncthreads();
@@ -690,10 +611,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
     pro[qt] = ((long)zz * T1 + qi[qt]) * a.ldp;
   }
   // ---- probabilities out, context^T = V^T Pd^T over this wave's key tiles ----
-  const bool drop = a.drop_p > 0.f;
-  const unsigned seed = drop ? eamd_drop_seed(a.drop_step, a.drop_salt) : 0u, thr = eamd_drop_thr16(a.drop_p);
-  const float dinv = eamd_drop_inv(thr);
-  const T* vs = a_v + (long)b * T2 * a.ldv + h * ATT_DK;
+  const AttnDrop drop = attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt);
+  const T* vs = a.v + (long)b * T2 * a.ldv + h * ATT_DK;
   f32x4 C[QT][4];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt)
@@ -709,16 +628,16 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
     for (int qt = 0; qt < QT; ++qt) {
       const float4 e = *reinterpret_cast<const float4*>(&X[rowx[qt] * XLD + kt * 16 + 4 * fq]);
       f32x4 Pv = (f32x4){e.x * inv[qt], e.y * inv[qt], e.z * inv[qt], e.w * inv[qt]};
-      if (qok[qt] && j0 < a.ldp) st4(a_P + pro[qt] + j0, make_float4(Pv[0], Pv[1], Pv[2], Pv[3]));
-      if (drop) {
+      if (qok[qt] && j0 < a.ldp) st4(a.P + pro[qt] + j0, f4(Pv));
+      if (drop.on) {
         bool kp[4];
-        eamd_drop_keep4(seed, (unsigned long long)(pro[qt] + min(j0, (int)a.ldp - 4)), thr, kp);
+        attn_keep4(drop, pro[qt], j0, a.ldp, kp);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Pv[r] = kp[r] ? Pv[r] * dinv : 0.f;
-        if (qok[qt] && j0 < a.ldp) st4(a_Pd + pro[qt] + j0, make_float4(Pv[0], Pv[1], Pv[2], Pv[3]));
+        for (int r = 0; r < 4; ++r) Pv[r] = kp[r] ? Pv[r] * drop.dinv : 0.f;
+        if (qok[qt] && j0 < a.ldp) st4(a.Pd + pro[qt] + j0, f4(Pv));
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Pv[r] = rnd(a_P, Pv[r]);      // the context is built from the probabilities backward will read
+      for (int r = 0; r < 4; ++r) Pv[r] = rnd(a.P, Pv[r]);      // the context is built from the probabilities backward will read
       tile_product(Tw, Pv, fr, fq, C[qt]);
     }
   }
@@ -726,31 +645,24 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_long_kernel(const AttnF32Arg
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
     if (qt > 0) __syncthreads();
-    reduce_store_ct<NW>(C[qt], X, wave, fr, fq, t, a_ctx + ((long)b * T1 + r0w + 16 * qt) * a.ldc + h * ATT_DK, a.ldc,
+    reduce_store_ct<NW>(C[qt], X, wave, fr, fq, t, a.ctx + ((long)b * T1 + r0w + 16 * qt) * a.ldc + h * ATT_DK, a.ldc,
                     live ? max(0, min(16, nq - 16 * qt)) : 0);
   }
 }
 
 template <typename T, int LQ, int NW>
-__global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32BwdArgs a, const int nkt, const int dq_bf16) {
+__global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnBwdArgs<T> a, const int nkt, const int dq_bf16) {
   constexpr int QT = LQ >= 16 ? LQ / 16 : 1;
   constexpr int NT = 64 * NW;                          // NW waves split the key tiles (4, or 8 where only one workgroup fits a CU)
-  const T* const a_dctx = reinterpret_cast<const T*>(a.dctx); const T* const a_k = reinterpret_cast<const T*>(a.k);
-  const T* const a_v = reinterpret_cast<const T*>(a.v); const T* const a_P = reinterpret_cast<const T*>(a.P);
-  T* const a_dS = reinterpret_cast<T*>(a.dS); T* const a_dbd = reinterpret_cast<T*>(a.dbd);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int XLD = nkt * 16 + 4;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nqb) * 8 + xcd;
-  const bool live = z < a.B * a.H;
-  const int zz = live ? z : 0;
-  const int h = zz / a.B, b = zz % a.B;
+  const AttnGeom g = attn_geom(blockIdx.x, a.nqb, a.B, a.H, a.T1, LQ);
+  const bool live = g.live;
+  const int zz = g.zz, h = g.h, b = g.b, r0w = g.r0w, nq = min(LQ, g.nq);
   const int T1 = a.T1, T2 = a.T2;
-  const int Ts = (a.dbd && a.tshift) ? min(max(a.tshift[0], 1), T2) : T2;
-  const int r0w = min((jb % a.nqb) * LQ, T1 - 1);
-  const int nq = min(LQ, T1 - r0w);
+  const int Ts = a.dbd ? attn_shift_len(a.tshift, T2) : T2;
   const long zo = (long)zz * T1 * a.ldp;
   int rowx[QT], qrow[QT];
   long pro[QT];
@@ -765,9 +677,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
   float* X = reinterpret_cast<float*>(smem_raw);
   float* Tw = X + LQ * XLD + wave * 16 * PLD;
   float* red = X + LQ * XLD + NW * 16 * PLD;
-  const bool drop = a.drop_p > 0.f;
-  const unsigned seed = drop ? eamd_drop_seed(a.drop_step, a.drop_salt) : 0u, thr = eamd_drop_thr16(a.drop_p);
-  const float dinv = eamd_drop_inv(thr);
+  const AttnDrop drop = attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt);
   // ---- dP tiles (gradient of the dropped probabilities -> of P), row sums of P dP ----
   float s[QT];
   {
@@ -775,9 +685,9 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       s[qt] = 0.f;
-      load_frag_t(a_dctx + ((long)b * T1 + qrow[qt]) * a.ldd + h * ATT_DK, fq, df[qt]);
+      load_frag_t(a.dctx + ((long)b * T1 + qrow[qt]) * a.ldd + h * ATT_DK, fq, df[qt]);
     }
-    const T* vs = a_v + (long)b * T2 * a.ldv + h * ATT_DK;
+    const T* vs = a.v + (long)b * T2 * a.ldv + h * ATT_DK;
     float4 vf[4], vfn[4];
     if (wave < nkt) load_frag_t(vs + (long)min(wave * 16 + fr, T2 - 1) * a.ldv, fq, vf);
     for (int kt = wave; kt < nkt; kt += NW) {
@@ -786,18 +696,18 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
 #pragma unroll
       for (int qt = 0; qt < QT; ++qt) {
         f32x4 c = dot_tile(vf, df[qt], (f32x4){0.f, 0.f, 0.f, 0.f});      // c[r]: key 16 kt + 4 fq + r, query 16 qt + fr
-        float4 pr = ld4(a_P + pro[qt] + min(j0, (int)a.ldp - 4));
+        float4 pr = ld4(a.P + pro[qt] + min(j0, (int)a.ldp - 4));
         if (j0 >= (int)a.ldp) pr = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (drop) {
+        if (drop.on) {
           bool kp[4];
-          eamd_drop_keep4(seed, (unsigned long long)(pro[qt] + min(j0, (int)a.ldp - 4)), thr, kp);
+          attn_keep4(drop, pro[qt], j0, a.ldp, kp);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) c[r] = kp[r] ? c[r] * dinv : 0.f;
+          for (int r = 0; r < 4; ++r) c[r] = kp[r] ? c[r] * drop.dinv : 0.f;
         }
         const float p4[4] = {pr.x, pr.y, pr.z, pr.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) if (j0 + r < T2) s[qt] += p4[r] * c[r];
-        *reinterpret_cast<float4*>(&X[rowx[qt] * XLD + kt * 16 + 4 * fq]) = make_float4(c[0], c[1], c[2], c[3]);
+        *reinterpret_cast<float4*>(&X[rowx[qt] * XLD + kt * 16 + 4 * fq]) = f4(c);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) vf[j] = vfn[j];
@@ -805,7 +715,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
   }
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
-    s[qt] = xsum16_32(s[qt]);
+    s[qt] = attn_sum16_32(s[qt]);
     if (fq == 0) red[wave * LQ + rowx[qt]] = s[qt];
   }
   __syncthreads();
@@ -818,7 +728,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
     s[qt] = s_;
   }
   // ---- dS (+ the inverse rel_shift scatter dbd), dq^T = K^T dS^T over this wave's key tiles ----
-  const T* ks = a_k + (long)b * T2 * a.ldk + h * ATT_DK;
+  const T* ks = a.k + (long)b * T2 * a.ldk + h * ATT_DK;
   f32x4 C[QT][4];
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt)
@@ -833,7 +743,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
       const int i = r0w + fr + 16 * qt;
-      float4 pr = ld4(a_P + pro[qt] + min(j0, (int)a.ldp - 4));
+      float4 pr = ld4(a.P + pro[qt] + min(j0, (int)a.ldp - 4));
       if (j0 >= (int)a.ldp) pr = make_float4(0.f, 0.f, 0.f, 0.f);
       const float4 dp = *reinterpret_cast<const float4*>(&X[rowx[qt] * XLD + kt * 16 + 4 * fq]);
       const float p4[4] = {pr.x, pr.y, pr.z, pr.w}, d4[4] = {dp.x, dp.y, dp.z, dp.w};
@@ -843,23 +753,15 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
         const int j = j0 + r;
         const float g = j < T2 ? p4[r] * (d4[r] - s[qt]) * a.scale : 0.f;
         G[r] = g;
-        if (a.dbd && qok[qt]) {
-          if (j < Ts && i < Ts) {
-            const int R = j <= i ? i : i + 1, c = j <= i ? Ts + j - i : j - i - 1;
-            if (c != 0) st1(a_dbd + zo + (long)R * a.ldp + (c - 1), g);
-          } else if (j < (int)a.ldp) {
-            st1(a_dbd + zo + (long)i * a.ldp + j, 0.f);
-          }
-        }
+        if (a.dbd && qok[qt]) attn_dbd_put(a.dbd, zo, a.ldp, i, j, Ts, g);
       }
-      if (qok[qt] && j0 < (int)a.ldp) st4(a_dS + pro[qt] + j0, make_float4(G[0], G[1], G[2], G[3]));
+      if (qok[qt] && j0 < (int)a.ldp) st4(a.dS + pro[qt] + j0, f4(G));
 #pragma unroll
-      for (int r = 0; r < 4; ++r) G[r] = rnd(a_dS, G[r]);       // dq from the dS the key-side kernels will read
+      for (int r = 0; r < 4; ++r) G[r] = rnd(a.dS, G[r]);       // dq from the dS the key-side kernels will read
       tile_product(Tw, G, fr, fq, C[qt]);
     }
   }
-  if (a.dbd && live && r0w == 0)                      // the head of row 0 the scatter never reaches
-    for (int f = 1 + t; f < Ts; f += NT) st1(a_dbd + zo + (f - 1), 0.f);
+  if (a.dbd && live && r0w == 0) attn_dbd_zero_head(a.dbd, zo, Ts, t, NT);
   __syncthreads();
 #pragma unroll
   for (int qt = 0; qt < QT; ++qt) {
@@ -867,26 +769,23 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_q_long_kernel(const AttnF32B
     const int nqt = live ? max(0, min(16, nq - 16 * qt)) : 0;
     const long orow = ((long)b * T1 + r0w + 16 * qt) * a.ldo + h * ATT_DK;
     if (dq_bf16)
-      reduce_store_ct<NW>(C[qt], X, wave, fr, fq, t, reinterpret_cast<bfbits*>(a.dq) + orow, a.ldo, nqt);
+      reduce_store_ct<NW>(C[qt], X, wave, fr, fq, t, reinterpret_cast<bf16_t*>(a.dq) + orow, a.ldo, nqt);
     else
-      reduce_store_ct<NW>(C[qt], X, wave, fr, fq, t, a.dq + orow, a.ldo, nqt);
+      reduce_store_ct<NW>(C[qt], X, wave, fr, fq, t, reinterpret_cast<float*>(a.dq) + orow, a.ldo, nqt);
   }
 }
 
+// the smallest LDS a long-row launch may have is the reduction scratch of reduce_store_ct; the largest, 160 KB
+template <int NW>
+inline bool long_lds_ok(size_t smem) { return smem <= 160 * 1024 && smem >= (size_t)NW * 64 * 17 * sizeof(float); }
+
 template <typename T, bool REL, int LQ, int NW>
-int launch_fwd_long_q(AttnF32Args a, hipStream_t stream) {
+int launch_fwd_long_q(AttnArgs<T> a, hipStream_t stream) {
   const int nkt = (a.T2 + 15) / 16;
-  const size_t smem = ((size_t)LQ * (nkt * 16 + 4) + NW * 16 * PLD + 2 * NW * LQ) * sizeof(float);
-  if (smem > 160 * 1024 || smem < (size_t)NW * 64 * 17 * sizeof(float)) return EAMD_EUNSUPPORTED;
-  static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_long_kernel<T, REL, LQ, NW>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr_err != hipSuccess) return (int)attr_err;
+  const size_t smem = attn_long_lds(LQ, NW, nkt);
   a.nqb = (a.T1 + LQ - 1) / LQ;
-  const int nz = (a.B * a.H + 7) / 8 * 8;
-  if ((long)a.nqb * nz >= (1L << 31)) return EAMD_EUNSUPPORTED;
-  hipLaunchKernelGGL((attn_fwd_long_kernel<T, REL, LQ, NW>), dim3((unsigned)(a.nqb * nz)), dim3(64 * NW), smem, stream, a, nkt);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
+  if (!long_lds_ok<NW>(smem) || (long)a.nqb * attn_grid(1, a.B, a.H) >= (1L << 31)) return EAMD_EUNSUPPORTED;
+  return attn_launch<&attn_fwd_long_kernel<T, REL, LQ, NW>>(160 * 1024, attn_grid(a.nqb, a.B, a.H), 64 * NW, smem, stream, a, nkt);
 }
 // queries and waves per workgroup.  These kernels are bound by latency, not by their L2 traffic: measured (DESIGN.md §6, item 2,
 // B = 16, forward / query-side backward TFLOP/s) 16 queries x 4 waves give 45 - 49 / 32 - 39 while TWO workgroups share a CU (LDS <= 80 KB:
@@ -896,18 +795,17 @@ int launch_fwd_long_q(AttnF32Args a, hipStream_t stream) {
 // split eight ways: 45 - 48 / 36 up to 1900 keys), six where the tile buffers of eight no longer fit (2048 keys); 8 queries beyond
 // 2048 keys (to 4096: the MFMA tiles run half empty).
 struct LongGeom { int lq, nw; };
-inline LongGeom long_geom(int T1, int T2) {
+inline LongGeom long_geom(int T2) {
   const int nkt = (T2 + 15) / 16;
-  auto bytes = [&](int lq, int nw) { return ((size_t)lq * (nkt * 16 + 4) + nw * 16 * PLD + 2 * nw * lq) * sizeof(float); };
   LongGeom g{16, 4};
-  if (bytes(16, 4) > 160 * 1024) g = LongGeom{8, 4};
-  if (bytes(g.lq, 4) > 80 * 1024) g.nw = bytes(g.lq, 8) <= 160 * 1024 ? 8 : bytes(g.lq, 6) <= 160 * 1024 ? 6 : 4;   // one workgroup per CU: more waves
-  (void)T1;
+  if (attn_long_lds(16, 4, nkt) > 160 * 1024) g = LongGeom{8, 4};
+  if (attn_long_lds(g.lq, 4, nkt) > 80 * 1024)      // one workgroup per CU: more waves
+    g.nw = attn_long_lds(g.lq, 8, nkt) <= 160 * 1024 ? 8 : attn_long_lds(g.lq, 6, nkt) <= 160 * 1024 ? 6 : 4;
   return g;
 }
 template <typename T, bool REL>
-int launch_fwd_long(AttnF32Args a, hipStream_t stream) {
-  const LongGeom g = long_geom(a.T1, a.T2);
+int launch_fwd_long(const AttnArgs<T>& a, hipStream_t stream) {
+  const LongGeom g = long_geom(a.T2);
   if (g.lq == 16) return g.nw == 8 ? launch_fwd_long_q<T, REL, 16, 8>(a, stream) : g.nw == 6 ? launch_fwd_long_q<T, REL, 16, 6>(a, stream)
                                                                                                : launch_fwd_long_q<T, REL, 16, 4>(a, stream);
   return g.nw == 8 ? launch_fwd_long_q<T, REL, 8, 8>(a, stream) : g.nw == 6 ? launch_fwd_long_q<T, REL, 8, 6>(a, stream)
@@ -915,85 +813,40 @@ int launch_fwd_long(AttnF32Args a, hipStream_t stream) {
 }
 
 template <typename T, int LQ, int NW>
-int launch_bwd_long_q(AttnF32BwdArgs a, int dq_bf16, hipStream_t stream) {
+int launch_bwd_long_q(AttnBwdArgs<T> a, int dq_bf16, hipStream_t stream) {
   const int nkt = (a.T2 + 15) / 16;
-  const size_t smem = ((size_t)LQ * (nkt * 16 + 4) + NW * 16 * PLD + 2 * NW * LQ) * sizeof(float);
-  if (smem > 160 * 1024 || smem < (size_t)NW * 64 * 17 * sizeof(float)) return EAMD_EUNSUPPORTED;
-  static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_long_kernel<T, LQ, NW>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (attr_err != hipSuccess) return (int)attr_err;
+  const size_t smem = attn_long_lds(LQ, NW, nkt);
   a.nqb = (a.T1 + LQ - 1) / LQ;
-  const int nz = (a.B * a.H + 7) / 8 * 8;
-  if ((long)a.nqb * nz >= (1L << 31)) return EAMD_EUNSUPPORTED;
-  hipLaunchKernelGGL((attn_bwd_q_long_kernel<T, LQ, NW>), dim3((unsigned)(a.nqb * nz)), dim3(64 * NW), smem, stream, a, nkt, dq_bf16);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
+  if (!long_lds_ok<NW>(smem) || (long)a.nqb * attn_grid(1, a.B, a.H) >= (1L << 31)) return EAMD_EUNSUPPORTED;
+  return attn_launch<&attn_bwd_q_long_kernel<T, LQ, NW>>(160 * 1024, attn_grid(a.nqb, a.B, a.H), 64 * NW, smem, stream, a, nkt, dq_bf16);
 }
 template <typename T>
-int launch_bwd_long(AttnF32BwdArgs a, int dq_bf16, hipStream_t stream) {
-  const LongGeom g = long_geom(a.T1, a.T2);
+int launch_bwd_long(const AttnBwdArgs<T>& a, int dq_bf16, hipStream_t stream) {
+  const LongGeom g = long_geom(a.T2);
   // (six waves: measured SLOWER than four in this kernel at 2048 keys - 1058 against 760 us - while the forward gains, 639 against 820)
   if (g.lq == 16) return g.nw == 8 ? launch_bwd_long_q<T, 16, 8>(a, dq_bf16, stream) : launch_bwd_long_q<T, 16, 4>(a, dq_bf16, stream);
   return g.nw == 8 ? launch_bwd_long_q<T, 8, 8>(a, dq_bf16, stream) : launch_bwd_long_q<T, 8, 4>(a, dq_bf16, stream);
 }
 
+// short rows: the V / K panel decides the LDS (the score matrix X is smaller)
 template <bool REL, int NKT>
-int launch_fwd(const AttnF32Args& a, size_t smem, hipStream_t stream) {
-  static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_fwd_kernel<REL, NKT>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, NKT * 16 * PLD * 4);
-  if (attr_err != hipSuccess) return (int)attr_err;
-  const int nz = (a.B * a.H + 7) / 8 * 8;
-  hipLaunchKernelGGL((attn_f32_fwd_kernel<REL, NKT>), dim3((unsigned)(a.nqb * nz)), dim3(256), smem, stream, a);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
+int launch_fwd(const AttnArgs<float>& a, hipStream_t stream) {
+  constexpr int smem = NKT * 16 * PLD * sizeof(float);
+  return attn_launch<&attn_f32_fwd_kernel<REL, NKT>>(smem, attn_grid(a.nqb, a.B, a.H), 256, smem, stream, a);
 }
-
 template <int NKT>
-int launch_bwd(const AttnF32BwdArgs& a, hipStream_t stream) {
-  static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_bwd_q_kernel<NKT>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, NKT * 16 * PLD * 4);
-  if (attr_err != hipSuccess) return (int)attr_err;
-  const int nz = (a.B * a.H + 7) / 8 * 8;
-  hipLaunchKernelGGL((attn_f32_bwd_q_kernel<NKT>), dim3((unsigned)(a.nqb * nz)), dim3(256),
-                     (size_t)NKT * 16 * PLD * sizeof(float), stream, a);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
+int launch_bwd(const AttnBwdArgs<float>& a, hipStream_t stream) {
+  constexpr int smem = NKT * 16 * PLD * sizeof(float);
+  return attn_launch<&attn_f32_bwd_q_kernel<NKT>>(smem, attn_grid(a.nqb, a.B, a.H), 256, smem, stream, a);
 }
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
-// bf16-operand mode, rows of 513 .. ATT_LONG_MAXK keys: called by eamd_attn_fwd / eamd_attn_bwd_q (attn_fused.hip), which
-// have validated the operands; pointers are bf16 tensors, leading dimensions in elements
-int eamd_attn_long_fwd_bf16(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v,
-                            int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mb, int64_t mi,
-                            void* P, int64_t ldp, void* ctx, int64_t ldc, int B, int H, int T1, int T2, float scale, void* Pd,
-                            float drop_p, const uint64_t* drop_step, uint64_t drop_salt, const int32_t* shift_len, void* stream) {
-  if (T2 > ATT_LONG_MAXK || ldq % 4 || ldk % 4 || ldv % 4 || ldc % 4 || ldp % 4) return EAMD_EUNSUPPORTED;
-  AttnF32Args a;
-  a.qu = (const float*)qu; a.qv = (const float*)qv; a.k = (const float*)k; a.v = (const float*)v; a.pos = (const float*)pos;
-  a.mask = mask; a.P = (float*)P; a.ctx = (float*)ctx;
-  a.ldq = ldq; a.ldqv = ldqv; a.ldk = ldk; a.ldv = ldv; a.ldpos = ldpos; a.ldc = ldc; a.ldp = ldp; a.mb = mb; a.mi = mi;
-  a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nqb = 0; a.scale = scale;
-  a.Pd = (float*)Pd; a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt;
-  a.tshift = shift_len;
-  return pos ? launch_fwd_long<bfbits, true>(a, (hipStream_t)stream) : launch_fwd_long<bfbits, false>(a, (hipStream_t)stream);
+int eamd_attn_long_fwd_bf16(const AttnArgs<bf16_t>& a, hipStream_t stream) {
+  return a.pos ? launch_fwd_long<bf16_t, true>(a, stream) : launch_fwd_long<bf16_t, false>(a, stream);
 }
-
-int eamd_attn_long_bwd_q_bf16(const void* dctx, int64_t ldd, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* P,
-                              int64_t ldp, void* dS, void* dbd, void* dq, int64_t ldo, int dq_is_bf16, int B, int H, int T1, int T2,
-                              float scale, float drop_p, const uint64_t* drop_step, uint64_t drop_salt, const int32_t* shift_len,
-                              void* stream) {
-  if (T2 > ATT_LONG_MAXK || ldd % 4 || ldk % 4 || ldv % 4 || ldp % 4 || ldo % 4) return EAMD_EUNSUPPORTED;
-  AttnF32BwdArgs a;
-  a.dctx = (const float*)dctx; a.k = (const float*)k; a.v = (const float*)v; a.P = (const float*)P;
-  a.dS = (float*)dS; a.dbd = (float*)dbd; a.dq = (float*)dq;
-  a.ldd = ldd; a.ldk = ldk; a.ldv = ldv; a.ldp = ldp; a.ldo = ldo;
-  a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nqb = 0; a.scale = scale;
-  a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt;
-  a.tshift = shift_len;
-  return launch_bwd_long<bfbits>(a, dq_is_bf16, (hipStream_t)stream);
+int eamd_attn_long_bwd_q_bf16(const AttnBwdArgs<bf16_t>& a, int dq_bf16, hipStream_t stream) {
+  return launch_bwd_long<bf16_t>(a, dq_bf16, stream);
 }
 
 extern "C" int eamd_attn_fwd_f32(const float* qu, int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk,
@@ -1001,49 +854,27 @@ extern "C" int eamd_attn_fwd_f32(const float* qu, int64_t ldq, const float* qv, 
                                  int64_t mask_bstride, int64_t mask_qstride, float* P, int64_t ldp, float* ctx,
                                  int64_t ldc, int B, int H, int T1, int T2, int dk, float scale, float* Pd, float drop_p,
                                  const uint64_t* drop_step, uint64_t drop_salt, const int32_t* shift_len, void* stream) {
-  if (!qu || !k || !v || !P || !ctx || B <= 0 || H <= 0 || T1 <= 0 || T2 <= 0) return EAMD_EINVAL;
-  if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && (!Pd || !drop_step || !al16(Pd)))) return EAMD_EINVAL;
-  if ((pos == nullptr) != (qv == nullptr)) return EAMD_EINVAL;
-  if (dk != ATT_DK || T2 > ATT_LONG_MAXK || (pos && T1 != T2)) return EAMD_EUNSUPPORTED;
-  if (ldq % 4 || ldk % 4 || ldv % 4 || ldc % 4 || ldp % 4 || ldp < T2 || (pos && (ldqv % 4 || ldpos % 4)))
-    return EAMD_EUNSUPPORTED;
-  if (!al16(qu) || !al16(k) || !al16(v) || !al16(P) || !al16(ctx) || (pos && (!al16(qv) || !al16(pos))))
-    return EAMD_EUNSUPPORTED;
-  if ((long)B * H * ((T1 + 63) / 64) >= (1L << 28)) return EAMD_EUNSUPPORTED;
-  AttnF32Args a;
-  a.qu = qu; a.qv = qv; a.k = k; a.v = v; a.pos = pos; a.mask = mask; a.P = P; a.ctx = ctx;
-  a.ldq = ldq; a.ldqv = ldqv; a.ldk = ldk; a.ldv = ldv; a.ldpos = ldpos; a.ldc = ldc; a.ldp = ldp;
-  a.mb = mask_bstride; a.mi = mask_qstride;
-  a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nqb = (T1 + 63) / 64; a.scale = scale;
-  a.Pd = Pd; a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt;
-  a.tshift = shift_len;
-  if (T2 > ATT_MAXK) return pos ? launch_fwd_long<float, true>(a, (hipStream_t)stream) : launch_fwd_long<float, false>(a, (hipStream_t)stream);
-  const int nkt = T2 <= 128 ? 8 : T2 <= 256 ? 16 : 32;               // key tiles of 16 the instantiation covers
-  const size_t smem = (size_t)nkt * 16 * PLD * sizeof(float);        // V panel (the score matrix X is smaller)
+  const AttnArgs<float> a = attn_args<float>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, P, ldp,
+                                             ctx, ldc, B, H, T1, T2, scale, Pd, drop_p, drop_step, drop_salt, shift_len);
+  if (const int rc = attn_check_fwd(a, dk)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (pos) return nkt == 8 ? launch_fwd<true, 8>(a, smem, s) : nkt == 16 ? launch_fwd<true, 16>(a, smem, s) : launch_fwd<true, 32>(a, smem, s);
-  return nkt == 8 ? launch_fwd<false, 8>(a, smem, s) : nkt == 16 ? launch_fwd<false, 16>(a, smem, s) : launch_fwd<false, 32>(a, smem, s);
+  if (T2 > ATT_MAXK) return pos ? launch_fwd_long<float, true>(a, s) : launch_fwd_long<float, false>(a, s);
+  const int nkt = attn_nkt(T2);
+  if (pos) return nkt == 8 ? launch_fwd<true, 8>(a, s) : nkt == 16 ? launch_fwd<true, 16>(a, s) : launch_fwd<true, 32>(a, s);
+  return nkt == 8 ? launch_fwd<false, 8>(a, s) : nkt == 16 ? launch_fwd<false, 16>(a, s) : launch_fwd<false, 32>(a, s);
 }
 
 extern "C" int eamd_attn_bwd_q_f32(const float* dctx, int64_t ldd, const float* k, int64_t ldk, const float* v, int64_t ldv,
                                    const float* P, int64_t ldp, float* dS, float* dbd, float* dq, int64_t ldo, int B, int H,
                                    int T1, int T2, int dk, float scale, float drop_p, const uint64_t* drop_step,
                                    uint64_t drop_salt, const int32_t* shift_len, void* stream) {
-  if (!dctx || !k || !v || !P || !dS || !dq || B <= 0 || H <= 0 || T1 <= 0 || T2 <= 0) return EAMD_EINVAL;
-  if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && !drop_step)) return EAMD_EINVAL;
-  if (dk != ATT_DK || T2 > ATT_LONG_MAXK || (dbd && T1 != T2)) return EAMD_EUNSUPPORTED;
-  if (ldd % 4 || ldk % 4 || ldv % 4 || ldp % 4 || ldp < T2 || ldo % 4) return EAMD_EUNSUPPORTED;
-  if (!al16(dctx) || !al16(k) || !al16(v) || !al16(P) || !al16(dS) || !al16(dq)) return EAMD_EUNSUPPORTED;
-  if ((long)B * H * ((T1 + 63) / 64) >= (1L << 28)) return EAMD_EUNSUPPORTED;
-  AttnF32BwdArgs a;
-  a.dctx = dctx; a.k = k; a.v = v; a.P = P; a.dS = dS; a.dbd = dbd; a.dq = dq;
-  a.ldd = ldd; a.ldk = ldk; a.ldv = ldv; a.ldp = ldp; a.ldo = ldo;
-  a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nqb = (T1 + 63) / 64; a.scale = scale;
-  a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt;
-  a.tshift = shift_len;
-  if (T2 > ATT_MAXK) return launch_bwd_long<float>(a, 0, (hipStream_t)stream);
-  return T2 <= 128 ? launch_bwd<8>(a, (hipStream_t)stream) : T2 <= 256 ? launch_bwd<16>(a, (hipStream_t)stream)
-                                                                         : launch_bwd<32>(a, (hipStream_t)stream);
+  const AttnBwdArgs<float> a = attn_bwd_args<float>(dctx, ldd, k, ldk, v, ldv, P, ldp, dS, dbd, dq, ldo, B, H, T1, T2, scale, drop_p,
+                                                    drop_step, drop_salt, shift_len);
+  if (const int rc = attn_check_bwd(a, dk, 0)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (T2 > ATT_MAXK) return launch_bwd_long<float>(a, 0, s);
+  const int nkt = attn_nkt(T2);
+  return nkt == 8 ? launch_bwd<8>(a, s) : nkt == 16 ? launch_bwd<16>(a, s) : launch_bwd<32>(a, s);
 }
 
 // ---- backward, key side: dV = Pd^T dctx, dK = dS^T qu and (relative positions) dpos += dbd^T qv in one launch ----
@@ -1104,12 +935,11 @@ __global__ __launch_bounds__(256, 2) void attn_f32_bwd_kv_kernel(const AttnF32Kv
   __shared__ __attribute__((aligned(16))) float sX[64 * KLD];     // [query][channel] tile
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nkb) * 8 + xcd;            // z = h * B + b
+  const int z = attn_xcd_pair(blockIdx.x, a.nkb);  // z = h * B + b
   if (z >= a.B * a.H) return;                      // whole workgroup
   const int h = z / a.B, b = z % a.B;
   const int T1 = a.T1, T2 = a.T2;
-  const int j0 = (jb % a.nkb) * 64;                // first key of the workgroup
+  const int j0 = attn_xcd_block(blockIdx.x, a.nkb) * 64;                         // first key of the workgroup
   const long zo = (long)z * T1 * a.ldp;
   const float* Wsrc[3] = {a.Pd + zo, a.dS + zo, REL ? a.dbd + zo : nullptr};
   const float* Xsrc[3] = {a.dctx + (long)b * T1 * a.ldd + h * ATT_DK, a.qu + (long)b * T1 * a.ldq + h * ATT_DK,
@@ -1178,10 +1008,9 @@ extern "C" int eamd_attn_bwd_kv_f32(const float* Pd, const float* dS, const floa
   a.ldp = ldp; a.ldd = ldd; a.ldq = ldq; a.ldqv = ldqv; a.ldo = ldo; a.ldpos = ldpos;
   a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nkb = (T2 + 63) / 64;
   if ((long)B * H * a.nkb >= (1L << 28)) return EAMD_EUNSUPPORTED;
-  const int nz = (B * H + 7) / 8 * 8;
   hipStream_t s = (hipStream_t)stream;
-  if (dbd) hipLaunchKernelGGL((attn_f32_bwd_kv_kernel<true>), dim3((unsigned)(a.nkb * nz)), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((attn_f32_bwd_kv_kernel<false>), dim3((unsigned)(a.nkb * nz)), dim3(256), 0, s, a);
+  if (dbd) hipLaunchKernelGGL((attn_f32_bwd_kv_kernel<true>), dim3(attn_grid(a.nkb, B, H)), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_f32_bwd_kv_kernel<false>), dim3(attn_grid(a.nkb, B, H)), dim3(256), 0, s, a);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }

@@ -15,33 +15,13 @@
 //     {0..3}, then 32 s + 16 + 4 q + {0..3}" the probabilities of tiles 2s, 2s+1 ARE the MFMA operand.  The V fragments
 //     of the same order come from ds_read_b64_tr_b16 on a V panel staged over X once the scores are in registers;
 //   * the context is accumulated as C^T = V^T P^T, which leaves four adjacent channels per lane (8-byte stores).
+// Shared with attn_f32.hip through attn_common.h: the argument structs, attn_geom, attn_shift_len (forward), the 16-lane-group
+// reductions, the XCD dealing of the key-side kernel, st4 / f4 in its stores, and on the host the argument checks and the launch.
+// The rel_shift stores, mask, softmax, dropout and the bf16 packing of the two query-side kernels are written out here.
 #include "gemm_bf16_common.h"
+#include "attn_common.h"
 
 namespace {
-
-constexpr int ATT_DK = 64;
-constexpr int ATT_MAXK = 512;                 // keys per row: 8 / 16 / 32 accumulator tiles of 16 (32: one workgroup per CU)
-
-struct AttnArgs {
-  const bf16_t* qu; const bf16_t* qv; const bf16_t* k; const bf16_t* v; const bf16_t* pos;
-  const unsigned char* mask;
-  bf16_t* P; bf16_t* ctx;
-  long ldq, ldqv, ldk, ldv, ldpos, ldc, ldp, mb, mi;
-  int B, H, T1, T2, nqb;
-  float scale;
-  // attention dropout (attention.py:91): Pd = dropout(P) feeds the context; mask index = element index in P
-  bf16_t* Pd; float drop_p; const unsigned long long* drop_step; unsigned long long drop_salt;
-  const int* tshift;     // device scalar: length the legacy rel_shift works on (NULL: T2) - see eamd_attn_fwd
-};
-
-__device__ __forceinline__ float xor_max16_32(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16));
-  return fmaxf(v, __shfl_xor(v, 32));
-}
-__device__ __forceinline__ float xor_sum16_32(float v) {
-  v += __shfl_xor(v, 16);
-  return v + __shfl_xor(v, 32);
-}
 
 // NKT = key tiles of 16 the instantiation covers (T2 <= 16 NKT).  Every loop over tiles is fully unrolled and free of
 // branches: rows past T2 / T1 are clamped re-reads whose scores are masked / never stored.
@@ -93,32 +73,26 @@ __device__ __forceinline__ float dot8_bf16(uint4 x, uint4 y) {
   return s;
 }
 
+// (Of attn_common.h's device pieces the two query-side kernels below use the argument structs, attn_geom, the reductions and - the
+// forward - attn_shift_len; the rest stays written out: as shared functions it changed the register allocation or the
+// instructions of these instantiations - DESIGN.md, "What the attention kernels share".)
 template <bool REL, int NKT>
-__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_fwd_kernel(const AttnArgs a) {
+__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_fwd_kernel(const AttnArgs<bf16_t> a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   constexpr int XLD = NKT * 16 + 4;
   constexpr int TPW = NKT / 4;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  // (batch, head) pairs are dealt to the XCDs in contiguous runs: the query blocks of one pair share an L2
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nqb) * 8 + xcd;            // z = h * B + b, as the score tensors are laid out
-  const bool live = z < a.B * a.H;                 // whole workgroup; dead ones only keep the barriers company
-  const int zz = live ? z : 0;
-  const int h = zz / a.B, b = zz % a.B;
+  const AttnGeom g = attn_geom(blockIdx.x, a.nqb, a.B, a.H, a.T1, 64);
+  const bool live = g.live;
+  const int zz = g.zz, h = g.h, b = g.b, r0w = g.r0w, nq = g.nq;
   const int T1 = a.T1, T2 = a.T2;
-  const int r0w = min((jb % a.nqb) * 64, T1 - 1);  // first query of the workgroup
-  const int nq = T1 - r0w;                         // its queries (up to 64)
   const int r0 = r0w + wave * 16;                  // first query this wave owns in the softmax / context phases
   const bool active = live && r0 < T1;
   const int qi = min(r0 + fr, T1 - 1);             // this lane's query (clamped lanes are never stored)
 
   float* X = reinterpret_cast<float*>(smem_raw);
-  // Ts: the length the legacy rel_shift is taken over.  A batch padded beyond its own longest utterance (shape-bucketed
-  // graphs) passes that utterance's length here: the shift then maps bd exactly as the reference's T' x T' matrix does;
-  // keys from Ts on are masked by the caller's mask, and the score matrix is cleared first so that the rows / columns the
-  // shift no longer reaches hold zeros instead of stale LDS.
-  const int Ts = (REL && a.tshift) ? min(max(a.tshift[0], 1), T2) : T2;
+  const int Ts = REL ? attn_shift_len(a.tshift, T2) : T2;
   if (REL) {
     if (Ts < T2) {
       for (int e = t; e < 64 * XLD; e += 256) X[e] = 0.f;
@@ -214,7 +188,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_fwd_kernel(const A
         mx = fmaxf(mx, x);
       }
     }
-    mx = xor_max16_32(mx);
+    mx = attn_max16_32(mx);
     const bool dead = mx == -INFINITY;              // every key masked: softmax(min, ...) = uniform, then masked_fill(0)
     float sum = 0.f;
 #pragma unroll
@@ -225,7 +199,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_fwd_kernel(const A
         S[kt][r] = e;
         sum += e;
       }
-    sum = xor_sum16_32(sum);
+    sum = attn_sum16_32(sum);
     const float inv = dead ? 0.f : 1.f / sum;
     const bool qok = r0 + fr < T1;
     const long pro = ((long)zz * T1 + qi) * a.ldp;
@@ -304,31 +278,32 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_fwd_kernel(const A
 // GEMMs (dK = dS^T q, and with relative positions dqv / dpos from the inverse rel_shift scatter dbd, written here
 // element by element exactly as eamd_softmax_bwd does) and dq^T = K^T dS^T from the K panel in LDS - the context
 // product of the forward with K in place of V.  reference: autograd of attention.py:63-114, :141-206.
-struct AttnBwdArgs {
+// (this kernel takes its arguments in its own field order, dq_bf16 beside nqb: with the shared struct's order, which the fp32
+// kernel needs, the 16-tile instantiation gained 48 VALU instructions and ran 3 - 4 % slower)
+struct AttnBwdArgs16 {
   const bf16_t* dctx; const bf16_t* k; const bf16_t* v; const bf16_t* P;
   bf16_t* dS; bf16_t* dbd; void* dq;
   long ldd, ldk, ldv, ldp, ldo;
   int B, H, T1, T2, nqb, dq_bf16;
   float scale;
-  float drop_p; const unsigned long long* drop_step; unsigned long long drop_salt;   // the forward's attention dropout
+  float drop_p; const unsigned long long* drop_step; unsigned long long drop_salt;
   const int* tshift;
 };
+// launch_attn_bwd copies AttnBwdArgs<bf16_t> field by field: a field added there must be added here, and the sizes say so
+static_assert(sizeof(AttnBwdArgs16) == sizeof(AttnBwdArgs<bf16_t>) && sizeof(AttnBwdArgs16) == 12 * 8 + 8 * 4 + 3 * 8,
+              "AttnBwdArgs16 = AttnBwdArgs<bf16_t> + dq_bf16 (which fills the padding behind nqb)");
 
 template <int NKT>
-__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_bwd_q_kernel(const AttnBwdArgs a) {
+__global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_bwd_q_kernel(const AttnBwdArgs16 a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nqb) * 8 + xcd;
-  const bool live = z < a.B * a.H;
-  const int zz = live ? z : 0;
-  const int h = zz / a.B, b = zz % a.B;
+  const AttnGeom g = attn_geom(blockIdx.x, a.nqb, a.B, a.H, a.T1, 64);
+  const bool live = g.live;
+  const int zz = g.zz, h = g.h, b = g.b, r0w = g.r0w, nq = g.nq;
   constexpr int XLD = NKT * 16 + 4;
   const int T1 = a.T1, T2 = a.T2;
-  const int Ts = (a.dbd && a.tshift) ? min(max(a.tshift[0], 1), T2) : T2;      // rel_shift length (see the forward kernel)
-  const int r0w = min((jb % a.nqb) * 64, T1 - 1);
-  const int nq = T1 - r0w;
+  const int Ts = (a.dbd && a.tshift) ? min(max(a.tshift[0], 1), T2) : T2;      // (attn_shift_len; as the call, the two tests compile to other scalar code here)
   const int r0 = r0w + wave * 16;
   const bool active = live && r0 < T1;
   const int qi = min(r0 + fr, T1 - 1);
@@ -381,7 +356,7 @@ __global__ __launch_bounds__(256, NKT > 16 ? 1 : 2) void attn_bwd_q_kernel(const
     for (int kt = 0; kt < NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) if (kt * 16 + fq * 4 + r < T2) s += unpack(kt, r) * S[kt][r];
-    s = xor_sum16_32(s);
+    s = attn_sum16_32(s);
     const long zo = (long)zz * T1 * a.ldp;
     bf16_t* srow = a.dS + zo + (long)qi * a.ldp;
     const int i = r0 + fr;
@@ -518,12 +493,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const AttnKvArgs a)
   __shared__ __attribute__((aligned(16))) bf16_t sX[64 * 64];     // [query][channel] tile
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
-  const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-  const int z = (jb / a.nkb) * 8 + xcd;            // z = h * B + b
+  const int z = attn_xcd_pair(blockIdx.x, a.nkb);  // z = h * B + b
   if (z >= a.B * a.H) return;                      // whole workgroup
   const int h = z / a.B, b = z % a.B;
   const int T1 = a.T1, T2 = a.T2;
-  const int j0 = (jb % a.nkb) * 64;                // first key of the workgroup
+  const int j0 = attn_xcd_block(blockIdx.x, a.nkb) * 64;      // first key of the workgroup
   const long zo = (long)z * T1 * a.ldp;
   const bf16_t* W0 = a.Pd + zo;
   const bf16_t* W1 = a.dS + zo;
@@ -556,112 +530,54 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kv_kernel(const AttnKvArgs a)
     const long ro = ((long)b * T2 + j) * a.ldo + h * ATT_DK + 4 * fq;
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
-      uint2 o;
-      o.x = (unsigned)eamd_f2bf(acc[0][ct][0]) | ((unsigned)eamd_f2bf(acc[0][ct][1]) << 16);
-      o.y = (unsigned)eamd_f2bf(acc[0][ct][2]) | ((unsigned)eamd_f2bf(acc[0][ct][3]) << 16);
-      *reinterpret_cast<uint2*>(a.dv + ro + ct * 16) = o;
-      o.x = (unsigned)eamd_f2bf(acc[1][ct][0]) | ((unsigned)eamd_f2bf(acc[1][ct][1]) << 16);
-      o.y = (unsigned)eamd_f2bf(acc[1][ct][2]) | ((unsigned)eamd_f2bf(acc[1][ct][3]) << 16);
-      *reinterpret_cast<uint2*>(a.dk + ro + ct * 16) = o;
+      st4(a.dv + ro + ct * 16, f4(acc[0][ct]));
+      st4(a.dk + ro + ct * 16, f4(acc[1][ct]));
     }
   }
 }
 
-template <int NKT>
-int launch_attn_bwd(const AttnBwdArgs& a, hipStream_t stream) {
-  const int nz = (a.B * a.H + 7) / 8 * 8;
-  static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<NKT>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, NKT > 16 ? 144 * 1024 : 72 * 1024);
-  if (attr_err != hipSuccess) return (int)attr_err;
-  hipLaunchKernelGGL((attn_bwd_q_kernel<NKT>), dim3((unsigned)(a.nqb * nz)), dim3(256), (size_t)64 * (NKT * 16 + 4) * sizeof(float),
-                     stream, a);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
-}
-
+// short rows: the score matrix X decides the LDS (the V / K panel staged over it is smaller)
 template <bool REL, int NKT>
-int launch_attn(const AttnArgs& a, size_t smem, hipStream_t stream) {
-  static const hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<REL, NKT>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, NKT > 16 ? 144 * 1024 : 72 * 1024);
-  if (attr_err != hipSuccess) return (int)attr_err;
-  const int nz = (a.B * a.H + 7) / 8 * 8;
-  hipLaunchKernelGGL((attn_fwd_kernel<REL, NKT>), dim3((unsigned)(a.nqb * nz)), dim3(256), smem, stream, a);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
+int launch_attn(const AttnArgs<bf16_t>& a, hipStream_t stream) {
+  return attn_launch<&attn_fwd_kernel<REL, NKT>>(NKT > 16 ? 144 * 1024 : 72 * 1024, attn_grid(a.nqb, a.B, a.H), 256,
+                                                 (size_t)64 * (NKT * 16 + 4) * sizeof(float), stream, a);
 }
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <int NKT>
+int launch_attn_bwd(const AttnBwdArgs<bf16_t>& s, int dq_bf16, hipStream_t stream) {
+  const AttnBwdArgs16 a = {s.dctx, s.k, s.v, s.P, s.dS, s.dbd, s.dq, s.ldd, s.ldk, s.ldv, s.ldp, s.ldo, s.B, s.H, s.T1, s.T2, s.nqb,
+                           dq_bf16, s.scale, s.drop_p, s.drop_step, s.drop_salt, s.tshift};
+  return attn_launch<&attn_bwd_q_kernel<NKT>>(NKT > 16 ? 144 * 1024 : 72 * 1024, attn_grid(a.nqb, a.B, a.H), 256,
+                                              (size_t)64 * (NKT * 16 + 4) * sizeof(float), stream, a);
+}
 
 }  // namespace
-
-int eamd_attn_long_fwd_bf16(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v,
-                            int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mb, int64_t mi,
-                            void* P, int64_t ldp, void* ctx, int64_t ldc, int B, int H, int T1, int T2, float scale, void* Pd,
-                            float drop_p, const uint64_t* drop_step, uint64_t drop_salt, const int32_t* shift_len, void* stream);   // attn_f32.hip
-int eamd_attn_long_bwd_q_bf16(const void* dctx, int64_t ldd, const void* k, int64_t ldk, const void* v, int64_t ldv, const void* P,
-                              int64_t ldp, void* dS, void* dbd, void* dq, int64_t ldo, int dq_is_bf16, int B, int H, int T1, int T2,
-                              float scale, float drop_p, const uint64_t* drop_step, uint64_t drop_salt, const int32_t* shift_len,
-                              void* stream);
 
 extern "C" int eamd_attn_fwd(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk,
                              const void* v, int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask,
                              int64_t mask_bstride, int64_t mask_qstride, void* P_bf16, int64_t ldp, void* ctx_bf16,
                              int64_t ldc, int B, int H, int T1, int T2, int dk, float scale, void* Pd_bf16, float drop_p,
                              const uint64_t* drop_step, uint64_t drop_salt, const int32_t* shift_len, void* stream) {
-  if (!qu || !k || !v || !P_bf16 || !ctx_bf16 || B <= 0 || H <= 0 || T1 <= 0 || T2 <= 0) return EAMD_EINVAL;
-  if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && (!Pd_bf16 || !drop_step || !al16(Pd_bf16)))) return EAMD_EINVAL;
-  if ((pos == nullptr) != (qv == nullptr)) return EAMD_EINVAL;
-  if (dk != ATT_DK || (pos && T1 != T2)) return EAMD_EUNSUPPORTED;
-  if (ldq % 8 || ldk % 8 || ldv % 8 || ldc % 4 || ldp % 8 || ldp < T2 || (pos && (ldqv % 8 || ldpos % 8)))
-    return EAMD_EUNSUPPORTED;
-  if (!al16(qu) || !al16(k) || !al16(v) || !al16(P_bf16) || (reinterpret_cast<uintptr_t>(ctx_bf16) & 7) ||
-      (pos && (!al16(qv) || !al16(pos))))
-    return EAMD_EUNSUPPORTED;
-  if ((long)B * H * ((T1 + 15) / 16) >= (1L << 28)) return EAMD_EUNSUPPORTED;
-  if (T2 > ATT_MAXK)            // rows of 513 .. 2048 keys: the key-split long-row kernels (attn_f32.hip), operands widened on load
-    return eamd_attn_long_fwd_bf16(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, P_bf16, ldp,
-                                   ctx_bf16, ldc, B, H, T1, T2, scale, Pd_bf16, drop_p, drop_step, drop_salt, shift_len, stream);
-  AttnArgs a;
-  a.qu = (const bf16_t*)qu; a.qv = (const bf16_t*)qv; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v;
-  a.pos = (const bf16_t*)pos; a.mask = mask; a.P = (bf16_t*)P_bf16; a.ctx = (bf16_t*)ctx_bf16;
-  a.ldq = ldq; a.ldqv = ldqv; a.ldk = ldk; a.ldv = ldv; a.ldpos = ldpos; a.ldc = ldc; a.ldp = ldp;
-  a.mb = mask_bstride; a.mi = mask_qstride;
-  a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nqb = (T1 + 63) / 64; a.scale = scale;
-  a.Pd = (bf16_t*)Pd_bf16; a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt;
-  a.tshift = shift_len;
-  const int nkt = T2 <= 128 ? 8 : T2 <= 256 ? 16 : 32;               // key tiles of 16 the instantiation covers
-  const size_t smem = (size_t)64 * (nkt * 16 + 4) * sizeof(float);   // score matrix X (the V panel staged over it is smaller)
+  const AttnArgs<bf16_t> a = attn_args<bf16_t>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, P_bf16,
+                                               ldp, ctx_bf16, ldc, B, H, T1, T2, scale, Pd_bf16, drop_p, drop_step, drop_salt, shift_len);
+  if (const int rc = attn_check_fwd(a, dk)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (pos)
-    return nkt == 8 ? launch_attn<true, 8>(a, smem, s) : nkt == 16 ? launch_attn<true, 16>(a, smem, s) : launch_attn<true, 32>(a, smem, s);
-  return nkt == 8 ? launch_attn<false, 8>(a, smem, s) : nkt == 16 ? launch_attn<false, 16>(a, smem, s)
-                                                                   : launch_attn<false, 32>(a, smem, s);
+  if (T2 > ATT_MAXK) return eamd_attn_long_fwd_bf16(a, s);      // rows of 513 .. 4096 keys: the key-split long-row kernels (attn_f32.hip)
+  const int nkt = attn_nkt(T2);
+  if (pos) return nkt == 8 ? launch_attn<true, 8>(a, s) : nkt == 16 ? launch_attn<true, 16>(a, s) : launch_attn<true, 32>(a, s);
+  return nkt == 8 ? launch_attn<false, 8>(a, s) : nkt == 16 ? launch_attn<false, 16>(a, s) : launch_attn<false, 32>(a, s);
 }
 
 extern "C" int eamd_attn_bwd_q(const void* dctx, int64_t ldd, const void* k, int64_t ldk, const void* v, int64_t ldv,
                                const void* P_bf16, int64_t ldp, void* dS_bf16, void* dbd_bf16, void* dq, int64_t ldo,
                                int dq_is_bf16, int B, int H, int T1, int T2, int dk, float scale, float drop_p,
                                const uint64_t* drop_step, uint64_t drop_salt, const int32_t* shift_len, void* stream) {
-  if (!dctx || !k || !v || !P_bf16 || !dS_bf16 || !dq || B <= 0 || H <= 0 || T1 <= 0 || T2 <= 0) return EAMD_EINVAL;
-  if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && !drop_step)) return EAMD_EINVAL;
-  if (dk != ATT_DK || (dbd_bf16 && T1 != T2)) return EAMD_EUNSUPPORTED;
-  if (ldd % 8 || ldk % 8 || ldv % 8 || ldp % 8 || ldp < T2 || ldo % 4) return EAMD_EUNSUPPORTED;
-  if (!al16(dctx) || !al16(k) || !al16(v) || !al16(P_bf16) || !al16(dS_bf16) ||
-      (reinterpret_cast<uintptr_t>(dq) & (dq_is_bf16 ? 7 : 15)))
-    return EAMD_EUNSUPPORTED;
-  if ((long)B * H * ((T1 + 15) / 16) >= (1L << 28)) return EAMD_EUNSUPPORTED;
-  if (T2 > ATT_MAXK)
-    return eamd_attn_long_bwd_q_bf16(dctx, ldd, k, ldk, v, ldv, P_bf16, ldp, dS_bf16, dbd_bf16, dq, ldo, dq_is_bf16, B, H, T1, T2,
-                                     scale, drop_p, drop_step, drop_salt, shift_len, stream);
-  AttnBwdArgs a;
-  a.dctx = (const bf16_t*)dctx; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.P = (const bf16_t*)P_bf16;
-  a.dS = (bf16_t*)dS_bf16; a.dbd = (bf16_t*)dbd_bf16; a.dq = dq;
-  a.ldd = ldd; a.ldk = ldk; a.ldv = ldv; a.ldp = ldp; a.ldo = ldo;
-  a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nqb = (T1 + 63) / 64; a.dq_bf16 = dq_is_bf16; a.scale = scale;
-  a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt;
-  a.tshift = shift_len;
-  return T2 <= 128 ? launch_attn_bwd<8>(a, (hipStream_t)stream) : T2 <= 256 ? launch_attn_bwd<16>(a, (hipStream_t)stream)
-                                                                             : launch_attn_bwd<32>(a, (hipStream_t)stream);
+  const AttnBwdArgs<bf16_t> a = attn_bwd_args<bf16_t>(dctx, ldd, k, ldk, v, ldv, P_bf16, ldp, dS_bf16, dbd_bf16, dq, ldo, B, H,
+                                                      T1, T2, scale, drop_p, drop_step, drop_salt, shift_len);
+  if (const int rc = attn_check_bwd(a, dk, dq_is_bf16)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (T2 > ATT_MAXK) return eamd_attn_long_bwd_q_bf16(a, dq_is_bf16, s);
+  const int nkt = attn_nkt(T2);
+  return nkt == 8 ? launch_attn_bwd<8>(a, dq_is_bf16, s) : nkt == 16 ? launch_attn_bwd<16>(a, dq_is_bf16, s) : launch_attn_bwd<32>(a, dq_is_bf16, s);
 }
 
 extern "C" int eamd_attn_bwd_kv(const void* Pd_bf16, const void* dS_bf16, int64_t ldp, const void* dctx, int64_t ldd,
@@ -679,8 +595,7 @@ extern "C" int eamd_attn_bwd_kv(const void* Pd_bf16, const void* dS_bf16, int64_
   a.ldp = ldp; a.ldd = ldd; a.ldq = ldq; a.ldo = ldo;
   a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.nkb = (T2 + 63) / 64;
   if ((long)B * H * a.nkb >= (1L << 28)) return EAMD_EUNSUPPORTED;
-  const int nz = (B * H + 7) / 8 * 8;
-  hipLaunchKernelGGL(attn_bwd_kv_kernel, dim3((unsigned)(a.nkb * nz)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(attn_bwd_kv_kernel, dim3(attn_grid(a.nkb, B, H)), dim3(256), 0, (hipStream_t)stream, a);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }

@@ -132,6 +132,15 @@ __device__ __forceinline__ unsigned short eamd_f2bf(float f) {
   __bf16 b = (__bf16)f;
   return __builtin_bit_cast(unsigned short, b);
 }
+typedef unsigned short bf16_t;     // a bf16 value as its 16 bits
+__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((unsigned)h) << 16); }
+// four floats -> four bf16 (round to nearest even, eamd_f2bf) in two 32-bit words
+__device__ __forceinline__ uint2 eamd_pack_bf16x4(const float4 v) {
+  uint2 h;
+  h.x = eamd_f2bf(v.x) | ((unsigned)eamd_f2bf(v.y) << 16);
+  h.y = eamd_f2bf(v.z) | ((unsigned)eamd_f2bf(v.w) << 16);
+  return h;
+}
 
 // Wave-wide reductions (result in every lane).  The four steps inside a 16-lane row are DPP modifiers on the
 // VALU operand (quad_perm, row_half_mirror, row_mirror: no LDS crossbar trip), only the two cross-row steps go

@@ -27,7 +27,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
 constexpr int BHC = 128;                       // hidden units per chunk
 constexpr int HLD = rb_ld(BHC);                  // bf16 elements per LDS row of a chunk image (272 bytes: 16-byte aligned rows)
 constexpr int HSZ = RB_M * HLD;                 // elements per chunk image
@@ -35,8 +34,6 @@ constexpr int YLD = RB_D + 4;                    // fp32 staging of the output r
 constexpr int XLDB = rb_ld(RB_D);                 // bf16 elements per LDS row of the input image
 constexpr size_t B_CHUNKS = (size_t)4 * HSZ * 2, B_XS = (size_t)RB_M * XLDB * 2;
 constexpr size_t B_SMEM = (B_CHUNKS + B_XS) > (size_t)RB_M * YLD * 4 ? (B_CHUNKS + B_XS) : (size_t)RB_M * YLD * 4;
-
-__device__ __forceinline__ float bf2f_(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
 
 template <bool BWD, int ACT>
 __global__ __launch_bounds__(RB_NT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) {
@@ -62,10 +59,10 @@ __global__ __launch_bounds__(RB_NT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) 
   if (!BWD && p.ln_x) {        // LayerNorm in front: normalise the fp32 rows on their way into the bf16 LDS image; p.x receives them
     rb_stage_ln(p, m0, t,
                 [&](int row, int col, float4 y) __attribute__((always_inline)) {
-                  *reinterpret_cast<uint2*>(&xs[row * XLDB + col]) = rb_pack_bf16x4(y);
+                  *reinterpret_cast<uint2*>(&xs[row * XLDB + col]) = eamd_pack_bf16x4(y);
                 },
                 [&](long gr, int col, float4 y) __attribute__((always_inline)) {
-                  *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(const_cast<float*>(p.x)) + gr * RB_D + col) = rb_pack_bf16x4(y);
+                  *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(const_cast<float*>(p.x)) + gr * RB_D + col) = eamd_pack_bf16x4(y);
                 });
   } else {
 #pragma unroll
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(RB_NT, 2) void ffn_bf16_kernel(const eamd_ffn_t p) 
           }
           fb[lr * HLD + lc] = eamd_f2bf(fv);
         } else {
-          hv = (z[i][r] * bf2f_(fb[lr * HLD + lc])) * p.alpha;
+          hv = (z[i][r] * bf2f(fb[lr * HLD + lc])) * p.alpha;
         }
         hb[lr * HLD + lc] = eamd_f2bf(hv);
       }

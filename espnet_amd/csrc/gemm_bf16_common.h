@@ -10,7 +10,6 @@ namespace {
 
 constexpr int BK = 64;
 constexpr int NT_ = 256;
-typedef unsigned short bf16_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 // LDS images are unpadded and XOR-swizzled at 16-byte chunk granularity so that both the staging
@@ -84,8 +83,6 @@ inline bool gather_taps_fit(const eamd_gather_t& g) {
     if (g.dh[tp] < -8 || g.dh[tp] > 7 || g.dw[tp] < -8 || g.dw[tp] > 7) return false;
   return true;
 }
-
-__device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((unsigned)h) << 16); }
 
 // 8 consecutive bf16 starting at p[idx]; `nvalid` of them are in range (0..8); vec = 16-byte path usable
 __device__ __forceinline__ uint4 load8(const bf16_t* __restrict__ p, long idx, int nvalid, bool vec) {

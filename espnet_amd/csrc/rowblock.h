@@ -19,14 +19,6 @@ __host__ __device__ constexpr int rb_ld(int K) { return K + 8; }
 
 inline bool rb_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
-// four floats -> four bf16 (round to nearest even, eamd_f2bf) in two 32-bit words
-__device__ __forceinline__ uint2 rb_pack_bf16x4(const float4 v) {
-  uint2 h;
-  h.x = eamd_f2bf(v.x) | ((unsigned)eamd_f2bf(v.y) << 16);
-  h.y = eamd_f2bf(v.z) | ((unsigned)eamd_f2bf(v.w) << 16);
-  return h;
-}
-
 // ---- staging ----
 // LayerNorm of the RB_M input rows while they are staged (p.ln_x [M, RB_D] fp32; eamd_ffn_t and eamd_rowproj_t name the ln_* fields alike).
 // reference: transformer/layer_norm.py:12-38 in front of positionwise_feed_forward.py:12-32 / attention.py / convolution.py

@@ -304,6 +304,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_reduce_batched_kernel(const
 // scores layout: [nb][T1][ld] rows, nb = H*B blocks (block index z -> batch b = z % B).
 //   s[i,j] = scale * (ac[i,j] + (bd ? shift(bd)[i,j] : 0))
 //   shift(x)[i,j] = P_flat[T1 + i*T2 + j] with P = [0 | x] of shape (T1, T2+1)
+//   (the flat-index form: it also serves T1 != T2; attn_common.h has the closed form of the same map for T1 == T2)
 // mask: uint8, element (b,i,j) at mask[b*mb + i*mi + j] (mi = 0 broadcasts over queries); 0 = masked.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float shifted_bd(const float* __restrict__ bd, int T1, int T2, long ld, int i,

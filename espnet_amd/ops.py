@@ -1106,6 +1106,14 @@ def attn_fwd_supported(T1, T2, dk, rel):
     return (fast() or F32_FUSED_ATTN) and T2 <= 4096
 
 
+def _attn_tail(drop, device, rel, T1, T2, shift_len, Pd=()):
+    """the argument tail attn_fwd and attn_bwd_q share: (Pd,) drop_p, drop_step, drop_salt, shift_len.  drop = (p, salt) or None;
+    relative positions on a padded batch take the rel_shift over the batch's own length (shift_len: int32 device scalar)"""
+    dropping = drop is not None and drop[0] > 0.0
+    dargs = (drop[0], ptr(rng_state(device)), drop[1]) if dropping else (0.0, None, 0)
+    return tuple(ptr(t) if dropping else None for t in Pd) + dargs + (ptr(shift_len) if (rel and T1 == T2) else None,)
+
+
 def attn_fwd(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldp, scale, drop=None, shift_len=None):
     """qu / qv / k / v: (tensor, element offset, row stride) views of [rows, *] matrices, heads side by side, all bf16
     (eamd_attn_fwd) or all fp32 (eamd_attn_fwd_f32); pos: such a view of the [T2, H*dk] projected positions, or None.
@@ -1129,14 +1137,11 @@ def attn_fwd(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldp, scale, drop=None, s
     cx = torch.empty(B * T1, D, device=dev, dtype=dt)
     dropping = drop is not None and drop[0] > 0.0
     Pd = torch.empty_like(P) if dropping else P
-    dargs = ((ptr(Pd), drop[0], ptr(rng_state(dev)), drop[1]) if dropping
-             else (None, 0.0, None, 0))
     args = (ptr(qu[0], qu[1]), qu[2], ptr(qv[0], qv[1]) if qv is not None else None, qv[2] if qv is not None else 0,
             ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(pos[0], pos[1]) if pos is not None else None,
             pos[2] if pos is not None else 0,
-            ptr(mask), mb, mi, ptr(P), ldp, ptr(cx), D, B, H, T1, T2, dk, scale) + dargs
-    # relative positions on a padded batch: the rel_shift is taken over the batch's own length (shift_len: int32 device scalar)
-    args = args + (ptr(shift_len) if (pos is not None and T1 == T2) else None,)
+            ptr(mask), mb, mi, ptr(P), ldp, ptr(cx), D, B, H, T1, T2, dk, scale)
+    args = args + _attn_tail(drop, dev, pos is not None, T1, T2, shift_len, Pd=(Pd,))
     name = "eamd_attn_fwd" if dt == torch.bfloat16 else "eamd_attn_fwd_f32"
     fn = getattr(_lib.lib(), name)
     rc = fn(*args, stream_ptr())
@@ -1152,21 +1157,19 @@ def attn_bwd_q(dctx, k, v, P, dS, dbd, dq, B, T1, T2, H, dk, ldp, scale, drop=No
     """dctx / k / v / dq: (tensor, element offset, row stride) views; P, dS (and dbd or None): [H*B*T1*ldp], bf16
     (eamd_attn_bwd_q; dq fp32 or bf16) or everything fp32 (eamd_attn_bwd_q_f32).
     dS, dbd and dq are written.  Returns False if the library declines the operands (EAMD_EUNSUPPORTED)."""
-    dropping = drop is not None and drop[0] > 0.0      # the forward's attention dropout: dP <- mask * dP / (1 - p)
-    dargs = ((drop[0], ptr(rng_state(P.device)), drop[1]) if dropping
-             else (0.0, None, 0))
     if P.dtype == torch.bfloat16:
         name = "eamd_attn_bwd_q"
         args = (ptr(dctx[0], dctx[1]), dctx[2], ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(P), ldp,
                 ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), dq[2], dq[0].dtype == torch.bfloat16, B, H, T1, T2, dk,
-                scale) + dargs
+                scale)
     else:
         name = "eamd_attn_bwd_q_f32"
         for t_ in (dctx[0], k[0], v[0], P, dS, dq[0]) + ((dbd,) if dbd is not None else ()):
             assert t_.dtype == torch.float32
         args = (ptr(dctx[0], dctx[1]), dctx[2], ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(P), ldp,
-                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), dq[2], B, H, T1, T2, dk, scale) + dargs
-    args = args + (ptr(shift_len) if (dbd is not None and T1 == T2) else None,)
+                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), dq[2], B, H, T1, T2, dk, scale)
+    # the forward's attention dropout: dP <- mask * dP / (1 - p)
+    args = args + _attn_tail(drop, P.device, dbd is not None, T1, T2, shift_len)
     fn = getattr(_lib.lib(), name)
     rc = fn(*args, stream_ptr())
     if rc == _lib.EAMD_EUNSUPPORTED:

@@ -53,6 +53,52 @@ def test_bad_arguments_are_rejected_without_a_gpu(lib):
     assert lib.eamd_layernorm_fwd(None, None, None, None, None, None, None, 4, 8, ctypes.c_float(1e-12), None) < 0
 
 
+_ATTN_FWD = ("qu ldq qv ldqv k ldk v ldv pos ldpos mask mb mi P ldp ctx ldc B H T1 T2 dk scale Pd drop_p drop_step drop_salt "
+             "shift_len stream").split()
+_ATTN_BWD = "dctx ldd k ldk v ldv P ldp dS dbd dq ldo dq_is_bf16 B H T1 T2 dk scale drop_p drop_step drop_salt shift_len stream".split()
+_ATTN_ENTRY = {"eamd_attn_fwd": _ATTN_FWD, "eamd_attn_fwd_f32": _ATTN_FWD, "eamd_attn_bwd_q": _ATTN_BWD,
+               "eamd_attn_bwd_q_f32": [n for n in _ATTN_BWD if n != "dq_is_bf16"]}
+_EINVAL, _EUNSUP = -1, -2
+# (what is wrong, the arguments changed from a well-formed relative-position call, the code, forward only?).  Every row is refused
+# on the host, before anything is launched: the pointers are made-up addresses, so no row may be a valid call.
+_ATTN_ROWS = [
+    ("null operand", dict(k=None), _EINVAL, False),
+    ("dk != 64", dict(dk=32), _EUNSUP, False),
+    ("pos without qv", dict(qv=None), _EINVAL, True),
+    ("T1 != T2 with positions", dict(T1=90), _EUNSUP, False),
+    ("leading dimension off its unit (a multiple of 2)", dict(ldk=258), _EUNSUP, False),
+    ("misaligned pointer", dict(v=0x30008), _EUNSUP, False),
+    ("ldp < T2", dict(ldp=96), _EUNSUP, False),
+    ("T2 > 4096", dict(T1=4104, T2=4104, ldp=4104), _EUNSUP, False),
+    ("drop_p out of range", dict(drop_p=1.0), _EINVAL, False),
+    ("drop_p > 0 without Pd", dict(drop_p=0.1, drop_step=0x90000), _EINVAL, True),
+    ("drop_p > 0 without the step counter", dict(drop_p=0.1), _EINVAL, False),
+]
+
+
+def test_attention_entry_points_reject_bad_arguments_without_a_gpu():
+    """the argument checks of the four query-side attention entry points (one forward and one backward check in
+    csrc/attn_common.h, parameterised by the 16-byte unit: 4 fp32 / 8 bf16 elements) keep the code of every combination"""
+    from espnet_amd import _lib
+    L = _lib.lib()
+    good = dict(qu=0x10000, qv=0x20000, k=0x30000, v=0x40000, pos=0x50000, mask=None, mb=0, mi=0, P=0x60000, ctx=0x70000,
+                dctx=0x10000, dS=0x20000, dbd=0x50000, dq=0x70000, dq_is_bf16=0, ldq=256, ldqv=256, ldk=256, ldv=256, ldpos=256,
+                ldc=256, ldd=256, ldo=256, ldp=104, B=2, H=4, T1=100, T2=100, dk=64, scale=0.125, Pd=None, drop_p=0.0,
+                drop_step=None, drop_salt=0, shift_len=None, stream=None)
+    for name, params in _ATTN_ENTRY.items():
+        forward = "fwd" in name
+        for what, change, code, forward_only in _ATTN_ROWS:
+            if forward_only and not forward:
+                continue
+            assert set(change) <= set(params), (name, what)
+            args = dict(good, **change)
+            if forward and what.endswith("step counter"):
+                args["Pd"] = 0xa0000                       # the forward names Pd first
+            assert getattr(L, name)(*[args[p] for p in params]) == code, (name, what)
+        if not name.endswith("_f32"):                      # the unit is 8 elements for bf16 operands: 260 is a multiple of 4 only
+            assert getattr(L, name)(*[dict(good, ldv=260)[p] for p in params]) == _EUNSUP, name
+
+
 def header_prototypes():
     """(return type, name, parameter list) of every prototype, by a regex of this file's own over the comment-free header"""
     src = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)

@@ -1318,6 +1318,69 @@ def _long_attention_case(ops, oracle, case, prec, F_):
         report("long attn dpos vs oracle %s" % case, dpos.float().view(T2, D), gp.reshape(T2, D), tol_g)
 
 
+@pytest.mark.parametrize("Ts,T", [(70, 96), (64, 80), (530, 560)])
+@pytest.mark.parametrize("prec", ["bf16", "fp32"])
+def test_attention_shift_len_vs_oracle(ops, oracle, Ts, T, prec):
+    """shift_len shorter than the padded matrix (a shape-bucketed batch): T1 = T2 = T with the legacy rel_shift taken over
+    Ts, against the oracle in float64 on the Ts x Ts problem.  (70, 96): short kernels, the shift crosses a 64-query block
+    (bd row 64 feeds query 63: the VALU dot products); (64, 80): the block boundary exactly; (530, 560): long-row kernels.
+    The length mask keeps every key >= Ts out and dctx is zero on the pad rows, as the padded rows of a batch are:
+    P[:Ts, :Ts], the context rows < Ts and dq / dqv / dk / dv / dpos must then be the Ts x Ts problem's, P zero at keys
+    >= Ts and dbd zero outside the Ts x Ts square.  Tolerances as test_attention_fused_vs_oracle.
+    What the dbd check can see: with dctx zero on the pad rows and P zero at the masked keys, every gradient that could land outside
+    the square is zero anyway, so it catches elements the kernel never WROTE (dbd comes from torch.empty), not elements scattered to
+    a wrong place outside it; a wrong place inside the square shows in dq(v) / dpos."""
+    import espnet_amd
+    from espnet_amd import functional as F_
+    espnet_amd.set_precision(prec)
+    tol_f, tol_g = (4e-3, 8e-3) if prec == "bf16" else (2e-6, 1e-5)
+    try:
+        B, H, dk = 2, 2, 64
+        D = H * dk
+        g = torch.Generator().manual_seed(T * 11 + Ts)
+        bf = lambda *s: (0.5 * torch.randn(*s, generator=g)).to(torch.bfloat16).to(ops.act_dtype()).to(DEV)
+        qu, qv, k, v, p = bf(B * T, D), bf(B * T, D), bf(B * T, D), bf(B * T, D), bf(T, D)
+        lens = torch.linspace(Ts, max(1, Ts // 2), B).long()
+        mask = (torch.arange(T)[None, :] < lens[:, None]).to(torch.uint8).view(B, 1, T).contiguous().to(DEV)
+        sl = torch.tensor([Ts], dtype=torch.int32, device=DEV)
+        dctx = bf(B * T, D)
+        dctx.view(B, T, D)[:, Ts:] = 0
+        fused = F_.attn_fwd_fused(qu, qv, k, v, p, mask, B, T, T, H, dk, shift_len=sl)
+        assert fused is not None, "the fused forward declined the operands"
+        P1, _Pd, c1 = fused
+        seen, orig = [], ops.attn_bwd_q
+
+        def spy(*a_, **k_):
+            seen.append((orig(*a_, **k_), a_[5]))
+            return seen[-1][0]
+        ops.attn_bwd_q = spy
+        try:
+            dqu, dqv, dkk, dvv, dpos = F_.attn_core_bwd(dctx, P1, qu, qv, k, v, p, B, T, T, H, dk, shift_len=sl)
+        finally:
+            ops.attn_bwd_q = orig
+        assert len(seen) == 1 and seen[0][0] is True, "the query-side backward left the fused path"
+        cut = lambda t: t.view(B, T, D)[:, :Ts].reshape(B * Ts, D)
+        attn, ctx, gq, gqv, gk, gv, gp = _oracle_attention(oracle, cut(qu), cut(qv), cut(k), cut(v), p[:Ts], mask[..., :Ts],
+                                                           cut(dctx), B, Ts, Ts, H, dk)
+        ldp = F_._ldp(T)
+        Pv = P1.view(H, B, T, ldp).float().permute(1, 0, 2, 3)
+        name = "shift_len %d in %d %s " % (Ts, T, prec)
+        report(name + "P", Pv[:, :, :Ts, :Ts], attn, tol_f)
+        assert bool((Pv[..., Ts:] == 0).all())
+        report(name + "ctx", cut(c1.float()), ctx, tol_f)
+        r2 = lambda t: t.reshape(B * Ts, D)
+        report(name + "dq(u)", cut(dqu.float()), r2(gq), tol_g)
+        report(name + "dq(v)", cut(dqv.float()), r2(gqv), tol_g)
+        report(name + "dk", cut(dkk.float()), r2(gk), tol_g)
+        report(name + "dv", cut(dvv.float()), r2(gv), tol_g)
+        report(name + "dpos", dpos.float().view(T, D)[:Ts], gp.reshape(Ts, D), tol_g)
+        dbd = seen[0][1].view(H, B, T, ldp).float()
+        assert bool((dbd[:, :, Ts:] == 0).all()) and bool((dbd[..., Ts:] == 0).all())
+    finally:
+        F_.FUSE_ATTN = True
+        espnet_amd.set_precision("fp32")
+
+
 @pytest.mark.parametrize("shape", [(7968, 256, 768), (333, 64, 64), (70, 320, 320), (5, 512, 1024)])
 def test_add_cast_colsum2(ops, shape):
     """one pass: out = bf16(a + b) into a column block, both column sums accumulated"""
