@@ -139,6 +139,10 @@ class TransformerDecoder(AbsDecoder, BatchScorerInterface):
     def forward_one_step(self, tgt, tgt_mask, memory, cache=None):
         return self._dec[0].forward_one_step(tgt, tgt_mask, memory, cache=cache)
 
+    def forward_nbest(self, ys_in, ulen, memory, memory_mask):
+        """the hidden rows of N teacher-forced hypotheses per utterance (nets.modules.Decoder.forward_nbest)"""
+        return self._dec[0].forward_nbest(ys_in, ulen, memory, memory_mask)
+
     def init_state(self, x):
         return None
 

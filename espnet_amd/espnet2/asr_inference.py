@@ -16,6 +16,7 @@ from ..nets.batch_beam_search import BatchBeamSearch
 from ..nets.beam_search import BeamSearch, Hypothesis
 from ..nets.ctc_prefix_beam import CTCPrefixBeamSearch
 from ..nets.ctc_prefix_score import CTCPrefixScorer, LengthBonus
+from ..nets.nbest_rescore import NBestRescorer
 from ..nets.scorer_interface import BatchScorerInterface
 
 
@@ -50,9 +51,17 @@ class Speech2Text:
                  graph_steps=False, ctc_search="label", ngram=None, ngram_weight=0.0, ctc_cand_size=None):
         """ctc_search (not in the reference): "label" decodes through the label-synchronous BeamSearch whatever the weights;
         "time" with ctc_weight == 1.0 runs the time-synchronous CTC prefix beam search (nets.ctc_prefix_beam) with an optional
-        n-gram LM (ngram: an ArpaLM or n-gram scorer, ngram_weight) and ctc_cand_size candidates per frame"""
-        if ctc_search not in ("label", "time"):
-            raise ValueError("ctc_search: 'label' or 'time', not %r" % (ctc_search,))
+        n-gram LM (ngram: an ArpaLM or n-gram scorer, ngram_weight) and ctc_cand_size candidates per frame; "rescore" with
+        0 < ctc_weight <= 1 is two-pass decoding: that search (ngram / ctc_cand_size belong to it) proposes its whole beam and
+        nets.nbest_rescore.NBestRescorer re-ranks it with the decoder (ctc_weight < 1) and / or lm (lm_weight)"""
+        if ctc_search not in ("label", "time", "rescore"):
+            raise ValueError("ctc_search: 'label', 'time' or 'rescore', not %r" % (ctc_search,))
+        if ctc_search == "rescore":
+            if not 0.0 < ctc_weight <= 1.0:
+                raise ValueError("ctc_search='rescore': 0 < ctc_weight <= 1, not %r (the first pass proposes the hypotheses)"
+                                 % (ctc_weight,))
+            if ctc_weight == 1.0 and lm is None:
+                raise ValueError("ctc_search='rescore' with ctc_weight == 1.0 and no lm: there is nothing to rescore with")
         if ctc_search == "time" and ctc_weight != 1.0:
             raise ValueError("ctc_search='time' is the pure-CTC search: ctc_weight must be 1.0, not %r" % (ctc_weight,))
         if ctc_search == "label" and (ngram is not None or ctc_cand_size is not None):
@@ -60,11 +69,19 @@ class Speech2Text:
         if ctc_search == "time" and lm is not None:
             raise ValueError("ctc_search='time' fuses n-gram LMs only (ngram=): a neural lm is not fused time-synchronously")
         self.ctc_search, self.ctc_prefix_beam = ctc_search, None
-        if ctc_search == "time":
-            self.ctc_prefix_beam = dict(beam_size=beam_size, cand_size=ctc_cand_size, nbest=min(nbest, beam_size), penalty=penalty,
-                                        ngram=ngram, ngram_weight=ngram_weight if ngram is not None else 0.0)
+        if ctc_search in ("time", "rescore"):       # the second pass re-ranks the whole beam
+            self.ctc_prefix_beam = dict(beam_size=beam_size, cand_size=ctc_cand_size, penalty=penalty, ngram=ngram,
+                                        nbest=min(nbest, beam_size) if ctc_search == "time" else beam_size,
+                                        ngram_weight=ngram_weight if ngram is not None else 0.0)
             CTCPrefixBeamSearch(**self.ctc_prefix_beam)            # the limits are checked here, before any model work
+        self.rescorer = None
         asr_model.to(device).eval()
+        if ctc_search == "rescore":
+            if ctc_weight < 1.0 and getattr(asr_model, "decoder", None) is None:
+                raise ValueError("ctc_search='rescore' with ctc_weight < 1 needs an attention decoder; this model has none")
+            self.rescorer = NBestRescorer(decoder=asr_model.decoder if ctc_weight < 1.0 else None,
+                                          lm=None if lm is None else lm.to(device).eval(), ctc_weight=ctc_weight,
+                                          lm_weight=lm_weight if lm is not None else 0.0, sos=asr_model.sos, eos=asr_model.eos)
         token_list = token_list if token_list is not None else getattr(asr_model, "token_list", None)
         vocab = len(token_list) if token_list is not None else asr_model.vocab_size
         scorers = dict(decoder=asr_model.decoder, ctc=CTCPrefixScorer(ctc=asr_model.ctc, eos=asr_model.eos),
@@ -98,6 +115,13 @@ class Speech2Text:
         if self.ctc_search == "time":
             hyps = self.asr_model.ctc.prefix_beam_search(enc, [enc.shape[1]], **self.ctc_prefix_beam)[0]
             nbest_hyps = [Hypothesis(yseq=torch.tensor(h["yseq"], dtype=torch.long), score=h["score"], scores=dict(ctc=h["score"]),
+                                     states=dict()) for h in hyps]
+        elif self.ctc_search == "rescore":
+            ctc = self.asr_model.ctc
+            search = CTCPrefixBeamSearch(blank=0, eos=ctc.ctc_lo.out_features - 1, **self.ctc_prefix_beam)
+            nbest = search.search_device(ctc.log_softmax(enc.contiguous()), [enc.shape[1]])
+            hyps = self.rescorer.rescore(enc, [enc.shape[1]], nbest)[0]
+            nbest_hyps = [Hypothesis(yseq=torch.tensor(h["yseq"], dtype=torch.long), score=h["score"], scores=h["scores"],
                                      states=dict()) for h in hyps]
         else:
             nbest_hyps = self.beam_search(x=enc[0], maxlenratio=self.maxlenratio, minlenratio=self.minlenratio)

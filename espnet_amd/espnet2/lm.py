@@ -64,8 +64,12 @@ class TransformerLM(AbsLM):
 
     def forward(self, input, hidden=None):
         """input (B, L) token ids -> (logits (B, L, V), None)"""
+        return F_.LinearFn.apply(self.forward_hidden(input), self.decoder.weight, self.decoder.bias), None
+
+    def forward_hidden(self, input):
+        """forward() up to the rows (B, L, att_unit) that `decoder` reads"""
         h, _ = self.encoder(self._emb(input), self._target_mask(input))
-        return F_.LinearFn.apply(h, self.decoder.weight, self.decoder.bias), None
+        return h
 
     def score(self, y, state, x):
         y = y.unsqueeze(0)
@@ -135,6 +139,11 @@ class SequentialRNNLM(AbsLM):
 
     def forward(self, input, hidden=None):
         """input (B, L) -> (logits (B, L, V), hidden); seq_rnn_lm.py:81-96"""
+        out, hidden = self.forward_hidden(input, hidden)
+        return F_.LinearFn.apply(out, self.decoder.weight, self.decoder.bias), hidden
+
+    def forward_hidden(self, input, hidden=None):
+        """forward() up to the rows (B, L, nhid) that `decoder` reads"""
         B, L = input.shape
         dev = input.device
         emb = R_.PlainEmbedFn.apply(input, self.encoder.weight, self.encoder.padding_idx)
@@ -146,8 +155,7 @@ class SequentialRNNLM(AbsLM):
         for t in range(L):
             y, hidden = self._step(emb[:, t].contiguous(), hidden)
             outs.append(y)
-        out = F_.dropout(torch.stack(outs, dim=1), self.drop.p, self.salts[-1] + 1, self.training)
-        return F_.LinearFn.apply(out, self.decoder.weight, self.decoder.bias), hidden
+        return F_.dropout(torch.stack(outs, dim=1), self.drop.p, self.salts[-1] + 1, self.training), hidden
 
     def score(self, y, state, x):
         y, new_state = self(y[-1].view(1, 1), state)

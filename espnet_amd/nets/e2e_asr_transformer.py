@@ -310,7 +310,10 @@ class E2E(ASRInterface, torch.nn.Module):
         """reference: e2e_asr_transformer.py:259-477 (greedy CTC when ctc_weight == 1 and beam_size == 1, else joint
         CTC/attention beam search through the scorer interface).  ngram: an n-gram scorer (nets.ngram), fused with weight
         recog_args.ngram_weight as asr/pytorch_backend/recog.py:68-87 does.  ctc_weight == 1 with beam_size > 1 (the reference
-        raises there): the time-synchronous CTC prefix beam search of nets.ctc_prefix_beam."""
+        raises there): the time-synchronous CTC prefix beam search of nets.ctc_prefix_beam.  recog_args.ctc_search == "rescore"
+        (not in the reference): two-pass decoding, _recognize_rescore."""
+        if getattr(recog_args, "ctc_search", "label") == "rescore":
+            return self._recognize_rescore([x], recog_args, rnnlm, ngram)[0]
         if self.mtlalpha == 1.0:
             recog_args.ctc_weight = 1.0
         if self.mtlalpha > 0 and recog_args.ctc_weight == 1.0 and recog_args.beam_size > 1:
@@ -343,11 +346,54 @@ class E2E(ASRInterface, torch.nn.Module):
             nbest=min(getattr(recog_args, "nbest", 1), recog_args.beam_size), penalty=getattr(recog_args, "penalty", 0.0),
             ngram=ngram, ngram_weight=getattr(recog_args, "ngram_weight", 0.0) if ngram is not None else 0.0)
 
+    def _rescore_ctc_weight(self, recog_args, rnnlm):
+        """the first-pass weight of two-pass decoding, or a ValueError for a combination with nothing to search or nothing to
+        rescore with (raised before any GPU work)"""
+        if self.mtlalpha == 0 or self.ctc is None:
+            raise ValueError("ctc_search='rescore': the model has no CTC head (mtlalpha == 0) for the first pass")
+        w = 1.0 if self.mtlalpha == 1.0 else float(recog_args.ctc_weight)
+        if w == 0.0:
+            raise ValueError("ctc_search='rescore': ctc_weight == 0 leaves the first pass, which proposes the hypotheses, no say")
+        if not 0.0 < w <= 1.0:
+            raise ValueError("ctc_search='rescore': 0 < ctc_weight <= 1, not %r" % (w,))
+        if w == 1.0 and rnnlm is None:
+            raise ValueError("ctc_search='rescore' with ctc_weight == 1.0 (or a CTC-only model) and no rnnlm: "
+                             "there is nothing to rescore with")
+        if w < 1.0 and self.decoder is None:
+            raise ValueError("ctc_search='rescore' with ctc_weight < 1 needs an attention decoder; this model has none")
+        return w
+
+    def _recognize_rescore(self, xs, recog_args, rnnlm, ngram):
+        """two-pass decoding of a list of utterances: the whole beam of the CTC prefix beam search (beam_size, ctc_cand_size,
+        penalty, ngram of recog_args) re-ranked by nets.nbest_rescore.NBestRescorer with recog_args.ctc_weight, rnnlm and
+        recog_args.lm_weight -> the top recog_args.nbest per utterance, [{"score", "yseq", "scores"}]"""
+        from .ctc_prefix_beam import CTCPrefixBeamSearch
+        from .nbest_rescore import NBestRescorer
+        w = self._rescore_ctc_weight(recog_args, rnnlm)
+        if self.blank != 0 or self.eos != self.odim - 1:
+            raise ValueError("CTC prefix beam search: blank = 0 and eos = odim - 1, not %d / %d" % (self.blank, self.eos))
+        search = CTCPrefixBeamSearch(
+            recog_args.beam_size, cand_size=getattr(recog_args, "ctc_cand_size", None), nbest=recog_args.beam_size,
+            penalty=getattr(recog_args, "penalty", 0.0), ngram=ngram,
+            ngram_weight=getattr(recog_args, "ngram_weight", 0.0) if ngram is not None else 0.0, blank=0, eos=self.eos)
+        rescorer = NBestRescorer(decoder=self.decoder if w < 1.0 else None, lm=rnnlm, ctc_weight=w,
+                                 lm_weight=float(getattr(recog_args, "lm_weight", 0.0)) if rnnlm is not None else 0.0,
+                                 sos=self.sos, eos=self.eos)
+        encs = [self.encode(x) for x in xs]
+        hs_pad = torch.nn.utils.rnn.pad_sequence(encs, batch_first=True)
+        hlens = [e.shape[0] for e in encs]
+        with torch.no_grad():
+            nbest = search.search_device(self.ctc.log_softmax(hs_pad.contiguous()), hlens)
+        keep = max(1, int(getattr(recog_args, "nbest", 1)))
+        return [hyps[:keep] for hyps in rescorer.rescore(hs_pad, hlens, nbest)]
+
     @ops.inference_call
     def recognize_batch(self, xs, recog_args, char_list=None, rnnlm=None, ngram=None):
         """xs: list of (T_b, idim) features -> one n-best list each, what recognize() gives for that utterance: every utterance is
         encoded alone and the searches run in one BeamSearch.forward_batch (pure CTC with beam_size > 1: in one launch of the
         CTC prefix beam search)"""
+        if getattr(recog_args, "ctc_search", "label") == "rescore":
+            return self._recognize_rescore(xs, recog_args, rnnlm, ngram)
         if self.mtlalpha == 1.0 or (self.mtlalpha > 0 and recog_args.ctc_weight == 1.0):
             if recog_args.beam_size > 1:
                 self._refuse_rnnlm_for_pure_ctc(rnnlm)

@@ -44,6 +44,11 @@ class RNNLM(torch.nn.Module):
 
     def forward(self, state, x):
         """state None | {"c": [..], "h": [..]}, x (B,) token ids -> (new state, logits (B, V))"""
+        new, y = self.forward_hidden(state, x)
+        return new, F_.LinearFn.apply(y, self.lo.weight, self.lo.bias)
+
+    def forward_hidden(self, state, x):
+        """forward() up to the rows (B, n_units) that `lo` reads"""
         if state is None:
             state = {"h": [self.zero_state(x.size(0)) for _ in range(self.n_layers)]}
             if self.typ == "lstm":
@@ -59,7 +64,7 @@ class RNNLM(torch.nn.Module):
             y = h[n]
         y = F_.dropout(y, self.dropout[-1].p, self.salts[-1], self.training)
         new = {"c": c, "h": h} if self.typ == "lstm" else {"h": h}
-        return new, F_.LinearFn.apply(y, self.lo.weight, self.lo.bias)
+        return new, y
 
 
 class ClassifierWithState(torch.nn.Module):

@@ -992,6 +992,35 @@ class Decoder(torch.nn.Module, BatchScorerInterface):
             x = F_.LinearFn.apply(x, self.output_layer.weight, self.output_layer.bias)
         return x, tgt_mask
 
+    def forward_nbest(self, ys_in, ulen, memory, memory_mask):
+        """Teacher-forced forward of N hypotheses per utterance over the memory of B utterances, neither replicated nor
+        projected N times.  ys_in [B, N, U] int64, ulen [B * N] (or [B, N]) positions per hypothesis, memory [B, T', D],
+        memory_mask [B, 1, T'] -> the hidden rows [B*N*U, D] after after_norm, in front of output_layer (row (b*N + n)*U + i).
+        Self-attention runs on the batch B*N with the mask causal AND position < ulen; source attention on the batch B with the
+        N*U positions of an utterance as its queries (a view); LayerNorm, FFN and residuals are row-wise.  Rows at positions
+        i >= ulen carry no meaning (a hypothesis with ulen 0 is masked as if it had one position)."""
+        if not self.normalize_before or any(m.concat_after for m in self.decoders):
+            raise NotImplementedError("forward_nbest: decoder layers with normalize_before and without concat_after")
+        B, N, U = ys_in.shape
+        dev = memory.device
+        x = self._embed(ys_in.reshape(B * N, U))
+        D = x.shape[-1]
+        pos = torch.arange(U, device=dev)
+        live = pos.view(1, 1, U) < ulen.to(dev).reshape(B * N, 1, 1).clamp(min=1)
+        tgt_mask = live & (pos.view(1, 1, U) <= pos.view(1, U, 1))
+        shared = shared_stack_proj("kv", list(self.decoders), lambda m: m.src_attn, memory)
+        try:
+            for m in self.decoders:
+                p = m.dropout_rate
+                x = mha_block(m.norm1, m.self_attn, x, None, None, tgt_mask, p_out=p)
+                x = mha_block(m.norm2, m.src_attn, x.reshape(B, N * U, D), memory, None, memory_mask, p_out=p, pre=m._pre)
+                x = ffn_block(m.norm3, m.feed_forward, x.reshape(B * N, U, D), 1.0, p)
+        finally:
+            if shared:
+                for m in self.decoders:
+                    m._pre = None
+        return self.after_norm(x).reshape(B * N * U, D)
+
     def forward_one_step(self, tgt, tgt_mask, memory, cache=None, memory_mask=None):
         """reference: decoder.py:283-321 (memory_mask [n, 1, T]: padded frames of a batch of utterances - batched beam search)"""
         x = self._embed(tgt)

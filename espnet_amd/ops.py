@@ -2275,6 +2275,79 @@ def ctc_prefix_beam(logp, hlens, beam_size, cand_size, nbest, penalty=0.0, lm=No
     return ctc_prefix_beam_search(logp, cval, cid, hlens, beam_size, nbest, penalty, lm, ngram_weight)[0]
 
 
+# ---- second-pass n-best rescoring (csrc/rescore.hip) -----------------------------------------------
+def _nbest_dims(nbest):
+    if not (nbest.is_cuda and nbest.dtype == torch.int32 and nbest.dim() == 3 and nbest.is_contiguous() and nbest.shape[2] > 2):
+        raise _lib.EamdError("n-best: contiguous int32 [B, N, 2 + T] on the device")
+    B, N, W = nbest.shape
+    if not (1 <= N <= CTC_BEAM_MAX_W and W - 2 <= CTC_BEAM_MAX_T):
+        raise _lib.EamdError("n-best: 1 <= N <= %d, T <= %d" % (CTC_BEAM_MAX_W, CTC_BEAM_MAX_T))
+    return B, N, W - 2
+
+
+def nbest_pack(nbest, U, V, sos, eos):
+    """eamd_nbest_pack: the packed n-best [B, N, 2 + T] of ctc_prefix_beam -> (ys_in [B*N, U] int64, col [B*N*U] int32,
+    ulen [B*N] int32), the teacher-forcing operands over U positions (U = the longest length + 1, from the caller)"""
+    B, N, T = _nbest_dims(nbest)
+    U = int(U)
+    if not (1 <= U <= T + 1 and 0 <= sos < V and 0 <= eos < V):
+        raise _lib.EamdError("nbest_pack: 1 <= U <= T + 1 and sos, eos in [0, V)")
+    dev = nbest.device
+    ys_in = torch.empty(B * N, U, device=dev, dtype=torch.int64)
+    col = torch.empty(B * N * U, device=dev, dtype=torch.int32)
+    ulen = torch.empty(B * N, device=dev, dtype=torch.int32)
+    check(_lib.lib().eamd_nbest_pack(ptr(nbest), B, N, T, U, int(V), int(sos), int(eos), ptr(ys_in), ptr(col), ptr(ulen),
+                                     stream_ptr()), "eamd_nbest_pack")
+    return ys_in, col, ulen
+
+
+def row_target_stats(hidden, W, bias, col, tile=None):
+    """what log p(col[m] | row m) of softmax(hidden W^T + bias) needs, without the [rows, V] logits: eamd_gemm with the
+    row-statistics epilogue (epilogue 7) -> (part [rows, tiles_n, 2], zcol [rows], tiles_n).  hidden [rows, D] and W [V, D]
+    of one operand dtype, col [rows] int32 (-1: no target, zcol[m] is then not written).  No fall-back: a shape the GEMM
+    declines is an error.  tile: the GEMM's column tile, 64 or 128 (default: 128 from 2048 rows on, as the transducer loss)."""
+    rows, D = hidden.shape
+    V = W.shape[0]
+    if not (hidden.is_contiguous() and W.is_contiguous() and W.shape[1] == D and col.dtype == torch.int32 and col.numel() == rows):
+        raise _lib.EamdError("row_target_stats: contiguous hidden [rows, D], W [V, D] and int32 col [rows]")
+    tile = (128 if rows >= 2048 else 64) if tile is None else int(tile)
+    tn = (V + tile - 1) // tile
+    dev = hidden.device
+    part = torch.empty(rows, tn, 2, device=dev, dtype=torch.float32)
+    zcol = torch.zeros(rows, device=dev, dtype=torch.float32)
+    zfix = torch.empty(rows, device=dev, dtype=torch.float32)
+    gemm(hidden, W, None, rows, V, D, D, D, V, bias=bias, epilogue=EPI_ROW_STATS, tile=tile, stats=(part, col, zcol, zfix, 0))
+    return part, zcol, tn
+
+
+def nbest_rescore(nbest, ulen, U, scorers, w0):
+    """eamd_nbest_rescore: scorers = 1 or 2 of (part, zcol, tiles_n, weight) from row_target_stats over the B*N*U rows of
+    nbest_pack -> (nbest_out [B, N, 2 + T] re-ranked with word 0 = the bits of f = w0 * s1 + sum_s weight_s * term_s,
+    terms [B, N, 1 + S] fp32 = (s1, term_1 ..) and order [B, N] int32 = the first-pass index, all in the new order)"""
+    B, N, T = _nbest_dims(nbest)
+    S, rows = len(scorers), B * N * int(U)
+    if S not in (1, 2) or not 1 <= U <= T + 1:
+        raise _lib.EamdError("nbest_rescore: one or two scorers, 1 <= U <= T + 1")
+    if not (ulen.dtype == torch.int32 and ulen.numel() == B * N and ulen.is_contiguous() and ulen.device == nbest.device):
+        raise _lib.EamdError("nbest_rescore: ulen int32 [B * N] beside the n-best")
+    args = []
+    for part, zcol, tn, w in scorers:
+        if not (part.dtype == torch.float32 and zcol.dtype == torch.float32 and part.is_contiguous() and zcol.is_contiguous()
+                and tn >= 1 and part.numel() >= rows * tn * 2 and zcol.numel() >= rows and part.device == nbest.device
+                and zcol.device == nbest.device):
+            raise _lib.EamdError("nbest_rescore: part [B*N*U, tiles_n, 2] and zcol [B*N*U] float32 beside the n-best")
+        args += [ptr(part), ptr(zcol), int(tn), float(w)]
+    if S == 1:
+        args += [None, None, 0, 0.0]
+    dev = nbest.device
+    out = torch.empty_like(nbest)
+    terms = torch.empty(B, N, 1 + S, device=dev, dtype=torch.float32)
+    order = torch.empty(B, N, device=dev, dtype=torch.int32)
+    check(_lib.lib().eamd_nbest_rescore(ptr(nbest), ptr(ulen), B, N, T, int(U), S, *args, float(w0), ptr(out), ptr(terms),
+                                        ptr(order), stream_ptr()), "eamd_nbest_rescore")
+    return out, terms, order
+
+
 # ---- MVDR beamforming front-end (csrc/beamformer.hip) ----------------------------------------------
 BF_PSD, BF_PSD_BWD, BF_MVDR_BWD, BF_APPLY_BWD = 0, 1, 2, 3
 BF_TCHUNK = 64               # EAMD_BF_TCHUNK: frames per workgroup of the kernels that split the time axis

@@ -1292,6 +1292,36 @@ int eamd_ctc_prefix_beam(const float* logp, int64_t ld, const float* cand_val, c
                          int unk, float ngram_weight, void* workspace, int64_t workspace_bytes, int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Second-pass n-best rescoring, csrc/rescore.hip: the device glue between the packed n-best above, a teacher-forced
+ * attention-decoder / LM forward and eamd_gemm's row-statistics epilogue.  The reference rescores only inside its
+ * label-synchronous search (espnet/nets/beam_search.py); there is no second pass in it.  Plain vector stores, no atomics,
+ * fixed reduction orders: two launches give the same bits.  N <= 32 (the beam limit of the first pass), T <= 2048,
+ * S in {1, 2}: else EAMD_EUNSUPPORTED; NULL / non-positive arguments or U > T + 1: EAMD_EINVAL; both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+/* nbest [B, N, 2 + T] as eamd_ctc_prefix_beam writes it (score bits, length L or -1, tokens) -> teacher-forcing operands
+ * over U positions (the caller sizes U = longest L + 1), row r = b * N + n:
+ *   ys_in [B*N, U] int64 = sos, tok_0 .. tok_{L-1}, then eos;   col [B*N*U] int32 = tok_0 .. tok_{L-1}, eos, then -1 (the
+ *   epilogue-7 col array);   ulen [B*N] = L + 1, or 0 for an absent hypothesis (L = -1: ys_in = sos, eos .., col = -1).
+ * L = 0 is a hypothesis of one position (sos -> eos).  Device-read values are clamped: L to min(U - 1, T), tokens to [0, V). */
+int eamd_nbest_pack(const int32_t* nbest, int B, int N, int T, int U, int V, int sos, int eos, int64_t* ys_in, int32_t* col,
+                    int32_t* ulen, void* stream);
+/* One workgroup per utterance, one wave per hypothesis, lanes over positions.  Per scorer s (S of them): part_s
+ * [B*N*U, tiles_s, 2] and zcol_s [B*N*U] as epilogue 7 leaves them for the rows (b, n, i) with col from eamd_nbest_pack.
+ * For hypothesis (b, n) and every position i < ulen (clamped to [0, U]; none for an absent hypothesis):
+ *   m = max_j part[i][j][0];  lse_i = m + log(sum_j part[i][j][1] * exp(part[i][j][0] - m)), j in tile order (a tile
+ *   whose maximum is -inf adds 0);  lp_i = zcol[i] - lse_i;
+ *   term_s = sum_i lp_i: lane l adds i = l, l + 64, .. in that order, then the wave's fixed butterfly.
+ * With s1 = the fp32 whose bits are word 0, in fp32, every product and sum rounded on its own (nothing contracted):
+ *   f = w0 * s1;   f = f + w1 * term_1;   S == 2: f = f + w2 * term_2.
+ * Rank within the utterance: f descending (a NaN f ranks as -inf), equal f to the lower first-pass index, absent
+ * hypotheses last in their first-pass order.  In the new order: nbest_out [B, N, 2 + T] = the rows, word 0 of a present one
+ * replaced by the bits of f;  terms [B, N, 1 + S] = s1, term_1 ..;  order [B, N] = the first-pass index.
+ * part_s 8-byte aligned (else EAMD_EUNSUPPORTED); nbest_out must not be nbest. */
+int eamd_nbest_rescore(const int32_t* nbest, const int32_t* ulen, int B, int N, int T, int U, int S, const float* part1,
+                       const float* zcol1, int tiles1, float w1, const float* part2, const float* zcol2, int tiles2, float w2,
+                       float w0, int32_t* nbest_out, float* terms, int32_t* order, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mask-based MVDR beamforming front-end (reference: espnet/nets/pytorch_backend/frontends/beamformer.py:6-84,
  * dnn_beamformer.py:163-170), csrc/beamformer.hip.  All fp32; a complex number is an interleaved (re, im) pair with
  * frequency the fastest axis, as Stft.forward writes it.  2 <= C <= 8 channels (anything else: EAMD_EUNSUPPORTED).
