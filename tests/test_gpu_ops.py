@@ -1249,9 +1249,10 @@ def test_attention_fused_vs_oracle(ops, oracle, case, prec):
     dict(B=2, T1=77, T2=1090, rel=False, mask="dead")])
 @pytest.mark.parametrize("prec", ["fp32", "bf16"])
 def test_attention_fused_long_rows_vs_oracle(ops, oracle, case, prec):
-    """Rows of 513 .. 4096 keys stay on the fused path in both precision modes (attn_fwd_long_kernel / attn_bwd_q_long_kernel:
-    16 queries per workgroup up to 2048 keys - 32 between 977 and 1100 keys, two query tiles per wave -, 8 beyond; every phase split
-    over the keys; bf16 operands are widened on load):
+    """Rows of 513 .. 4096 keys stay on the fused path in both precision modes (attn_fwd_long_kernel / attn_bwd_q_long_kernel;
+    queries and waves per workgroup by T2, from attn_long_lds / long_geom: 513..992 (16, 4), 993..1984 (16, 8), 1985..2128 (16, 6),
+    2129..2272 (16, 4), 2273..4000 (8, 8), 4001..4096 (8, 6), the backward running four waves where the forward runs six; every
+    phase split over the keys; bf16 operands are widened on load):
     probabilities, context and every gradient against the oracle in float64, the legacy rel_shift at T1 = T2 = 999 / 1500 / 2048 /
     2500 / 4096, cross-attention 101 x 999 and 101 x 4096, causal masks and a fully masked utterance.  Tolerances as test_attention_fused_vs_oracle.
     reference: transformer/attention.py:63-92, 141-206."""
