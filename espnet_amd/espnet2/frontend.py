@@ -5,8 +5,9 @@ espnet2/layers/log_mel.py:8-75 (LogMel over librosa.filters.mel).  Same class na
 `forward(input, input_lengths) -> (feats, lens)`.
 
 frontend_conf with use_beamformer builds the mask-based MVDR beamformer of nets/frontends (default.py:58-94): a
-multi-channel waveform (B, L, C) then goes Stft.forward -> Frontend -> power spectrum -> LogMel.  WPE is refused.  Without
-an enabled frontend_conf, and for single-channel input, the path below is unchanged.
+multi-channel waveform (B, L, C) then goes Stft.forward -> Frontend -> power spectrum -> LogMel.  use_wpe in frontend_conf
+is refused; WPE dereverberation is attached afterwards (DefaultFrontend(...).frontend.attach_wpe(DNN_WPE(...))) and then
+runs in front of the beamformer.  Without an enabled frontend_conf, and for single-channel input, the path below is unchanged.
 
 MI355X mapping: the DFT of all frames is ONE fp32 MFMA GEMM - the reflect-padded waveform is read in place as
 overlapping rows (leading dimension = hop length), the window is folded into the [2F, n_fft] basis - followed by one
@@ -199,7 +200,8 @@ class DefaultFrontend(AbsFrontend):
     """Stft -> [Frontend: MVDR beamformer] -> power spectrum -> LogMel.
 
     frontend_conf: the keyword arguments of nets.frontends.frontend.Frontend (use_beamformer, btype, blayers, bunits,
-    bprojs, bnmask, badim, ref_channel, bdropout_rate); use_wpe=True raises NotImplementedError.  With use_beamformer a
+    bprojs, bnmask, badim, ref_channel, bdropout_rate); use_wpe=True raises NotImplementedError (attach a DNN_WPE with
+    `self.frontend.attach_wpe`: eval then runs WPE and the beamformer, training draws one of them).  With use_beamformer a
     3-D input (B, L, C) is beamformed to one channel (in training mode Frontend draws, as the reference does, between
     beamforming and passing the channels through, of which one is then picked at random).  None or all switches off:
     `frontend` is None and a 3-D input is reduced to one channel before the STFT, as before.

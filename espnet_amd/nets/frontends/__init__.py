@@ -1,2 +1,3 @@
-"""Speech-enhancement front-end of the reference (espnet/nets/pytorch_backend/frontends/*): the mask-based MVDR
-beamformer on the espnet_amd HIP kernels (csrc/beamformer.hip).  WPE dereverberation is not on this path."""
+"""Speech-enhancement front-end of the reference (espnet/nets/pytorch_backend/frontends/*) on the espnet_amd HIP
+kernels: WPE dereverberation (dnn_wpe.py, wpe.py, csrc/wpe.hip) and the mask-based MVDR beamformer (csrc/beamformer.hip).
+Frontend's constructor still refuses use_wpe=True; a DNN_WPE is attached with Frontend.attach_wpe."""

@@ -1,10 +1,12 @@
 """reference: espnet/nets/pytorch_backend/frontends/frontend.py (same class and function names and constructor
-arguments).  Only the beamformer is on the HIP path; WPE dereverberation (the reference delegates it to the pytorch_wpe
-package) is refused."""
+arguments).  The constructor builds the beamformer only and still refuses use_wpe=True; WPE dereverberation
+(dnn_wpe.py, csrc/wpe.hip) is attached to a built front-end with attach_wpe, after which forward runs the reference's
+full logic: in training WPE or the beamformer (never both), in eval WPE and then the beamformer."""
 import numpy
 import torch
 
 from .dnn_beamformer import DNN_Beamformer
+from .dnn_wpe import DNN_WPE
 
 
 class Frontend(torch.nn.Module):
@@ -25,8 +27,17 @@ class Frontend(torch.nn.Module):
         else:
             self.beamformer = None
 
+    def attach_wpe(self, wpe):
+        """run `wpe` (a DNN_WPE) as the first stage from now on"""
+        if not isinstance(wpe, DNN_WPE):
+            raise TypeError(f"attach_wpe takes a DNN_WPE, not {type(wpe).__name__}")
+        self.wpe = wpe
+        self.use_wpe = True
+        return self
+
     def forward(self, x, ilens):
-        """x [B,T,F,2] or [B,T,C,F,2] -> (h, ilens, mask): the beamformer's [B,T,F,2] and speech mask, or x itself"""
+        """x [B,T,F,2] or [B,T,C,F,2] -> (h, ilens, mask): the beamformer's [B,T,F,2] and speech mask, the dereverberated
+        [B,T,C,F,2] and the WPE mask when only WPE ran, or x itself"""
         assert len(x) == len(ilens), (len(x), len(ilens))
         if x.dim() not in (4, 5):
             raise ValueError(f"Input dim must be 4 or 5 with the trailing (re, im) axis: {x.dim()}")
@@ -37,11 +48,15 @@ class Frontend(torch.nn.Module):
         if h.dim() == 5:
             if self.training:                       # frontend.py:101-109: the same draw, so a seeded run makes the same choices
                 choices = [(False, False)] if not self.use_frontend_for_all else []
+                if self.use_wpe:
+                    choices.append((True, False))
                 if self.use_beamformer:
                     choices.append((False, True))
-                _, use_beamformer = choices[numpy.random.randint(len(choices))]
+                use_wpe, use_beamformer = choices[numpy.random.randint(len(choices))]
             else:
-                use_beamformer = self.use_beamformer
+                use_wpe, use_beamformer = self.use_wpe, self.use_beamformer
+            if use_wpe:
+                h, ilens, mask = self.wpe(h, ilens)
             if use_beamformer:
                 h, ilens, mask = self.beamformer(h, ilens)
         return h, ilens, mask

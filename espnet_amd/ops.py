@@ -2453,6 +2453,124 @@ def bf_apply_bwd(gy, x, out=None):
     return gw
 
 
+# ---- WPE dereverberation (csrc/wpe.hip) ------------------------------------------------------------
+WPE_FTILE = 32               # EAMD_WPE_FTILE: frequency bins per workgroup of the correlation and filter kernels
+WPE_MAX_UNKNOWNS = 64        # EAMD_WPE_MAX_UNKNOWNS: C * taps
+_WPE_TASKS = 8               # 4 x 4 tiles of [R | P] per correlation workgroup (csrc/wpe.hip: kSlots)
+
+
+def wpe_check_shape(Cn, taps, delay):
+    """the limits of csrc/wpe.hip, refused here by name before anything is launched"""
+    if taps < 1 or Cn < 1:
+        raise ValueError(f"WPE needs taps >= 1 and at least one channel (taps={taps}, C={Cn})")
+    if delay < 0:
+        raise ValueError(f"WPE needs delay >= 0 (delay={delay})")
+    if Cn * taps > WPE_MAX_UNKNOWNS:
+        raise ValueError(f"WPE kernels solve at most C * taps = {WPE_MAX_UNKNOWNS} unknowns per bin (C={Cn}, taps={taps})")
+
+
+def wpe_nchunk(B, T, Cn, F, taps, backward=False):
+    """into how many chunks the correlation pass cuts the time axis: enough workgroups to fill the chip, chunks of at
+    least 64 frames, a workspace of at most 1 GiB.  A function of the shape alone, so a launch repeats bit for bit."""
+    N = Cn * taps
+    nt, pt = -(-N // 4), -(-Cn // 4)
+    tasks = nt * pt if backward else nt * (nt + 1) // 2 + nt * pt
+    base = -(-F // WPE_FTILE) * -(-tasks // _WPE_TASKS) * B
+    n = max(1, min(-(-1024 // base), -(-T // 64)))
+    per = B * F * N * (Cn if backward else N + Cn) * 16
+    return max(1, min(n, (1 << 30) // per))
+
+
+def _wpe_lens(lens, B, device):
+    if lens is not None:
+        assert lens.shape == (B,) and lens.dtype == torch.int32 and lens.device == device and lens.is_contiguous()
+    return lens
+
+
+def wpe_power(y, z=None, out=None):
+    """y [B,T,C,F,2], mask logits z [1,B,C,Tm,F] or None -> power [B,T,F] = mean_c |y|^2 sigmoid(z) (eamd_wpe_power)"""
+    B, T, Cn, F, two = y.shape
+    Tm = T if z is None else z.shape[3]
+    assert two == 2 and (z is None or (z.shape == (1, B, Cn, Tm, F) and Tm <= T))
+    _bf_f32(y, z)
+    power = torch.empty(B, T, F, device=y.device, dtype=torch.float32) if out is None else out
+    assert power.shape == (B, T, F)
+    _bf_f32(power)
+    check(_lib.lib().eamd_wpe_power(ptr(y), ptr(z), ptr(power), B, T, Tm, Cn, F, stream_ptr()), "eamd_wpe_power")
+    return power
+
+
+def wpe_power_bwd(y, z, gpower, out=None):
+    """-> dz [1,B,C,Tm,F] (eamd_wpe_power_bwd)"""
+    B, T, Cn, F, _ = y.shape
+    Tm = z.shape[3]
+    assert z.shape == (1, B, Cn, Tm, F) and Tm <= T and gpower.shape == (B, T, F)
+    _bf_f32(y, z, gpower)
+    dz = torch.empty_like(z) if out is None else out
+    assert dz.shape == z.shape
+    _bf_f32(dz)
+    check(_lib.lib().eamd_wpe_power_bwd(ptr(y), ptr(z), ptr(gpower), ptr(dz), B, T, Tm, Cn, F, stream_ptr()),
+          "eamd_wpe_power_bwd")
+    return dz
+
+
+def wpe_taps(y, power, lens, taps, delay, eps=1e-10, inverse_power=True, keep_factor=True, nchunk=None, out=None):
+    """y [B,T,C,F,2], power [B,T,F], lens [B] int32 on the device or None -> (G [B,N,C,F,2], fac [B,F,N,N,2] float64 or None):
+    the prediction filter, row i = k * C + c of the stacked history, and the factor the backward takes (eamd_wpe_taps)"""
+    B, T, Cn, F, two = y.shape
+    wpe_check_shape(Cn, taps, delay)
+    N = Cn * taps
+    assert two == 2 and power.shape == (B, T, F)
+    _bf_f32(y, power)
+    lens = _wpe_lens(lens, B, y.device)
+    nchunk = wpe_nchunk(B, T, Cn, F, taps) if nchunk is None else nchunk
+    if out is None:
+        out = (torch.empty(B, N, Cn, F, 2, device=y.device, dtype=torch.float32),
+               torch.empty(B, F, N, N, 2, device=y.device, dtype=torch.float64) if keep_factor else None)
+    G, fac = out
+    assert G.shape == (B, N, Cn, F, 2) and (fac is None or (fac.shape == (B, F, N, N, 2) and fac.dtype == torch.float64
+                                                             and fac.is_contiguous()))
+    _bf_f32(G)
+    ws = torch.empty(nchunk * B * F * N * (N + Cn) * 2, device=y.device, dtype=torch.float64)
+    check(_lib.lib().eamd_wpe_taps(ptr(y), ptr(power), ptr(lens), ptr(G), ptr(fac), ptr(ws), B, T, Cn, F, taps, delay, eps,
+                                   int(bool(inverse_power)), nchunk, stream_ptr()), "eamd_wpe_taps")
+    return G, fac
+
+
+def wpe_filter(y, G, lens, taps, delay, out=None):
+    """-> x [B,T,C,F,2] = y - G^H (stacked history), exactly 0 past each length (eamd_wpe_filter)"""
+    B, T, Cn, F, _ = y.shape
+    wpe_check_shape(Cn, taps, delay)
+    assert G.shape == (B, Cn * taps, Cn, F, 2)
+    _bf_f32(y, G)
+    lens = _wpe_lens(lens, B, y.device)
+    x = torch.empty_like(y) if out is None else out
+    assert x.shape == y.shape
+    _bf_f32(x)
+    check(_lib.lib().eamd_wpe_filter(ptr(y), ptr(G), ptr(lens), ptr(x), B, T, Cn, F, taps, delay, stream_ptr()),
+          "eamd_wpe_filter")
+    return x
+
+
+def wpe_bwd(y, x, gx, power, lens, fac, taps, delay, eps=1e-10, inverse_power=True, nchunk=None, out=None):
+    """gx [B,T,C,F,2], the cotangent of x -> gpower [B,T,F] (eamd_wpe_bwd); x, power, fac as the forward took / wrote them"""
+    B, T, Cn, F, _ = y.shape
+    wpe_check_shape(Cn, taps, delay)
+    N = Cn * taps
+    assert x.shape == y.shape and gx.shape == y.shape and power.shape == (B, T, F)
+    assert fac.shape == (B, F, N, N, 2) and fac.dtype == torch.float64 and fac.is_contiguous()
+    _bf_f32(y, x, gx, power)
+    lens = _wpe_lens(lens, B, y.device)
+    nchunk = wpe_nchunk(B, T, Cn, F, taps, backward=True) if nchunk is None else nchunk
+    gpower = torch.empty_like(power) if out is None else out
+    assert gpower.shape == power.shape
+    _bf_f32(gpower)
+    ws = torch.empty((2 * nchunk + 1) * B * F * N * Cn, device=y.device, dtype=torch.float64)
+    check(_lib.lib().eamd_wpe_bwd(ptr(y), ptr(x), ptr(gx), ptr(power), ptr(lens), ptr(fac), ptr(gpower), ptr(ws), B, T, Cn, F,
+                                  taps, delay, eps, int(bool(inverse_power)), nchunk, stream_ptr()), "eamd_wpe_bwd")
+    return gpower
+
+
 # ---- CTC -----------------------------------------------------------------------------------------
 def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True, time_major=False,
              keep_workspace=False):

@@ -1355,6 +1355,39 @@ int eamd_bf_mvdr_bwd(const float* psd_s, const float* psd_n, const float* u, con
 int eamd_bf_apply(const float* w, const float* x, float* y, int B, int T, int C, int F, void* stream);
 int eamd_bf_apply_bwd(const float* gy, const float* x, float* gw, void* workspace, int B, int T, int C, int F, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * WPE dereverberation (the algorithm behind the reference's DNN_WPE, frontends/dnn_wpe.py), csrc/wpe.hip.
+ * y [B,T,C,F,2] fp32 as above, power [B,T,F], lens [B] int32 (NULL: every utterance has T frames), K = taps, D = delay,
+ * N = C K <= EAMD_WPE_MAX_UNKNOWNS (more: EAMD_EUNSUPPORTED).  Per (b, f), n = lens[b], t0 = D + K - 1 and the stacked
+ * history h_t[k C + c] = y[t - D - k, c] (0 before frame 0):
+ *   w_t = 1 / max(power_t, eps)  (inverse_power == 0: w_t = power_t)
+ *   R = sum_{t0 <= t < n} w_t h_t h_t^H,  P = sum_{t0 <= t < n} w_t h_t y_t^H,  G = R^-1 P,  x_t = y_t - G^H h_t  (0 for t >= n)
+ * The sums stop at the utterance's own length.  Memory is fp32; products, sums and the LDL^H solve are fp64.  A pivot
+ * that is zero, negative or not finite takes reciprocal 0: a singular bin gives a finite answer, an all-zero bin exactly 0.
+ * No atomics: the time axis is cut into nchunk equal chunks (1 <= nchunk <= T, the caller's choice), whose partial sums the
+ * solve adds in chunk order.  NULL or non-positive arguments: EAMD_EINVAL before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define EAMD_WPE_FTILE 32            /* frequency bins per workgroup of the correlation and filter kernels */
+#define EAMD_WPE_MAX_UNKNOWNS 64     /* C * taps */
+/* power [B,T,F] = mean_c |y|^2 m, m = sigmoid(z[0,b,c,t,f]) for t < Tm and 0 for Tm <= t < T (z [1,B,C,Tm,F] mask LOGITS);
+ * z == NULL: m = 1.  Backward: dz [1,B,C,Tm,F] = gpower |y_c|^2 / C sigmoid'(z). */
+int eamd_wpe_power(const float* y, const float* z, float* power, int B, int T, int Tm, int C, int F, void* stream);
+int eamd_wpe_power_bwd(const float* y, const float* z, const float* gpower, float* dz, int B, int T, int Tm, int C, int F,
+                       void* stream);
+/* G [B,N,C,F,2] (row i = k C + c of the history, column = output channel, f fastest).  fac [B,F,N,N] complex double (NULL:
+ * not kept) is the factor R = L d L^H that eamd_wpe_bwd takes: L d below the diagonal, 1 / d on it, 0 above.
+ * workspace: nchunk B F N (N + C) 16 bytes. */
+int eamd_wpe_taps(const float* y, const float* power, const int32_t* lens, float* G, double* fac, void* workspace, int B, int T,
+                  int C, int F, int taps, int delay, float eps, int inverse_power, int nchunk, void* stream);
+int eamd_wpe_filter(const float* y, const float* G, const int32_t* lens, float* x, int B, int T, int C, int F, int taps, int delay,
+                    void* stream);
+/* gpower [B,T,F] from gx, the cotangent of x (y gets none):  gG = -sum_{t < n} h_t gx_t^H,  Z = R^-1 gG,
+ * gw_t = Re(h_t^H Z x_t) for t0 <= t < n,  gpower_t = -gw_t / power_t^2 where power_t > eps  (inverse_power == 0: gw_t),
+ * 0 elsewhere.  x, power, fac as the forward took and wrote them.  workspace: (2 nchunk + 1) B F N C 8 bytes. */
+int eamd_wpe_bwd(const float* y, const float* x, const float* gx, const float* power, const int32_t* lens, const double* fac,
+                 float* gpower, void* workspace, int B, int T, int C, int F, int taps, int delay, float eps, int inverse_power,
+                 int nchunk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
