@@ -200,7 +200,8 @@ class DefaultFrontend(AbsFrontend):
     """Stft -> [Frontend: MVDR beamformer] -> power spectrum -> LogMel.
 
     frontend_conf: the keyword arguments of nets.frontends.frontend.Frontend (use_beamformer, btype, blayers, bunits,
-    bprojs, bnmask, badim, ref_channel, bdropout_rate); use_wpe=True raises NotImplementedError (attach a DNN_WPE with
+    bprojs, bnmask, badim, ref_channel, bdropout_rate, beamformer_type - "mvdr", "mpdr" or the convolutional "wpd" - btaps,
+    bdelay); use_wpe=True raises NotImplementedError (attach a DNN_WPE with
     `self.frontend.attach_wpe`: eval then runs WPE and the beamformer, training draws one of them).  With use_beamformer a
     3-D input (B, L, C) is beamformed to one channel (in training mode Frontend draws, as the reference does, between
     beamforming and passing the channels through, of which one is then picked at random).  None or all switches off:

@@ -1,5 +1,6 @@
 """reference: espnet/nets/pytorch_backend/frontends/frontend.py (same class and function names and constructor
-arguments).  The constructor builds the beamformer only and still refuses use_wpe=True; WPE dereverberation
+arguments, plus beamformer_type ("mvdr", "mpdr" or "wpd"), btaps and bdelay of DNN_Beamformer).  The constructor builds
+the beamformer only and still refuses use_wpe=True; WPE dereverberation
 (dnn_wpe.py, csrc/wpe.hip) is attached to a built front-end with attach_wpe, after which forward runs the reference's
 full logic: in training WPE or the beamformer (never both), in eval WPE and then the beamformer."""
 import numpy
@@ -12,7 +13,7 @@ from .dnn_wpe import DNN_WPE
 class Frontend(torch.nn.Module):
     def __init__(self, idim, use_wpe=False, wtype="blstmp", wlayers=3, wunits=300, wprojs=320, wdropout_rate=0.0, taps=5,
                  delay=3, use_dnn_mask_for_wpe=True, use_beamformer=False, btype="blstmp", blayers=3, bunits=300, bprojs=320,
-                 bnmask=2, badim=320, ref_channel=-1, bdropout_rate=0.0):
+                 bnmask=2, badim=320, ref_channel=-1, bdropout_rate=0.0, beamformer_type="mvdr", btaps=5, bdelay=3):
         super().__init__()
         self.use_beamformer = use_beamformer
         self.use_wpe = use_wpe
@@ -23,7 +24,8 @@ class Frontend(torch.nn.Module):
         self.wpe = None
         if self.use_beamformer:
             self.beamformer = DNN_Beamformer(btype=btype, bidim=idim, bunits=bunits, bprojs=bprojs, blayers=blayers, bnmask=bnmask,
-                                             dropout_rate=bdropout_rate, badim=badim, ref_channel=ref_channel)
+                                             dropout_rate=bdropout_rate, badim=badim, ref_channel=ref_channel,
+                                             beamformer_type=beamformer_type, btaps=btaps, bdelay=bdelay)
         else:
             self.beamformer = None
 
@@ -67,4 +69,6 @@ def frontend_for(args, idim):
                     wprojs=args.wprojs, wdropout_rate=args.wdropout_rate, taps=args.wpe_taps, delay=args.wpe_delay,
                     use_dnn_mask_for_wpe=args.use_dnn_mask_for_wpe, use_beamformer=args.use_beamformer, btype=args.btype,
                     blayers=args.blayers, bunits=args.bunits, bprojs=args.bprojs, bnmask=args.bnmask, badim=args.badim,
-                    ref_channel=args.ref_channel, bdropout_rate=args.bdropout_rate)
+                    ref_channel=args.ref_channel, bdropout_rate=args.bdropout_rate,
+                    beamformer_type=getattr(args, "beamformer_type", "mvdr"), btaps=getattr(args, "btaps", 5),
+                    bdelay=getattr(args, "bdelay", 3))

@@ -2571,6 +2571,152 @@ def wpe_bwd(y, x, gx, power, lens, fac, taps, delay, eps=1e-10, inverse_power=Tr
     return gpower
 
 
+# ---- WPD / MPDR convolutional beamformers (csrc/wpd.hip) -------------------------------------------
+def wpd_check_shape(Cn, btaps, bdelay):
+    """the limits of csrc/wpd.hip, refused here by name before anything is launched"""
+    if btaps < 0 or Cn < 1:
+        raise ValueError(f"WPD needs btaps >= 0 and at least one channel (btaps={btaps}, C={Cn})")
+    if bdelay < 1:
+        raise ValueError(f"WPD needs bdelay >= 1 (bdelay={bdelay})")
+    if Cn * (btaps + 1) > WPE_MAX_UNKNOWNS:
+        raise ValueError(f"WPD kernels solve at most (btaps + 1) * C = {WPE_MAX_UNKNOWNS} unknowns per bin (C={Cn}, "
+                         f"btaps={btaps})")
+
+
+def wpd_nchunk(B, T, Cn, F, btaps, backward=False):
+    """into how many chunks the covariance pass (backward: the pass that forms gh) cuts the time axis; the rule of
+    wpe_nchunk.  A function of the shape alone, so a launch repeats bit for bit."""
+    N = Cn * (btaps + 1)
+    nt = -(-N // 4)
+    groups = -(-N // 8) if backward else -(-(nt * (nt + 1) // 2) // _WPE_TASKS)
+    base = -(-F // WPE_FTILE) * groups * B
+    n = max(1, min(-(-1024 // base), -(-T // 64)))
+    per = B * F * N * (1 if backward else N) * 16
+    return max(1, min(n, (1 << 30) // per))
+
+
+def _wpd_f64(t, shape):
+    assert t.shape == shape and t.dtype == torch.float64 and t.is_contiguous(), (tuple(t.shape), t.dtype, shape)
+
+
+def wpd_cov(y, power, lens, btaps, bdelay, eps=1e-10, inverse_power=True, nchunk=None, out=None):
+    """y [B,T,C,F,2], power [B,T,F] or None (unit weights), lens [B] int32 on the device or None -> Rf [B,F,N,N,2] float64,
+    N = (btaps + 1) C: the weighted covariance of the stacked frames, exactly Hermitian (eamd_wpd_cov)"""
+    B, T, Cn, F, two = y.shape
+    wpd_check_shape(Cn, btaps, bdelay)
+    N = Cn * (btaps + 1)
+    assert two == 2 and (power is None or power.shape == (B, T, F))
+    _bf_f32(y, power)
+    lens = _wpe_lens(lens, B, y.device)
+    nchunk = wpd_nchunk(B, T, Cn, F, btaps) if nchunk is None else nchunk
+    Rf = torch.empty(B, F, N, N, 2, device=y.device, dtype=torch.float64) if out is None else out
+    _wpd_f64(Rf, (B, F, N, N, 2))
+    ws = torch.empty(nchunk * B * F * N * N * 2, device=y.device, dtype=torch.float64)
+    check(_lib.lib().eamd_wpd_cov(ptr(y), ptr(power), ptr(lens), ptr(Rf), ptr(ws), B, T, Cn, F, btaps, bdelay, eps,
+                                  int(bool(inverse_power)), nchunk, stream_ptr()), "eamd_wpd_cov")
+    return Rf
+
+
+def wpd_cov_bwd(y, gRf, power, lens, btaps, bdelay, eps=1e-10, inverse_power=True, out=None):
+    """gRf [B,F,N,N,2] float64, the cotangent of Rf -> gpower [B,T,F] (eamd_wpd_cov_bwd)"""
+    B, T, Cn, F, _ = y.shape
+    wpd_check_shape(Cn, btaps, bdelay)
+    N = Cn * (btaps + 1)
+    assert power.shape == (B, T, F)
+    _wpd_f64(gRf, (B, F, N, N, 2))
+    _bf_f32(y, power)
+    lens = _wpe_lens(lens, B, y.device)
+    gpower = torch.empty_like(power) if out is None else out
+    assert gpower.shape == power.shape
+    _bf_f32(gpower)
+    ws = torch.empty(B * F * N * N * 2, device=y.device, dtype=torch.float64)
+    check(_lib.lib().eamd_wpd_cov_bwd(ptr(y), ptr(gRf), ptr(power), ptr(lens), ptr(gpower), ptr(ws), B, T, Cn, F, btaps, bdelay,
+                                      eps, int(bool(inverse_power)), stream_ptr()), "eamd_wpd_cov_bwd")
+    return gpower
+
+
+def wpd_vector(Rf, phi, u, keep=True, out=None):
+    """Rf [B,F,N,N,2] float64, phi [B,F,C,C,2], u [B,C] -> (h [B,F,N,2], fac [B,F,N,N,2], xkeep [B,F,N,C,2]); fac and xkeep,
+    float64, are what wpd_vector_bwd takes (None unless keep) (eamd_wpd_vector)"""
+    B, F, N = Rf.shape[:3]
+    Cn = u.shape[1]
+    assert N % Cn == 0 and phi.shape == (B, F, Cn, Cn, 2) and u.shape == (B, Cn)
+    btaps = N // Cn - 1
+    wpd_check_shape(Cn, btaps, 1)
+    _wpd_f64(Rf, (B, F, N, N, 2))
+    _bf_f32(phi, u)
+    if out is None:
+        out = (torch.empty(B, F, N, 2, device=Rf.device, dtype=torch.float32),
+               torch.empty(B, F, N, N, 2, device=Rf.device, dtype=torch.float64) if keep else None,
+               torch.empty(B, F, N, Cn, 2, device=Rf.device, dtype=torch.float64) if keep else None)
+    h, fac, xk = out
+    assert h.shape == (B, F, N, 2)
+    _bf_f32(h)
+    if fac is not None:
+        _wpd_f64(fac, (B, F, N, N, 2))
+    if xk is not None:
+        _wpd_f64(xk, (B, F, N, Cn, 2))
+    check(_lib.lib().eamd_wpd_vector(ptr(Rf), ptr(phi), ptr(u), ptr(h), ptr(fac), ptr(xk), B, F, Cn, btaps, stream_ptr()),
+          "eamd_wpd_vector")
+    return h, fac, xk
+
+
+def wpd_vector_bwd(fac, xk, phi, u, gh, out=None):
+    """gh [B,F,N,2] -> (gphi [B,F,C,C,2], gu [B,C], gRf [B,F,N,N,2] float64) (eamd_wpd_vector_bwd)"""
+    B, F, N = fac.shape[:3]
+    Cn = u.shape[1]
+    btaps = N // Cn - 1
+    _wpd_f64(fac, (B, F, N, N, 2))
+    _wpd_f64(xk, (B, F, N, Cn, 2))
+    assert phi.shape == (B, F, Cn, Cn, 2) and u.shape == (B, Cn) and gh.shape == (B, F, N, 2)
+    _bf_f32(phi, u, gh)
+    if out is None:
+        out = (torch.empty_like(phi), torch.empty_like(u), torch.empty_like(fac))
+    gphi, gu, gRf = out
+    assert gphi.shape == phi.shape and gu.shape == u.shape
+    _bf_f32(gphi, gu)
+    _wpd_f64(gRf, (B, F, N, N, 2))
+    ws = torch.empty(B * F * Cn, device=fac.device, dtype=torch.float64)
+    check(_lib.lib().eamd_wpd_vector_bwd(ptr(fac), ptr(xk), ptr(phi), ptr(u), ptr(gh), ptr(gphi), ptr(gu), ptr(gRf), ptr(ws), B,
+                                         F, Cn, btaps, stream_ptr()), "eamd_wpd_vector_bwd")
+    return gphi, gu, gRf
+
+
+def wpd_apply(h, y, lens, btaps, bdelay, out=None):
+    """h [B,F,N,2], y [B,T,C,F,2] -> e [B,T,F,2] = h^H (stacked frames), exactly 0 past each length (eamd_wpd_apply)"""
+    B, T, Cn, F, _ = y.shape
+    wpd_check_shape(Cn, btaps, bdelay)
+    N = Cn * (btaps + 1)
+    assert h.shape == (B, F, N, 2)
+    _bf_f32(h, y)
+    lens = _wpe_lens(lens, B, y.device)
+    e = torch.empty(B, T, F, 2, device=y.device, dtype=torch.float32) if out is None else out
+    assert e.shape == (B, T, F, 2)
+    _bf_f32(e)
+    ws = torch.empty(B * N * F * 2, device=y.device, dtype=torch.float32)
+    check(_lib.lib().eamd_wpd_apply(ptr(h), ptr(y), ptr(lens), ptr(e), ptr(ws), B, T, Cn, F, btaps, bdelay, stream_ptr()),
+          "eamd_wpd_apply")
+    return e
+
+
+def wpd_apply_bwd(ge, y, lens, btaps, bdelay, nchunk=None, out=None):
+    """ge [B,T,F,2], the cotangent of e -> gh [B,F,N,2] (eamd_wpd_apply_bwd)"""
+    B, T, Cn, F, _ = y.shape
+    wpd_check_shape(Cn, btaps, bdelay)
+    N = Cn * (btaps + 1)
+    assert ge.shape == (B, T, F, 2)
+    _bf_f32(ge, y)
+    lens = _wpe_lens(lens, B, y.device)
+    nchunk = wpd_nchunk(B, T, Cn, F, btaps, backward=True) if nchunk is None else nchunk
+    gh = torch.empty(B, F, N, 2, device=y.device, dtype=torch.float32) if out is None else out
+    assert gh.shape == (B, F, N, 2)
+    _bf_f32(gh)
+    ws = torch.empty(nchunk * B * F * N * 2, device=y.device, dtype=torch.float64)
+    check(_lib.lib().eamd_wpd_apply_bwd(ptr(ge), ptr(y), ptr(lens), ptr(gh), ptr(ws), B, T, Cn, F, btaps, bdelay, nchunk,
+                                        stream_ptr()), "eamd_wpd_apply_bwd")
+    return gh
+
+
 # ---- CTC -----------------------------------------------------------------------------------------
 def ctc_loss(acts_btv, ys_pad, ilens, blank=0, ignore_id=-1, grad_scale=1.0, want_grad=True, time_major=False,
              keep_workspace=False):

@@ -1388,6 +1388,44 @@ int eamd_wpe_bwd(const float* y, const float* x, const float* gx, const float* p
                  float* gpower, void* workspace, int B, int T, int C, int F, int taps, int delay, float eps, int inverse_power,
                  int nchunk, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * WPD convolutional beamformer (Nakatani and Kinoshita 2019; the reference's espnet2/enh/layers/conv_beamformer.py) and
+ * the MPDR covariance, csrc/wpd.hip.  y, power, lens as for WPE; K = btaps >= 0, D = bdelay >= 1, N = (K + 1) C <=
+ * EAMD_WPE_MAX_UNKNOWNS (more: EAMD_EUNSUPPORTED).  Per (b, f), n = lens[b], t0 = D + K - 1 and the stacked vector
+ * v_t[c] = y[t, c], v_t[(k + 1) C + c] = y[t - D - k, c] (0 before frame 0):
+ *   Rf = sum_{t0 <= t < n} w_t v_t v_t^H,   w_t as for WPE (power == NULL: w_t = 1; with K = 0 that is MPDR's covariance)
+ *   X = Rf^-1 E (E: the first C columns of I_N),  M = X Phi,  tau = tr(M[:C]) + 1e-15,  h = M u / tau
+ *   e_t = h^H v_t for t < n, 0 for t >= n
+ * The sums stop at lens[b], like WPE's.  Sums and the solve are fp64 and Rf stays fp64 in memory; no atomics, time chunks
+ * as for WPE.  NULL or non-positive arguments: EAMD_EINVAL before any launch.
+ * ------------------------------------------------------------------------------------------ */
+/* Rf [B,F,N,N] complex double, exactly Hermitian.  workspace: nchunk B F N N 16 bytes. */
+int eamd_wpd_cov(const float* y, const float* power, const int32_t* lens, double* Rf, void* workspace, int B, int T, int C,
+                 int F, int btaps, int bdelay, float eps, int inverse_power, int nchunk, void* stream);
+/* gpower [B,T,F] from gRf [B,F,N,N] complex double, the cotangent of Rf as a full matrix (y gets none):
+ * gw_t = Re(v_t^H gRf v_t) for t0 <= t < n, gpower_t = -gw_t / power_t^2 where power_t > eps (inverse_power == 0: gw_t),
+ * 0 elsewhere.  workspace: B F N N 16 bytes. */
+int eamd_wpd_cov_bwd(const float* y, const double* gRf, const float* power, const int32_t* lens, float* gpower, void* workspace,
+                     int B, int T, int C, int F, int btaps, int bdelay, float eps, int inverse_power, void* stream);
+/* Rf as above (its upper triangle is read), phi [B,F,C,C,2] fp32, u [B,C] real -> h [B,F,N,2] fp32.  LDL^H without
+ * pivoting; a pivot that is zero, negative or not finite takes reciprocal 0, so an all-zero bin gives exactly 0.
+ * fac [B,F,N,N] and xkeep [B,F,N,C] complex double (NULL: not kept) are the factor (as eamd_wpe_taps writes it) and X,
+ * which eamd_wpd_vector_bwd takes.  More than 160 KiB of LDS (N = 64 with C > 19): EAMD_EUNSUPPORTED. */
+int eamd_wpd_vector(const double* Rf, const float* phi, const float* u, float* h, double* fac, double* xkeep, int B, int F, int C,
+                    int btaps, void* stream);
+/* gh [B,F,N,2] -> gphi [B,F,C,C,2], gu [B,C], gRf [B,F,N,N] complex double:  gv = gh / conj(tau),
+ * gtau = -(sum_i gh_i conj(h_i)) / conj(tau), gM = gv u^T + gtau E, gu = Re(M^H gv) summed over f in order, gphi = X^H gM,
+ * gX = gM Phi^H, Z = Rf^-1 gX from the kept factor, gRf = -Z X^H.  workspace: B F C 8 bytes. */
+int eamd_wpd_vector_bwd(const double* fac, const double* xkeep, const float* phi, const float* u, const float* gh, float* gphi,
+                        float* gu, double* gRf, void* workspace, int B, int F, int C, int btaps, void* stream);
+/* e [B,T,F,2] = h^H v_t, exact zeros for t >= n.  workspace: B N F 8 bytes. */
+int eamd_wpd_apply(const float* h, const float* y, const int32_t* lens, float* e, void* workspace, int B, int T, int C, int F,
+                   int btaps, int bdelay, void* stream);
+/* gh [B,F,N,2] = sum_{t < n} conj(ge_t) v_t, the time axis in nchunk chunks added in order.  workspace: nchunk B F N 16
+ * bytes. */
+int eamd_wpd_apply_bwd(const float* ge, const float* y, const int32_t* lens, float* gh, void* workspace, int B, int T, int C,
+                       int F, int btaps, int bdelay, int nchunk, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
