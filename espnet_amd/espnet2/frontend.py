@@ -84,6 +84,7 @@ class Stft(torch.nn.Module):
             raise ValueError(f"{window} window is not implemented")
         self.window = window
         self._basis = None
+        self._inverse = {}
 
     def extra_repr(self):
         return (f"n_fft={self.n_fft}, win_length={self.win_length}, hop_length={self.hop_length}, "
@@ -155,6 +156,69 @@ class Stft(torch.nn.Module):
         rows = out.view(-1, (out.numel() // keep.numel()))
         out = ops.mask_rows(rows, ops.h2d_cached("stft_keep", keep.contiguous().numpy().reshape(-1), out.device)).view(out.shape)
         return out, olens
+
+    def inverse_basis(self, device, window=None):
+        """-> (inv_basis [n_fft, 2F], bwd_basis [2F, n_fft], synthesis window [n_fft] on the device, the same on the host),
+        both matrices in the [N, K] layout of eamd_gemm's right operand.
+
+        inv_basis is the transpose of b [2F, n_fft], the inverse DFT of one frame on the interleaved (re, im) spectrum:
+        rows 2j / 2j+1 of b = c_j/N cos(2 pi j k / N) / -c_j/N sin(2 pi j k / N) with c_0 = c_{N/2} = 1 and every other
+        c_j = 2; the imaginary parts of DC and Nyquist drop out, as in a c2r transform.  A two-sided spectrum is rebuilt
+        from its bins 0 .. N/2 in the same way (c_j = 0 above N/2): torch.istft, which the reference calls, slices the
+        upper bins off.  Times N^0.5 with `normalized`.  bwd_basis is b with the synthesis window folded in, the right
+        operand of the backward's GEMM.
+        window: None = rectangular ones of win_length centred in n_fft (what `inverse` documents), the name of a torch
+        window function, or win_length / n_fft values.  The few bases in use are kept, keyed by the device and the
+        window's values (a window given as values on the device is copied back to form the key)."""
+        N, F = self.n_fft, self.n_freq
+        if window is None:
+            w = np.ones(self.win_length)
+        elif isinstance(window, str):
+            w = getattr(torch, f"{window}_window")(self.win_length, dtype=torch.float64).numpy()
+        else:
+            w = torch.as_tensor(window).detach().double().cpu().numpy()
+        key = (str(torch.device(device)), w.tobytes())
+        if key not in self._inverse:
+            if w.shape == (N,):
+                wf = w.copy()
+            else:
+                if w.shape != (self.win_length,):
+                    raise ValueError(f"the synthesis window needs win_length={self.win_length} or n_fft={N} values")
+                left = (N - self.win_length) // 2
+                wf = np.zeros(N)
+                wf[left:left + self.win_length] = w
+            j = np.arange(F)
+            ang = 2.0 * math.pi * ((j[:, None] * np.arange(N)[None, :]) % N) / N
+            c = np.where(j <= N // 2, 2.0, 0.0)              # bins above N/2 of a two-sided spectrum are not read
+            c[0] = 1.0
+            if N % 2 == 0:
+                c[N // 2] = 1.0
+            scale = c / N * (N ** 0.5 if self.normalized else 1.0)
+            b = np.empty((2 * F, N))
+            b[0::2] = np.cos(ang) * scale[:, None]
+            b[1::2] = -np.sin(ang) * scale[:, None]
+            b[1] = 0.0
+            if N % 2 == 0:
+                b[2 * (N // 2) + 1] = 0.0
+            f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.float32)).to(device)  # noqa: E731
+            if len(self._inverse) >= 8:
+                self._inverse.clear()
+            self._inverse[key] = (f32(b.T), f32(b * wf[None, :]), f32(wf), wf.astype(np.float32).astype(np.float64))
+        return self._inverse[key]
+
+    def inverse(self, input, ilens=None, window=None):
+        """input (B, T, F, 2) -> (wavs (B, max(ilens)), ilens); stft.py:116-157 over ops.istft, differentiable in input.
+
+        The reference hands torch.istft NO window, so its synthesis window is rectangular: ones of win_length, centred in
+        n_fft, also when the analysis window is Hann.  window=None reproduces that literally: with hop = n_fft / 4 and a
+        Hann analysis window the result is 0.5 x, not x (SI-SNR does not see the scale).  window="hann" (or any window
+        values) gives the true inverse of `forward`."""
+        assert input.dim() == 4 and input.shape[-1] == 2 and input.shape[2] == self.n_freq, tuple(input.shape)
+        length = None if ilens is None else int(max(int(v) for v in ilens))
+        inv_basis, bwd_basis, w, w_host = self.inverse_basis(input.device, window)
+        wavs = ops.istft(input.contiguous().float(), inv_basis, bwd_basis, w, self.hop_length, self.center, length,
+                         window_host=w_host)
+        return wavs, ilens
 
 
 class LogMel(torch.nn.Module):

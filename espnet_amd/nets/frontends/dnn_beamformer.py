@@ -75,8 +75,23 @@ class DNN_Beamformer(torch.nn.Module):
             if mask_speech.size(1) < T:
                 mask_speech = torch.nn.functional.pad(mask_speech, [0, 0, 0, 0, 0, T - mask_speech.size(1)], value=0)
         if return_all:
-            return enhanced, ilens, mask_speech, dict(psd_speech=psd[0], u=u, ws=ws, **extra)
+            return enhanced, ilens, mask_speech, dict(psd_speech=psd[0], u=u, ws=ws, logits=logits, **extra)
         return enhanced, ilens, mask_speech
+
+    def predict_mask_logits(self, data, ilens):
+        """data [B,T,C,F,2], ilens [B] -> the mask estimator's logits [nmask, B, Tm, C, F], Tm = max(ilens), in the
+        layout of the masks the reference's predict_mask returns"""
+        return self.mask.logits(data, ilens).permute(0, 1, 3, 2, 4).contiguous()
+
+    def predict_mask(self, data, ilens):
+        """espnet2/enh/layers/dnn_beamformer.py:272-287: only the masks, for training them against ideal-mask labels
+        -> (tuple of nmask masks (B, T, C, F), zero for Tm <= t < T, ilens)"""
+        logits = self.predict_mask_logits(data, ilens)
+        masks, _ = ops.EnhMaskFn.apply(logits, None, ops.ENH_ACTS["sigmoid"], False)
+        T = data.shape[1]
+        if masks.shape[2] < T:
+            masks = torch.nn.functional.pad(masks, [0, 0, 0, 0, 0, T - masks.shape[2]], value=0)
+        return tuple(masks.unbind(0)), ilens
 
 
 class AttentionReference(torch.nn.Module):

@@ -3750,3 +3750,297 @@ def fold1d(dcol, B, T, Cc, k):
     dx = torch.empty(B * T, Cc, device=dcol.device, dtype=torch.float32)
     check(_lib.lib().eamd_fold1d(ptr(dcol), ptr(dx), B, T, Cc, k, stream_ptr()), "eamd_fold1d")
     return dx
+
+
+# ---- speech enhancement training (csrc/enh.hip; see include/espnet_amd.h) ----------------------------------------------
+ENH_ACTS = {"sigmoid": 0, "relu": 1, "tanh": 2, "none": 3}
+ENH_MASK, ENH_MAG, ENH_SPEC, ENH_REAL = 0, 1, 2, 3
+ENH_LABELS = {"IBM": 0, "IRM": 1, "IAM": 2, "PSM": 3, "NPSM": 4, "PSM^2": 5}
+ENH_SNR_ZEROMEAN, ENH_SNR_L2NORM = 0, 1
+ENH_CHUNK = 4096             # elements of one utterance per workgroup of the reduction kernels
+ENH_MAX_SPK = 3
+ISTFT_MAX_OVERLAP = 16
+
+
+def _enh_f32(*ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.EamdError("enhancement kernels take contiguous float32 tensors, complex as a trailing (re, im) axis")
+
+
+def _enh_out(out, shape, device, dtype=torch.float32):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous(), (tuple(out.shape), tuple(shape))
+    return out
+
+
+_istft_env_seen = {}
+
+
+def istft_check(window, T, n_fft, hop, center, length):
+    """the limits of the overlap-add kernel, and torch.istft's check of the window envelope over the written range, on the
+    host (the envelope depends on the window and the shape alone) -> the number of samples written before the zeros"""
+    if hop < 1 or n_fft > ISTFT_MAX_OVERLAP * hop:
+        raise _lib.EamdError(f"istft: n_fft / hop_length = {n_fft}/{hop} > {ISTFT_MAX_OVERLAP} overlapping frames "
+                             f"(code {_lib.EAMD_EUNSUPPORTED})")
+    import numpy as np
+    w = np.asarray(window, dtype=np.float64)
+    assert w.shape == (n_fft,)
+    full = hop * (T - 1) + n_fft
+    start = n_fft // 2 if center else 0
+    end = min(start + length, full)
+    if end <= start:
+        raise ValueError(f"istft: no sample to write (T={T}, n_fft={n_fft}, hop={hop}, length={length})")
+    key = (w.tobytes(), T, hop, start, end)
+    if key not in _istft_env_seen:
+        env = np.zeros(full)
+        for t in range(T):
+            env[t * hop:t * hop + n_fft] += w * w
+        if len(_istft_env_seen) > 64:
+            _istft_env_seen.clear()
+        _istft_env_seen[key] = float(np.abs(env[start:end]).min())
+    if not _istft_env_seen[key] > 1e-11:                      # torch.istft: "window overlap add min: 1"
+        raise RuntimeError("istft(n_fft=%d, hop_length=%d): window overlap add min: %g" % (n_fft, hop, _istft_env_seen[key]))
+    return end - start
+
+
+def istft_ola(frames, window, hop, center, length, out=None):
+    """frames [B,T,n_fft], synthesis window [n_fft] -> wav [B,length] (eamd_istft_ola); the caller has run istft_check"""
+    B, T, N = frames.shape
+    _enh_f32(frames, window)
+    assert window.shape == (N,)
+    wav = _enh_out(out, (B, length), frames.device)
+    check(_lib.lib().eamd_istft_ola(ptr(frames), ptr(window), ptr(wav), B, T, N, hop, int(bool(center)), length, stream_ptr()),
+          "eamd_istft_ola")
+    return wav
+
+
+def istft_rows(T, n_fft, hop):
+    """rows of `hop` samples per utterance of the backward's buffer"""
+    return T - 1 + -(-n_fft // hop)
+
+
+def istft_ola_bwd(dwav, window, T, hop, center, out=None):
+    """dwav [B,length] -> g, flat [B * istft_rows * hop + n_fft] (eamd_istft_ola_bwd)"""
+    B, length = dwav.shape
+    N = window.numel()
+    _enh_f32(dwav, window)
+    rpu = istft_rows(T, N, hop)
+    g = _enh_out(out, (B * rpu * hop + N,), dwav.device)
+    check(_lib.lib().eamd_istft_ola_bwd(ptr(dwav), ptr(window), ptr(g), B, T, N, hop, int(bool(center)), length, rpu,
+                                        stream_ptr()), "eamd_istft_ola_bwd")
+    return g
+
+
+class IstftFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, inv_basis, bwd_basis, window, hop, center, length):
+        B, T, F, _ = spec.shape
+        N, F2 = inv_basis.shape
+        frames = torch.empty(B * T, N, device=spec.device, dtype=torch.float32)
+        gemm(spec, inv_basis, frames, B * T, N, F2, F2, F2, N, precision=0)
+        ctx.save_for_backward(bwd_basis, window)
+        ctx.dims = (B, T, F, hop, center)
+        return istft_ola(frames.view(B, T, N), window, hop, center, length)
+
+    @staticmethod
+    def backward(ctx, dwav):
+        bwd_basis, window = ctx.saved_tensors
+        B, T, F, hop, center = ctx.dims
+        N = window.numel()
+        rpu = istft_rows(T, N, hop)
+        g = istft_ola_bwd(dwav.contiguous(), window, T, hop, center)
+        out = torch.empty(B * rpu, 2 * F, device=dwav.device, dtype=torch.float32)
+        # g is read in place as overlapping rows (leading dimension hop), as Stft.spectrum reads the padded waveform
+        gemm(g, bwd_basis, out, B * rpu, 2 * F, N, hop, N, 2 * F, precision=0)
+        return out.view(B, rpu, F, 2)[:, :T].contiguous(), None, None, None, None, None, None
+
+
+def istft(spec, inv_basis, bwd_basis, window, hop, center=True, length=None, window_host=None):
+    """spec [B,T,F,2] -> wav [B,length], differentiable in spec.  inv_basis [n_fft, 2F]: the inverse DFT of one frame,
+    frames = spec @ inv_basis^T (espnet2.frontend.Stft.inverse_basis); bwd_basis [2F, n_fft]: its transpose with the
+    synthesis window folded in (both in the [N, K] layout of eamd_gemm's right operand);
+    window [n_fft]: the synthesis window, on the device (window_host: the same on the host, which saves the envelope check a
+    copy back).  length None: every sample the frames cover (less the centre
+    padding).  One GEMM and one overlap-add kernel; backward one kernel and one GEMM."""
+    B, T, F, two = spec.shape
+    N, F2 = inv_basis.shape
+    assert two == 2 and F2 == 2 * F and bwd_basis.shape == (F2, N) and window.shape == (N,)
+    _enh_f32(spec, inv_basis, bwd_basis, window)
+    if length is None:
+        length = hop * (T - 1) + N - (2 * (N // 2) if center else 0)
+    istft_check(window.cpu().numpy() if window_host is None else window_host, T, N, hop, center, int(length))
+    return IstftFn.apply(spec, inv_basis, bwd_basis, window, hop, bool(center), int(length))
+
+
+def enh_mask_apply(logits, X, act, want_mask=True, want_spec=True, out=None):
+    """logits [S, ...], X [..., 2] or None -> (mask [S, ...] = act(logits) or None, P [S, ..., 2] or None) (eamd_enh_mask_apply)"""
+    S = logits.shape[0]
+    Bn = logits[0].numel()
+    _enh_f32(logits, X)
+    want_spec = want_spec and X is not None
+    assert X is None or tuple(X.shape) == tuple(logits.shape[1:]) + (2,)
+    mask, P = out if out is not None else (None, None)
+    mask = _enh_out(mask, logits.shape, logits.device) if want_mask else None
+    P = _enh_out(P, tuple(logits.shape) + (2,), logits.device) if want_spec else None
+    check(_lib.lib().eamd_enh_mask_apply(ptr(logits), ptr(X), ptr(mask), ptr(P), S, Bn, act, stream_ptr()), "eamd_enh_mask_apply")
+    return mask, P
+
+
+def enh_mask_apply_bwd(logits, X, gmask, gP, act, out=None):
+    """-> dlogits [S, ...] (eamd_enh_mask_apply_bwd); gmask or gP may be None"""
+    S = logits.shape[0]
+    Bn = logits[0].numel()
+    _enh_f32(logits, X, gmask, gP)
+    dl = _enh_out(out, logits.shape, logits.device)
+    check(_lib.lib().eamd_enh_mask_apply_bwd(ptr(logits), ptr(X), ptr(gmask), ptr(gP), ptr(dl), S, Bn, act, stream_ptr()),
+          "eamd_enh_mask_apply_bwd")
+    return dl
+
+
+class EnhMaskFn(torch.autograd.Function):
+    """(logits [S, ...], X [..., 2] or None) -> (act(logits), X act(logits) |X| / (|X| + 10e-12) or None); X is data"""
+
+    @staticmethod
+    def forward(ctx, logits, X, act, want_spec):
+        ctx.set_materialize_grads(False)
+        logits = logits.contiguous()
+        mask, P = enh_mask_apply(logits, X, act, True, want_spec)
+        ctx.save_for_backward(logits, X)
+        ctx.act = act
+        return mask, P
+
+    @staticmethod
+    def backward(ctx, gmask, gP):
+        logits, X = ctx.saved_tensors
+        if gmask is None and gP is None:
+            return None, None, None, None
+        gmask = None if gmask is None else gmask.contiguous()
+        gP = None if gP is None else gP.contiguous()
+        return enh_mask_apply_bwd(logits, X, gmask, gP, ctx.act), None, None, None
+
+
+def enh_nchunk(n):
+    return -(-n // ENH_CHUNK)
+
+
+def enh_check_spk(S):
+    if not 1 <= S <= ENH_MAX_SPK:
+        raise _lib.EamdError(f"the permutation kernels take 1 to {ENH_MAX_SPK} speakers, not {S} (code {_lib.EAMD_EUNSUPPORTED})")
+
+
+def enh_pair_tf(est, ref, mix, mode, label=0, act=3, out=None):
+    """pair [B,S,S] float64: pair[b,s,t] = mean squared error of (reference s, estimate t) over the inner extent (eamd_enh_pair_tf).
+    mode ENH_MASK: est [S,B,...] real (act is applied), ref [S,B,...,2] and mix [B,...,2] spectra, the reference is the
+    ideal-mask label `label`; ENH_MAG / ENH_SPEC: est, ref [S,B,...,2]; ENH_REAL: est, ref [S,B,...]"""
+    S, B = est.shape[:2]
+    enh_check_spk(S)
+    cplx = mode in (ENH_MAG, ENH_SPEC)
+    n = est[0, 0].numel() // (2 if cplx else 1)
+    _enh_f32(est, ref, mix)
+    assert ref.numel() == S * B * n * (1 if mode == ENH_REAL else 2), (tuple(est.shape), tuple(ref.shape))
+    assert mode != ENH_MASK or (mix is not None and mix.numel() == B * n * 2)
+    nchunk = enh_nchunk(n)
+    pair = _enh_out(out, (B, S, S), est.device, torch.float64)
+    ws = torch.empty(B * nchunk * S * S, device=est.device, dtype=torch.float64)
+    check(_lib.lib().eamd_enh_pair_tf(ptr(est), ptr(ref), ptr(mix), ptr(pair), ptr(ws), S, B, n, nchunk, mode, label, act,
+                                      stream_ptr()), "eamd_enh_pair_tf")
+    return pair
+
+
+def enh_pair_tf_bwd(est, ref, mix, perm_index, cot, mode, label=0, act=3, out=None):
+    """the gradient of the estimate under the permutations perm_index [B] int64, cot [B] the cotangent of the loss per
+    utterance (eamd_enh_pair_tf_bwd)"""
+    S, B = est.shape[:2]
+    enh_check_spk(S)
+    n = est[0, 0].numel() // (2 if mode in (ENH_MAG, ENH_SPEC) else 1)
+    _enh_f32(est, ref, mix, cot)
+    assert perm_index.dtype == torch.int64 and perm_index.numel() == B and cot.numel() == B and perm_index.is_contiguous()
+    dest = _enh_out(out, est.shape, est.device)
+    check(_lib.lib().eamd_enh_pair_tf_bwd(ptr(est), ptr(ref), ptr(mix), ptr(perm_index), ptr(cot), ptr(dest), S, B, n, mode,
+                                          label, act, stream_ptr()), "eamd_enh_pair_tf_bwd")
+    return dest
+
+
+def enh_pair_sisnr(est, ref, mode=ENH_SNR_ZEROMEAN, out=None):
+    """est, ref [S,B,L] -> (pair [B,S,S] float64, sums [B, 4S + S^2] float64, kept for the backward) (eamd_enh_pair_sisnr)"""
+    S, B, L = est.shape
+    enh_check_spk(S)
+    assert ref.shape == est.shape
+    _enh_f32(est, ref)
+    NV = 4 * S + S * S
+    nchunk = enh_nchunk(L)
+    pair, sums = out if out is not None else (None, None)
+    pair = _enh_out(pair, (B, S, S), est.device, torch.float64)
+    sums = _enh_out(sums, (B, NV), est.device, torch.float64)
+    ws = torch.empty(B * nchunk * NV, device=est.device, dtype=torch.float64)
+    check(_lib.lib().eamd_enh_pair_sisnr(ptr(est), ptr(ref), ptr(pair), ptr(sums), ptr(ws), S, B, L, nchunk, mode, stream_ptr()),
+          "eamd_enh_pair_sisnr")
+    return pair, sums
+
+
+def enh_pair_sisnr_bwd(est, ref, sums, perm_index, cot, mode=ENH_SNR_ZEROMEAN, out=None):
+    """-> d est [S,B,L] = a est_t + b ref_s + c per (b, t) (eamd_enh_pair_sisnr_bwd)"""
+    S, B, L = est.shape
+    enh_check_spk(S)
+    _enh_f32(est, ref, cot)
+    assert sums.dtype == torch.float64 and sums.shape == (B, 4 * S + S * S) and sums.is_contiguous()
+    assert perm_index.dtype == torch.int64 and perm_index.numel() == B and cot.numel() == B and perm_index.is_contiguous()
+    dest = _enh_out(out, est.shape, est.device)
+    check(_lib.lib().eamd_enh_pair_sisnr_bwd(ptr(est), ptr(ref), ptr(sums), ptr(perm_index), ptr(cot), ptr(dest), S, B, L, mode,
+                                             stream_ptr()), "eamd_enh_pair_sisnr_bwd")
+    return dest
+
+
+def enh_pit_pick(pair, forced=None, out=None):
+    """pair [B,S,S] float64 -> (loss [B] float32, perm_index [B] int64): the best permutation in itertools order, or `forced` [B] int64
+    (eamd_enh_pit_pick).  Nothing visits the host."""
+    B, S, S2 = pair.shape
+    assert S == S2
+    enh_check_spk(S)
+    assert pair.dtype == torch.float64 and pair.is_contiguous()
+    assert forced is None or (forced.dtype == torch.int64 and forced.numel() == B and forced.is_contiguous() and forced.is_cuda)
+    loss, perm = out if out is not None else (None, None)
+    loss = _enh_out(loss, (B,), pair.device)
+    perm = _enh_out(perm, (B,), pair.device, torch.int64)
+    check(_lib.lib().eamd_enh_pit_pick(ptr(pair), ptr(forced), ptr(loss), ptr(perm), B, S, stream_ptr()), "eamd_enh_pit_pick")
+    return loss, perm
+
+
+class EnhTFLossFn(torch.autograd.Function):
+    """(est, ref, mix) -> (loss [B] under the best or the forced permutation, perm_index [B]); gradient to est only"""
+
+    @staticmethod
+    def forward(ctx, est, ref, mix, mode, label, act, forced):
+        est = est.contiguous()
+        loss, perm = enh_pit_pick(enh_pair_tf(est, ref, mix, mode, label, act), forced)
+        ctx.save_for_backward(est, ref, mix, perm)
+        ctx.conf = (mode, label, act)
+        ctx.mark_non_differentiable(perm)
+        return loss, perm
+
+    @staticmethod
+    def backward(ctx, gloss, _gperm):
+        est, ref, mix, perm = ctx.saved_tensors
+        mode, label, act = ctx.conf
+        return enh_pair_tf_bwd(est, ref, mix, perm, gloss.contiguous(), mode, label, act), None, None, None, None, None, None
+
+
+class EnhSisnrLossFn(torch.autograd.Function):
+    """(est [S,B,L], ref [S,B,L]) -> (loss [B], perm_index [B]); gradient to est only"""
+
+    @staticmethod
+    def forward(ctx, est, ref, mode, forced):
+        est = est.contiguous()
+        pair, sums = enh_pair_sisnr(est, ref, mode)
+        loss, perm = enh_pit_pick(pair, forced)
+        ctx.save_for_backward(est, ref, sums, perm)
+        ctx.mode = mode
+        ctx.mark_non_differentiable(perm)
+        return loss, perm
+
+    @staticmethod
+    def backward(ctx, gloss, _gperm):
+        est, ref, sums, perm = ctx.saved_tensors
+        return enh_pair_sisnr_bwd(est, ref, sums, perm, gloss.contiguous(), ctx.mode), None, None, None

@@ -1426,6 +1426,61 @@ int eamd_wpd_apply(const float* h, const float* y, const int32_t* lens, float* e
 int eamd_wpd_apply_bwd(const float* ge, const float* y, const int32_t* lens, float* gh, void* workspace, int B, int T, int C,
                        int F, int btaps, int bdelay, int nchunk, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Speech enhancement training (the reference's espnet2/enh task), csrc/enh.hip: the inverse STFT's overlap-add, mask
+ * application, the pairwise criteria of ESPnetEnhancementModel and the permutation pick.  Spectra are interleaved
+ * (re, im) fp32; n is the flat inner size of one utterance (T F or T C F); S = 1, 2 or 3 speakers (other S:
+ * EAMD_EUNSUPPORTED).  Elements are evaluated in fp64 from the fp32 operands (the activation itself in fp32), sums are
+ * fp64, in two stages of fixed order: chunks of 4096 elements per utterance, nchunk = ceil(n / 4096) (anything else:
+ * EAMD_EINVAL), then the chunks in order.  No atomics: a launch repeats bit for bit.  NULL or non-positive arguments:
+ * EAMD_EINVAL before any launch.  The pair matrices stay fp64 in memory (S S numbers per utterance): the loss is rounded once.
+ * activation ids: 0 sigmoid, 1 relu, 2 tanh, 3 none.
+ * ------------------------------------------------------------------------------------------ */
+/* frames [B,T,n_fft] (the inverse DFT of every frame, an eamd_gemm) -> wav [B,length]:
+ * wav[b,m] = sum_t w[p - t hop] frames[b,t,p - t hop] / sum_t w[p - t hop]^2 over the frames t covering p = m + pad,
+ * pad = n_fft / 2 with center, else 0, for m < min(length, hop (T - 1) + n_fft - pad); zeros from there up to length.
+ * window [n_fft] is the synthesis window; the caller checks its envelope (torch.istft's 1e-11).  n_fft > 16 hop:
+ * EAMD_EUNSUPPORTED. */
+int eamd_istft_ola(const float* frames, const float* window, float* wav, int B, int T, int n_fft, int hop, int center, int length,
+                   void* stream);
+/* dwav [B,length] -> g [B * rows_per_utt * hop + n_fft]: g[b * rows_per_utt * hop + p] = dwav[b,p - pad] / envelope[p] on
+ * the written range, 0 elsewhere and in the tail; rows_per_utt hop >= hop (T - 1) + n_fft.  The frame gradient is
+ * w[k] g[b, t hop + k]: eamd_gemm reads g in place as overlapping rows of leading dimension hop. */
+int eamd_istft_ola_bwd(const float* dwav, const float* window, float* g, int B, int T, int n_fft, int hop, int center, int length,
+                       int rows_per_utt, void* stream);
+/* logits [S,Bn], X [Bn,2] -> mask [S,Bn] = act(logits) and P [S,Bn,2] = X mask |X| / (|X| + 10e-12) (tf_mask_net.py:94-116);
+ * either output may be NULL, X may be NULL without P. */
+int eamd_enh_mask_apply(const float* logits, const float* X, float* mask, float* P, int S, int64_t Bn, int act, void* stream);
+/* dlogits [S,Bn] = act'(logits) (gmask + Re(conj(X) gP) |X| / (|X| + 10e-12)); either cotangent may be NULL. */
+int eamd_enh_mask_apply_bwd(const float* logits, const float* X, const float* gmask, const float* gP, float* dlogits, int S,
+                            int64_t Bn, int act, void* stream);
+/* pair [B,S,S] fp64: pair[b,s,t] = the mean over n of the squared error between reference s and estimate t.
+ * mode 0 MASK: est [S,B,n] real, the estimate is act(est); the reference is the ideal-mask label of ref [S,B,n,2] against
+ *   mix [B,n,2], formed on the fly (espnet_model.py:47-104, eps 10e-8); label 0 IBM, 1 IRM, 2 IAM, 3 PSM, 4 NPSM (clamped to
+ *   [-1, 1] like PSM, as the reference does), 5 PSM^2.
+ * mode 1 MAG: (|ref| - |est|)^2, both [S,B,n,2].   mode 2 SPEC: |ref - est|^2, both [S,B,n,2].
+ * mode 3 REAL: (ref - est)^2, both real [S,B,n].   mix, label and act are read in mode 0 only.
+ * workspace: B nchunk S S 8 bytes. */
+int eamd_enh_pair_tf(const float* est, const float* ref, const float* mix, double* pair, void* workspace, int S, int B, int64_t n,
+                     int nchunk, int mode, int label, int act, void* stream);
+/* dest, shaped like est: cot[b] times the gradient of sum_s pair[b,s,perm[s]] / S with respect to the estimate, perm the
+ * permutation perm_index[b] of itertools.permutations(range(S)).  The references are data.  mode 1 takes the gradient of
+ * |est| at est = 0 as 0. */
+int eamd_enh_pair_tf_bwd(const float* est, const float* ref, const float* mix, const int64_t* perm_index, const float* cot,
+                         float* dest, int S, int B, int64_t n, int mode, int label, int act, void* stream);
+/* est, ref [S,B,L] waveforms -> pair [B,S,S] fp64 and sums [B, 4 S + S S] fp64 (sum r_s, sum r_s^2, sum e_t, sum e_t^2,
+ * sum r_s e_t), from which both criteria follow in closed form: mode 0 si_snr_loss_zeromean (espnet_model.py:367-405, eps
+ * 1e-8, over the full padded L), mode 1 si_snr_loss (:348-364, L2-normalised, no eps).  workspace: B nchunk (4 S + S S) 8
+ * bytes, nchunk = ceil(L / 4096). */
+int eamd_enh_pair_sisnr(const float* est, const float* ref, double* pair, double* sums, void* workspace, int S, int B, int64_t L,
+                        int nchunk, int mode, void* stream);
+/* dest [S,B,L] = a est_t + b ref_s + c with s the reference paired with t under perm_index[b]; a, b, c from sums and cot[b]. */
+int eamd_enh_pair_sisnr_bwd(const float* est, const float* ref, const double* sums, const int64_t* perm_index, const float* cot,
+                            float* dest, int S, int B, int64_t L, int mode, void* stream);
+/* pair [B,S,S] fp64 -> loss [B] fp32 = min over the permutations of range(S), itertools order, first minimum, of sum_s pair[b,s,perm[s]] / S, and its
+ * index perm_index [B]; forced != NULL: loss[b] of permutation forced[b] alone, which is copied to perm_index. */
+int eamd_enh_pit_pick(const double* pair, const int64_t* forced, float* loss, int64_t* perm_index, int B, int S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
