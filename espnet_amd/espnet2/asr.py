@@ -2,6 +2,7 @@
 signatures and `ESPnetASRModel.forward(speech, speech_lengths, text, text_lengths) -> (loss, stats, weight)`.
 
 reference: espnet2/asr/encoder/conformer_encoder.py:39-255, espnet2/asr/encoder/transformer_encoder.py:28-175,
+espnet2/asr/encoder/e_branchformer_encoder.py,
 espnet2/asr/decoder/transformer_decoder.py:31-275, espnet2/asr/ctc.py:6-111,
 espnet2/asr/espnet_model.py:35-290, espnet2/train/abs_espnet_model.py,
 registries: espnet2/tasks/asr.py:77-101 (`encoder_choices`, `decoder_choices`).
@@ -12,6 +13,7 @@ import torch
 
 from .. import functional as F_
 from .. import ops
+from ..nets import branchformer as EB
 from ..nets import modules as M
 from ..nets.scorer_interface import BatchScorerInterface
 
@@ -99,6 +101,52 @@ class TransformerEncoder(AbsEncoder):
         xs_pad, masks = self.encoders(xs_pad, masks)
         if self.normalize_before:
             xs_pad = self.after_norm(xs_pad)
+        olens = torch.tensor(M.embed_output_lengths(self.embed, il, self._tin), dtype=torch.int64).to(xs_pad.device)
+        return xs_pad, olens, None
+
+
+class EBranchformerEncoder(AbsEncoder):
+    """reference: espnet2/asr/encoder/e_branchformer_encoder.py (EBranchformerEncoder); same arguments, except that
+    rel_pos_type defaults to "legacy", the relative-position form this project implements (nets/branchformer.py)."""
+
+    def __init__(self, input_size, output_size=256, attention_heads=4, attention_layer_type="rel_selfattn",
+                 pos_enc_layer_type="rel_pos", rel_pos_type="legacy", cgmlp_linear_units=2048, cgmlp_conv_kernel=31,
+                 use_linear_after_conv=False, gate_activation="identity", num_blocks=12, dropout_rate=0.1,
+                 positional_dropout_rate=0.1, attention_dropout_rate=0.0, input_layer="conv2d", zero_triu=False,
+                 padding_idx=-1, layer_drop_rate=0.0, max_pos_emb_len=5000, use_ffn=False, macaron_ffn=False,
+                 ffn_activation_type="swish", linear_units=2048, positionwise_layer_type="linear", merge_conv_kernel=3,
+                 interctc_layer_idx=None, interctc_use_conditioning=False):
+        super().__init__()
+        assert not zero_triu, "zero_triu is not on the HIP path"
+        self._output_size = output_size
+        enc = EB.EBranchformerEncoder(
+            idim=input_size, attention_dim=output_size, attention_heads=attention_heads,
+            attention_layer_type=attention_layer_type, pos_enc_layer_type=pos_enc_layer_type, rel_pos_type=rel_pos_type,
+            cgmlp_linear_units=cgmlp_linear_units, cgmlp_conv_kernel=cgmlp_conv_kernel,
+            use_linear_after_conv=use_linear_after_conv, gate_activation=gate_activation, num_blocks=num_blocks,
+            dropout_rate=dropout_rate, positional_dropout_rate=positional_dropout_rate,
+            attention_dropout_rate=attention_dropout_rate, input_layer=input_layer, padding_idx=padding_idx,
+            layer_drop_rate=layer_drop_rate, use_ffn=use_ffn, macaron_ffn=macaron_ffn, ffn_activation_type=ffn_activation_type,
+            linear_units=linear_units, positionwise_layer_type=positionwise_layer_type, merge_conv_kernel=merge_conv_kernel,
+            interctc_layer_idx=interctc_layer_idx, interctc_use_conditioning=interctc_use_conditioning)
+        # same attribute names as the reference class => identical state_dict keys
+        self.embed, self.encoders, self.after_norm = enc.embed, enc.encoders, enc.after_norm
+
+    def output_size(self):
+        return self._output_size
+
+    def forward(self, xs_pad, ilens, prev_states=None):
+        il = _lens(ilens)
+        self._tin = xs_pad.size(1)
+        masks = M.make_non_pad_mask(il, xs_pad.size(1))[:, None, :].to(xs_pad.device).to(torch.uint8)
+        if isinstance(self.embed, M.Conv2dSubsampling):
+            xs_pad, masks = self.embed(xs_pad, masks)
+        else:
+            xs_pad = self.embed(xs_pad)
+        xs_pad, masks = self.encoders(xs_pad, masks)
+        if isinstance(xs_pad, tuple):
+            xs_pad = xs_pad[0]
+        xs_pad = self.after_norm(xs_pad)
         olens = torch.tensor(M.embed_output_lengths(self.embed, il, self._tin), dtype=torch.int64).to(xs_pad.device)
         return xs_pad, olens, None
 
@@ -313,6 +361,7 @@ def register_choices(asr_task_module):
     --decoder transformer_mi355x` selects them."""
     asr_task_module.encoder_choices.classes["conformer_mi355x"] = ConformerEncoder
     asr_task_module.encoder_choices.classes["transformer_mi355x"] = TransformerEncoder
+    asr_task_module.encoder_choices.classes["e_branchformer_mi355x"] = EBranchformerEncoder
     asr_task_module.decoder_choices.classes["transformer_mi355x"] = TransformerDecoder
     from .rnn import RNNDecoder, RNNEncoder, VGGRNNEncoder
     asr_task_module.decoder_choices.classes["rnn_mi355x"] = RNNDecoder

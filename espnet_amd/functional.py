@@ -1103,6 +1103,61 @@ class ConvModuleBlockFn(torch.autograd.Function):
 
 
 # =================================================================================================
+# E-Branchformer: the cgMLP's convolutional spatial gating unit and the merge's depthwise convolution
+# reference: espnet2/asr/layers/cgmlp.py (ConvolutionalSpatialGatingUnit), espnet2/asr/encoder/e_branchformer_encoder.py
+# =================================================================================================
+class CSGUFn(torch.autograd.Function):
+    """y [B, T, Ch] = GELU(a_r) * conv(LayerNorm(GELU(a_g))) from channel_proj1's pre-activation a [B, T, 2*Ch] in one
+    statistics pass and one tile kernel (csrc/cgmlp.hip); backward recomputes from a and the [B*T, 2] row statistics"""
+
+    @staticmethod
+    def forward(ctx, a, ln_w, ln_b, conv_w, conv_b, eps):
+        B, T, C2 = a.shape
+        Ch, K = C2 // 2, conv_w.shape[-1]
+        a2 = a.contiguous()
+        y, stats = ops.csgu_fwd(a2, ln_w, ln_b, conv_w, conv_b, eps, B, T, Ch, K)
+        ctx.save_for_backward(a2, stats)
+        ctx.pr = GradSink.use((ln_w, ln_b, conv_w, conv_b))
+        return y.view(B, T, Ch)
+
+    @staticmethod
+    def backward(ctx, dy):
+        a2, stats = ctx.saved_tensors
+        ln_w, ln_b, conv_w, conv_b = ctx.pr
+        B, T, C2 = a2.shape
+        Ch, K = C2 // 2, conv_w.shape[-1]
+        sink = GradSink([ln_w, ln_b, conv_w, conv_b])
+        da = ops.csgu_bwd(dy.contiguous(), a2, stats, ln_w, ln_b, conv_w, conv_b, sink.buf(2), sink.buf(3), sink.buf(0),
+                          sink.buf(1), B, T, Ch, K)
+        return (da.view(B, T, C2),) + sink.results() + (None,)
+
+
+class DepthwiseConvFn(torch.autograd.Function):
+    """torch.nn.Conv1d(C, C, K, 1, (K-1)//2, groups=C) along time on a channels-last [B, T, C] activation (the generic
+    eamd_dwconv_* kernels: the E-Branchformer's depthwise_conv_fusion at C = 2 * size)"""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        B, T, Cc = x.shape
+        x2 = x.contiguous()
+        ctx.save_for_backward(x2)
+        ctx.pr = GradSink.use((w, b))
+        return ops.dwconv_fwd(x2, w, b, B, T, Cc, w.shape[-1]).view(B, T, Cc)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x2,) = ctx.saved_tensors
+        w, b = ctx.pr
+        B, T, Cc = x2.shape
+        K = w.shape[-1]
+        sink = GradSink([w, b])
+        dy2 = dy.contiguous()
+        dx = ops.dwconv_bwd_x(dy2, w, B, T, Cc, K)
+        ops.dwconv_bwd_w(dy2, x2, sink.buf(0), sink.buf(1), B, T, Cc, K)
+        return (dx,) + sink.results()
+
+
+# =================================================================================================
 # Conv2dSubsampling (1/4 length): conv3x3 s2 + ReLU, conv3x3 s2 + ReLU, Linear, x * sqrt(d)
 # reference: transformer/subsampling.py:14-59; embedding.py:80-91,143-161 (x * xscale)
 # params: c1_w [C,1,3,3], c1_b, c2_w [C,C,3,3], c2_b, lin_w [D, C*W2], lin_b

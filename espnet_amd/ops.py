@@ -2036,6 +2036,45 @@ def dwconv_glu_bwd_w(dy, a, dw, db, B, T, Cc, K):
           "eamd_dwconv_glu_bwd_w")
 
 
+# ---- convolutional spatial gating unit (csrc/cgmlp.hip) -------------------------------------------
+CSGU_LIMITS = "kernel_size odd in 3..31 and size // 2 a multiple of 8 up to 2048"
+
+
+def csgu_supported(Ch, K):
+    return 3 <= K <= 31 and K % 2 == 1 and 8 <= Ch <= 2048 and Ch % 8 == 0
+
+
+def _csgu_check(rc, name, Ch, K):
+    if rc == _lib.EAMD_EUNSUPPORTED:
+        raise _lib.EamdError(f"{name}: kernel_size {K}, size // 2 = {Ch} has no HIP kernel (supported: {CSGU_LIMITS})")
+    check(rc, name)
+
+
+def csgu_fwd(a, gamma, beta, w, bias, eps, B, T, Ch, K):
+    """y [B*T, Ch] = GELU(a[:, :Ch]) * (bias + dwconv_K(LayerNorm(GELU(a[:, Ch:])))) for a [B*T, 2*Ch] (value | gate columns);
+    -> (y, stats [B*T, 2] = mean, rstd of the gate rows: with `a`, all that csgu_bwd reads)"""
+    assert a.numel() == B * T * 2 * Ch and w.numel() == Ch * K and gamma.numel() == Ch and a.is_contiguous()
+    y = torch.empty(B * T, Ch, device=a.device, dtype=torch.float32)
+    stats = torch.empty(B * T, 2, device=a.device, dtype=torch.float32)
+    _csgu_check(_lib.lib().eamd_csgu_fwd(ptr(_lib.f32(a)), ptr(gamma), ptr(beta), ptr(w), ptr(bias), eps, ptr(y), ptr(stats),
+                                         B, T, Ch, K, stream_ptr()), "eamd_csgu_fwd", Ch, K)
+    return y, stats
+
+
+def csgu_bwd(dy, a, stats, gamma, beta, w, bias, dw, dbias, dgamma, dbeta, B, T, Ch, K):
+    """-> da [B*T, 2*Ch]; dw [Ch, K], dbias, dgamma, dbeta [Ch] are accumulated (fixed-order reductions, no atomics)"""
+    assert dy.numel() == B * T * Ch and dy.is_contiguous() and dw.numel() == Ch * K
+    assert dbias.numel() == Ch and dgamma.numel() == Ch and dbeta.numel() == Ch
+    L = _lib.lib()
+    da = torch.empty(B * T, 2 * Ch, device=a.device, dtype=torch.float32)
+    nws = L.eamd_csgu_bwd_workspace(B, T, Ch, K)
+    _csgu_check(min(nws, 0), "eamd_csgu_bwd_workspace", Ch, K)
+    ws = torch.empty(nws, device=a.device, dtype=torch.float32)
+    _csgu_check(L.eamd_csgu_bwd(ptr(_lib.f32(dy)), ptr(a), ptr(stats), ptr(gamma), ptr(beta), ptr(w), ptr(bias), ptr(da), ptr(dw),
+                                ptr(dbias), ptr(dgamma), ptr(dbeta), ptr(ws), B, T, Ch, K, stream_ptr()), "eamd_csgu_bwd", Ch, K)
+    return da
+
+
 def bn_stats(x, M, Cc, eps, momentum, running_mean, running_var, num_batches_tracked=None, bound=None):
     """bound = (T, int32 device scalar): rows (b, t) with t >= bound[0] are left out (eamd_bn_stats_bounded)"""
     nslab = _lib.lib().eamd_bn_nslab(M, Cc)

@@ -620,6 +620,25 @@ int eamd_conv1_bwd_w(const void* dy, const float* x, float* dw, float* db, float
                      int C, int dy_bf16, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Convolutional spatial gating unit of the E-Branchformer's cgMLP branch (csrc/cgmlp.hip).
+ * `a` = channel_proj1's Linear output [B, T, 2C] (value columns | gate columns), h = GELU(a) in the exact erf form:
+ *   y [B, T, C] = h[.., :C] * (bias + depthwise_conv1d_K(LayerNorm_C(h[.., C:]; gamma, beta, eps); w [C, K])),
+ * the convolution over time with zero padding (K-1)/2 on each side of every utterance.  h, the normalised gate and the
+ * convolution output are never written; stats [B*T, 2] receives (mean, rstd) of the gate rows and is, with `a`, all that
+ * backward reads.  K odd in 3..31 and C a multiple of 8 up to 2048, anything else is EAMD_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------ */
+int eamd_csgu_fwd(const float* a, const float* gamma, const float* beta, const float* w, const float* bias, float eps, float* y,
+                  float* stats, int B, int T, int C, int K, void* stream);
+/* da [B, T, 2C] is written; dw [C, K], dbias [C], dgamma [C], dbeta [C] are ACCUMULATED, by two-stage reductions in a
+ * fixed order (no atomics: bit-identical from launch to launch).  workspace: eamd_csgu_bwd_workspace(B, T, C, K) floats
+ * of scratch (required: NULL is EAMD_EINVAL); a shape that is not supported, or whose workspace would pass 2^31 - 1
+ * floats, is EAMD_EUNSUPPORTED from both. */
+int eamd_csgu_bwd_workspace(int B, int T, int C, int K);
+int eamd_csgu_bwd(const float* dy, const float* a, const float* stats, const float* gamma, const float* beta, const float* w,
+                  const float* bias, float* da, float* dw, float* dbias, float* dgamma, float* dbeta, float* workspace, int B,
+                  int T, int C, int K, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CTC loss (warp-ctc operator slot).  reference: ctc.py:30-47,53-66 (ctc_type warpctc|builtin),
  * espnet2/asr/ctc.py:32-66.  acts are RAW activations (softmax fused), element strides select
  * (T,B,V) or (B,T,V) layout.  nll[b] = -log p(y_b|x_b) (+inf if infeasible);
