@@ -512,6 +512,23 @@ def attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=None, shift_len
                         _ldp(T2), 1.0 / math.sqrt(dk), drop=drop, shift_len=shift_len)
 
 
+# Without autograd (F_.run's inference branch), attention dropout and the attention tap, rows of MORE keys than this run the
+# memory-linear forward of csrc/attn_stream.hip, which stores no probabilities.  The default leaves every shape that has a fused
+# stored-P path on it, bit for bit; lower it (0: always) to trade the stored-P kernels for O(T') memory at shorter lengths.
+ATTN_STREAM_KEYS = 4096
+
+
+def attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None):
+    """ctx from eamd_attn_fwd_stream, or None when the library declines the operands"""
+    qu, k, v = _mv(qu), _mv(k), _mv(v)
+    qv3 = p3 = None
+    if p is not None:
+        qvm, pm = _mv(qv), _mv(p)
+        qv3, p3 = (qvm.t, qvm.off, qvm.ld), (pm.t, pm.off, pm.ld)
+    return ops.attn_fwd_stream((qu.t, qu.off, qu.ld), qv3, (k.t, k.off, k.ld), (v.t, v.off, v.ld), p3, mask, B, T1, T2, H, dk,
+                               scale=1.0 / math.sqrt(dk), shift_len=shift_len)
+
+
 def attn_context_fwd(P, v, B, T1, T2, H, dk):
     D = H * dk
     ldp = _ldp(T2)
@@ -837,13 +854,17 @@ class MHABlockFn(torch.autograd.Function):
         fwd = None
         tb = ops.time_bound() if (rel and T1 == T2) else None      # padded batch: rel_shift over the batch's own length
         ctx.shift_len = tb
-        if FUSE_ATTN and ops.attn_fwd_supported(T1, T2, dk, rel):
+        P = Pd = cx = None
+        if isinstance(ctx, _NoGradCtx) and ATTN_TAP is None and p_att <= 0.0 and dk == 64 and T2 > ATTN_STREAM_KEYS:
+            # inference on long rows: nobody reads the probabilities - online softmax, O(T') memory, any number of keys
+            cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=tb)
+        if cx is None and FUSE_ATTN and ops.attn_fwd_supported(T1, T2, dk, rel):
             # scores, softmax, attention dropout and context in one launch
             fwd = attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=(p_att, s_att) if p_att > 0.0 else None,
                                  shift_len=tb)
         if fwd is not None:
             P, Pd, cx = fwd
-        else:
+        elif cx is None:
             if tb is not None:
                 # a padded batch needs the rel_shift over its own length; only the fused kernels take it (shift_len)
                 raise ops._lib.EamdError("relative-position attention on a shape-bucketed batch needs the fused attention kernels "

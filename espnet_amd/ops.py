@@ -1153,6 +1153,48 @@ def attn_fwd(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldp, scale, drop=None, s
     return P, Pd, cx
 
 
+ATTN_STREAM_QB = 64     # queries per workgroup and keys per staged tile of csrc/attn_stream.hip (eamd_attn_stream_qb / _kt):
+ATTN_STREAM_KT = 32     # shapes that straddle them are its edge cases
+
+
+def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1.0, shift_len=None, out=None):
+    """ctx [B*T1, ldc] (ldc: H*dk unless given) of attn_fwd without dropout, by the online-softmax kernel of
+    csrc/attn_stream.hip: no probabilities are stored, any number of keys, forward only (inference).  Views as for attn_fwd;
+    out: such a view to write ctx into (its tensor is returned) instead of a fresh tensor.  Returns None if the library
+    declines the operands (EAMD_EUNSUPPORTED)."""
+    dev = qu[0].device
+    dt = qu[0].dtype
+    D = H * dk
+    ldc = D if ldc is None else ldc
+    mb = mi = 0
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 3 and mask.shape[0] in (1, B)
+        assert mask.shape[2] == T2 and mask.shape[1] in (1, T1)
+        mb = 0 if mask.shape[0] == 1 else mask.shape[1] * mask.shape[2]
+        mi = 0 if mask.shape[1] == 1 else T2
+    assert dt in (torch.bfloat16, torch.float32) and ldc >= D
+    for t_, _, _ in (qu, k, v) + ((qv,) if qv is not None else ()):
+        assert t_.dtype == dt and t_.is_cuda
+    assert pos is None or (pos[0].dtype == dt and pos[2] >= D)
+    if out is None:
+        out = (torch.empty(B * T1, ldc, device=dev, dtype=dt), 0, ldc)
+    cx, ldc = out[0], out[2]
+    assert cx.dtype == dt and cx.is_cuda and ldc >= D
+    rel = pos is not None
+    args = (ptr(qu[0], qu[1]), qu[2], ptr(qv[0], qv[1]) if qv is not None else None, qv[2] if qv is not None else 0,
+            ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(pos[0], pos[1]) if rel else None, pos[2] if rel else 0,
+            ptr(mask), mb, mi, ptr(cx, out[1]), ldc, B, H, T1, T2, dk, scale, ptr(shift_len) if (rel and T1 == T2) else None)
+    name = "eamd_attn_fwd_stream" if dt == torch.bfloat16 else "eamd_attn_fwd_stream_f32"
+    fn = getattr(_lib.lib(), name)
+    rc = fn(*args, stream_ptr())
+    if rc == _lib.EAMD_EUNSUPPORTED:
+        return None
+    check(rc, name)
+    if _gemm_record is not None:
+        _gemm_record.append((dict(kind=name, flop=0.0), (qu, qv, k, v, pos, mask, cx), lambda sp, args=args: check(fn(*args, sp), name)))
+    return cx
+
+
 def attn_bwd_q(dctx, k, v, P, dS, dbd, dq, B, T1, T2, H, dk, ldp, scale, drop=None, shift_len=None):
     """dctx / k / v / dq: (tensor, element offset, row stride) views; P, dS (and dbd or None): [H*B*T1*ldp], bf16
     (eamd_attn_bwd_q; dq fp32 or bf16) or everything fp32 (eamd_attn_bwd_q_f32).

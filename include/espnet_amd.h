@@ -366,6 +366,24 @@ int eamd_attn_bwd_q_f32(const float* dctx, int64_t ldd, const float* k, int64_t 
                         int T2, int dk, float scale, float drop_p, const uint64_t* drop_step, uint64_t drop_salt,
                         const int32_t* shift_len, void* stream);
 
+/* Memory-linear attention forward for inference (csrc/attn_stream.hip): the ctx of eamd_attn_fwd / eamd_attn_fwd_f32 without
+ * attention dropout, by an online softmax over key tiles - no score or probability is stored, ctx (b, t, h, d) at
+ * ctx[(b*T1 + t)*ldc + h*64 + d] is the only output; no workspace, no atomics, the same bits on every launch.  Operand
+ * layouts, alignment rules, mask and shift_len as for eamd_attn_fwd (bf16 storage) / eamd_attn_fwd_f32; d_k = 64; any T2
+ * (no 4096-key bound); qv / pos both NULL (any T1, T2: cross-attention, T1 = 1 for cached decoding) or both set (T1 == T2).
+ * Fully masked rows give zeros.  EAMD_EINVAL / EAMD_EUNSUPPORTED are returned before anything is launched.
+ * eamd_attn_stream_qb / _kt: the queries per workgroup and keys per staged tile (shapes that straddle them are the edge cases). */
+int eamd_attn_fwd_stream(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v,
+                         int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                         int64_t mask_qstride, void* ctx_bf16, int64_t ldc, int B, int H, int T1, int T2, int dk, float scale,
+                         const int32_t* shift_len, void* stream);
+int eamd_attn_fwd_stream_f32(const float* qu, int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk,
+                             const float* v, int64_t ldv, const float* pos, int64_t ldpos, const unsigned char* mask,
+                             int64_t mask_bstride, int64_t mask_qstride, float* ctx, int64_t ldc, int B, int H, int T1, int T2,
+                             int dk, float scale, const int32_t* shift_len, void* stream);
+int eamd_attn_stream_qb(void);
+int eamd_attn_stream_kt(void);
+
 /* Key side of the attention backward in one launch (fp32 tensors, d_k = 64; any T1 / T2): dv = Pd^T dctx, dk = dS^T qu and,
  * with relative positions (dbd, qv, dpos all set; T1 == T2), dpos += dbd^T qv summed over the batch (dpos is ACCUMULATED
  * into: positions are shared by the batch; zero it first).  Pd / dS / dbd: [H][B][T1][ldp] as eamd_attn_fwd_f32 /

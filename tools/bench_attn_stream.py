@@ -1,0 +1,128 @@
+#!/usr/bin/env python
+"""Times the memory-linear attention forward (csrc/attn_stream.hip, ops.attn_fwd_stream) beside the paths that store the
+probabilities, for fp32 and bf16 storage, with and without relative positions, at B * H = 32 (batch, head) pairs:
+at T = 4096 beside the fused long-row forward (F_.attn_fwd_fused), at T = 8192 and 22 528 (fifteen minutes of 10 ms frames behind
+conv2d subsampling) beside the GEMM + softmax + GEMM composition where that fits into free device memory and its kernels
+take the shape.  Writes one JSON file.
+
+    python tools/bench_attn_stream.py [--out profiles/attn_stream_bench.json] [--commit <id>] [--T 4096 8192 22528]
+
+Times are device events around at least `iters` calls and at least 50 ms of work after `warmup` calls, the best of `rounds`
+alternating rounds; peak memory is the rise of torch.cuda.max_memory_allocated over one call (operands excluded).  tflops counts
+the two (three with positions) T x T x 64 products of the streamed kernel over its time."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+WINDOW_MS = 50.0
+
+
+def _window(fn, warmup, iters):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def timed(fn, warmup, iters):
+    first = _window(fn, warmup, iters)
+    more = int(WINDOW_MS / max(first, 1e-4)) + 1
+    return first if more <= iters else _window(fn, 0, more)
+
+
+def peak_rise(fn):
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_stream_bench.json"))
+    ap.add_argument("--commit", default=None)
+    ap.add_argument("--T", type=int, nargs="+", default=[4096, 8192, 22528])
+    ap.add_argument("--B", type=int, default=8)
+    ap.add_argument("--H", type=int, default=4)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=2)
+    args = ap.parse_args()
+    import espnet_amd
+    from espnet_amd import functional as F_, ops
+    commit = args.commit
+    if commit is None:
+        try:
+            commit = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+        except (OSError, subprocess.CalledProcessError):
+            commit = "unknown"
+    dev, B, H, dk = "cuda", args.B, args.H, 64
+    D = H * dk
+    res = dict(commit=commit, device=torch.cuda.get_device_name(0), pairs=B * H, QB=ops.ATTN_STREAM_QB, KT=ops.ATTN_STREAM_KT, rows=[])
+    for prec in ("fp32", "bf16"):
+        espnet_amd.set_precision(prec)
+        adt = ops.act_dtype()
+        for rel in (True, False):
+            for T in args.T:
+                torch.manual_seed(T)
+                mk = lambda *s: torch.randn(*s, device=dev).to(adt)  # noqa: E731
+                qkv = mk(B * T, 3 * D)
+                k, v = F_._MV(qkv, D, 3 * D), F_._MV(qkv, 2 * D, 3 * D)
+                qu = mk(B * T, D) if rel else F_._MV(qkv, 0, 3 * D)
+                qv, p = (mk(B * T, D), mk(T, D)) if rel else (None, None)
+                mask = torch.ones(B, 1, T, dtype=torch.uint8, device=dev)
+                stream = lambda: F_.attn_fwd_stream(qu, qv, k, v, p, mask, B, T, T, H, dk)  # noqa: E731
+
+                def composed():
+                    P = F_.attn_scores_fwd(qu, qv, k, p, mask, B, T, T, H, dk)
+                    return F_.attn_context_fwd(P, v, B, T, T, H, dk)
+                if ops.attn_fwd_supported(T, T, dk, rel):
+                    other_name, other = "fused_long_row", lambda: F_.attn_fwd_fused(qu, qv, k, v, p, mask, B, T, T, H, dk)  # noqa: E731
+                    need = H * B * T * T * qkv.element_size()
+                else:
+                    other_name, other = "gemm_softmax_gemm", composed
+                    need = H * B * T * T * 4 * (2 if rel else 1) + (H * B * T * T * 2 if prec == "bf16" else 0)
+                assert stream() is not None
+                row = dict(precision=prec, rel=rel, T=T, other=other_name, rounds=[])
+                fits = need < 0.8 * torch.cuda.mem_get_info()[0]
+                row["stream_peak_bytes"] = peak_rise(stream)
+                row["other_peak_bytes"] = None
+                try:
+                    if fits:
+                        row["other_peak_bytes"] = peak_rise(other)
+                except ops._lib.EamdError as e:          # the composition's own kernels decline the shape
+                    fits, row["other_error"] = False, str(e)
+                for _ in range(args.rounds):
+                    r = dict(stream_ms=timed(stream, args.warmup, args.iters))
+                    if fits:
+                        r["other_ms"] = timed(other, args.warmup, args.iters)
+                    row["rounds"].append(r)
+                row["stream_ms"] = min(r["stream_ms"] for r in row["rounds"])
+                row["other_ms"] = min(r["other_ms"] for r in row["rounds"]) if fits else None
+                row["stream_tflops"] = B * H * T * T * dk * 2 * (3 if rel else 2) / (row["stream_ms"] * 1e-3) / 1e12
+                res["rows"].append(row)
+                print(json.dumps({k_: v_ for k_, v_ in row.items() if k_ != "rounds"}), flush=True)
+                del qkv, k, v, qu, qv, p
+                torch.cuda.empty_cache()
+    espnet_amd.set_precision("fp32")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
