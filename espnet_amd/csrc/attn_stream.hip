@@ -75,8 +75,10 @@ __device__ __forceinline__ int band_pos_row(int c, int Ts) {
   return min(max(m, 0), Ts - 1);
 }
 
-template <typename T, bool REL>
-__global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a) {
+// LSE (training, attn_stream_bwd.hip): each wave also writes lse[z][i] = running maximum + log(denominator) of its 16 queries - the
+// row statistic of the scaled, masked scores the streamed backward rebuilds P from; 0 for a row masked everywhere
+template <typename T, bool REL, bool LSE>
+__global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a, float* __restrict__ lse) {
   __shared__ __attribute__((aligned(16))) float Ks[SKT * SPLD];
   __shared__ __attribute__((aligned(16))) float Vs[SKT * SPLD];
   __shared__ __attribute__((aligned(16))) float Ps[REL ? SBR * SPLD : 4];
@@ -245,6 +247,7 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
   T* crow = a.ctx + ((long)b * T1 + i) * a.ldc + h * ATT_DK;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) st4(crow + dt * 16 + fq * 4, f4(C[dt] * inv));
+  if (LSE && fq == 0) lse[(long)z * T1 + i] = den > 0.f ? mrun + logf(den) : 0.f;
 }
 
 // the checks of the stored forward (attn_check_fwd) without P, Pd, the dropout arguments and the bound on T2
@@ -264,15 +267,19 @@ int stream_check(const AttnArgs<T>& a, int dk) {
 template <typename T>
 int stream_entry(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v, int64_t ldv,
                  const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mb, int64_t mi, void* ctx, int64_t ldc, int B,
-                 int H, int T1, int T2, int dk, float scale, const int32_t* shift_len, void* stream) {
+                 int H, int T1, int T2, int dk, float scale, const int32_t* shift_len, void* stream, float* lse = nullptr,
+                 bool want_lse = false) {
+  if (want_lse && !lse) return EAMD_EINVAL;
   AttnArgs<T> a = attn_args<T>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mb, mi, nullptr, 0, ctx, ldc, B, H, T1, T2, scale,
                                nullptr, 0.f, nullptr, 0, shift_len);
   if (const int rc = stream_check(a, dk)) return rc;
   a.nqb = (T1 + SQB - 1) / SQB;
   const unsigned grid = attn_grid(a.nqb, B, H);
   hipStream_t s = (hipStream_t)stream;
-  if (pos) hipLaunchKernelGGL((attn_stream_kernel<T, true>), dim3(grid), dim3(SNT), 0, s, a);
-  else hipLaunchKernelGGL((attn_stream_kernel<T, false>), dim3(grid), dim3(SNT), 0, s, a);
+  if (want_lse && pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, true>), dim3(grid), dim3(SNT), 0, s, a, lse);
+  else if (want_lse) hipLaunchKernelGGL((attn_stream_kernel<T, false, true>), dim3(grid), dim3(SNT), 0, s, a, lse);
+  else if (pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, false>), dim3(grid), dim3(SNT), 0, s, a, nullptr);
+  else hipLaunchKernelGGL((attn_stream_kernel<T, false, false>), dim3(grid), dim3(SNT), 0, s, a, nullptr);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
@@ -296,4 +303,22 @@ extern "C" int eamd_attn_fwd_stream(const void* qu, int64_t ldq, const void* qv,
                                     int T2, int dk, float scale, const int32_t* shift_len, void* stream) {
   return stream_entry<bf16_t>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, ctx_bf16, ldc, B, H, T1,
                               T2, dk, scale, shift_len, stream);
+}
+
+// the same launches with the row statistic lse [H*B][T1] (fp32, z = h * B + b) written beside ctx: what the streamed backward
+// (attn_stream_bwd.hip) keeps instead of the probabilities.  ctx has the bits of the entry points above.
+extern "C" int eamd_attn_fwd_stream_lse_f32(const float* qu, int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk,
+                                            const float* v, int64_t ldv, const float* pos, int64_t ldpos, const unsigned char* mask,
+                                            int64_t mask_bstride, int64_t mask_qstride, float* ctx, int64_t ldc, int B, int H, int T1,
+                                            int T2, int dk, float scale, const int32_t* shift_len, float* lse, void* stream) {
+  return stream_entry<float>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, ctx, ldc, B, H, T1, T2,
+                             dk, scale, shift_len, stream, lse, true);
+}
+
+extern "C" int eamd_attn_fwd_stream_lse(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk,
+                                        const void* v, int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask,
+                                        int64_t mask_bstride, int64_t mask_qstride, void* ctx_bf16, int64_t ldc, int B, int H, int T1,
+                                        int T2, int dk, float scale, const int32_t* shift_len, float* lse, void* stream) {
+  return stream_entry<bf16_t>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, ctx_bf16, ldc, B, H, T1,
+                              T2, dk, scale, shift_len, stream, lse, true);
 }

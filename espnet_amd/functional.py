@@ -516,17 +516,51 @@ def attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=None, shift_len
 # memory-linear forward of csrc/attn_stream.hip, which stores no probabilities.  The default leaves every shape that has a fused
 # stored-P path on it, bit for bit; lower it (0: always) to trade the stored-P kernels for O(T') memory at shorter lengths.
 ATTN_STREAM_KEYS = 4096
+# With autograd the same holds for blocks WITHOUT relative positions: rows of more keys than this keep ctx and the row statistic
+# lse [H, B, T1] instead of probabilities, and backward rebuilds them tile by tile (csrc/attn_stream_bwd.hip): O(T') memory kept
+# and used.  Blocks with relative positions train on the stored-P paths at every length.
+ATTN_STREAM_TRAIN_KEYS = 4096
 
 
-def attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None):
-    """ctx from eamd_attn_fwd_stream, or None when the library declines the operands"""
+def attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, lse=None):
+    """ctx from eamd_attn_fwd_stream (with lse: eamd_attn_fwd_stream_lse), or None when the library declines the operands"""
     qu, k, v = _mv(qu), _mv(k), _mv(v)
     qv3 = p3 = None
     if p is not None:
         qvm, pm = _mv(qv), _mv(p)
         qv3, p3 = (qvm.t, qvm.off, qvm.ld), (pm.t, pm.off, pm.ld)
     return ops.attn_fwd_stream((qu.t, qu.off, qu.ld), qv3, (k.t, k.off, k.ld), (v.t, v.off, v.ld), p3, mask, B, T1, T2, H, dk,
-                               scale=1.0 / math.sqrt(dk), shift_len=shift_len)
+                               scale=1.0 / math.sqrt(dk), shift_len=shift_len, lse=lse)
+
+
+def attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T1, T2, H, dk, dqkv=None, dkv_out=None):
+    """backward of the streamed forward without relative positions -> (dq, dk, dv) in the GEMM-operand dtype, or None when the
+    library declines the operands.  dqkv / dkv_out as in attn_core_bwd: the three gradients are written into the column blocks
+    of dqkv (dq is then returned as None), dk / dv into dkv_out's."""
+    D = H * dk
+    dev, adt = dctx.device, ops.act_dtype()
+    qu, k, v = _mv(qu), _mv(k), _mv(v)
+    if dctx.dtype != adt or cx.dtype != adt or qu.t.dtype != adt:
+        return None
+    dq = None
+    if dqkv is not None:
+        dq3, dk3, dv3 = (dqkv, 0, 3 * D), (dqkv, D, 3 * D), (dqkv, 2 * D, 3 * D)
+        dkk = dv = dqkv
+    else:
+        dq = torch.empty(B * T1, D, device=dev, dtype=adt)
+        dq3 = (dq, 0, D)
+        if dkv_out is not None:
+            if dkv_out.t.dtype != adt:
+                return None
+            dkk = dv = dkv_out.t
+            dk3, dv3 = (dkk, dkv_out.off, dkv_out.ld), (dv, dkv_out.off + D, dkv_out.ld)
+        else:
+            dkk, dv = torch.empty(B * T2, D, device=dev, dtype=adt), torch.empty(B * T2, D, device=dev, dtype=adt)
+            dk3, dv3 = (dkk, 0, D), (dv, 0, D)
+    if not ops.attn_bwd_stream((dctx, 0, D), (cx, 0, D), (qu.t, qu.off, qu.ld), (k.t, k.off, k.ld), (v.t, v.off, v.ld), mask, lse,
+                               dq3, dk3, dv3, B, T1, T2, H, dk, 1.0 / math.sqrt(dk)):
+        return None
+    return dq, dkk, dv
 
 
 def attn_context_fwd(P, v, B, T1, T2, H, dk):
@@ -858,6 +892,16 @@ class MHABlockFn(torch.autograd.Function):
         if isinstance(ctx, _NoGradCtx) and ATTN_TAP is None and p_att <= 0.0 and dk == 64 and T2 > ATTN_STREAM_KEYS:
             # inference on long rows: nobody reads the probabilities - online softmax, O(T') memory, any number of keys
             cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=tb)
+        lse = None
+        if not isinstance(ctx, _NoGradCtx) and not rel and p_att <= 0.0 and ATTN_TAP is None and dk == 64 and not last_query_only \
+                and T2 > ATTN_STREAM_TRAIN_KEYS and (pre_kv is None or pre_kv[1].grad_dtype == adt):
+            # training on long rows without relative positions: keep ctx and the row statistic, no probabilities; backward
+            # rebuilds them tile by tile (attn_stream_bwd)
+            lse = torch.empty(H * B * T1, device=x2.device, dtype=torch.float32)
+            cx = attn_fwd_stream(qu, None, k, v, None, mask, B, T1, T2, H, dk, lse=lse)
+            if cx is None:
+                lse = None
+        ctx.stream = None if lse is None else (lse, mask)
         if cx is None and FUSE_ATTN and ops.attn_fwd_supported(T1, T2, dk, rel):
             # scores, softmax, attention dropout and context in one launch
             fwd = attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=(p_att, s_att) if p_att > 0.0 else None,
@@ -945,15 +989,28 @@ class MHABlockFn(torch.autograd.Function):
             if f is None:
                 raise ops._lib.EamdError("attention recompute: the fused forward declined operands it took in forward")
             return f[0], (f[1] if p_att > 0.0 else None)
+        def stored(qu_, k_, v_):
+            """the library declined the streamed backward: the probabilities of today's path, rebuilt"""
+            if FUSE_ATTN and ops.attn_fwd_supported(T1, T2, dk, False):
+                f = attn_fwd_fused(qu_, None, k_, v_, None, ctx.stream[1], B, T1, T2, H, dk)
+                if f is not None:
+                    return f[0]
+            return attn_scores_fwd(qu_, None, k_, None, ctx.stream[1], B, T1, T2, H, dk)
         if ctx.fused:
             qkv = k
             dqkv = torch.empty(B * T1, 3 * D, device=do.device, dtype=adt)
             quv = qu if rel else _MV(qkv, 0, 3 * D)
-            if P is None:
-                P, Pd = again(quv, qv, _MV(qkv, D, 3 * D), _MV(qkv, 2 * D, 3 * D))
-            dqu, dqv, _, _, dp = attn_core_bwd(dctx, P, quv, qv, _MV(qkv, D, 3 * D), _MV(qkv, 2 * D, 3 * D), p, B, T1,
-                                               T2, H, dk, Pd=Pd, attn_drop=(p_att, s_att), dqkv=dqkv, dp_out=dp_out,
-                                               shift_len=ctx.shift_len)
+            kb, vb = _MV(qkv, D, 3 * D), _MV(qkv, 2 * D, 3 * D)
+            done = ctx.stream is not None and attn_stream_bwd(dctx, cx, ctx.stream[0], quv, kb, vb, ctx.stream[1], B, T1, T2, H, dk,
+                                                              dqkv=dqkv) is not None
+            if not done:
+                if ctx.stream is not None:
+                    P = stored(quv, kb, vb)
+                elif P is None:
+                    P, Pd = again(quv, qv, kb, vb)
+                dqu, dqv, _, _, dp = attn_core_bwd(dctx, P, quv, qv, kb, vb, p, B, T1,
+                                                   T2, H, dk, Pd=Pd, attn_drop=(p_att, s_att), dqkv=dqkv, dp_out=dp_out,
+                                                   shift_len=ctx.shift_len)
             if rel:
                 wpos = params[10]
                 # dq = dqu + dqv (operand dtype, into the fused buffer) + both bias gradients in one pass
@@ -972,12 +1029,21 @@ class MHABlockFn(torch.autograd.Function):
         if pre_kv is not None:
             k, v = pre_kv[1].block(pre_kv[2], 0), pre_kv[1].block(pre_kv[2], D)
             dkv_out = pre_kv[1].grad_block(pre_kv[2])
-        if P is None:
-            P, Pd = again(qu, qv, k, v)
-        dqu, dqv, dkk, dv, dp = attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk,
-                                              Pd=Pd, attn_drop=(p_att, s_att), dkv_out=dkv_out, dp_out=dp_out,
-                                              shift_len=ctx.shift_len)
-        if rel:
+        sb = attn_stream_bwd(dctx, cx, ctx.stream[0], qu, k, v, ctx.stream[1], B, T1, T2, H, dk, dkv_out=dkv_out) \
+            if ctx.stream is not None else None
+        if sb is not None:
+            dkk, dv = sb[1:]
+        else:
+            if ctx.stream is not None:
+                P = stored(qu, k, v)
+            elif P is None:
+                P, Pd = again(qu, qv, k, v)
+            dqu, dqv, dkk, dv, dp = attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk,
+                                                  Pd=Pd, attn_drop=(p_att, s_att), dkv_out=dkv_out, dp_out=dp_out,
+                                                  shift_len=ctx.shift_len)
+        if sb is not None:       # dq is already a GEMM operand
+            dq = sb[0]
+        elif rel:
             wpos = params[10]
             dq = ops.add_cast_colsum2(dqu, dqv, sink.buf(11).view(-1), sink.buf(12).view(-1))
             if dp_out is None:

@@ -1157,11 +1157,21 @@ ATTN_STREAM_QB = 64     # queries per workgroup and keys per staged tile of csrc
 ATTN_STREAM_KT = 32     # shapes that straddle them are its edge cases
 
 
-def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1.0, shift_len=None, out=None):
+def _mask_strides(mask, B, T1, T2):
+    """(batch stride, query stride) of a uint8 [1 | B, 1 | T1, T2] mask; (0, 0) without one"""
+    if mask is None:
+        return 0, 0
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 3 and mask.shape[0] in (1, B)
+    assert mask.shape[2] == T2 and mask.shape[1] in (1, T1)
+    return (0 if mask.shape[0] == 1 else mask.shape[1] * mask.shape[2]), (0 if mask.shape[1] == 1 else T2)
+
+
+def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1.0, shift_len=None, out=None, lse=None):
     """ctx [B*T1, ldc] (ldc: H*dk unless given) of attn_fwd without dropout, by the online-softmax kernel of
-    csrc/attn_stream.hip: no probabilities are stored, any number of keys, forward only (inference).  Views as for attn_fwd;
-    out: such a view to write ctx into (its tensor is returned) instead of a fresh tensor.  Returns None if the library
-    declines the operands (EAMD_EUNSUPPORTED)."""
+    csrc/attn_stream.hip: no probabilities are stored, any number of keys.  Views as for attn_fwd;
+    out: such a view to write ctx into (its tensor is returned) instead of a fresh tensor.  lse: an fp32 [H*B*T1] tensor that
+    receives the row statistic attn_bwd_stream rebuilds the probabilities from (training; eamd_attn_fwd_stream_lse).  Returns
+    None if the library declines the operands (EAMD_EUNSUPPORTED)."""
     dev = qu[0].device
     dt = qu[0].dtype
     D = H * dk
@@ -1185,14 +1195,44 @@ def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1
             ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(pos[0], pos[1]) if rel else None, pos[2] if rel else 0,
             ptr(mask), mb, mi, ptr(cx, out[1]), ldc, B, H, T1, T2, dk, scale, ptr(shift_len) if (rel and T1 == T2) else None)
     name = "eamd_attn_fwd_stream" if dt == torch.bfloat16 else "eamd_attn_fwd_stream_f32"
+    if lse is not None:
+        assert lse.dtype == torch.float32 and lse.is_cuda and lse.is_contiguous() and lse.numel() >= H * B * T1
+        name = name.replace("_stream", "_stream_lse")
+        args = args + (ptr(lse),)
     fn = getattr(_lib.lib(), name)
     rc = fn(*args, stream_ptr())
     if rc == _lib.EAMD_EUNSUPPORTED:
         return None
     check(rc, name)
     if _gemm_record is not None:
-        _gemm_record.append((dict(kind=name, flop=0.0), (qu, qv, k, v, pos, mask, cx), lambda sp, args=args: check(fn(*args, sp), name)))
+        _gemm_record.append((dict(kind=name, flop=0.0), (qu, qv, k, v, pos, mask, cx, lse), lambda sp, args=args: check(fn(*args, sp), name)))
     return cx
+
+
+def attn_bwd_stream(dctx, ctx, qu, k, v, mask, lse, dq, dk_, dv, B, T1, T2, H, dk, scale):
+    """The backward of attn_fwd_stream(..., lse=lse) without relative positions (csrc/attn_stream_bwd.hip): dq, dk_ and dv are
+    written from dctx, the forward's ctx and lse and the operands, the probabilities rebuilt tile by tile - no [T1, T2] tensor.
+    All nine matrices are (tensor, element offset, row stride) views in one dtype (bf16: eamd_attn_bwd_stream, fp32: _f32).
+    Returns False if the library declines the operands (EAMD_EUNSUPPORTED)."""
+    dt = qu[0].dtype
+    assert dt in (torch.bfloat16, torch.float32)
+    for t_, _, _ in (dctx, ctx, qu, k, v, dq, dk_, dv):
+        assert t_.dtype == dt and t_.is_cuda
+    assert lse.dtype == torch.float32 and lse.is_cuda and lse.is_contiguous() and lse.numel() >= H * B * T1
+    mb, mi = _mask_strides(mask, B, T1, T2)
+    ws = torch.empty(H * B * T1, device=lse.device, dtype=torch.float32)      # delta: query side -> key side
+    args = sum(((ptr(t_, off), ld) for t_, off, ld in (dctx, ctx, qu, k, v)), ()) + (ptr(mask), mb, mi, ptr(lse), ptr(ws))
+    args = args + sum(((ptr(t_, off), ld) for t_, off, ld in (dq, dk_, dv)), ()) + (B, H, T1, T2, dk, scale)
+    name = "eamd_attn_bwd_stream" if dt == torch.bfloat16 else "eamd_attn_bwd_stream_f32"
+    fn = getattr(_lib.lib(), name)
+    rc = fn(*args, stream_ptr())
+    if rc == _lib.EAMD_EUNSUPPORTED:
+        return False
+    check(rc, name)
+    if _gemm_record is not None:
+        _gemm_record.append((dict(kind=name, flop=0.0), (dctx, ctx, qu, k, v, mask, lse, ws, dq, dk_, dv),
+                             lambda sp, args=args: check(fn(*args, sp), name)))
+    return True
 
 
 def attn_bwd_q(dctx, k, v, P, dS, dbd, dq, B, T1, T2, H, dk, ldp, scale, drop=None, shift_len=None):

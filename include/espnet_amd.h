@@ -384,6 +384,35 @@ int eamd_attn_fwd_stream_f32(const float* qu, int64_t ldq, const float* qv, int6
 int eamd_attn_stream_qb(void);
 int eamd_attn_stream_kt(void);
 
+/* Memory-linear attention for TRAINING without relative positions (csrc/attn_stream.hip, csrc/attn_stream_bwd.hip).
+ * eamd_attn_fwd_stream_lse[_f32]: the launch, checks and ctx bits of eamd_attn_fwd_stream[_f32], and beside ctx the row statistic
+ * lse [H*B][T1] fp32 (pair z = h*B + b): log sum_j exp(s_ij) of the scaled, masked scores, 0 for a row masked everywhere.  It is
+ * all a block keeps for backward besides ctx.
+ * eamd_attn_bwd_stream[_f32]: two launches, query side then key side, that rebuild P = exp(s - lse) tile by tile:
+ * dS = scale P (dctx v^T - delta), delta_i = sum_c dctx_ic ctx_ic, dq = dS k, dk = dS^T qu, dv = P^T dctx.  No [T1, T2] buffer, no
+ * atomics, the same bits on every launch.  dctx / ctx / qu: (b, t, h, d) at [(b*T1 + t)*ld + h*64 + d]; k / v and dk / dv: T2 rows
+ * per batch; mask as for eamd_attn_fwd; lse from the forward; delta_ws: fp32 workspace [H*B][T1] (written by the query side,
+ * read by the key side); dq / dk / dv are written in the operands' storage type, each with its own row stride (column blocks
+ * of wider buffers are fine).  d_k = 64, any T1 / T2.  EAMD_EINVAL (missing operand) / EAMD_EUNSUPPORTED (d_k, alignment: rules
+ * of eamd_attn_fwd_stream, outputs as ctx) are returned before anything is launched. */
+int eamd_attn_fwd_stream_lse(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v,
+                             int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                             int64_t mask_qstride, void* ctx_bf16, int64_t ldc, int B, int H, int T1, int T2, int dk, float scale,
+                             const int32_t* shift_len, float* lse, void* stream);
+int eamd_attn_fwd_stream_lse_f32(const float* qu, int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk,
+                                 const float* v, int64_t ldv, const float* pos, int64_t ldpos, const unsigned char* mask,
+                                 int64_t mask_bstride, int64_t mask_qstride, float* ctx, int64_t ldc, int B, int H, int T1, int T2,
+                                 int dk, float scale, const int32_t* shift_len, float* lse, void* stream);
+int eamd_attn_bwd_stream(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq, const void* k,
+                         int64_t ldk, const void* v, int64_t ldv, const unsigned char* mask, int64_t mask_bstride,
+                         int64_t mask_qstride, const float* lse, float* delta_ws, void* dq_bf16, int64_t lddq, void* dk_bf16,
+                         int64_t lddk, void* dv_bf16, int64_t lddv, int B, int H, int T1, int T2, int dk, float scale, void* stream);
+int eamd_attn_bwd_stream_f32(const float* dctx, int64_t ldd, const float* ctx, int64_t ldc, const float* qu, int64_t ldq,
+                             const float* k, int64_t ldk, const float* v, int64_t ldv, const unsigned char* mask,
+                             int64_t mask_bstride, int64_t mask_qstride, const float* lse, float* delta_ws, float* dq, int64_t lddq,
+                             float* dk_out, int64_t lddk, float* dv, int64_t lddv, int B, int H, int T1, int T2, int dk, float scale,
+                             void* stream);
+
 /* Key side of the attention backward in one launch (fp32 tensors, d_k = 64; any T1 / T2): dv = Pd^T dctx, dk = dS^T qu and,
  * with relative positions (dbd, qv, dpos all set; T1 == T2), dpos += dbd^T qv summed over the batch (dpos is ACCUMULATED
  * into: positions are shared by the batch; zero it first).  Pd / dS / dbd: [H][B][T1][ldp] as eamd_attn_fwd_f32 /

@@ -3,9 +3,11 @@
 probabilities, for fp32 and bf16 storage, with and without relative positions, at B * H = 32 (batch, head) pairs:
 at T = 4096 beside the fused long-row forward (F_.attn_fwd_fused), at T = 8192 and 22 528 (fifteen minutes of 10 ms frames behind
 conv2d subsampling) beside the GEMM + softmax + GEMM composition where that fits into free device memory and its kernels
-take the shape.  Writes one JSON file.
+take the shape.  Writes one JSON file.  With --train: forward + backward without relative positions, the streamed pair
+(F_.attn_fwd_stream with lse, F_.attn_stream_bwd: csrc/attn_stream_bwd.hip) beside today's route - the stored-P kernels at 4096
+keys, GEMM + softmax in both directions beyond - into profiles/attn_stream_train_bench.json.
 
-    python tools/bench_attn_stream.py [--out profiles/attn_stream_bench.json] [--commit <id>] [--T 4096 8192 22528]
+    python tools/bench_attn_stream.py [--train] [--out profiles/attn_stream_bench.json] [--commit <id>] [--T 4096 8192 22528]
 
 Times are device events around at least `iters` calls and at least 50 ms of work after `warmup` calls, the best of `rounds`
 alternating rounds; peak memory is the rise of torch.cuda.max_memory_allocated over one call (operands excluded).  tflops counts
@@ -51,9 +53,61 @@ def peak_rise(fn):
     return torch.cuda.max_memory_allocated() - base
 
 
+def train_rows(args, res):
+    """forward + backward, no relative positions: streamed against today's route, alternating in the same call"""
+    import espnet_amd
+    from espnet_amd import functional as F_, ops
+    dev, B, H, dk = "cuda", args.B, args.H, 64
+    D = H * dk
+    for prec in ("fp32", "bf16"):
+        espnet_amd.set_precision(prec)
+        adt = ops.act_dtype()
+        for T in args.T:
+            torch.manual_seed(T)
+            qkv, dctx = (torch.randn(B * T, n, device=dev).to(adt) for n in (3 * D, D))
+            dqkv = torch.empty_like(qkv)
+            qu, k, v = (F_._MV(qkv, i * D, 3 * D) for i in range(3))
+            mask = torch.ones(B, 1, T, dtype=torch.uint8, device=dev)
+            stored = ops.attn_fwd_supported(T, T, dk, False)
+
+            def stream():
+                lse = torch.empty(H * B * T, device=dev, dtype=torch.float32)
+                cx = F_.attn_fwd_stream(qu, None, k, v, None, mask, B, T, T, H, dk, lse=lse)
+                assert F_.attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T, T, H, dk, dqkv=dqkv) is not None
+
+            def other():
+                P = F_.attn_fwd_fused(qu, None, k, v, None, mask, B, T, T, H, dk)[0] if stored else F_.attn_scores_fwd(qu, None, k, None, mask, B, T, T, H, dk)
+                if not stored:
+                    F_.attn_context_fwd(P, v, B, T, T, H, dk)
+                F_.attn_core_bwd(dctx, P, qu, None, k, v, None, B, T, T, H, dk, dqkv=dqkv)
+            need = H * B * T * T * (2 * qkv.element_size() if stored else 8 if prec == "fp32" else 12)
+            fits = need < 0.8 * torch.cuda.mem_get_info()[0]
+            row = dict(precision=prec, T=T, other="stored_p" if stored else "gemm_softmax", rounds=[], stream_peak_bytes=peak_rise(stream),
+                       other_peak_bytes=None)
+            try:
+                if fits:
+                    row["other_peak_bytes"] = peak_rise(other)
+            except ops._lib.EamdError as e:          # today's route cannot run: its own kernels decline the shape
+                fits, row["other_error"] = False, str(e)
+            for _ in range(args.rounds):
+                r = dict(stream_ms=timed(stream, args.warmup, args.iters))
+                if fits:
+                    r["other_ms"] = timed(other, args.warmup, args.iters)
+                row["rounds"].append(r)
+            row["stream_ms"] = min(r["stream_ms"] for r in row["rounds"])
+            row["other_ms"] = min(r["other_ms"] for r in row["rounds"]) if fits else None
+            row["stream_tflops"] = B * H * T * T * dk * 2 * 9 / (row["stream_ms"] * 1e-3) / 1e12      # 2 forward + 3 + 4 backward products
+            res["rows"].append(row)
+            print(json.dumps({k_: v_ for k_, v_ in row.items() if k_ != "rounds"}), flush=True)
+            del qkv, dqkv, dctx, qu, k, v
+            torch.cuda.empty_cache()
+    espnet_amd.set_precision("fp32")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_stream_bench.json"))
+    ap.add_argument("--train", action="store_true", help="forward + backward rows (no relative positions)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--T", type=int, nargs="+", default=[4096, 8192, 22528])
     ap.add_argument("--B", type=int, default=8)
@@ -62,6 +116,8 @@ def main():
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "attn_stream_train_bench.json" if args.train else "attn_stream_bench.json")
     import espnet_amd
     from espnet_amd import functional as F_, ops
     commit = args.commit
@@ -73,7 +129,9 @@ def main():
     dev, B, H, dk = "cuda", args.B, args.H, 64
     D = H * dk
     res = dict(commit=commit, device=torch.cuda.get_device_name(0), pairs=B * H, QB=ops.ATTN_STREAM_QB, KT=ops.ATTN_STREAM_KT, rows=[])
-    for prec in ("fp32", "bf16"):
+    if args.train:
+        train_rows(args, res)
+    for prec in () if args.train else ("fp32", "bf16"):
         espnet_amd.set_precision(prec)
         adt = ops.act_dtype()
         for rel in (True, False):
