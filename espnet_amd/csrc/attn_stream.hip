@@ -31,42 +31,14 @@
 // exponential is then exp(-inf) = 0 and the accumulator stays 0); a row masked everywhere ends with denominator 0 and is
 // written as zeros; V rows past T2 are staged as zeros, K / pos / q rows are clamped re-reads whose scores are masked or
 // whose queries are never stored.
-#include "attn_common.h"
+#include "attn_stream_common.h"
 
 namespace {
 
-constexpr int SQB = 64;                       // queries per workgroup
-constexpr int SKT = 32;                       // keys per staged tile
-constexpr int SNW = SQB / 16;                 // waves: 16 queries each
-constexpr int SNT = 64 * SNW;
-constexpr int SPLD = ATT_PLD;                 // row stride (floats) of the K / V / band tiles in LDS
-constexpr int SBR = SKT + SQB;                // band rows staged (KT + QB - 1 are used)
-constexpr int SNKT = SKT / 16;                // 16-key column tiles of a key tile
-constexpr int SNBT = SNKT + 1;                // 16-row column tiles of a wave's band
+constexpr int SBR = STR_KT + STR_QB;             // band rows staged (KT + QB - 1 are used)
+constexpr int SNBT = STR_NKT + 1;                // 16-row column tiles of a wave's band
 constexpr int SGLD = 16 * SNBT + 4;           // row stride of a wave's band tile G[16][KT + 16]
-constexpr int SKQ = SKT * 16 / SNT;           // 16-byte pieces per thread of a K / V tile
-constexpr int SBQ = SBR * 16 / SNT;           // ... of the band
-
-template <typename T>
-__device__ __forceinline__ void frag_global(const T* row, int fq, float4 (&f)[4]) {   // this lane's share of a 64-channel row: chunks 4 j + fq
-#pragma unroll
-  for (int j = 0; j < 4; ++j) f[j] = ld4(row + 16 * j + 4 * fq);
-}
-__device__ __forceinline__ void frag_lds(const float* row, int fq, float4 (&f)[4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) f[j] = *reinterpret_cast<const float4*>(row + 16 * j + 4 * fq);
-}
-// c[r] += sum over the 64 channels of x[row 4 fq + r] y[row fr]: x rows / y rows held as frag_* leave them
-__device__ __forceinline__ f32x4 dot64(const float4 (&x)[4], const float4 (&y)[4], f32x4 c) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].x, y[j].x, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].y, y[j].y, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].z, y[j].z, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].w, y[j].w, c, 0, 0, 0);
-  }
-  return c;
-}
+constexpr int SBQ = SBR * 16 / STR_NT;           // 16-byte pieces per thread of the band
 
 // the staged band: row n of the band of key tile j0 holds element c = c0 + n of the flat [0 | bd] rows (c0 = Ts + j0 - r0w - 63);
 // the position row behind it, clamped into [0, Ts) where the band leaves the matrix (c <= 0, c == Ts + 1, c > 2 Ts + 1: never used)
@@ -78,24 +50,24 @@ __device__ __forceinline__ int band_pos_row(int c, int Ts) {
 // LSE (training, attn_stream_bwd.hip): each wave also writes lse[z][i] = running maximum + log(denominator) of its 16 queries - the
 // row statistic of the scaled, masked scores the streamed backward rebuilds P from; 0 for a row masked everywhere
 template <typename T, bool REL, bool LSE>
-__global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a, float* __restrict__ lse) {
-  __shared__ __attribute__((aligned(16))) float Ks[SKT * SPLD];
-  __shared__ __attribute__((aligned(16))) float Vs[SKT * SPLD];
-  __shared__ __attribute__((aligned(16))) float Ps[REL ? SBR * SPLD : 4];
-  __shared__ __attribute__((aligned(16))) float Gs[REL ? SNW * 16 * SGLD : 4];
+__global__ __launch_bounds__(STR_NT, 2) void attn_stream_kernel(const AttnArgs<T> a, float* __restrict__ lse) {
+  __shared__ __attribute__((aligned(16))) float Ks[STR_KT * STR_PLD];
+  __shared__ __attribute__((aligned(16))) float Vs[STR_KT * STR_PLD];
+  __shared__ __attribute__((aligned(16))) float Ps[REL ? SBR * STR_PLD : 4];
+  __shared__ __attribute__((aligned(16))) float Gs[REL ? STR_NW * 16 * SGLD : 4];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   const int z = attn_xcd_pair(blockIdx.x, a.nqb);            // z = h * B + b
   if (z >= a.B * a.H) return;                                // whole workgroup
   const int h = z / a.B, b = z % a.B;
   const int T1 = a.T1, T2 = a.T2;
-  const int r0w = attn_xcd_block(blockIdx.x, a.nqb) * SQB;   // < T1: nqb = ceil(T1 / QB)
+  const int r0w = attn_xcd_block(blockIdx.x, a.nqb) * STR_QB;   // < T1: nqb = ceil(T1 / QB)
   const int i0 = r0w + 16 * wave;
   const bool active = i0 < T1;                               // wave-uniform; idle waves still stage and keep the barriers
   const int i = i0 + fr;                                     // this lane's query (rows past T1 are clamped re-reads, never stored)
   const int qi = min(i, T1 - 1);
   const int Ts = REL ? attn_shift_len(a.tshift, T2) : T2;
-  const int ntile = (T2 + SKT - 1) / SKT;
+  const int ntile = (T2 + STR_KT - 1) / STR_KT;
   const T* ks = a.k + (long)b * T2 * a.ldk + h * ATT_DK;
   const T* vs = a.v + (long)b * T2 * a.ldv + h * ATT_DK;
   const T* ps = REL ? a.pos + h * ATT_DK : nullptr;
@@ -109,28 +81,28 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
   }
 
   // ---- register stage: one key tile's K, V, band and mask words on their way to LDS ----
-  float4 kr[SKQ], vr[SKQ], pr[REL ? SBQ : 1];
-  unsigned mkn[SNKT];
+  float4 kr[STR_KQ], vr[STR_KQ], pr[REL ? SBQ : 1];
+  unsigned mkn[STR_NKT];
   auto request = [&](int jt) {
-    const int j0 = jt * SKT;
+    const int j0 = jt * STR_KT;
 #pragma unroll
-    for (int q = 0; q < SKQ; ++q) {
-      const int c = t + SNT * q, row = c >> 4, c4 = c & 15;
+    for (int q = 0; q < STR_KQ; ++q) {
+      const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
       const long key = min(j0 + row, T2 - 1);
       kr[q] = ld4(ks + key * a.ldk + 4 * c4);
       vr[q] = ld4(vs + key * a.ldv + 4 * c4);
       if (j0 + row >= T2) vr[q] = make_float4(0.f, 0.f, 0.f, 0.f);     // a zero probability times a stale value may not be NaN
     }
     if (REL) {
-      const int c0 = Ts + j0 - r0w - (SQB - 1);
+      const int c0 = Ts + j0 - r0w - (STR_QB - 1);
 #pragma unroll
       for (int q = 0; q < SBQ; ++q) {
-        const int c = t + SNT * q, row = c >> 4, c4 = c & 15;
+        const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
         pr[q] = ld4(ps + (long)band_pos_row(c0 + row, Ts) * a.ldpos + 4 * c4);
       }
     }
 #pragma unroll
-    for (int kt = 0; kt < SNKT; ++kt) mkn[kt] = mr ? attn_mask4(mr, j0 + 16 * kt + 4 * fq, T2) : 0x01010101u;
+    for (int kt = 0; kt < STR_NKT; ++kt) mkn[kt] = mr ? attn_mask4(mr, j0 + 16 * kt + 4 * fq, T2) : 0x01010101u;
   };
 
   float mrun = -INFINITY, lrun = 0.f;                        // running maximum of query fr; this lane's share of its denominator
@@ -140,40 +112,40 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
 
   request(0);
   for (int jt = 0; jt < ntile; ++jt) {
-    const int j0 = jt * SKT;
+    const int j0 = jt * STR_KT;
     __syncthreads();                                         // the previous tile's reads are done
 #pragma unroll
-    for (int q = 0; q < SKQ; ++q) {
-      const int c = t + SNT * q, row = c >> 4, c4 = c & 15;
-      *reinterpret_cast<float4*>(&Ks[row * SPLD + 4 * c4]) = kr[q];
-      *reinterpret_cast<float4*>(&Vs[row * SPLD + 4 * c4]) = vr[q];
+    for (int q = 0; q < STR_KQ; ++q) {
+      const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
+      *reinterpret_cast<float4*>(&Ks[row * STR_PLD + 4 * c4]) = kr[q];
+      *reinterpret_cast<float4*>(&Vs[row * STR_PLD + 4 * c4]) = vr[q];
     }
     if (REL) {
 #pragma unroll
       for (int q = 0; q < SBQ; ++q) {
-        const int c = t + SNT * q, row = c >> 4, c4 = c & 15;
-        *reinterpret_cast<float4*>(&Ps[row * SPLD + 4 * c4]) = pr[q];
+        const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
+        *reinterpret_cast<float4*>(&Ps[row * STR_PLD + 4 * c4]) = pr[q];
       }
     }
-    unsigned mk[SNKT];
+    unsigned mk[STR_NKT];
 #pragma unroll
-    for (int kt = 0; kt < SNKT; ++kt) mk[kt] = mkn[kt];
+    for (int kt = 0; kt < STR_NKT; ++kt) mk[kt] = mkn[kt];
     __syncthreads();
     if (jt + 1 < ntile) request(jt + 1);                     // in flight under this tile's products
     if (!active) continue;
 
-    f32x4 S[SNKT];                                           // S[kt][r]: key j0 + 16 kt + 4 fq + r, query fr
+    f32x4 S[STR_NKT];                                           // S[kt][r]: key j0 + 16 kt + 4 fq + r, query fr
 #pragma unroll
-    for (int kt = 0; kt < SNKT; ++kt) S[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < STR_NKT; ++kt) S[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (REL) {
       float* G = Gs + wave * 16 * SGLD;
-      const int nw0 = (SQB - 16) - 16 * wave;                // this wave's first row of the staged band
-      const int cw = Ts + j0 - r0w - (SQB - 1) + nw0;        // ... and the flat column it stands for
+      const int nw0 = (STR_QB - 16) - 16 * wave;                // this wave's first row of the staged band
+      const int cw = Ts + j0 - r0w - (STR_QB - 1) + nw0;        // ... and the flat column it stands for
 #pragma unroll
       for (int bt = 0; bt < SNBT; ++bt) {
         const int cb = cw + 16 * bt;
         float4 pf[4];
-        frag_lds(&Ps[(nw0 + 16 * bt + fr) * SPLD], fq, pf);
+        frag_lds(&Ps[(nw0 + 16 * bt + fr) * STR_PLD], fq, pf);
         f32x4 g;                                             // g[r] = G[query fr][band row 16 bt + 4 fq + r]
         if (cb + 15 <= Ts) {                                 // wave-uniform: wholly in the lower part (bd row i)
           g = dot64(pf, qlo, (f32x4){0.f, 0.f, 0.f, 0.f});
@@ -190,7 +162,7 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-      for (int kt = 0; kt < SNKT; ++kt)
+      for (int kt = 0; kt < STR_NKT; ++kt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int jj = 16 * kt + 4 * fq + r, j = j0 + jj;
@@ -201,15 +173,15 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
       __builtin_amdgcn_wave_barrier();                       // the next tile's G stores come after these reads
     }
 #pragma unroll
-    for (int kt = 0; kt < SNKT; ++kt) {
+    for (int kt = 0; kt < STR_NKT; ++kt) {
       float4 kf[4];
-      frag_lds(&Ks[(16 * kt + fr) * SPLD], fq, kf);
+      frag_lds(&Ks[(16 * kt + fr) * STR_PLD], fq, kf);
       S[kt] = dot64(kf, qf, S[kt]);
     }
     // ---- scale, mask, online softmax ----
     float tmax = -INFINITY;
 #pragma unroll
-    for (int kt = 0; kt < SNKT; ++kt)
+    for (int kt = 0; kt < STR_NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         S[kt][r] = attn_score(S[kt][r], a.scale, j0 + 16 * kt + 4 * fq + r, T2, mk[kt], r);
@@ -221,7 +193,7 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
     mrun = mnew;
     float psum = 0.f;
 #pragma unroll
-    for (int kt = 0; kt < SNKT; ++kt)
+    for (int kt = 0; kt < STR_NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float e = __expf(S[kt][r] - msub);
@@ -233,10 +205,10 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
     for (int dt = 0; dt < 4; ++dt) C[dt] *= alpha;
     // ---- C^T[channel][query] += V_tile^T[channel][key] P^T[key][query] ----
 #pragma unroll
-    for (int kt = 0; kt < SNKT; ++kt)
+    for (int kt = 0; kt < STR_NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float* row = &Vs[(16 * kt + 4 * fq + r) * SPLD + fr];
+        const float* row = &Vs[(16 * kt + 4 * fq + r) * STR_PLD + fr];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) C[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[dt * 16], S[kt][r], C[dt], 0, 0, 0);
       }
@@ -253,13 +225,11 @@ __global__ __launch_bounds__(SNT, 2) void attn_stream_kernel(const AttnArgs<T> a
 // the checks of the stored forward (attn_check_fwd) without P, Pd, the dropout arguments and the bound on T2
 template <typename T>
 int stream_check(const AttnArgs<T>& a, int dk) {
-  constexpr int U = 16 / sizeof(T);
   if (const int rc = attn_check_common(a.qu && a.k && a.v && a.ctx, a.B, a.H, a.T1, a.T2, 0.f, nullptr)) return rc;
   if ((a.pos == nullptr) != (a.qv == nullptr)) return EAMD_EINVAL;
   if (dk != ATT_DK || (a.pos && a.T1 != a.T2)) return EAMD_EUNSUPPORTED;
-  if (a.ldq % U || a.ldk % U || a.ldv % U || a.ldc % 4 || (a.pos && (a.ldqv % U || a.ldpos % U))) return EAMD_EUNSUPPORTED;
-  if (!al16(a.qu) || !al16(a.k) || !al16(a.v) || (reinterpret_cast<uintptr_t>(a.ctx) & (4 * sizeof(T) - 1)) ||
-      (a.pos && (!al16(a.qv) || !al16(a.pos))))
+  if (!stream_in_ok(a.qu, a.ldq) || !stream_in_ok(a.k, a.ldk) || !stream_in_ok(a.v, a.ldv) || !stream_out_ok(a.ctx, a.ldc) ||
+      (a.pos && (!stream_in_ok(a.qv, a.ldqv) || !stream_in_ok(a.pos, a.ldpos))))
     return EAMD_EUNSUPPORTED;
   return attn_too_many<T>(a.B, a.H, a.T1) ? EAMD_EUNSUPPORTED : EAMD_OK;
 }
@@ -273,21 +243,21 @@ int stream_entry(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, cons
   AttnArgs<T> a = attn_args<T>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mb, mi, nullptr, 0, ctx, ldc, B, H, T1, T2, scale,
                                nullptr, 0.f, nullptr, 0, shift_len);
   if (const int rc = stream_check(a, dk)) return rc;
-  a.nqb = (T1 + SQB - 1) / SQB;
+  a.nqb = (T1 + STR_QB - 1) / STR_QB;
   const unsigned grid = attn_grid(a.nqb, B, H);
   hipStream_t s = (hipStream_t)stream;
-  if (want_lse && pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, true>), dim3(grid), dim3(SNT), 0, s, a, lse);
-  else if (want_lse) hipLaunchKernelGGL((attn_stream_kernel<T, false, true>), dim3(grid), dim3(SNT), 0, s, a, lse);
-  else if (pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, false>), dim3(grid), dim3(SNT), 0, s, a, nullptr);
-  else hipLaunchKernelGGL((attn_stream_kernel<T, false, false>), dim3(grid), dim3(SNT), 0, s, a, nullptr);
+  if (want_lse && pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, true>), dim3(grid), dim3(STR_NT), 0, s, a, lse);
+  else if (want_lse) hipLaunchKernelGGL((attn_stream_kernel<T, false, true>), dim3(grid), dim3(STR_NT), 0, s, a, lse);
+  else if (pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, false>), dim3(grid), dim3(STR_NT), 0, s, a, nullptr);
+  else hipLaunchKernelGGL((attn_stream_kernel<T, false, false>), dim3(grid), dim3(STR_NT), 0, s, a, nullptr);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
 
 }  // namespace
 
-extern "C" int eamd_attn_stream_qb(void) { return SQB; }
-extern "C" int eamd_attn_stream_kt(void) { return SKT; }
+extern "C" int eamd_attn_stream_qb(void) { return STR_QB; }
+extern "C" int eamd_attn_stream_kt(void) { return STR_KT; }
 
 extern "C" int eamd_attn_fwd_stream_f32(const float* qu, int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk,
                                         const float* v, int64_t ldv, const float* pos, int64_t ldpos, const unsigned char* mask,

@@ -32,17 +32,9 @@
 //     nothing to dk / dv; its ctx is zero, so delta = 0;
 //   * T1 != T2, T1 = 1 and operands / outputs that are column blocks of wider buffers: every tensor has its own row stride and
 //     outputs are written in pieces of four elements inside their 64 columns only.
-#include "attn_common.h"
+#include "attn_stream_common.h"
 
 namespace {
-
-constexpr int BQB = 64;                       // rows (queries / keys) a workgroup owns
-constexpr int BKT = 32;                       // rows (keys / queries) per staged tile
-constexpr int BNW = BQB / 16;
-constexpr int BNT = 64 * BNW;
-constexpr int BPLD = ATT_PLD;
-constexpr int BNKT = BKT / 16;
-constexpr int BKQ = BKT * 16 / BNT;           // 16-byte pieces per thread of a staged tile
 
 template <typename T>
 struct StreamBwdArgs {
@@ -55,85 +47,65 @@ struct StreamBwdArgs {
   float scale;
 };
 
-template <typename T>
-__device__ __forceinline__ void bfrag_global(const T* row, int fq, float4 (&f)[4]) {   // this lane's share of a 64-channel row: chunks 4 j + fq
-#pragma unroll
-  for (int j = 0; j < 4; ++j) f[j] = ld4(row + 16 * j + 4 * fq);
-}
-__device__ __forceinline__ void bfrag_lds(const float* row, int fq, float4 (&f)[4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) f[j] = *reinterpret_cast<const float4*>(row + 16 * j + 4 * fq);
-}
-// c[r] += sum over the 64 channels of x[row 4 fq + r] y[row fr]
-__device__ __forceinline__ f32x4 bdot64(const float4 (&x)[4], const float4 (&y)[4], f32x4 c) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].x, y[j].x, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].y, y[j].y, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].z, y[j].z, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].w, y[j].w, c, 0, 0, 0);
-  }
-  return c;
-}
 // acc^T[channel 16 dt + 4 fq + r][column fr] += sum over the tile's rows of X[row][channel] w[row][column fr]; w[t][r]: row 16 t + 4 fq + r
-__device__ __forceinline__ void baccum(const float* X, int fr, int fq, const f32x4 (&w)[BNKT], f32x4 (&acc)[4]) {
+__device__ __forceinline__ void baccum(const float* X, int fr, int fq, const f32x4 (&w)[STR_NKT], f32x4 (&acc)[4]) {
 #pragma unroll
-  for (int t = 0; t < BNKT; ++t)
+  for (int t = 0; t < STR_NKT; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float* row = &X[(16 * t + 4 * fq + r) * BPLD + fr];
+      const float* row = &X[(16 * t + 4 * fq + r) * STR_PLD + fr];
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[dt * 16], w[t][r], acc[dt], 0, 0, 0);
     }
 }
 
 template <typename T>
-__global__ __launch_bounds__(BNT, 2) void stream_bwd_q_kernel(const StreamBwdArgs<T> a) {
-  __shared__ __attribute__((aligned(16))) float Ks[BKT * BPLD];
-  __shared__ __attribute__((aligned(16))) float Vs[BKT * BPLD];
+__global__ __launch_bounds__(STR_NT, 2) void stream_bwd_q_kernel(const StreamBwdArgs<T> a) {
+  __shared__ __attribute__((aligned(16))) float Ks[STR_KT * STR_PLD];
+  __shared__ __attribute__((aligned(16))) float Vs[STR_KT * STR_PLD];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   const int z = attn_xcd_pair(blockIdx.x, a.nqb);            // z = h * B + b
   if (z >= a.B * a.H) return;                                // whole workgroup
   const int h = z / a.B, b = z % a.B;
   const int T1 = a.T1, T2 = a.T2;
-  const int i0 = attn_xcd_block(blockIdx.x, a.nqb) * BQB + 16 * wave;
+  const int i0 = attn_xcd_block(blockIdx.x, a.nqb) * STR_QB + 16 * wave;
   const bool active = i0 < T1;                               // wave-uniform; idle waves still stage and keep the barriers
   const int i = i0 + fr;                                     // this lane's query (rows past T1: clamped re-reads, never stored)
   const int qi = min(i, T1 - 1);
-  const int ntile = (T2 + BKT - 1) / BKT;
+  const int ntile = (T2 + STR_KT - 1) / STR_KT;
   const T* ks = a.k + (long)b * T2 * a.ldk + h * ATT_DK;
   const T* vs = a.v + (long)b * T2 * a.ldv + h * ATT_DK;
   const unsigned char* mr = a.mask ? a.mask + (long)b * a.mb + (long)qi * a.mi : nullptr;
 
   float4 qf[4], df[4];
-  bfrag_global(a.qu + ((long)b * T1 + qi) * a.ldq + h * ATT_DK, fq, qf);
-  bfrag_global(a.dctx + ((long)b * T1 + qi) * a.ldd + h * ATT_DK, fq, df);
+  frag_global(a.qu + ((long)b * T1 + qi) * a.ldq + h * ATT_DK, fq, qf);
+  frag_global(a.dctx + ((long)b * T1 + qi) * a.ldd + h * ATT_DK, fq, df);
   const float lse = a.lse[(long)z * T1 + qi];
   float delta = 0.f;
   {
     float4 cf[4];
-    bfrag_global(a.ctx + ((long)b * T1 + qi) * a.ldc + h * ATT_DK, fq, cf);
+    frag_global(a.ctx + ((long)b * T1 + qi) * a.ldc + h * ATT_DK, fq, cf);
 #pragma unroll
     for (int j = 0; j < 4; ++j) delta += df[j].x * cf[j].x + df[j].y * cf[j].y + df[j].z * cf[j].z + df[j].w * cf[j].w;
     delta = attn_sum16_32(delta);
     if (active && fq == 0 && i < T1) a.delta[(long)z * T1 + i] = delta;
   }
 
-  float4 kr[BKQ], vr[BKQ];                                   // register stage: one key tile on its way to LDS
-  unsigned mkn[BNKT];
+  float4 kr[STR_KQ], vr[STR_KQ];                                   // register stage: one key tile on its way to LDS
+  unsigned mkn[STR_NKT];
   auto request = [&](int jt) {
-    const int j0 = jt * BKT;
+    const int j0 = jt * STR_KT;
 #pragma unroll
-    for (int q = 0; q < BKQ; ++q) {
-      const int c = t + BNT * q, row = c >> 4, c4 = c & 15;
+    for (int q = 0; q < STR_KQ; ++q) {
+      const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
       const long key = min(j0 + row, T2 - 1);
       kr[q] = ld4(ks + key * a.ldk + 4 * c4);
       vr[q] = ld4(vs + key * a.ldv + 4 * c4);
       if (j0 + row >= T2) vr[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
-    for (int kt = 0; kt < BNKT; ++kt) mkn[kt] = mr ? attn_mask4(mr, j0 + 16 * kt + 4 * fq, T2) : 0x01010101u;
+    for (int kt = 0; kt < STR_NKT; ++kt) mkn[kt] = mr ? attn_mask4(mr, j0 + 16 * kt + 4 * fq, T2) : 0x01010101u;
   };
 
   f32x4 DQ[4];                                               // DQ[dt][r]: channel 16 dt + 4 fq + r of query fr
@@ -142,32 +114,32 @@ __global__ __launch_bounds__(BNT, 2) void stream_bwd_q_kernel(const StreamBwdArg
 
   request(0);
   for (int jt = 0; jt < ntile; ++jt) {
-    const int j0 = jt * BKT;
+    const int j0 = jt * STR_KT;
     __syncthreads();                                         // the previous tile's reads are done
 #pragma unroll
-    for (int q = 0; q < BKQ; ++q) {
-      const int c = t + BNT * q, row = c >> 4, c4 = c & 15;
-      *reinterpret_cast<float4*>(&Ks[row * BPLD + 4 * c4]) = kr[q];
-      *reinterpret_cast<float4*>(&Vs[row * BPLD + 4 * c4]) = vr[q];
+    for (int q = 0; q < STR_KQ; ++q) {
+      const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
+      *reinterpret_cast<float4*>(&Ks[row * STR_PLD + 4 * c4]) = kr[q];
+      *reinterpret_cast<float4*>(&Vs[row * STR_PLD + 4 * c4]) = vr[q];
     }
-    unsigned mk[BNKT];
+    unsigned mk[STR_NKT];
 #pragma unroll
-    for (int kt = 0; kt < BNKT; ++kt) mk[kt] = mkn[kt];
+    for (int kt = 0; kt < STR_NKT; ++kt) mk[kt] = mkn[kt];
     __syncthreads();
     if (jt + 1 < ntile) request(jt + 1);                     // in flight under this tile's products
     if (!active) continue;
 
-    f32x4 S[BNKT], dP[BNKT];                                 // [kt][r]: key j0 + 16 kt + 4 fq + r, query fr
+    f32x4 S[STR_NKT], dP[STR_NKT];                                 // [kt][r]: key j0 + 16 kt + 4 fq + r, query fr
 #pragma unroll
-    for (int kt = 0; kt < BNKT; ++kt) {
+    for (int kt = 0; kt < STR_NKT; ++kt) {
       float4 xf[4];
-      bfrag_lds(&Ks[(16 * kt + fr) * BPLD], fq, xf);
-      S[kt] = bdot64(xf, qf, (f32x4){0.f, 0.f, 0.f, 0.f});
-      bfrag_lds(&Vs[(16 * kt + fr) * BPLD], fq, xf);
-      dP[kt] = bdot64(xf, df, (f32x4){0.f, 0.f, 0.f, 0.f});
+      frag_lds(&Ks[(16 * kt + fr) * STR_PLD], fq, xf);
+      S[kt] = dot64(xf, qf, (f32x4){0.f, 0.f, 0.f, 0.f});
+      frag_lds(&Vs[(16 * kt + fr) * STR_PLD], fq, xf);
+      dP[kt] = dot64(xf, df, (f32x4){0.f, 0.f, 0.f, 0.f});
     }
 #pragma unroll
-    for (int kt = 0; kt < BNKT; ++kt)
+    for (int kt = 0; kt < STR_NKT; ++kt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float p = __expf(attn_score(S[kt][r], a.scale, j0 + 16 * kt + 4 * fq + r, T2, mk[kt], r) - lse);
@@ -182,21 +154,21 @@ __global__ __launch_bounds__(BNT, 2) void stream_bwd_q_kernel(const StreamBwdArg
 }
 
 template <typename T>
-__global__ __launch_bounds__(BNT, 2) void stream_bwd_kv_kernel(const StreamBwdArgs<T> a) {
-  __shared__ __attribute__((aligned(16))) float Qs[BKT * BPLD];
-  __shared__ __attribute__((aligned(16))) float Ds[BKT * BPLD];
-  __shared__ __attribute__((aligned(16))) float Ls[BKT], Es[BKT];                         // lse and delta of the staged queries
+__global__ __launch_bounds__(STR_NT, 2) void stream_bwd_kv_kernel(const StreamBwdArgs<T> a) {
+  __shared__ __attribute__((aligned(16))) float Qs[STR_KT * STR_PLD];
+  __shared__ __attribute__((aligned(16))) float Ds[STR_KT * STR_PLD];
+  __shared__ __attribute__((aligned(16))) float Ls[STR_KT], Es[STR_KT];                         // lse and delta of the staged queries
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   const int z = attn_xcd_pair(blockIdx.x, a.nkb);
   if (z >= a.B * a.H) return;                                // whole workgroup
   const int h = z / a.B, b = z % a.B;
   const int T1 = a.T1, T2 = a.T2;
-  const int j0w = attn_xcd_block(blockIdx.x, a.nkb) * BQB + 16 * wave;
+  const int j0w = attn_xcd_block(blockIdx.x, a.nkb) * STR_QB + 16 * wave;
   const bool active = j0w < T2;                              // wave-uniform
   const int j = j0w + fr;                                    // this lane's key (past T2: a clamped re-read, masked by index, never stored)
   const int kj = min(j, T2 - 1);
-  const int ntile = (T1 + BKT - 1) / BKT;
+  const int ntile = (T1 + STR_KT - 1) / STR_KT;
   const T* qs = a.qu + (long)b * T1 * a.ldq + h * ATT_DK;
   const T* ds = a.dctx + (long)b * T1 * a.ldd + h * ATT_DK;
   const float* ls = a.lse + (long)z * T1;
@@ -204,29 +176,29 @@ __global__ __launch_bounds__(BNT, 2) void stream_bwd_kv_kernel(const StreamBwdAr
   const unsigned char* mc = a.mask ? a.mask + (long)b * a.mb + kj : nullptr;     // this key's column of the pair's mask rows
 
   float4 kf[4], vf[4];
-  bfrag_global(a.k + ((long)b * T2 + kj) * a.ldk + h * ATT_DK, fq, kf);
-  bfrag_global(a.v + ((long)b * T2 + kj) * a.ldv + h * ATT_DK, fq, vf);
+  frag_global(a.k + ((long)b * T2 + kj) * a.ldk + h * ATT_DK, fq, kf);
+  frag_global(a.v + ((long)b * T2 + kj) * a.ldv + h * ATT_DK, fq, vf);
 
-  float4 qr[BKQ], dr[BKQ];                                   // register stage: one query tile on its way to LDS
+  float4 qr[STR_KQ], dr[STR_KQ];                                   // register stage: one query tile on its way to LDS
   float sr = 0.f;                                            // threads 0 .. 31: lse, 32 .. 63: delta of tile row t & 31
-  unsigned mkn[BNKT];
+  unsigned mkn[STR_NKT];
   auto request = [&](int it) {
-    const int i0 = it * BKT;
+    const int i0 = it * STR_KT;
 #pragma unroll
-    for (int q = 0; q < BKQ; ++q) {
-      const int c = t + BNT * q, row = c >> 4, c4 = c & 15;
+    for (int q = 0; q < STR_KQ; ++q) {
+      const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
       const long qrow = min(i0 + row, T1 - 1);
       qr[q] = ld4(qs + qrow * a.ldq + 4 * c4);
       dr[q] = ld4(ds + qrow * a.ldd + 4 * c4);
       if (i0 + row >= T1) qr[q] = dr[q] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    if (t < 2 * BKT) {
-      const int row = t & (BKT - 1);
-      sr = (t < BKT ? ls : es)[min(i0 + row, T1 - 1)];
+    if (t < 2 * STR_KT) {
+      const int row = t & (STR_KT - 1);
+      sr = (t < STR_KT ? ls : es)[min(i0 + row, T1 - 1)];
       if (i0 + row >= T1) sr = 0.f;
     }
 #pragma unroll
-    for (int qt = 0; qt < BNKT; ++qt) {
+    for (int qt = 0; qt < STR_NKT; ++qt) {
       unsigned w = 0x01010101u;
       if (mc) {
         w = 0u;
@@ -243,34 +215,34 @@ __global__ __launch_bounds__(BNT, 2) void stream_bwd_kv_kernel(const StreamBwdAr
 
   request(0);
   for (int it = 0; it < ntile; ++it) {
-    const int i0 = it * BKT;
+    const int i0 = it * STR_KT;
     __syncthreads();                                         // the previous tile's reads are done
 #pragma unroll
-    for (int q = 0; q < BKQ; ++q) {
-      const int c = t + BNT * q, row = c >> 4, c4 = c & 15;
-      *reinterpret_cast<float4*>(&Qs[row * BPLD + 4 * c4]) = qr[q];
-      *reinterpret_cast<float4*>(&Ds[row * BPLD + 4 * c4]) = dr[q];
+    for (int q = 0; q < STR_KQ; ++q) {
+      const int c = t + STR_NT * q, row = c >> 4, c4 = c & 15;
+      *reinterpret_cast<float4*>(&Qs[row * STR_PLD + 4 * c4]) = qr[q];
+      *reinterpret_cast<float4*>(&Ds[row * STR_PLD + 4 * c4]) = dr[q];
     }
-    if (t < BKT) Ls[t] = sr;
-    else if (t < 2 * BKT) Es[t - BKT] = sr;
-    unsigned mk[BNKT];
+    if (t < STR_KT) Ls[t] = sr;
+    else if (t < 2 * STR_KT) Es[t - STR_KT] = sr;
+    unsigned mk[STR_NKT];
 #pragma unroll
-    for (int qt = 0; qt < BNKT; ++qt) mk[qt] = mkn[qt];
+    for (int qt = 0; qt < STR_NKT; ++qt) mk[qt] = mkn[qt];
     __syncthreads();
     if (it + 1 < ntile) request(it + 1);                     // in flight under this tile's products
     if (!active) continue;
 
-    f32x4 P[BNKT], dS[BNKT];                                 // [qt][r]: query i0 + 16 qt + 4 fq + r, key fr
+    f32x4 P[STR_NKT], dS[STR_NKT];                                 // [qt][r]: query i0 + 16 qt + 4 fq + r, key fr
 #pragma unroll
-    for (int qt = 0; qt < BNKT; ++qt) {
+    for (int qt = 0; qt < STR_NKT; ++qt) {
       float4 xf[4];
-      bfrag_lds(&Qs[(16 * qt + fr) * BPLD], fq, xf);
-      P[qt] = bdot64(xf, kf, (f32x4){0.f, 0.f, 0.f, 0.f});
-      bfrag_lds(&Ds[(16 * qt + fr) * BPLD], fq, xf);
-      dS[qt] = bdot64(xf, vf, (f32x4){0.f, 0.f, 0.f, 0.f});
+      frag_lds(&Qs[(16 * qt + fr) * STR_PLD], fq, xf);
+      P[qt] = dot64(xf, kf, (f32x4){0.f, 0.f, 0.f, 0.f});
+      frag_lds(&Ds[(16 * qt + fr) * STR_PLD], fq, xf);
+      dS[qt] = dot64(xf, vf, (f32x4){0.f, 0.f, 0.f, 0.f});
     }
 #pragma unroll
-    for (int qt = 0; qt < BNKT; ++qt) {
+    for (int qt = 0; qt < STR_NKT; ++qt) {
       const float4 l4 = *reinterpret_cast<const float4*>(&Ls[16 * qt + 4 * fq]);
       const float4 e4 = *reinterpret_cast<const float4*>(&Es[16 * qt + 4 * fq]);
       const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, eq[4] = {e4.x, e4.y, e4.z, e4.w};
@@ -298,14 +270,11 @@ __global__ __launch_bounds__(BNT, 2) void stream_bwd_kv_kernel(const StreamBwdAr
 // the checks of stream_check (attn_stream.hip) for the backward's operands; they return before anything is launched
 template <typename T>
 int stream_bwd_check(const StreamBwdArgs<T>& a, int dk) {
-  constexpr int U = 16 / sizeof(T);
-  constexpr uintptr_t OA = 4 * sizeof(T) - 1;                // outputs are written in pieces of four elements
   const bool operands = a.dctx && a.ctx && a.qu && a.k && a.v && a.lse && a.delta && a.dq && a.dk && a.dv;
   if (const int rc = attn_check_common(operands, a.B, a.H, a.T1, a.T2, 0.f, nullptr)) return rc;
   if (dk != ATT_DK) return EAMD_EUNSUPPORTED;
-  if (a.ldd % U || a.ldc % U || a.ldq % U || a.ldk % U || a.ldv % U || a.lddq % 4 || a.lddk % 4 || a.lddv % 4) return EAMD_EUNSUPPORTED;
-  if (!al16(a.dctx) || !al16(a.ctx) || !al16(a.qu) || !al16(a.k) || !al16(a.v) || (reinterpret_cast<uintptr_t>(a.dq) & OA) ||
-      (reinterpret_cast<uintptr_t>(a.dk) & OA) || (reinterpret_cast<uintptr_t>(a.dv) & OA))
+  if (!stream_in_ok(a.dctx, a.ldd) || !stream_in_ok(a.ctx, a.ldc) || !stream_in_ok(a.qu, a.ldq) || !stream_in_ok(a.k, a.ldk) ||
+      !stream_in_ok(a.v, a.ldv) || !stream_out_ok(a.dq, a.lddq) || !stream_out_ok(a.dk, a.lddk) || !stream_out_ok(a.dv, a.lddv))
     return EAMD_EUNSUPPORTED;
   return attn_too_many<T>(a.B, a.H, a.T1 > a.T2 ? a.T1 : a.T2) ? EAMD_EUNSUPPORTED : EAMD_OK;
 }
@@ -322,12 +291,12 @@ int stream_bwd_entry(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc
   a.ldd = ldd; a.ldc = ldc; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.mb = mb; a.mi = mi; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
   a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.scale = scale;
   if (const int rc = stream_bwd_check(a, dk)) return rc;
-  a.nqb = (T1 + BQB - 1) / BQB;
-  a.nkb = (T2 + BQB - 1) / BQB;
+  a.nqb = (T1 + STR_QB - 1) / STR_QB;
+  a.nkb = (T2 + STR_QB - 1) / STR_QB;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((stream_bwd_q_kernel<T>), dim3(attn_grid(a.nqb, B, H)), dim3(BNT), 0, s, a);
+  hipLaunchKernelGGL((stream_bwd_q_kernel<T>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);
   EAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL((stream_bwd_kv_kernel<T>), dim3(attn_grid(a.nkb, B, H)), dim3(BNT), 0, s, a);   // reads the delta written above
+  hipLaunchKernelGGL((stream_bwd_kv_kernel<T>), dim3(attn_grid(a.nkb, B, H)), dim3(STR_NT), 0, s, a);   // reads the delta written above
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }

@@ -1,0 +1,45 @@
+// What the memory-linear attention kernels share (attn_stream.hip: forward, attn_stream_bwd.hip: backward): the tile geometry, the
+// fragment loads and the matrix-core product of 64-channel rows, and the operand rules of the host-side checks.  A workgroup of
+// four waves owns 64 rows (queries; keys on the backward's key side), 16 per wave, and sweeps the other side in staged tiles of
+// 32 rows kept as [row][STR_PLD] floats.  The header owns no LDS: tiles, barriers and the order of the global requests belong to
+// the kernels.  So do the register -> LDS staging loops and the forward's context product: moved into functions here they
+// compiled to other instruction streams than written out in the kernels (register allocation and schedule of the whole kernel).
+#pragma once
+#include "attn_common.h"
+
+constexpr int STR_QB = 64;                        // rows a workgroup owns
+constexpr int STR_KT = 32;                        // rows per staged tile
+constexpr int STR_NW = STR_QB / 16;               // waves: 16 owned rows each
+constexpr int STR_NT = 64 * STR_NW;
+constexpr int STR_PLD = ATT_PLD;                  // row stride (floats) of a staged tile in LDS
+constexpr int STR_NKT = STR_KT / 16;              // 16-row pieces of a staged tile
+constexpr int STR_KQ = STR_KT * 16 / STR_NT;      // 16-byte pieces per thread of a staged tile
+
+template <typename T>
+__device__ __forceinline__ void frag_global(const T* row, int fq, float4 (&f)[4]) {   // this lane's share of a 64-channel row: chunks 4 j + fq
+#pragma unroll
+  for (int j = 0; j < 4; ++j) f[j] = ld4(row + 16 * j + 4 * fq);
+}
+__device__ __forceinline__ void frag_lds(const float* row, int fq, float4 (&f)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) f[j] = *reinterpret_cast<const float4*>(row + 16 * j + 4 * fq);
+}
+// c[r] += sum over the 64 channels of x[row 4 fq + r] y[row fr]: x rows / y rows held as frag_* leave them
+__device__ __forceinline__ f32x4 dot64(const float4 (&x)[4], const float4 (&y)[4], f32x4 c) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].x, y[j].x, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].y, y[j].y, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].z, y[j].z, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(x[j].w, y[j].w, c, 0, 0, 0);
+  }
+  return c;
+}
+
+// operand rules of both directions; a matrix that breaks one makes the entry point decline (EAMD_EUNSUPPORTED) before any launch.
+// Read in 16-byte pieces: 16-byte aligned, row stride a multiple of 16 bytes
+template <typename T>
+inline bool stream_in_ok(const T* p, long ld) { return ld % (16 / (long)sizeof(T)) == 0 && al16(p); }
+// written in pieces of four elements inside its 64 columns
+template <typename T>
+inline bool stream_out_ok(const T* p, long ld) { return ld % 4 == 0 && (reinterpret_cast<uintptr_t>(p) & (4 * sizeof(T) - 1)) == 0; }

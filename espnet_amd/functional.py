@@ -5,6 +5,7 @@ torch.autograd is only the tape between blocks.  Weight gradients are accumulate
 the flat gradient arena (``param._eamd_grad`` installed by espnet_amd.train.FlatParams) when
 present, otherwise they are returned to autograd like any other Function would.
 """
+import collections
 import math
 
 import torch
@@ -459,17 +460,16 @@ def _ldp(T2):
     return (T2 + 7) // 8 * 8
 
 
-class _MV:
-    """[rows, D] matrix stored as a column block of a wider row-major tensor: element (r, c) at off + r*ld + c"""
-
-    __slots__ = ("t", "off", "ld")
-
-    def __init__(self, t, off=0, ld=None):
-        self.t, self.off, self.ld = t, off, (t.shape[-1] if ld is None else ld)
+_MV = ops.MatView      # the view of a column block that the ops attention wrappers take as it is
 
 
 def _mv(x):
     return x if isinstance(x, _MV) else _MV(x)
+
+
+def _rel_views(qv, p):
+    """the views of the position-biased queries and the projected positions; (None, None) without relative positions"""
+    return (None, None) if p is None else (_mv(qv), _mv(p))
 
 
 def attn_scores_fwd(qu, qv, k, p, mask, B, T1, T2, H, dk):
@@ -503,13 +503,9 @@ ATTN_TAP = None    # a list while E2E.calculate_all_attentions runs: every atten
 def attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=None, shift_len=None):
     """(P, Pd, ctx) from eamd_attn_fwd, or None when the library declines the operands; drop = (p, salt): attention
     dropout inside the kernel (Pd = dropout(P) is what the context is built from; Pd is P without dropout)"""
-    qu, k, v = _mv(qu), _mv(k), _mv(v)
-    qv3 = p3 = None
-    if p is not None:
-        qvm, pm = _mv(qv), _mv(p)
-        qv3, p3 = (qvm.t, qvm.off, qvm.ld), (pm.t, pm.off, pm.ld)
-    return ops.attn_fwd((qu.t, qu.off, qu.ld), qv3, (k.t, k.off, k.ld), (v.t, v.off, v.ld), p3, mask, B, T1, T2, H, dk,
-                        _ldp(T2), 1.0 / math.sqrt(dk), drop=drop, shift_len=shift_len)
+    qv, p = _rel_views(qv, p)
+    return ops.attn_fwd(_mv(qu), qv, _mv(k), _mv(v), p, mask, B, T1, T2, H, dk, _ldp(T2), 1.0 / math.sqrt(dk), drop=drop,
+                        shift_len=shift_len)
 
 
 # Without autograd (F_.run's inference branch), attention dropout and the attention tap, rows of MORE keys than this run the
@@ -524,13 +520,9 @@ ATTN_STREAM_TRAIN_KEYS = 4096
 
 def attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, lse=None):
     """ctx from eamd_attn_fwd_stream (with lse: eamd_attn_fwd_stream_lse), or None when the library declines the operands"""
-    qu, k, v = _mv(qu), _mv(k), _mv(v)
-    qv3 = p3 = None
-    if p is not None:
-        qvm, pm = _mv(qv), _mv(p)
-        qv3, p3 = (qvm.t, qvm.off, qvm.ld), (pm.t, pm.off, pm.ld)
-    return ops.attn_fwd_stream((qu.t, qu.off, qu.ld), qv3, (k.t, k.off, k.ld), (v.t, v.off, v.ld), p3, mask, B, T1, T2, H, dk,
-                               scale=1.0 / math.sqrt(dk), shift_len=shift_len, lse=lse)
+    qv, p = _rel_views(qv, p)
+    return ops.attn_fwd_stream(_mv(qu), qv, _mv(k), _mv(v), p, mask, B, T1, T2, H, dk, scale=1.0 / math.sqrt(dk),
+                               shift_len=shift_len, lse=lse)
 
 
 def attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T1, T2, H, dk, dqkv=None, dkv_out=None):
@@ -544,23 +536,20 @@ def attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T1, T2, H, dk, dqkv=None, 
         return None
     dq = None
     if dqkv is not None:
-        dq3, dk3, dv3 = (dqkv, 0, 3 * D), (dqkv, D, 3 * D), (dqkv, 2 * D, 3 * D)
-        dkk = dv = dqkv
+        dqm, dkm, dvm = _MV(dqkv, 0, 3 * D), _MV(dqkv, D, 3 * D), _MV(dqkv, 2 * D, 3 * D)
     else:
         dq = torch.empty(B * T1, D, device=dev, dtype=adt)
-        dq3 = (dq, 0, D)
+        dqm = _MV(dq, 0, D)
         if dkv_out is not None:
             if dkv_out.t.dtype != adt:
                 return None
-            dkk = dv = dkv_out.t
-            dk3, dv3 = (dkk, dkv_out.off, dkv_out.ld), (dv, dkv_out.off + D, dkv_out.ld)
+            dkm, dvm = dkv_out, _MV(dkv_out.t, dkv_out.off + D, dkv_out.ld)
         else:
-            dkk, dv = torch.empty(B * T2, D, device=dev, dtype=adt), torch.empty(B * T2, D, device=dev, dtype=adt)
-            dk3, dv3 = (dkk, 0, D), (dv, 0, D)
-    if not ops.attn_bwd_stream((dctx, 0, D), (cx, 0, D), (qu.t, qu.off, qu.ld), (k.t, k.off, k.ld), (v.t, v.off, v.ld), mask, lse,
-                               dq3, dk3, dv3, B, T1, T2, H, dk, 1.0 / math.sqrt(dk)):
+            dkm, dvm = (_MV(torch.empty(B * T2, D, device=dev, dtype=adt), 0, D) for _ in range(2))
+    if not ops.attn_bwd_stream(_MV(dctx, 0, D), _MV(cx, 0, D), qu, k, v, mask, lse, dqm, dkm, dvm, B, T1, T2, H, dk,
+                               1.0 / math.sqrt(dk)):
         return None
-    return dq, dkk, dv
+    return dq, dkm.t, dvm.t
 
 
 def attn_context_fwd(P, v, B, T1, T2, H, dk):
@@ -611,9 +600,9 @@ def attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk, Pd=None, attn_drop
         dS = torch.empty(H * B * T1 * ldp, device=dev, dtype=adt)
         dbd = torch.empty(H * B * T1 * ldp, device=dev, dtype=adt) if p is not None else None
         dqu = None if dq_in_qkv else torch.empty(B * T1, D, device=dev, dtype=torch.float32)
-        dq_view = (dqkv, 0, ldo) if dq_in_qkv else (dqu, 0, D)
-        if not ops.attn_bwd_q((dctx, 0, D), (k.t, k.off, k.ld), (v.t, v.off, v.ld), P, dS, dbd, dq_view, B, T1, T2, H, dk,
-                              ldp, 1.0 / math.sqrt(dk), drop=attn_drop if Pd is not None else None, shift_len=shift_len):
+        dq_view = _MV(dqkv, 0, ldo) if dq_in_qkv else _MV(dqu, 0, D)
+        if not ops.attn_bwd_q(_MV(dctx, 0, D), k, v, P, dS, dbd, dq_view, B, T1, T2, H, dk, ldp, 1.0 / math.sqrt(dk),
+                              drop=attn_drop if Pd is not None else None, shift_len=shift_len):
             dS = None
     if dS is None and shift_len is not None:
         raise ops._lib.EamdError("relative-position attention backward on a shape-bucketed batch needs the fused kernel")
@@ -653,8 +642,8 @@ def attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk, Pd=None, attn_drop
         # dv and dk in one launch.  (The kernel can also accumulate dpos += dbd^T qv - eamd_attn_bwd_kv_f32 with dbd / qv /
         # dpos set - but that product reduces over the BATCH too: 32-way contended atomics made it slower than the
         # split-K GEMM below, measured 133.6 vs 133.2 us for the whole backward; it is left to the GEMM.)
-        kv_fused = ops.attn_bwd_kv(Pd if Pd is not None else P, dS, None, (dctx, 0, D), (qu.t, qu.off, qu.ld), None,
-                                   (dv, dv_off, ldo), (dkk, dk_off, ldo), None, B, T1, T2, H, dk, ldp)
+        kv_fused = ops.attn_bwd_kv(Pd if Pd is not None else P, dS, None, _MV(dctx, 0, D), qu, None, _MV(dv, dv_off, ldo),
+                                   _MV(dkk, dk_off, ldo), None, B, T1, T2, H, dk, ldp)
     if not kv_fused:
         if kv_try:       # the library declined the operands: dv was skipped above
             ops.gemm(Pd if Pd is not None else P, dctx, dv, T2, dk, T1, ldp, D, ldo, transA=1, transB=1, batch=(B, H), sA=sP,
@@ -670,7 +659,83 @@ def attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk, Pd=None, attn_drop
     return dqu, dqv, dkk, dv, dp
 
 
-FUSE_QKV = True   # tests flip this to compare against the three-GEMM path
+# ---- which route an attention block takes, what it keeps for backward, what it falls back to -------------------------------
+def attn_stored_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=None, shift_len=None, context=True):
+    """(P, Pd, ctx, fused) on a route that stores the probabilities: the fused forward where FUSE_ATTN and
+    ops.attn_fwd_supported allow it and the library takes the operands (fused = True), else GEMM + softmax (+ dropout) + GEMM;
+    context=False leaves that last GEMM out (ctx is None) for a caller that wants the probabilities only.  drop = (p, salt) or
+    None; without dropout Pd is P."""
+    if FUSE_ATTN and ops.attn_fwd_supported(T1, T2, dk, p is not None):
+        # scores, softmax, attention dropout and context in one launch
+        fwd = attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=drop, shift_len=shift_len)
+        if fwd is not None:
+            return fwd + (True,)
+    if shift_len is not None:
+        # a padded batch needs the rel_shift over its own length; only the fused kernels take it (shift_len)
+        raise ops._lib.EamdError("relative-position attention on a shape-bucketed batch needs the fused attention kernels "
+                                 "(d_k = 64, T' <= 4096: ops.attn_fwd_supported; train.BucketedGraphStep checks this per bucket up front); "
+                                 "this shape runs the GEMM + softmax path")
+    P = attn_scores_fwd(qu, qv, k, p, mask, B, T1, T2, H, dk)
+    Pd = ops.dropout(P, drop[0], drop[1]) if drop is not None else P
+    return P, Pd, (attn_context_fwd(Pd, v, B, T1, T2, H, dk) if context else None), False
+
+
+# what attn_block_bwd needs of a forward, per route: "stream" - lse and mask (lse None: no autograd, no backward); "kept" (fused)
+# and "gemm" - P and Pd (the dropped copy, None without dropout); "recompute" - mask
+AttnKept = collections.namedtuple("AttnKept", "route P Pd lse mask", defaults=(None,) * 4)
+
+
+def attn_block_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop, shift_len, grad, last_query_only, stream_bwd_ok):
+    """-> (ctx [B*T1, H*dk], AttnKept) of one attention block.  drop = (p, salt) of the attention dropout; grad: autograd is on;
+    stream_bwd_ok: a shared k / v projection collects gradients in the operand dtype, which the streamed backward writes."""
+    p_att = drop[0]
+    unread = ATTN_TAP is None and p_att <= 0.0 and dk == 64       # nobody reads the probabilities, and the streamed kernels fit
+    if not grad and unread and T2 > ATTN_STREAM_KEYS:
+        # inference on long rows: online softmax, O(T') memory, any number of keys
+        cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=shift_len)
+        if cx is not None:
+            return cx, AttnKept("stream")
+    if grad and unread and p is None and not last_query_only and T2 > ATTN_STREAM_TRAIN_KEYS and stream_bwd_ok:
+        # training on long rows without relative positions: keep ctx and the row statistic, no probabilities; backward
+        # rebuilds them tile by tile (attn_stream_bwd)
+        lse = torch.empty(H * B * T1, device=_mv(qu).t.device, dtype=torch.float32)
+        cx = attn_fwd_stream(qu, None, k, v, None, mask, B, T1, T2, H, dk, lse=lse)
+        if cx is not None:
+            return cx, AttnKept("stream", lse=lse, mask=mask)
+    P, Pd, cx, fused = attn_stored_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=drop if p_att > 0.0 else None,
+                                       shift_len=shift_len)
+    if ATTN_TAP is not None:      # calculate_all_attentions: the probabilities in the reference's (B, H, T1, T2) layout
+        ATTN_TAP.append(Pd.view(H, B, T1, _ldp(T2))[..., :T2].permute(1, 0, 2, 3).float())
+    # O(T') memory kept for backward: beyond ATTN_RECOMPUTE_MB of probabilities (P and its dropped copy: B x H x T1 x T2 each) they
+    # are NOT kept - backward runs the fused forward kernel again (same operands, same dropout counter: the same bits) into
+    # transient buffers.  One more attention-forward launch per block in backward (2 - 3 % of a step at T' = 249, where it is
+    # off by default; at T' = 1000 P and Pd are 0.98 GB of the 2.57 GB a block keeps)
+    if fused and ATTN_RECOMPUTE_MB >= 0 and P.numel() * P.element_size() * (2 if p_att > 0.0 else 1) >= ATTN_RECOMPUTE_MB * 2 ** 20:
+        return cx, AttnKept("recompute", mask=mask)
+    return cx, AttnKept("kept" if fused else "gemm", P, Pd if p_att > 0.0 else None)
+
+
+def attn_block_bwd(kept, dctx, cx, qu, qv, k, v, p, B, T1, T2, H, dk, drop, shift_len, dqkv=None, dkv_out=None, dp_out=None):
+    """backward of attn_block_fwd -> (dqu, dqv, dk, dv, dp) as attn_core_bwd returns them (dqkv / dkv_out / dp_out as there).
+    After the streamed backward dqu is already a GEMM operand (ops.to_act passes it through), or None with dqkv."""
+    P, Pd = kept.P, kept.Pd
+    if kept.route == "stream":
+        sb = attn_stream_bwd(dctx, cx, kept.lse, qu, k, v, kept.mask, B, T1, T2, H, dk, dqkv=dqkv, dkv_out=dkv_out)
+        if sb is not None:
+            return sb[0], None, sb[1], sb[2], None
+        # the library declined the streamed backward: the probabilities of the stored route, rebuilt
+        P = attn_stored_fwd(qu, None, k, v, None, kept.mask, B, T1, T2, H, dk, context=False)[0]
+    elif kept.route == "recompute":
+        # the probabilities this block did not keep: the fused forward once more (attn_block_fwd, ATTN_RECOMPUTE_MB)
+        fwd = attn_fwd_fused(qu, qv, k, v, p, kept.mask, B, T1, T2, H, dk, drop=drop if drop[0] > 0.0 else None, shift_len=shift_len)
+        if fwd is None:
+            raise ops._lib.EamdError("attention recompute: the fused forward declined operands it took in forward")
+        P, Pd = fwd[0], (fwd[1] if drop[0] > 0.0 else None)
+    return attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk, Pd=Pd, attn_drop=drop, dqkv=dqkv, dkv_out=dkv_out,
+                         dp_out=dp_out, shift_len=shift_len)
+
+
+FUSE_QKV = True  # tests flip this to compare against the three-GEMM path
 
 
 def _adjacent3(a, b, c):
@@ -885,40 +950,9 @@ class MHABlockFn(torch.autograd.Function):
                 qu, qv = ops.add_bias2(q, pu.reshape(-1), pv.reshape(-1))
         else:
             p, qu, qv = None, q, None
-        fwd = None
-        tb = ops.time_bound() if (rel and T1 == T2) else None      # padded batch: rel_shift over the batch's own length
-        ctx.shift_len = tb
-        P = Pd = cx = None
-        if isinstance(ctx, _NoGradCtx) and ATTN_TAP is None and p_att <= 0.0 and dk == 64 and T2 > ATTN_STREAM_KEYS:
-            # inference on long rows: nobody reads the probabilities - online softmax, O(T') memory, any number of keys
-            cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=tb)
-        lse = None
-        if not isinstance(ctx, _NoGradCtx) and not rel and p_att <= 0.0 and ATTN_TAP is None and dk == 64 and not last_query_only \
-                and T2 > ATTN_STREAM_TRAIN_KEYS and (pre_kv is None or pre_kv[1].grad_dtype == adt):
-            # training on long rows without relative positions: keep ctx and the row statistic, no probabilities; backward
-            # rebuilds them tile by tile (attn_stream_bwd)
-            lse = torch.empty(H * B * T1, device=x2.device, dtype=torch.float32)
-            cx = attn_fwd_stream(qu, None, k, v, None, mask, B, T1, T2, H, dk, lse=lse)
-            if cx is None:
-                lse = None
-        ctx.stream = None if lse is None else (lse, mask)
-        if cx is None and FUSE_ATTN and ops.attn_fwd_supported(T1, T2, dk, rel):
-            # scores, softmax, attention dropout and context in one launch
-            fwd = attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=(p_att, s_att) if p_att > 0.0 else None,
-                                 shift_len=tb)
-        if fwd is not None:
-            P, Pd, cx = fwd
-        elif cx is None:
-            if tb is not None:
-                # a padded batch needs the rel_shift over its own length; only the fused kernels take it (shift_len)
-                raise ops._lib.EamdError("relative-position attention on a shape-bucketed batch needs the fused attention kernels "
-                                         "(d_k = 64, T' <= 4096: ops.attn_fwd_supported; train.BucketedGraphStep checks this per bucket up front); "
-                                         "this shape runs the GEMM + softmax path")
-            P = attn_scores_fwd(qu, qv, k, p, mask, B, T1, T2, H, dk)
-            Pd = ops.dropout(P, p_att, s_att) if p_att > 0.0 else P
-            cx = attn_context_fwd(Pd, v, B, T1, T2, H, dk)
-        if ATTN_TAP is not None:      # calculate_all_attentions: the probabilities in the reference's (B, H, T1, T2) layout
-            ATTN_TAP.append(Pd.view(H, B, T1, _ldp(T2))[..., :T2].permute(1, 0, 2, 3).float())
+        ctx.shift_len = ops.time_bound() if (rel and T1 == T2) else None      # padded batch: rel_shift over the batch's own length
+        cx, kept = attn_block_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, (p_att, s_att), ctx.shift_len,
+                                  not isinstance(ctx, _NoGradCtx), last_query_only, pre_kv is None or pre_kv[1].grad_dtype == adt)
         if rp is not None:
             out = ops.rowproj(cx, rp[2], D, bias=bo, R=res, drop=(p_out, s_out) if p_out > 0.0 else None)
         elif p_out > 0.0 and (ops.fast() or ops.f32_epilogue_drop()):
@@ -929,27 +963,16 @@ class MHABlockFn(torch.autograd.Function):
         else:
             out = ops.linear_fwd(cx, ops.wshadow(wo), bo, R=res)
         ctx.rp = rp
-        # O(T') memory kept for backward: beyond ATTN_RECOMPUTE_MB of probabilities (P and its dropped copy: B x H x T1 x T2 each) they
-        # are NOT kept - backward runs the fused forward kernel again (same operands, same dropout counter: the same bits) into
-        # transient buffers.  One more attention-forward launch per block in backward (2 - 3 % of a step at T' = 249, where it is
-        # off by default; at T' = 1000 P and Pd are 0.98 GB of the 2.57 GB a block keeps)
-        ctx.recompute = None
-        if fwd is not None and ATTN_RECOMPUTE_MB >= 0:
-            held = P.numel() * P.element_size() * (2 if p_att > 0.0 else 1)
-            if held >= ATTN_RECOMPUTE_MB * 2 ** 20:
-                ctx.recompute = mask
-                P = Pd = None
+        ctx.kept = kept._replace(P=None, Pd=None)      # the probabilities travel with the saved tensors
         # tensors that live in a SharedProj stay out of save_for_backward (they are no outputs of this Function)
         p_sv = None if pre_pos is not None else p
         if fused:   # k, v (and q without relative positions) are column blocks of qkv
-            ctx.save_for_backward(x2, mean, rstd, xn, None, qu if rel else None, qv, qkv, None, p_sv, P, cx, pos2,
-                                  Pd if (p_att > 0.0 and P is not None) else None)
+            ctx.save_for_backward(x2, mean, rstd, xn, None, qu if rel else None, qv, qkv, None, p_sv, kept.P, cx, pos2, kept.Pd)
         elif pre_kv is not None:
-            ctx.save_for_backward(x2, mean, rstd, xn, None, qu, qv, None, None, p_sv, P, cx, pos2,
-                                  Pd if (p_att > 0.0 and P is not None) else None)
+            ctx.save_for_backward(x2, mean, rstd, xn, None, qu, qv, None, None, p_sv, kept.P, cx, pos2, kept.Pd)
         else:
-            ctx.save_for_backward(x2, mean, rstd, xn, kv_in if memory is not None else None, qu, qv, k, v, p_sv, P, cx,
-                                  pos2, Pd if (p_att > 0.0 and P is not None) else None)
+            ctx.save_for_backward(x2, mean, rstd, xn, kv_in if memory is not None else None, qu, qv, k, v, p_sv, kept.P, cx,
+                                  pos2, kept.Pd)
         ctx.pre = pre
         if pre is not None:      # the shared projection owns these parameters' gradients
             skip = (4, 5, 6, 7) if pre_kv is not None else (10,)
@@ -982,35 +1005,14 @@ class MHABlockFn(torch.autograd.Function):
             dctx = ops.rowproj(dob, rp[3], D)
         else:
             dctx = ops.linear_bwd_x(dob, ops.wshadow(wo), out_dtype=adt)
-        def again(qu_, qv_, k_, v_):
-            """the probabilities this block did not keep: the fused forward once more (MHABlockFn.forward, ATTN_RECOMPUTE_MB)"""
-            f = attn_fwd_fused(qu_, qv_, k_, v_, p, ctx.recompute, B, T1, T2, H, dk, drop=(p_att, s_att) if p_att > 0.0 else None,
-                               shift_len=ctx.shift_len)
-            if f is None:
-                raise ops._lib.EamdError("attention recompute: the fused forward declined operands it took in forward")
-            return f[0], (f[1] if p_att > 0.0 else None)
-        def stored(qu_, k_, v_):
-            """the library declined the streamed backward: the probabilities of today's path, rebuilt"""
-            if FUSE_ATTN and ops.attn_fwd_supported(T1, T2, dk, False):
-                f = attn_fwd_fused(qu_, None, k_, v_, None, ctx.stream[1], B, T1, T2, H, dk)
-                if f is not None:
-                    return f[0]
-            return attn_scores_fwd(qu_, None, k_, None, ctx.stream[1], B, T1, T2, H, dk)
+        kept = ctx.kept._replace(P=P, Pd=Pd)
         if ctx.fused:
             qkv = k
             dqkv = torch.empty(B * T1, 3 * D, device=do.device, dtype=adt)
             quv = qu if rel else _MV(qkv, 0, 3 * D)
             kb, vb = _MV(qkv, D, 3 * D), _MV(qkv, 2 * D, 3 * D)
-            done = ctx.stream is not None and attn_stream_bwd(dctx, cx, ctx.stream[0], quv, kb, vb, ctx.stream[1], B, T1, T2, H, dk,
-                                                              dqkv=dqkv) is not None
-            if not done:
-                if ctx.stream is not None:
-                    P = stored(quv, kb, vb)
-                elif P is None:
-                    P, Pd = again(quv, qv, kb, vb)
-                dqu, dqv, _, _, dp = attn_core_bwd(dctx, P, quv, qv, kb, vb, p, B, T1,
-                                                   T2, H, dk, Pd=Pd, attn_drop=(p_att, s_att), dqkv=dqkv, dp_out=dp_out,
-                                                   shift_len=ctx.shift_len)
+            dqu, dqv, _, _, dp = attn_block_bwd(kept, dctx, cx, quv, qv, kb, vb, p, B, T1, T2, H, dk, (p_att, s_att), ctx.shift_len,
+                                                dqkv=dqkv, dp_out=dp_out)
             if rel:
                 wpos = params[10]
                 # dq = dqu + dqv (operand dtype, into the fused buffer) + both bias gradients in one pass
@@ -1029,27 +1031,15 @@ class MHABlockFn(torch.autograd.Function):
         if pre_kv is not None:
             k, v = pre_kv[1].block(pre_kv[2], 0), pre_kv[1].block(pre_kv[2], D)
             dkv_out = pre_kv[1].grad_block(pre_kv[2])
-        sb = attn_stream_bwd(dctx, cx, ctx.stream[0], qu, k, v, ctx.stream[1], B, T1, T2, H, dk, dkv_out=dkv_out) \
-            if ctx.stream is not None else None
-        if sb is not None:
-            dkk, dv = sb[1:]
-        else:
-            if ctx.stream is not None:
-                P = stored(qu, k, v)
-            elif P is None:
-                P, Pd = again(qu, qv, k, v)
-            dqu, dqv, dkk, dv, dp = attn_core_bwd(dctx, P, qu, qv, k, v, p, B, T1, T2, H, dk,
-                                                  Pd=Pd, attn_drop=(p_att, s_att), dkv_out=dkv_out, dp_out=dp_out,
-                                                  shift_len=ctx.shift_len)
-        if sb is not None:       # dq is already a GEMM operand
-            dq = sb[0]
-        elif rel:
+        dqu, dqv, dkk, dv, dp = attn_block_bwd(kept, dctx, cx, qu, qv, k, v, p, B, T1, T2, H, dk, (p_att, s_att), ctx.shift_len,
+                                               dkv_out=dkv_out, dp_out=dp_out)
+        if rel:
             wpos = params[10]
             dq = ops.add_cast_colsum2(dqu, dqv, sink.buf(11).view(-1), sink.buf(12).view(-1))
             if dp_out is None:
                 ops.linear_bwd_w(ops.to_act(dp), pos2, sink.buf(10))
         else:
-            dq = ops.to_act(dqu)
+            dq = ops.to_act(dqu)       # (the streamed backward's dq is a GEMM operand already)
         kv_in = mem2 if cross else xn
         ops.linear_bwd_w(dq, xn, sink.buf(2), db=sink.buf(3))
         dxn = ops.linear_bwd_x(dq, ops.wshadow(wq))

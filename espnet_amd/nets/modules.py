@@ -1172,16 +1172,8 @@ class Decoder(torch.nn.Module, BatchScorerInterface):
             # (... 32 utterances: one workgroup per (utterance, head) for all its hypotheses, keys / values read once)
             cx = ops.decode_src_attn(q2, k2.t, k2.off, v2.off, k2.ld, mask, G, n // G, T, H, group=n > 32) \
                 if (k2.t.dtype == torch.float32 and (mask is None or mask.shape[1] == 1)) else None
-            fwd = None
-            if cx is None and F_.FUSE_ATTN and ops.attn_fwd_supported(n // G, T, a.d_k, False):
-                fwd = F_.attn_fwd_fused(q2, None, k2, v2, None, mask, G, n // G, T, H, a.d_k)
-            if cx is not None:
-                pass
-            elif fwd is not None:
-                cx = fwd[2]
-            else:
-                P = F_.attn_scores_fwd(q2, None, k2, None, mask, G, n // G, T, H, a.d_k)
-                cx = F_.attn_context_fwd(P, v2, G, n // G, T, H, a.d_k)
+            if cx is None:
+                cx = F_.attn_stored_fwd(q2, None, k2, v2, None, mask, G, n // G, T, H, a.d_k)[2]
             x = ops.linear_fwd(cx, a.linear_out.weight, a.linear_out.bias, R=x)
             ff = m.feed_forward
             h = self._ln_rows(x, m.norm3, ff.w_1.weight, ff.w_1.bias, act=ff.act_id)      # (ACT_RELU / ACT_SWISH = EPI_RELU / EPI_SWISH)

@@ -3,6 +3,7 @@
 No arithmetic happens here: every function validates shapes on the host (a faulting kernel can
 take the whole GPU node down), fills the argument struct and launches on torch's current stream.
 """
+import collections
 import ctypes as C
 import os
 import math
@@ -1106,6 +1107,33 @@ def attn_fwd_supported(T1, T2, dk, rel):
     return (fast() or F32_FUSED_ATTN) and T2 <= 4096
 
 
+class MatView(collections.namedtuple("MatView", "t off ld")):
+    """[rows, D] matrix stored as a column block of a wider row-major tensor: element (r, c) at off + r*ld + c.  What the
+    attention wrappers below take for their matrix operands; a plain (tensor, element offset, row stride) tuple does as well."""
+    __slots__ = ()
+
+    def __new__(cls, t, off=0, ld=None):
+        return super().__new__(cls, t, off, t.shape[-1] if ld is None else ld)
+
+
+def _view_args(*views):
+    """(address, row stride) of each view in turn; (NULL, 0) for None"""
+    return sum(((None, 0) if v is None else (ptr(v[0], v[1]), v[2]) for v in views), ())
+
+
+def _attn_launch(name, args, keep):
+    """one attention entry point on the current stream: False if the library declines the operands (EAMD_EUNSUPPORTED); any
+    other failure raises.  `keep` holds the operands alive beside the replay closure of a recorded step."""
+    fn = getattr(_lib.lib(), name)
+    rc = fn(*args, stream_ptr())
+    if rc == _lib.EAMD_EUNSUPPORTED:
+        return False
+    check(rc, name)
+    if _gemm_record is not None:
+        _gemm_record.append((dict(kind=name, flop=0.0), keep, lambda sp: check(fn(*args, sp), name)))
+    return True
+
+
 def _attn_tail(drop, device, rel, T1, T2, shift_len, Pd=()):
     """the argument tail attn_fwd and attn_bwd_q share: (Pd,) drop_p, drop_step, drop_salt, shift_len.  drop = (p, salt) or None;
     relative positions on a padded batch take the rel_shift over the batch's own length (shift_len: int32 device scalar)"""
@@ -1123,12 +1151,7 @@ def attn_fwd(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldp, scale, drop=None, s
     dev = qu[0].device
     dt = qu[0].dtype
     D = H * dk
-    mb = mi = 0
-    if mask is not None:
-        assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 3 and mask.shape[0] in (1, B)
-        assert mask.shape[2] == T2 and mask.shape[1] in (1, T1)
-        mb = 0 if mask.shape[0] == 1 else mask.shape[1] * mask.shape[2]
-        mi = 0 if mask.shape[1] == 1 else T2
+    mb, mi = _mask_strides(mask, B, T1, T2)
     assert dt in (torch.bfloat16, torch.float32)
     for t_, _, _ in (qu, k, v) + ((qv,) if qv is not None else ()):
         assert t_.dtype == dt and t_.is_cuda
@@ -1137,20 +1160,10 @@ def attn_fwd(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldp, scale, drop=None, s
     cx = torch.empty(B * T1, D, device=dev, dtype=dt)
     dropping = drop is not None and drop[0] > 0.0
     Pd = torch.empty_like(P) if dropping else P
-    args = (ptr(qu[0], qu[1]), qu[2], ptr(qv[0], qv[1]) if qv is not None else None, qv[2] if qv is not None else 0,
-            ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(pos[0], pos[1]) if pos is not None else None,
-            pos[2] if pos is not None else 0,
-            ptr(mask), mb, mi, ptr(P), ldp, ptr(cx), D, B, H, T1, T2, dk, scale)
+    args = _view_args(qu, qv, k, v, pos) + (ptr(mask), mb, mi, ptr(P), ldp, ptr(cx), D, B, H, T1, T2, dk, scale)
     args = args + _attn_tail(drop, dev, pos is not None, T1, T2, shift_len, Pd=(Pd,))
     name = "eamd_attn_fwd" if dt == torch.bfloat16 else "eamd_attn_fwd_f32"
-    fn = getattr(_lib.lib(), name)
-    rc = fn(*args, stream_ptr())
-    if rc == _lib.EAMD_EUNSUPPORTED:
-        return None
-    check(rc, name)
-    if _gemm_record is not None:
-        _gemm_record.append((dict(kind=name, flop=0.0), (qu, qv, k, v, pos, mask, P, Pd, cx), lambda sp, args=args: check(fn(*args, sp), name)))
-    return P, Pd, cx
+    return (P, Pd, cx) if _attn_launch(name, args, (qu, qv, k, v, pos, mask, P, Pd, cx)) else None
 
 
 ATTN_STREAM_QB = 64     # queries per workgroup and keys per staged tile of csrc/attn_stream.hip (eamd_attn_stream_qb / _kt):
@@ -1176,12 +1189,7 @@ def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1
     dt = qu[0].dtype
     D = H * dk
     ldc = D if ldc is None else ldc
-    mb = mi = 0
-    if mask is not None:
-        assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.dim() == 3 and mask.shape[0] in (1, B)
-        assert mask.shape[2] == T2 and mask.shape[1] in (1, T1)
-        mb = 0 if mask.shape[0] == 1 else mask.shape[1] * mask.shape[2]
-        mi = 0 if mask.shape[1] == 1 else T2
+    mb, mi = _mask_strides(mask, B, T1, T2)
     assert dt in (torch.bfloat16, torch.float32) and ldc >= D
     for t_, _, _ in (qu, k, v) + ((qv,) if qv is not None else ()):
         assert t_.dtype == dt and t_.is_cuda
@@ -1191,22 +1199,14 @@ def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1
     cx, ldc = out[0], out[2]
     assert cx.dtype == dt and cx.is_cuda and ldc >= D
     rel = pos is not None
-    args = (ptr(qu[0], qu[1]), qu[2], ptr(qv[0], qv[1]) if qv is not None else None, qv[2] if qv is not None else 0,
-            ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(pos[0], pos[1]) if rel else None, pos[2] if rel else 0,
-            ptr(mask), mb, mi, ptr(cx, out[1]), ldc, B, H, T1, T2, dk, scale, ptr(shift_len) if (rel and T1 == T2) else None)
+    args = _view_args(qu, qv, k, v, pos) + (ptr(mask), mb, mi, ptr(cx, out[1]), ldc, B, H, T1, T2, dk, scale,
+                                            ptr(shift_len) if (rel and T1 == T2) else None)
     name = "eamd_attn_fwd_stream" if dt == torch.bfloat16 else "eamd_attn_fwd_stream_f32"
     if lse is not None:
         assert lse.dtype == torch.float32 and lse.is_cuda and lse.is_contiguous() and lse.numel() >= H * B * T1
         name = name.replace("_stream", "_stream_lse")
         args = args + (ptr(lse),)
-    fn = getattr(_lib.lib(), name)
-    rc = fn(*args, stream_ptr())
-    if rc == _lib.EAMD_EUNSUPPORTED:
-        return None
-    check(rc, name)
-    if _gemm_record is not None:
-        _gemm_record.append((dict(kind=name, flop=0.0), (qu, qv, k, v, pos, mask, cx, lse), lambda sp, args=args: check(fn(*args, sp), name)))
-    return cx
+    return cx if _attn_launch(name, args, (qu, qv, k, v, pos, mask, cx, lse)) else None
 
 
 def attn_bwd_stream(dctx, ctx, qu, k, v, mask, lse, dq, dk_, dv, B, T1, T2, H, dk, scale):
@@ -1221,45 +1221,26 @@ def attn_bwd_stream(dctx, ctx, qu, k, v, mask, lse, dq, dk_, dv, B, T1, T2, H, d
     assert lse.dtype == torch.float32 and lse.is_cuda and lse.is_contiguous() and lse.numel() >= H * B * T1
     mb, mi = _mask_strides(mask, B, T1, T2)
     ws = torch.empty(H * B * T1, device=lse.device, dtype=torch.float32)      # delta: query side -> key side
-    args = sum(((ptr(t_, off), ld) for t_, off, ld in (dctx, ctx, qu, k, v)), ()) + (ptr(mask), mb, mi, ptr(lse), ptr(ws))
-    args = args + sum(((ptr(t_, off), ld) for t_, off, ld in (dq, dk_, dv)), ()) + (B, H, T1, T2, dk, scale)
+    args = _view_args(dctx, ctx, qu, k, v) + (ptr(mask), mb, mi, ptr(lse), ptr(ws)) + _view_args(dq, dk_, dv) + (B, H, T1, T2, dk, scale)
     name = "eamd_attn_bwd_stream" if dt == torch.bfloat16 else "eamd_attn_bwd_stream_f32"
-    fn = getattr(_lib.lib(), name)
-    rc = fn(*args, stream_ptr())
-    if rc == _lib.EAMD_EUNSUPPORTED:
-        return False
-    check(rc, name)
-    if _gemm_record is not None:
-        _gemm_record.append((dict(kind=name, flop=0.0), (dctx, ctx, qu, k, v, mask, lse, ws, dq, dk_, dv),
-                             lambda sp, args=args: check(fn(*args, sp), name)))
-    return True
+    return _attn_launch(name, args, (dctx, ctx, qu, k, v, mask, lse, ws, dq, dk_, dv))
 
 
 def attn_bwd_q(dctx, k, v, P, dS, dbd, dq, B, T1, T2, H, dk, ldp, scale, drop=None, shift_len=None):
     """dctx / k / v / dq: (tensor, element offset, row stride) views; P, dS (and dbd or None): [H*B*T1*ldp], bf16
     (eamd_attn_bwd_q; dq fp32 or bf16) or everything fp32 (eamd_attn_bwd_q_f32).
     dS, dbd and dq are written.  Returns False if the library declines the operands (EAMD_EUNSUPPORTED)."""
+    args = _view_args(dctx, k, v) + (ptr(P), ldp, ptr(dS), ptr(dbd)) + _view_args(dq)
     if P.dtype == torch.bfloat16:
         name = "eamd_attn_bwd_q"
-        args = (ptr(dctx[0], dctx[1]), dctx[2], ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(P), ldp,
-                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), dq[2], dq[0].dtype == torch.bfloat16, B, H, T1, T2, dk,
-                scale)
+        args = args + (dq[0].dtype == torch.bfloat16,)
     else:
         name = "eamd_attn_bwd_q_f32"
         for t_ in (dctx[0], k[0], v[0], P, dS, dq[0]) + ((dbd,) if dbd is not None else ()):
             assert t_.dtype == torch.float32
-        args = (ptr(dctx[0], dctx[1]), dctx[2], ptr(k[0], k[1]), k[2], ptr(v[0], v[1]), v[2], ptr(P), ldp,
-                ptr(dS), ptr(dbd), ptr(dq[0], dq[1]), dq[2], B, H, T1, T2, dk, scale)
     # the forward's attention dropout: dP <- mask * dP / (1 - p)
-    args = args + _attn_tail(drop, P.device, dbd is not None, T1, T2, shift_len)
-    fn = getattr(_lib.lib(), name)
-    rc = fn(*args, stream_ptr())
-    if rc == _lib.EAMD_EUNSUPPORTED:
-        return False
-    check(rc, name)
-    if _gemm_record is not None:
-        _gemm_record.append((dict(kind=name, flop=0.0), (dctx, k, v, P, dS, dbd, dq), lambda sp, args=args: check(fn(*args, sp), name)))
-    return True
+    args = args + (B, H, T1, T2, dk, scale) + _attn_tail(drop, P.device, dbd is not None, T1, T2, shift_len)
+    return _attn_launch(name, args, (dctx, k, v, P, dS, dbd, dq))
 
 
 FUSED_ATTN_KV = True   # fp32 mode: eamd_attn_bwd_kv_f32 (tests flip it to reach the batched GEMMs)
@@ -1276,25 +1257,16 @@ def attn_bwd_kv(Pd, dS, dbd, dctx, qu, qv, dv, dk_, dpos, B, T1, T2, H, dk, ldp)
         assert t_.dtype == dt and t_.is_cuda
     assert dv[2] == dk_[2]
     rel = dbd is not None
+    outs = (ptr(dv[0], dv[1]), ptr(dk_[0], dk_[1]), dv[2])
     if dt == torch.float32:
-        args = (ptr(Pd), ptr(dS), ptr(dbd) if rel else None, ldp, ptr(dctx[0], dctx[1]), dctx[2], ptr(qu[0], qu[1]),
-                qu[2], ptr(qv[0], qv[1]) if rel else None, qv[2] if rel else 0, ptr(dv[0], dv[1]), ptr(dk_[0], dk_[1]),
-                dv[2], ptr(dpos[0], dpos[1]) if rel else None, dpos[2] if rel else 0, B, H, T1, T2, dk)
+        args = (ptr(Pd), ptr(dS), ptr(dbd) if rel else None, ldp) + _view_args(dctx, qu, qv if rel else None) + outs \
+            + _view_args(dpos if rel else None) + (B, H, T1, T2, dk)
         name = "eamd_attn_bwd_kv_f32"
     else:
         assert not rel, "the bf16 key-side launch leaves the positional product to the GEMM"
-        args = (ptr(Pd), ptr(dS), ldp, ptr(dctx[0], dctx[1]), dctx[2], ptr(qu[0], qu[1]), qu[2],
-                ptr(dv[0], dv[1]), ptr(dk_[0], dk_[1]), dv[2], B, H, T1, T2, dk)
+        args = (ptr(Pd), ptr(dS), ldp) + _view_args(dctx, qu) + outs + (B, H, T1, T2, dk)
         name = "eamd_attn_bwd_kv"
-    fn = getattr(_lib.lib(), name)
-    rc = fn(*args, stream_ptr())
-    if rc == _lib.EAMD_EUNSUPPORTED:
-        return False
-    check(rc, name)
-    if _gemm_record is not None:
-        _gemm_record.append((dict(kind=name, flop=0.0), (Pd, dS, dbd, dctx, qu, qv, dv, dk_, dpos),
-                             lambda sp, args=args: check(fn(*args, sp), name)))
-    return True
+    return _attn_launch(name, args, (Pd, dS, dbd, dctx, qu, qv, dv, dk_, dpos))
 
 
 def softmax_fwd(ac, bd, mask, P, nblocks, B, T1, T2, ld, scale):

@@ -2,6 +2,7 @@
 same seeded inputs, and against the vectors recorded from the reference (tests/golden).
 Bar: integer work bit-exact; fp32 path rtol ~1e-4 (accumulation order differs from MKL);
 bf16-MFMA path within the bf16 input-rounding bound (stated per test)."""
+import itertools
 import math
 
 import numpy as np
@@ -1379,6 +1380,112 @@ def test_attention_shift_len_vs_oracle(ops, oracle, Ts, T, prec):
         assert bool((dbd[:, :, Ts:] == 0).all()) and bool((dbd[..., Ts:] == 0).all())
     finally:
         F_.FUSE_ATTN = True
+        espnet_amd.set_precision("fp32")
+
+
+# One MHABlockFn call per case: (name, "self" | "cross" | "last", relative positions, autograd, attention dropout, F_ flags,
+# launches).  launches: what ops._gemm_record collects, in order - "gemm": a plain eamd_gemm, the others eamd_attn_<name>, n * x: x
+# n times running - in fp32 mode; bf16 mode runs the entry points without the _f32 suffix, and where it differs beyond that the
+# entry is an (fp32, bf16) pair (without autograd the fp32 projections run the few-rows kernels, which record nothing).  Written
+# from a run of _attention_route_run BEFORE the route policy moved into F_.attn_block_fwd / attn_block_bwd, not from that code.
+_STREAM0 = dict(ATTN_STREAM_KEYS=0, ATTN_STREAM_TRAIN_KEYS=0)
+ATTN_ROUTE_CASES = [
+    ("self", "self", False, True, 0.0, {}, "gemm fwd_f32 3*gemm bwd_q_f32 bwd_kv_f32 2*gemm"),
+    ("self_rel", "self", True, True, 0.0, {}, "2*gemm fwd_f32 3*gemm bwd_q_f32 gemm bwd_kv_f32 4*gemm"),
+    ("cross", "cross", False, True, 0.0, {}, "3*gemm fwd_f32 3*gemm bwd_q_f32 bwd_kv_f32 6*gemm"),
+    ("last", "last", False, False, 0.0, {}, ("fwd_f32", "3*gemm fwd gemm")),
+    ("self_nograd", "self", False, False, 0.0, {}, ("fwd_f32", "gemm fwd gemm")),
+    ("self_rel_nograd", "self", True, False, 0.0, {}, ("fwd_f32", "2*gemm fwd gemm")),
+    ("self_drop", "self", False, True, 0.1, {}, "gemm fwd_f32 3*gemm bwd_q_f32 bwd_kv_f32 2*gemm"),
+    ("self_rel_drop", "self", True, True, 0.1, {}, "2*gemm fwd_f32 3*gemm bwd_q_f32 gemm bwd_kv_f32 4*gemm"),
+    ("self_recompute", "self", False, True, 0.0, dict(ATTN_RECOMPUTE_MB=0), "gemm fwd_f32 3*gemm fwd_f32 bwd_q_f32 bwd_kv_f32 2*gemm"),
+    ("self_rel_drop_recompute", "self", True, True, 0.1, dict(ATTN_RECOMPUTE_MB=0),
+     "2*gemm fwd_f32 3*gemm fwd_f32 bwd_q_f32 gemm bwd_kv_f32 4*gemm"),
+    ("cross_recompute", "cross", False, True, 0.0, dict(ATTN_RECOMPUTE_MB=0), "3*gemm fwd_f32 3*gemm fwd_f32 bwd_q_f32 bwd_kv_f32 6*gemm"),
+    ("self_rel_keep", "self", True, True, 0.0, dict(ATTN_RECOMPUTE_MB=-1), "2*gemm fwd_f32 3*gemm bwd_q_f32 gemm bwd_kv_f32 4*gemm"),
+    ("self_unfused", "self", False, True, 0.0, dict(FUSE_ATTN=False), "12*gemm"),
+    ("self_rel_drop_unfused", "self", True, True, 0.1, dict(FUSE_ATTN=False), "17*gemm"),
+    ("cross_unfused", "cross", False, True, 0.0, dict(FUSE_ATTN=False), "18*gemm"),
+    ("last_unfused", "last", False, False, 0.0, dict(FUSE_ATTN=False), ("2*gemm", "6*gemm")),
+    ("self_stream", "self", False, True, 0.0, _STREAM0, "gemm fwd_stream_lse_f32 3*gemm bwd_stream_f32 2*gemm"),
+    # relative positions under autograd, and attention dropout, stay on a stored route
+    ("self_rel_stream", "self", True, True, 0.0, _STREAM0, "2*gemm fwd_f32 3*gemm bwd_q_f32 gemm bwd_kv_f32 4*gemm"),
+    ("self_drop_stream", "self", False, True, 0.1, _STREAM0, "gemm fwd_f32 3*gemm bwd_q_f32 bwd_kv_f32 2*gemm"),
+    ("cross_stream", "cross", False, True, 0.0, _STREAM0, "3*gemm fwd_stream_lse_f32 3*gemm bwd_stream_f32 6*gemm"),
+    ("self_nograd_stream", "self", False, False, 0.0, _STREAM0, ("fwd_stream_f32", "gemm fwd_stream gemm")),
+    ("self_rel_nograd_stream", "self", True, False, 0.0, _STREAM0, ("fwd_stream_f32", "2*gemm fwd_stream gemm")),
+    ("last_stream", "last", False, False, 0.0, _STREAM0, ("fwd_stream_f32", "3*gemm fwd_stream gemm")),
+    ("self_stream_unfused", "self", False, True, 0.0, dict(_STREAM0, FUSE_ATTN=False),
+     "gemm fwd_stream_lse_f32 3*gemm bwd_stream_f32 2*gemm"),
+]
+
+
+def _attention_route_run(ops, mods, case):
+    """-> (recorded launches, block output, dx or None) of one F_.MHABlockFn forward (+ backward under autograd)"""
+    from espnet_amd import functional as F_
+    from espnet_amd.nets import modules as M
+    _name, kind, rel, grad, p_att, flags, _launches = case
+    norm, att, pos, x, mem, xq, gy, mask = mods["norm"], mods["rel" if rel else "abs"], *mods["data"]
+    att.dropout_rate = p_att
+    old = {k: getattr(F_, k) for k in flags}
+    ops.manual_seed(5)
+    rec = []
+    try:
+        for k, v in flags.items():
+            setattr(F_, k, v)
+        xin = (xq if kind == "cross" else x).detach().clone().requires_grad_(grad)
+        ops._gemm_record = rec
+        with torch.set_grad_enabled(grad):
+            y = M.mha_block(norm, att, xin, mem if kind == "cross" else None, pos if rel else None, mask, kind == "last")
+            if grad:
+                y.backward(gy[:, :y.shape[1]])
+    finally:
+        ops._gemm_record = None
+        for k, v in old.items():
+            setattr(F_, k, v)
+    kinds = [r[0]["kind"].replace("eamd_attn_", "") if isinstance(r[0], dict) else "gemm" for r in rec]
+    runs = [(k, len(list(g))) for k, g in itertools.groupby(kinds)]
+    return " ".join(k if n == 1 else "%d*%s" % (n, k) for k, n in runs), y.detach(), xin.grad
+
+
+def _attention_route_mods():
+    """LayerNorm + attention modules (d_model 128, H = 2, q / k / v weights back to back) and the inputs: B = 2, T = 70 rows -
+    past one 64-row workgroup and two 32-row tiles of the streamed kernels - a 5-row query side for cross-attention"""
+    from espnet_amd import train
+    from espnet_amd.nets import modules as M
+    torch.manual_seed(11)
+    mods = dict(norm=M.LayerNorm(128).to(DEV), abs=M.MultiHeadedAttention(2, 128, 0.0).to(DEV).train(),
+                rel=M.RelPositionMultiHeadedAttention(2, 128, 0.0).to(DEV).train())
+    for i, m in enumerate((mods["abs"], mods["rel"])):
+        m.salt_attn, m.salt_out = 1001 + 2 * i, 1002 + 2 * i
+        train.FlatParams(m)
+    rn = lambda *s: torch.randn(*s, device=DEV)  # noqa: E731
+    mods["data"] = (rn(1, 70, 128), rn(2, 70, 128), rn(2, 70, 128), rn(2, 5, 128), rn(2, 70, 128),
+                    M.make_non_pad_mask([70, 51]).unsqueeze(1))
+    return mods
+
+
+def test_attention_route_table(ops):
+    """Which launches one attention block makes - streamed, fused with P kept, fused with P recomputed in backward, GEMM +
+    softmax - for self-attention with and without relative positions, cross-attention 5 x 70, the cached last-query step,
+    with and without autograd, attention dropout, both ends of ATTN_RECOMPUTE_MB, FUSE_ATTN off and the streamed thresholds
+    at 0, in both precisions: the ordered kinds ops._gemm_record collects, against the literal entries of ATTN_ROUTE_CASES.
+    (A cross-attention block whose shared k / v projection collects fp32 gradients in bf16 mode - the case whose streamed
+    backward would be declined - is not here: SharedProjFn gives a "kv" projection the operand dtype, always.)"""
+    import espnet_amd
+    mods = _attention_route_mods()
+    try:
+        for prec in ("fp32", "bf16"):
+            espnet_amd.set_precision(prec)
+            for case in ATTN_ROUTE_CASES:
+                got, _y, _dx = _attention_route_run(ops, mods, case)
+                want = case[6]
+                if not isinstance(want, str):
+                    want = want[prec == "bf16"]
+                elif prec == "bf16":
+                    want = want.replace("_f32", "")
+                assert got == want, (case[0], prec, got)
+    finally:
         espnet_amd.set_precision("fp32")
 
 
