@@ -40,13 +40,6 @@ constexpr int SNBT = STR_NKT + 1;                // 16-row column tiles of a wav
 constexpr int SGLD = 16 * SNBT + 4;           // row stride of a wave's band tile G[16][KT + 16]
 constexpr int SBQ = SBR * 16 / STR_NT;           // 16-byte pieces per thread of the band
 
-// the staged band: row n of the band of key tile j0 holds element c = c0 + n of the flat [0 | bd] rows (c0 = Ts + j0 - r0w - 63);
-// the position row behind it, clamped into [0, Ts) where the band leaves the matrix (c <= 0, c == Ts + 1, c > 2 Ts + 1: never used)
-__device__ __forceinline__ int band_pos_row(int c, int Ts) {
-  const int m = c <= Ts ? c - 1 : c - Ts - 2;
-  return min(max(m, 0), Ts - 1);
-}
-
 // LSE (training, attn_stream_bwd.hip): each wave also writes lse[z][i] = running maximum + log(denominator) of its 16 queries - the
 // row statistic of the scaled, masked scores the streamed backward rebuilds P from; 0 for a row masked everywhere
 template <typename T, bool REL, bool LSE>

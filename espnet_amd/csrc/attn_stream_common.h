@@ -36,6 +36,14 @@ __device__ __forceinline__ f32x4 dot64(const float4 (&x)[4], const float4 (&y)[4
   return c;
 }
 
+// the staged band of the legacy rel_shift: row n of the band of key tile j0 holds element c = c0 + n of the flat [0 | bd] rows
+// (forward: c0 = Ts + j0 - r0w - 63); the position row behind it, clamped into [0, Ts) where the band leaves the matrix (c <= 0,
+// c == Ts + 1, c > 2 Ts + 1: never used)
+__device__ __forceinline__ int band_pos_row(int c, int Ts) {
+  const int m = c <= Ts ? c - 1 : c - Ts - 2;
+  return min(max(m, 0), Ts - 1);
+}
+
 // operand rules of both directions; a matrix that breaks one makes the entry point decline (EAMD_EUNSUPPORTED) before any launch.
 // Read in 16-byte pieces: 16-byte aligned, row stride a multiple of 16 bytes
 template <typename T>

@@ -514,8 +514,12 @@ def attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=None, shift_len
 ATTN_STREAM_KEYS = 4096
 # With autograd the same holds for blocks WITHOUT relative positions: rows of more keys than this keep ctx and the row statistic
 # lse [H, B, T1] instead of probabilities, and backward rebuilds them tile by tile (csrc/attn_stream_bwd.hip): O(T') memory kept
-# and used.  Blocks with relative positions train on the stored-P paths at every length.
+# and used.
 ATTN_STREAM_TRAIN_KEYS = 4096
+# Blocks WITH relative positions (self-attention, T1 == T2) have a threshold of their own: beyond it the forward keeps ctx and the
+# lse of the scores with the position term, and backward rebuilds the probabilities and forms the position-side gradients (dqv,
+# dpos) tile by tile (csrc/attn_stream_bwd_rel.hip).  Up to it they train on the stored-P kernels, as before.
+ATTN_STREAM_TRAIN_REL_KEYS = 4096
 
 
 def attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, lse=None):
@@ -550,6 +554,28 @@ def attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T1, T2, H, dk, dqkv=None, 
                                1.0 / math.sqrt(dk)):
         return None
     return dq, dkm.t, dvm.t
+
+
+def attn_stream_rel_bwd(dctx, cx, lse, qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, dqkv=None, dp_out=None):
+    """backward of the streamed forward with relative positions -> (dqu, dqv, dk, dv, dp) as attn_core_bwd returns them (dqu / dqv
+    fp32; dk / dv into column blocks 1 / 2 of dqkv; dp added into dp_out and returned as None), or None when the library
+    declines the operands"""
+    D = H * dk
+    dev, adt = dctx.device, ops.act_dtype()
+    qu, qv, k, v, p = _mv(qu), _mv(qv), _mv(k), _mv(v), _mv(p)
+    if any(t.dtype != adt for t in (dctx, cx, qu.t, qv.t, k.t, v.t, p.t)):
+        return None
+    if dqkv is not None:
+        dkm, dvm = _MV(dqkv, D, 3 * D), _MV(dqkv, 2 * D, 3 * D)
+    else:
+        dkm, dvm = (_MV(torch.empty(B * T2, D, device=dev, dtype=adt), 0, D) for _ in range(2))
+    dqu, dqv = (torch.empty(B * T1, D, device=dev, dtype=torch.float32) for _ in range(2))
+    dp = torch.zeros(T2, D, device=dev, dtype=torch.float32) if dp_out is None else None
+    if not ops.attn_bwd_stream_rel(_MV(dctx, 0, D), _MV(cx, 0, D), qu, qv, k, v, p, mask, lse, _MV(dqu, 0, D), _MV(dqv, 0, D), dkm, dvm,
+                                   _MV(dp, 0, D) if dp_out is None else dp_out, B, T1, T2, H, dk, 1.0 / math.sqrt(dk),
+                                   shift_len=shift_len):
+        return None
+    return dqu, dqv, dkm.t, dvm.t, dp
 
 
 def attn_context_fwd(P, v, B, T1, T2, H, dk):
@@ -702,6 +728,13 @@ def attn_block_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop, shift_len, gra
         cx = attn_fwd_stream(qu, None, k, v, None, mask, B, T1, T2, H, dk, lse=lse)
         if cx is not None:
             return cx, AttnKept("stream", lse=lse, mask=mask)
+    if grad and unread and p is not None and T1 == T2 and not last_query_only and T2 > ATTN_STREAM_TRAIN_REL_KEYS:
+        # training on long rows with relative positions: the same, the row statistic taken over the scores with the position
+        # term; backward rebuilds them and the position-side gradients (attn_stream_rel_bwd)
+        lse = torch.empty(H * B * T1, device=_mv(qu).t.device, dtype=torch.float32)
+        cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=shift_len, lse=lse)
+        if cx is not None:
+            return cx, AttnKept("stream", lse=lse, mask=mask)
     P, Pd, cx, fused = attn_stored_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=drop if p_att > 0.0 else None,
                                        shift_len=shift_len)
     if ATTN_TAP is not None:      # calculate_all_attentions: the probabilities in the reference's (B, H, T1, T2) layout
@@ -719,7 +752,14 @@ def attn_block_bwd(kept, dctx, cx, qu, qv, k, v, p, B, T1, T2, H, dk, drop, shif
     """backward of attn_block_fwd -> (dqu, dqv, dk, dv, dp) as attn_core_bwd returns them (dqkv / dkv_out / dp_out as there).
     After the streamed backward dqu is already a GEMM operand (ops.to_act passes it through), or None with dqkv."""
     P, Pd = kept.P, kept.Pd
-    if kept.route == "stream":
+    if kept.route == "stream" and p is not None:
+        sb = attn_stream_rel_bwd(dctx, cx, kept.lse, qu, qv, k, v, p, kept.mask, B, T1, T2, H, dk, shift_len=shift_len, dqkv=dqkv,
+                                 dp_out=dp_out)
+        if sb is not None:
+            return sb
+        # the library declined the streamed backward: the probabilities of the stored route, rebuilt with the position term
+        P = attn_stored_fwd(qu, qv, k, v, p, kept.mask, B, T1, T2, H, dk, shift_len=shift_len, context=False)[0]
+    elif kept.route == "stream":
         sb = attn_stream_bwd(dctx, cx, kept.lse, qu, k, v, kept.mask, B, T1, T2, H, dk, dqkv=dqkv, dkv_out=dkv_out)
         if sb is not None:
             return sb[0], None, sb[1], sb[2], None

@@ -1226,6 +1226,32 @@ def attn_bwd_stream(dctx, ctx, qu, k, v, mask, lse, dq, dk_, dv, B, T1, T2, H, d
     return _attn_launch(name, args, (dctx, ctx, qu, k, v, mask, lse, ws, dq, dk_, dv))
 
 
+def attn_bwd_stream_rel(dctx, ctx, qu, qv, k, v, pos, mask, lse, dqu, dqv, dk_, dv, dpos, B, T1, T2, H, dk, scale, shift_len=None):
+    """The backward of attn_fwd_stream(qu, qv, k, v, pos, ..., lse=lse) WITH relative positions (csrc/attn_stream_bwd_rel.hip):
+    the probabilities are rebuilt tile by tile with the position term - no [T1, T2] tensor.  dctx / ctx / qu / qv / k / v / pos and
+    dk_ / dv are (tensor, element offset, row stride) views in one dtype (bf16: eamd_attn_bwd_stream_rel, fp32: _f32); dqu / dqv /
+    dpos are such views of fp32 tensors.  dqu, dqv, dk_ and dv are written, dpos [T2, H*dk] is ADDED INTO (shared by the batch
+    and, through a shared positional projection, by the layers).  The fp32 workspaces are sized here from the shapes the header
+    documents: delta [H*B*T1], the upper-part row sums [B*T1, H*dk], the per-batch diagonal sums [B, 2*T1, H*dk].
+    Returns False if the library declines the operands (EAMD_EUNSUPPORTED)."""
+    dt = qu[0].dtype
+    assert dt in (torch.bfloat16, torch.float32)
+    for t_, _, _ in (dctx, ctx, qu, qv, k, v, pos, dk_, dv):
+        assert t_.dtype == dt and t_.is_cuda
+    for t_, _, _ in (dqu, dqv, dpos):
+        assert t_.dtype == torch.float32 and t_.is_cuda
+    assert lse.dtype == torch.float32 and lse.is_cuda and lse.is_contiguous() and lse.numel() >= H * B * T1
+    mb, mi = _mask_strides(mask, B, T1, T2)
+    D = H * dk
+    n0 = (H * B * T1 + 3) // 4 * 4                                               # 16-byte aligned pieces of one allocation
+    ws = torch.empty(n0 + 3 * B * T1 * D, device=lse.device, dtype=torch.float32)
+    args = _view_args(dctx, ctx, qu, qv, k, v, pos) + (ptr(mask), mb, mi, ptr(lse), ptr(shift_len) if T1 == T2 else None,
+                                                       ptr(ws), ptr(ws, n0), ptr(ws, n0 + B * T1 * D))
+    args = args + _view_args(dqu, dqv, dk_, dv, dpos) + (B, H, T1, T2, dk, scale)
+    name = "eamd_attn_bwd_stream_rel" if dt == torch.bfloat16 else "eamd_attn_bwd_stream_rel_f32"
+    return _attn_launch(name, args, (dctx, ctx, qu, qv, k, v, pos, mask, lse, shift_len, ws, dqu, dqv, dk_, dv, dpos))
+
+
 def attn_bwd_q(dctx, k, v, P, dS, dbd, dq, B, T1, T2, H, dk, ldp, scale, drop=None, shift_len=None):
     """dctx / k / v / dq: (tensor, element offset, row stride) views; P, dS (and dbd or None): [H*B*T1*ldp], bf16
     (eamd_attn_bwd_q; dq fp32 or bf16) or everything fp32 (eamd_attn_bwd_q_f32).

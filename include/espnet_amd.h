@@ -413,6 +413,33 @@ int eamd_attn_bwd_stream_f32(const float* dctx, int64_t ldd, const float* ctx, i
                              float* dk_out, int64_t lddk, float* dv, int64_t lddv, int B, int H, int T1, int T2, int dk, float scale,
                              void* stream);
 
+/* The streamed backward WITH the legacy relative positions (csrc/attn_stream_bwd_rel.hip): the backward of
+ * eamd_attn_fwd_stream_lse[_f32] called with qv / pos (T1 == T2).  P = exp(s - lse) is rebuilt tile by tile with the position term
+ * the forward added (rel_shift over shift_len, NULL: T2); besides dqu = dS k, dk = dS^T qu and dv = P^T dctx it returns the
+ * position side: dqv (the gradient of the position-biased queries) and dpos += the gradient of the projected positions summed over
+ * the batch (dpos is ADDED INTO: rows >= the shift length are left alone).  Five launches - query side, its row carry, key
+ * side, position side, its batch sum - and in bf16 storage one more in front, which takes delta_i = sum_j P_ij dP_ij from a sweep
+ * of its own instead of the rounded ctx; no [T1, T2] buffer, no atomics, the same bits on every launch.
+ * Layouts as for eamd_attn_bwd_stream; qv as qu; pos / dpos: (m, h, d) at [m*ld + h*64 + d].  dqu / dqv / dpos are fp32 with
+ * their own row strides, dk / dv in the operands' storage type.  fp32 workspaces: delta_ws [H*B][T1], dqv_ws [B*T1][H*64],
+ * dpos_ws [B][2*T1][H*64] (16-byte aligned, contents irrelevant).  d_k = 64, T1 == T2.  EAMD_EINVAL (a missing operand, output
+ * or workspace) / EAMD_EUNSUPPORTED (d_k, T1 != T2, alignment: inputs as eamd_attn_fwd_stream, outputs as ctx) are returned
+ * before anything is launched. */
+int eamd_attn_bwd_stream_rel(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq,
+                             const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                             const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                             int64_t mask_qstride, const float* lse, const int32_t* shift_len, float* delta_ws,
+                             float* dqv_ws, float* dpos_ws, float* dqu, int64_t lddqu, float* dqv, int64_t lddqv,
+                             void* dk_bf16, int64_t lddk, void* dv_bf16, int64_t lddv, float* dpos, int64_t lddpos, int B,
+                             int H, int T1, int T2, int dk, float scale, void* stream);
+int eamd_attn_bwd_stream_rel_f32(const float* dctx, int64_t ldd, const float* ctx, int64_t ldc, const float* qu, int64_t ldq,
+                                 const float* qv, int64_t ldqv, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                 const float* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                                 int64_t mask_qstride, const float* lse, const int32_t* shift_len, float* delta_ws,
+                                 float* dqv_ws, float* dpos_ws, float* dqu, int64_t lddqu, float* dqv, int64_t lddqv,
+                                 float* dk_out, int64_t lddk, float* dv, int64_t lddv, float* dpos, int64_t lddpos, int B,
+                                 int H, int T1, int T2, int dk, float scale, void* stream);
+
 /* Key side of the attention backward in one launch (fp32 tensors, d_k = 64; any T1 / T2): dv = Pd^T dctx, dk = dS^T qu and,
  * with relative positions (dbd, qv, dpos all set; T1 == T2), dpos += dbd^T qv summed over the batch (dpos is ACCUMULATED
  * into: positions are shared by the batch; zero it first).  Pd / dS / dbd: [H][B][T1][ldp] as eamd_attn_fwd_f32 /

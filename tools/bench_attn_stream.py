@@ -5,9 +5,12 @@ at T = 4096 beside the fused long-row forward (F_.attn_fwd_fused), at T = 8192 a
 conv2d subsampling) beside the GEMM + softmax + GEMM composition where that fits into free device memory and its kernels
 take the shape.  Writes one JSON file.  With --train: forward + backward without relative positions, the streamed pair
 (F_.attn_fwd_stream with lse, F_.attn_stream_bwd: csrc/attn_stream_bwd.hip) beside today's route - the stored-P kernels at 4096
-keys, GEMM + softmax in both directions beyond - into profiles/attn_stream_train_bench.json.
+keys, GEMM + softmax in both directions beyond - into profiles/attn_stream_train_bench.json.  With --train --rel: forward +
+backward of one rel-pos block (F_.attn_block_fwd / attn_block_bwd) at 8192 keys, the streamed route (csrc/attn_stream_bwd_rel.hip)
+beside the GEMM + softmax route of the same code with the threshold raised, every round's span kept, into
+profiles/attn_stream_train_rel_bench.json.
 
-    python tools/bench_attn_stream.py [--train] [--out profiles/attn_stream_bench.json] [--commit <id>] [--T 4096 8192 22528]
+    python tools/bench_attn_stream.py [--train [--rel]] [--out profiles/attn_stream_bench.json] [--commit <id>] [--T 4096 8192 22528]
 
 Times are device events around at least `iters` calls and at least 50 ms of work after `warmup` calls, the best of `rounds`
 alternating rounds; peak memory is the rise of torch.cuda.max_memory_allocated over one call (operands excluded).  tflops counts
@@ -104,20 +107,69 @@ def train_rows(args, res):
     espnet_amd.set_precision("fp32")
 
 
+def train_rel_rows(args, res):
+    """forward + backward of one rel-pos attention block through F_.attn_block_fwd / attn_block_bwd: the streamed route (threshold
+    at its default) against the GEMM + softmax route the same code takes with the threshold raised, alternating"""
+    import espnet_amd
+    from espnet_amd import functional as F_, ops
+    dev, B, H, dk = "cuda", args.B, args.H, 64
+    D = H * dk
+    default = F_.ATTN_STREAM_TRAIN_REL_KEYS
+    for prec in ("fp32", "bf16"):
+        espnet_amd.set_precision(prec)
+        adt = ops.act_dtype()
+        for T in args.T:
+            torch.manual_seed(T)
+            qkv, qu, qv, dctx, p = (torch.randn(r, n, device=dev).to(adt) for r, n in ((B * T, 3 * D), (B * T, D), (B * T, D), (B * T, D), (T, D)))
+            dqkv = torch.empty_like(qkv)
+            k, v = F_._MV(qkv, D, 3 * D), F_._MV(qkv, 2 * D, 3 * D)
+            mask = torch.ones(B, 1, T, dtype=torch.uint8, device=dev)
+
+            def block(keys, route):
+                F_.ATTN_STREAM_TRAIN_REL_KEYS = keys
+                try:
+                    cx, kept = F_.attn_block_fwd(qu, qv, k, v, p, mask, B, T, T, H, dk, (0.0, 0), None, True, False, True)
+                    assert kept.route == route, kept.route
+                    F_.attn_block_bwd(kept, dctx, cx, qu, qv, k, v, p, B, T, T, H, dk, (0.0, 0), None, dqkv=dqkv)
+                finally:
+                    F_.ATTN_STREAM_TRAIN_REL_KEYS = default
+            stream, other = (lambda: block(default, "stream")), (lambda: block(1 << 30, "gemm"))
+            fits = H * B * T * T * (16 if prec == "fp32" else 20) < 0.8 * torch.cuda.mem_get_info()[0]
+            row = dict(precision=prec, T=T, B=B, other="gemm_softmax", rounds=[], stream_peak_bytes=peak_rise(stream),
+                       other_peak_bytes=peak_rise(other) if fits else None)
+            for _ in range(args.rounds):
+                r = dict(stream_ms=timed(stream, args.warmup, args.iters))
+                if fits:
+                    r["other_ms"] = timed(other, args.warmup, args.iters)
+                row["rounds"].append(r)
+            for name in ("stream_ms", "other_ms") if fits else ("stream_ms",):
+                row[name + "_span"] = [min(r[name] for r in row["rounds"]), max(r[name] for r in row["rounds"])]
+            res["rows"].append(row)
+            print(json.dumps({k_: v_ for k_, v_ in row.items() if k_ != "rounds"}), flush=True)
+            del qkv, dqkv, qu, qv, dctx, p, k, v
+            torch.cuda.empty_cache()
+    espnet_amd.set_precision("fp32")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train", action="store_true", help="forward + backward rows (no relative positions)")
+    ap.add_argument("--rel", action="store_true", help="with --train: one rel-pos block, streamed against GEMM + softmax, at --T (default 8192)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
-    ap.add_argument("--T", type=int, nargs="+", default=[4096, 8192, 22528])
+    ap.add_argument("--T", type=int, nargs="+", default=None)
     ap.add_argument("--B", type=int, default=8)
     ap.add_argument("--H", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     args = ap.parse_args()
+    rel_train = args.train and args.rel
+    if args.T is None:
+        args.T = [8192] if rel_train else [4096, 8192, 22528]
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "attn_stream_train_bench.json" if args.train else "attn_stream_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "attn_stream_train_rel_bench.json" if rel_train else
+                                "attn_stream_train_bench.json" if args.train else "attn_stream_bench.json")
     import espnet_amd
     from espnet_amd import functional as F_, ops
     commit = args.commit
@@ -130,7 +182,7 @@ def main():
     D = H * dk
     res = dict(commit=commit, device=torch.cuda.get_device_name(0), pairs=B * H, QB=ops.ATTN_STREAM_QB, KT=ops.ATTN_STREAM_KT, rows=[])
     if args.train:
-        train_rows(args, res)
+        (train_rel_rows if args.rel else train_rows)(args, res)
     for prec in () if args.train else ("fp32", "bf16"):
         espnet_amd.set_precision(prec)
         adt = ops.act_dtype()
