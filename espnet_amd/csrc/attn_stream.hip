@@ -42,7 +42,10 @@ constexpr int SBQ = SBR * 16 / STR_NT;           // 16-byte pieces per thread of
 
 // LSE (training, attn_stream_bwd.hip): each wave also writes lse[z][i] = running maximum + log(denominator) of its 16 queries - the
 // row statistic of the scaled, masked scores the streamed backward rebuilds P from; 0 for a row masked everywhere
-template <typename T, bool REL, bool LSE>
+// DROP (attention dropout, the *_drop entry points; lse may then be NULL): the tile's weights e_ij go into the running denominator
+// as they are - row maximum, denominator and lse stay those of the undropped scores - and the copy that feeds the context product
+// takes the stored route's keep bits and 1 / (1 - p) (stream_drop_row): ctx = (P o M / (1 - p)) v after the final 1 / denominator
+template <typename T, bool REL, bool LSE, bool DROP = false>
 __global__ __launch_bounds__(STR_NT, 2) void attn_stream_kernel(const AttnArgs<T> a, float* __restrict__ lse) {
   __shared__ __attribute__((aligned(16))) float Ks[STR_KT * STR_PLD];
   __shared__ __attribute__((aligned(16))) float Vs[STR_KT * STR_PLD];
@@ -98,6 +101,8 @@ __global__ __launch_bounds__(STR_NT, 2) void attn_stream_kernel(const AttnArgs<T
     for (int kt = 0; kt < STR_NKT; ++kt) mkn[kt] = mr ? attn_mask4(mr, j0 + 16 * kt + 4 * fq, T2) : 0x01010101u;
   };
 
+  const AttnDrop drop = DROP ? attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt) : AttnDrop{};
+  const long pro = ((long)z * T1 + qi) * a.ldp;              // DROP: where this query's row of P would start
   float mrun = -INFINITY, lrun = 0.f;                        // running maximum of query fr; this lane's share of its denominator
   f32x4 C[4];                                                // C[dt][r]: channel 16 dt + 4 fq + r of query fr
 #pragma unroll
@@ -194,6 +199,7 @@ __global__ __launch_bounds__(STR_NT, 2) void attn_stream_kernel(const AttnArgs<T
         psum += e;
       }
     lrun = lrun * alpha + psum;
+    if (DROP) stream_drop_row(drop, pro, j0, fq, a.ldp, S);
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) C[dt] *= alpha;
     // ---- C^T[channel][query] += V_tile^T[channel][key] P^T[key][query] ----
@@ -212,13 +218,13 @@ __global__ __launch_bounds__(STR_NT, 2) void attn_stream_kernel(const AttnArgs<T
   T* crow = a.ctx + ((long)b * T1 + i) * a.ldc + h * ATT_DK;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) st4(crow + dt * 16 + fq * 4, f4(C[dt] * inv));
-  if (LSE && fq == 0) lse[(long)z * T1 + i] = den > 0.f ? mrun + logf(den) : 0.f;
+  if (LSE && (!DROP || lse) && fq == 0) lse[(long)z * T1 + i] = den > 0.f ? mrun + logf(den) : 0.f;
 }
 
-// the checks of the stored forward (attn_check_fwd) without P, Pd, the dropout arguments and the bound on T2
+// the checks of the stored forward (attn_check_fwd) without P, Pd and the bound on T2
 template <typename T>
 int stream_check(const AttnArgs<T>& a, int dk) {
-  if (const int rc = attn_check_common(a.qu && a.k && a.v && a.ctx, a.B, a.H, a.T1, a.T2, 0.f, nullptr)) return rc;
+  if (const int rc = attn_check_common(a.qu && a.k && a.v && a.ctx, a.B, a.H, a.T1, a.T2, a.drop_p, a.drop_step)) return rc;
   if ((a.pos == nullptr) != (a.qv == nullptr)) return EAMD_EINVAL;
   if (dk != ATT_DK || (a.pos && a.T1 != a.T2)) return EAMD_EUNSUPPORTED;
   if (!stream_in_ok(a.qu, a.ldq) || !stream_in_ok(a.k, a.ldk) || !stream_in_ok(a.v, a.ldv) || !stream_out_ok(a.ctx, a.ldc) ||
@@ -231,15 +237,17 @@ template <typename T>
 int stream_entry(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v, int64_t ldv,
                  const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mb, int64_t mi, void* ctx, int64_t ldc, int B,
                  int H, int T1, int T2, int dk, float scale, const int32_t* shift_len, void* stream, float* lse = nullptr,
-                 bool want_lse = false) {
+                 bool want_lse = false, float drop_p = 0.f, const uint64_t* drop_step = nullptr, uint64_t drop_salt = 0) {
   if (want_lse && !lse) return EAMD_EINVAL;
-  AttnArgs<T> a = attn_args<T>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mb, mi, nullptr, 0, ctx, ldc, B, H, T1, T2, scale,
-                               nullptr, 0.f, nullptr, 0, shift_len);
+  AttnArgs<T> a = attn_args<T>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mb, mi, nullptr, stream_ldp(T2), ctx, ldc, B, H, T1,
+                               T2, scale, nullptr, drop_p, drop_step, drop_salt, shift_len);
   if (const int rc = stream_check(a, dk)) return rc;
   a.nqb = (T1 + STR_QB - 1) / STR_QB;
   const unsigned grid = attn_grid(a.nqb, B, H);
   hipStream_t s = (hipStream_t)stream;
-  if (want_lse && pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, true>), dim3(grid), dim3(STR_NT), 0, s, a, lse);
+  if (drop_p > 0.f && pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, true, true>), dim3(grid), dim3(STR_NT), 0, s, a, lse);
+  else if (drop_p > 0.f) hipLaunchKernelGGL((attn_stream_kernel<T, false, true, true>), dim3(grid), dim3(STR_NT), 0, s, a, lse);
+  else if (want_lse && pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, true>), dim3(grid), dim3(STR_NT), 0, s, a, lse);
   else if (want_lse) hipLaunchKernelGGL((attn_stream_kernel<T, false, true>), dim3(grid), dim3(STR_NT), 0, s, a, lse);
   else if (pos) hipLaunchKernelGGL((attn_stream_kernel<T, true, false>), dim3(grid), dim3(STR_NT), 0, s, a, nullptr);
   else hipLaunchKernelGGL((attn_stream_kernel<T, false, false>), dim3(grid), dim3(STR_NT), 0, s, a, nullptr);
@@ -284,4 +292,25 @@ extern "C" int eamd_attn_fwd_stream_lse(const void* qu, int64_t ldq, const void*
                                         int T2, int dk, float scale, const int32_t* shift_len, float* lse, void* stream) {
   return stream_entry<bf16_t>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, ctx_bf16, ldc, B, H, T1,
                               T2, dk, scale, shift_len, stream, lse, true);
+}
+
+// the same with attention dropout (attention.py:91): ctx = dropout(P) v under the keep bits the stored route draws at
+// (drop_step, drop_salt) - see attn_stream_common.h; lse (NULL: not wanted) stays the statistic of the undropped scores.
+// drop_p == 0 launches the kernels of the entry points above: their bits
+extern "C" int eamd_attn_fwd_stream_drop_f32(const float* qu, int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk,
+                                             const float* v, int64_t ldv, const float* pos, int64_t ldpos, const unsigned char* mask,
+                                             int64_t mask_bstride, int64_t mask_qstride, float* ctx, int64_t ldc, int B, int H, int T1,
+                                             int T2, int dk, float scale, const int32_t* shift_len, float* lse, float drop_p,
+                                             const uint64_t* drop_step, uint64_t drop_salt, void* stream) {
+  return stream_entry<float>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, ctx, ldc, B, H, T1, T2,
+                             dk, scale, shift_len, stream, lse, lse != nullptr, drop_p, drop_step, drop_salt);
+}
+
+extern "C" int eamd_attn_fwd_stream_drop(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk,
+                                         const void* v, int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask,
+                                         int64_t mask_bstride, int64_t mask_qstride, void* ctx_bf16, int64_t ldc, int B, int H, int T1,
+                                         int T2, int dk, float scale, const int32_t* shift_len, float* lse, float drop_p,
+                                         const uint64_t* drop_step, uint64_t drop_salt, void* stream) {
+  return stream_entry<bf16_t>(qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, ctx_bf16, ldc, B, H, T1,
+                              T2, dk, scale, shift_len, stream, lse, lse != nullptr, drop_p, drop_step, drop_salt);
 }

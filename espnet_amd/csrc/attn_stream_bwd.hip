@@ -45,6 +45,8 @@ struct StreamBwdArgs {
   long ldd, ldc, ldq, ldk, ldv, mb, mi, lddq, lddk, lddv;
   int B, H, T1, T2, nqb, nkb;
   float scale;
+  // the forward's attention dropout (DROP kernels): the keep bits of P's stored layout [H*B][T1][ldp], attn_stream_common.h
+  float drop_p; const unsigned long long* drop_step; unsigned long long drop_salt; long ldp;
 };
 
 // acc^T[channel 16 dt + 4 fq + r][column fr] += sum over the tile's rows of X[row][channel] w[row][column fr]; w[t][r]: row 16 t + 4 fq + r
@@ -59,7 +61,9 @@ __device__ __forceinline__ void baccum(const float* X, int fr, int fq, const f32
     }
 }
 
-template <typename T>
+// DROP (both kernels): the forward built ctx from Pd = P o M / (1 - p).  delta = dctx . ctx is unchanged in form (sum_j P dP =
+// sum_j Pd dPd), dP <- M / (1 - p) o (dctx v^T) in dS, and dv takes Pd; M is regenerated per tile (stream_drop_row / _keep_col)
+template <typename T, bool DROP>
 __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_q_kernel(const StreamBwdArgs<T> a) {
   __shared__ __attribute__((aligned(16))) float Ks[STR_KT * STR_PLD];
   __shared__ __attribute__((aligned(16))) float Vs[STR_KT * STR_PLD];
@@ -108,6 +112,8 @@ __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_q_kernel(const StreamBwd
     for (int kt = 0; kt < STR_NKT; ++kt) mkn[kt] = mr ? attn_mask4(mr, j0 + 16 * kt + 4 * fq, T2) : 0x01010101u;
   };
 
+  const AttnDrop drop = DROP ? attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt) : AttnDrop{};
+  const long pro = ((long)z * T1 + qi) * a.ldp;              // DROP: where this query's row of P would start
   f32x4 DQ[4];                                               // DQ[dt][r]: channel 16 dt + 4 fq + r of query fr
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) DQ[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -138,6 +144,7 @@ __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_q_kernel(const StreamBwd
       frag_lds(&Vs[(16 * kt + fr) * STR_PLD], fq, xf);
       dP[kt] = dot64(xf, df, (f32x4){0.f, 0.f, 0.f, 0.f});
     }
+    if (DROP) stream_drop_row(drop, pro, j0, fq, a.ldp, dP);
 #pragma unroll
     for (int kt = 0; kt < STR_NKT; ++kt)
 #pragma unroll
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_q_kernel(const StreamBwd
   for (int dt = 0; dt < 4; ++dt) st4(drow + dt * 16 + fq * 4, f4(DQ[dt]));
 }
 
-template <typename T>
+template <typename T, bool DROP>
 __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_kv_kernel(const StreamBwdArgs<T> a) {
   __shared__ __attribute__((aligned(16))) float Qs[STR_KT * STR_PLD];
   __shared__ __attribute__((aligned(16))) float Ds[STR_KT * STR_PLD];
@@ -209,6 +216,8 @@ __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_kv_kernel(const StreamBw
     }
   };
 
+  const AttnDrop drop = DROP ? attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt) : AttnDrop{};
+  const long pcol = (long)z * T1 * a.ldp + j;                // DROP: this key's column of the pair's P
   f32x4 DV[4], DK[4];                                        // [dt][r]: channel 16 dt + 4 fq + r of key fr
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) DV[dt] = DK[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -246,12 +255,14 @@ __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_kv_kernel(const StreamBw
       const float4 l4 = *reinterpret_cast<const float4*>(&Ls[16 * qt + 4 * fq]);
       const float4 e4 = *reinterpret_cast<const float4*>(&Es[16 * qt + 4 * fq]);
       const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, eq[4] = {e4.x, e4.y, e4.z, e4.w};
+      float m[4];
+      if (DROP) stream_keep_col(drop, pcol + (long)(i0 + 16 * qt + 4 * fq) * a.ldp, a.ldp, m);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float p = __expf(attn_score(P[qt][r], a.scale, j, T2, mk[qt], r) - lq[r]);
         if (i0 + 16 * qt + 4 * fq + r >= T1) p = 0.f;        // by index: a clamped row would carry a live lse and delta
-        P[qt][r] = p;
-        dS[qt][r] = a.scale * p * (dS[qt][r] - eq[r]);
+        P[qt][r] = DROP ? p * m[r] : p;                      // Pd for dv
+        dS[qt][r] = a.scale * p * ((DROP ? dS[qt][r] * m[r] : dS[qt][r]) - eq[r]);
       }
     }
     baccum(Ds, fr, fq, P, DV);                               // dv^T[channel][key] += dCtx_tile^T[channel][query] P[query][key]
@@ -271,7 +282,7 @@ __global__ __launch_bounds__(STR_NT, 2) void stream_bwd_kv_kernel(const StreamBw
 template <typename T>
 int stream_bwd_check(const StreamBwdArgs<T>& a, int dk) {
   const bool operands = a.dctx && a.ctx && a.qu && a.k && a.v && a.lse && a.delta && a.dq && a.dk && a.dv;
-  if (const int rc = attn_check_common(operands, a.B, a.H, a.T1, a.T2, 0.f, nullptr)) return rc;
+  if (const int rc = attn_check_common(operands, a.B, a.H, a.T1, a.T2, a.drop_p, a.drop_step)) return rc;
   if (dk != ATT_DK) return EAMD_EUNSUPPORTED;
   if (!stream_in_ok(a.dctx, a.ldd) || !stream_in_ok(a.ctx, a.ldc) || !stream_in_ok(a.qu, a.ldq) || !stream_in_ok(a.k, a.ldk) ||
       !stream_in_ok(a.v, a.ldv) || !stream_out_ok(a.dq, a.lddq) || !stream_out_ok(a.dk, a.lddk) || !stream_out_ok(a.dv, a.lddv))
@@ -283,20 +294,24 @@ template <typename T>
 int stream_bwd_entry(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq, const void* k, int64_t ldk,
                      const void* v, int64_t ldv, const unsigned char* mask, int64_t mb, int64_t mi, const float* lse, float* delta_ws,
                      void* dq, int64_t lddq, void* dk_out, int64_t lddk, void* dv, int64_t lddv, int B, int H, int T1, int T2, int dk,
-                     float scale, void* stream) {
+                     float scale, void* stream, float drop_p = 0.f, const uint64_t* drop_step = nullptr, uint64_t drop_salt = 0) {
   StreamBwdArgs<T> a;
   a.dctx = (const T*)dctx; a.ctx = (const T*)ctx; a.qu = (const T*)qu; a.k = (const T*)k; a.v = (const T*)v;
   a.mask = mask; a.lse = lse; a.delta = delta_ws;
   a.dq = (T*)dq; a.dk = (T*)dk_out; a.dv = (T*)dv;
   a.ldd = ldd; a.ldc = ldc; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.mb = mb; a.mi = mi; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
   a.B = B; a.H = H; a.T1 = T1; a.T2 = T2; a.scale = scale;
+  a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt; a.ldp = stream_ldp(T2);
   if (const int rc = stream_bwd_check(a, dk)) return rc;
   a.nqb = (T1 + STR_QB - 1) / STR_QB;
   a.nkb = (T2 + STR_QB - 1) / STR_QB;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((stream_bwd_q_kernel<T>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);
+  const dim3 gq(attn_grid(a.nqb, B, H)), gk(attn_grid(a.nkb, B, H));
+  if (drop_p > 0.f) hipLaunchKernelGGL((stream_bwd_q_kernel<T, true>), gq, dim3(STR_NT), 0, s, a);
+  else hipLaunchKernelGGL((stream_bwd_q_kernel<T, false>), gq, dim3(STR_NT), 0, s, a);
   EAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL((stream_bwd_kv_kernel<T>), dim3(attn_grid(a.nkb, B, H)), dim3(STR_NT), 0, s, a);   // reads the delta written above
+  if (drop_p > 0.f) hipLaunchKernelGGL((stream_bwd_kv_kernel<T, true>), gk, dim3(STR_NT), 0, s, a);   // reads the delta written above
+  else hipLaunchKernelGGL((stream_bwd_kv_kernel<T, false>), gk, dim3(STR_NT), 0, s, a);
   EAMD_LAUNCH_CHECK();
   return EAMD_OK;
 }
@@ -319,4 +334,26 @@ extern "C" int eamd_attn_bwd_stream(const void* dctx, int64_t ldd, const void* c
                                     int dk, float scale, void* stream) {
   return stream_bwd_entry<bf16_t>(dctx, ldd, ctx, ldc, qu, ldq, k, ldk, v, ldv, mask, mask_bstride, mask_qstride, lse, delta_ws, dq_bf16,
                                   lddq, dk_bf16, lddk, dv_bf16, lddv, B, H, T1, T2, dk, scale, stream);
+}
+
+// the backward of eamd_attn_fwd_stream_drop[_f32] at the same (drop_p, drop_step, drop_salt): the keep bits are drawn again per
+// tile, nothing is stored.  drop_p == 0 launches the kernels of the entry points above: their bits
+extern "C" int eamd_attn_bwd_stream_drop_f32(const float* dctx, int64_t ldd, const float* ctx, int64_t ldc, const float* qu, int64_t ldq,
+                                             const float* k, int64_t ldk, const float* v, int64_t ldv, const unsigned char* mask,
+                                             int64_t mask_bstride, int64_t mask_qstride, const float* lse, float* delta_ws, float* dq,
+                                             int64_t lddq, float* dk_out, int64_t lddk, float* dv, int64_t lddv, int B, int H, int T1,
+                                             int T2, int dk, float scale, float drop_p, const uint64_t* drop_step, uint64_t drop_salt,
+                                             void* stream) {
+  return stream_bwd_entry<float>(dctx, ldd, ctx, ldc, qu, ldq, k, ldk, v, ldv, mask, mask_bstride, mask_qstride, lse, delta_ws, dq, lddq,
+                                 dk_out, lddk, dv, lddv, B, H, T1, T2, dk, scale, stream, drop_p, drop_step, drop_salt);
+}
+
+extern "C" int eamd_attn_bwd_stream_drop(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq,
+                                         const void* k, int64_t ldk, const void* v, int64_t ldv, const unsigned char* mask,
+                                         int64_t mask_bstride, int64_t mask_qstride, const float* lse, float* delta_ws, void* dq_bf16,
+                                         int64_t lddq, void* dk_bf16, int64_t lddk, void* dv_bf16, int64_t lddv, int B, int H, int T1,
+                                         int T2, int dk, float scale, float drop_p, const uint64_t* drop_step, uint64_t drop_salt,
+                                         void* stream) {
+  return stream_bwd_entry<bf16_t>(dctx, ldd, ctx, ldc, qu, ldq, k, ldk, v, ldv, mask, mask_bstride, mask_qstride, lse, delta_ws, dq_bf16,
+                                  lddq, dk_bf16, lddk, dv_bf16, lddv, B, H, T1, T2, dk, scale, stream, drop_p, drop_step, drop_salt);
 }

@@ -63,6 +63,8 @@ struct RelBwdArgs {
   long ldd, ldc, ldq, ldqv, ldk, ldv, ldpos, mb, mi, lddqu, lddqv, lddk, lddv, lddpos;
   int B, H, T, nqb, ndb;
   float scale;
+  // the forward's attention dropout (DROP kernels): the keep bits of P's stored layout [H*B][T][ldp], attn_stream_common.h
+  float drop_p; const unsigned long long* drop_step; unsigned long long drop_salt; long ldp;
 };
 
 constexpr int RQ_BR = STR_KT + STR_QB;           // query side: band rows staged (KT + QB - 1 are used)
@@ -111,7 +113,10 @@ __device__ __forceinline__ f32x4 band_product(const float4 (&pf)[4], const float
   return g;
 }
 
-template <typename E, bool DELTA>
+// DROP (query, key and position side): the forward built ctx from Pd = P o M / (1 - p), so dP <- M / (1 - p) o (dctx v^T) wherever
+// dS is formed - g and the position side's dbd are that dS -, dv takes Pd, and the DELTA sweep sums P (M / (1 - p) o dP) =
+// Pd dPd.  M is regenerated per tile from the element indices a lane holds (stream_drop_row / stream_keep_col)
+template <typename E, bool DELTA, bool DROP>
 __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_q_kernel(const RelBwdArgs<E> a) {
   __shared__ __attribute__((aligned(16))) float Ks[STR_KT * STR_PLD];
   __shared__ __attribute__((aligned(16))) float Vs[STR_KT * STR_PLD];
@@ -185,6 +190,7 @@ __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_q_kernel(const RelBwdArgs<E
   for (int dt = 0; dt < 4; ++dt) DQ[dt] = DLO[dt] = DHI[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float* G = Gs + wave * 16 * RQ_GLD;
   const int nw0 = (STR_QB - 16) - 16 * wave;                 // this wave's first row of the staged band
+  const AttnDrop drop = DROP ? attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt) : AttnDrop{};
 
   request(0);
   for (int jt = 0; jt < ntile; ++jt) {
@@ -235,6 +241,7 @@ __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_q_kernel(const RelBwdArgs<E
       frag_lds(&Vs[(16 * kt + fr) * STR_PLD], fq, xf);
       dP[kt] = dot64(xf, df, (f32x4){0.f, 0.f, 0.f, 0.f});
     }
+    if (DROP) stream_drop_row(drop, ((long)z * T + qi) * a.ldp, j0, fq, a.ldp, dP);     // the row offset is re-formed here: registers
     if (DELTA) {
 #pragma unroll
       for (int kt = 0; kt < STR_NKT; ++kt)
@@ -320,7 +327,7 @@ __global__ __launch_bounds__(256) void rel_bwd_dqv_shift_kernel(const RelBwdArgs
   *d = y;
 }
 
-template <typename E>
+template <typename E, bool DROP>
 __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_kv_kernel(const RelBwdArgs<E> a) {
   __shared__ __attribute__((aligned(16))) float Qs[STR_KT * STR_PLD];
   __shared__ __attribute__((aligned(16))) float Ds[STR_KT * STR_PLD];
@@ -398,6 +405,7 @@ __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_kv_kernel(const RelBwdArgs<
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) DV[dt] = DK[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float* G = Gs + wave * 16 * KV_GLD;
+  const AttnDrop drop = DROP ? attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt) : AttnDrop{};
 
   request(0);
   for (int it = 0; it < ntile; ++it) {
@@ -465,12 +473,14 @@ __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_kv_kernel(const RelBwdArgs<
       const float4 l4 = *reinterpret_cast<const float4*>(&Ls[16 * qt + 4 * fq]);
       const float4 e4 = *reinterpret_cast<const float4*>(&Es[16 * qt + 4 * fq]);
       const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, eq[4] = {e4.x, e4.y, e4.z, e4.w};
+      float m[4];
+      if (DROP) stream_keep_col(drop, ((long)z * T + i0 + 16 * qt + 4 * fq) * a.ldp + j, a.ldp, m);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float p = __expf(attn_score(P[qt][r], a.scale, j, T, mk[qt], r) - lq[r]);
         if (i0 + 16 * qt + 4 * fq + r >= T) p = 0.f;         // by index: a clamped row would carry a live lse and delta
-        P[qt][r] = p;
-        dS[qt][r] = a.scale * p * (dS[qt][r] - eq[r]);
+        P[qt][r] = DROP ? p * m[r] : p;                      // Pd for dv
+        dS[qt][r] = a.scale * p * ((DROP ? dS[qt][r] * m[r] : dS[qt][r]) - eq[r]);
       }
       baccum16(&Ds[16 * qt * STR_PLD], fr, fq, P[qt], DV);   // dv^T[channel][key] += dCtx_tile^T[channel][query] P[query][key]
       baccum16(&Qs[16 * qt * STR_PLD], fr, fq, dS[qt], DK);  // dk^T[channel][key] += Q_tile^T[channel][query] dS[query][key]
@@ -486,7 +496,7 @@ __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_kv_kernel(const RelBwdArgs<
   }
 }
 
-template <typename E>
+template <typename E, bool DROP>
 __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_dpos_kernel(const RelBwdArgs<E> a) {
   extern __shared__ __attribute__((aligned(16))) float dp_lds[];
   float* Kb = dp_lds;                                        // K, V rows of the band keys jbase .. jbase + 79
@@ -561,6 +571,7 @@ __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_dpos_kernel(const RelBwdArg
   for (int dt = 0; dt < 4; ++dt) DP[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   float* GS = GSs + wave * 16 * DP_GLD;
   float* GP = GPs + wave * 16 * DP_GLD;
+  const AttnDrop drop = DROP ? attn_drop_setup(a.drop_p, a.drop_step, a.drop_salt) : AttnDrop{};
 
   if (it0 < it1) request(it0);
   for (int it = it0; it < it1; ++it) {
@@ -624,13 +635,15 @@ __global__ __launch_bounds__(STR_NT, 2) void rel_bwd_dpos_kernel(const RelBwdArg
     const float4 e4 = *reinterpret_cast<const float4*>(&Es[4 * fq]);
     const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, eq[4] = {e4.x, e4.y, e4.z, e4.w};
     f32x4 g;
+    float m[4];                                              // DROP: element (ii, ii + o) of the pair's P, a diagonal: stride ldp + 1
+    if (DROP) stream_keep_col(drop, ((long)z * T + i0 + 4 * fq) * a.ldp + i0 + 4 * fq + o, a.ldp + 1, m);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int aq = 4 * fq + r, ii = i0 + aq, jj = ii + o;
       const float s = GS[aq * DP_GLD + aq + fr], dp = GP[aq * DP_GLD + aq + fr];          // band key (query + column) of the wave
       const bool on = ii < Ts && jj >= 0 && jj < Ts && jj != ii + 1 && ((mk >> (8 * r)) & 0xffu) != 0u;   // by index, then the mask byte
       const float p = __expf(a.scale * (s + bd[r]) - lq[r]);
-      g[r] = on ? a.scale * p * (dp - eq[r]) : 0.f;
+      g[r] = on ? a.scale * p * ((DROP ? dp * m[r] : dp) - eq[r]) : 0.f;
     }
     wave_handover();                                         // the next tile's stores come after these reads
     // ---- dflat^T[channel][c] += QV_tile^T[channel][query] g[query][c] ----
@@ -685,7 +698,7 @@ template <typename E>
 int rel_bwd_check(const RelBwdArgs<E>& a, int T1, int T2, int dk) {
   const bool operands = a.dctx && a.ctx && a.qu && a.qv && a.k && a.v && a.pos && a.lse && a.delta && a.hi && a.dflat && a.dqu &&
                         a.dqv && a.dk && a.dv && a.dpos;
-  if (const int rc = attn_check_common(operands, a.B, a.H, T1, T2, 0.f, nullptr)) return rc;
+  if (const int rc = attn_check_common(operands, a.B, a.H, T1, T2, a.drop_p, a.drop_step)) return rc;
   if (dk != ATT_DK || T1 != T2 || T1 > (1 << 29)) return EAMD_EUNSUPPORTED;
   if (!stream_in_ok(a.dctx, a.ldd) || !stream_in_ok(a.ctx, a.ldc) || !stream_in_ok(a.qu, a.ldq) || !stream_in_ok(a.qv, a.ldqv) ||
       !stream_in_ok(a.k, a.ldk) || !stream_in_ok(a.v, a.ldv) || !stream_in_ok(a.pos, a.ldpos) || !stream_out_ok(a.dqu, a.lddqu) ||
@@ -695,12 +708,33 @@ int rel_bwd_check(const RelBwdArgs<E>& a, int T1, int T2, int dk) {
   return attn_too_many<E>(a.B, a.H, 2 * T1) ? EAMD_EUNSUPPORTED : EAMD_OK;
 }
 
+template <typename E, bool DROP>
+int rel_bwd_launch(const RelBwdArgs<E>& a, hipStream_t s) {
+  const int B = a.B, H = a.H, T1 = a.T;
+  const long D4 = (long)H * ATT_DK / 4;
+  if constexpr (sizeof(E) == 2) {                            // bf16 storage: delta from its own sweep, not from the rounded ctx
+    hipLaunchKernelGGL((rel_bwd_q_kernel<E, true, DROP>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);
+    EAMD_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL((rel_bwd_q_kernel<E, false, DROP>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);
+  EAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL((rel_bwd_dqv_shift_kernel<E>), dim3((unsigned)(((long)B * T1 * D4 + 255) / 256)), dim3(256), 0, s, a);
+  EAMD_LAUNCH_CHECK();
+  hipLaunchKernelGGL((rel_bwd_kv_kernel<E, DROP>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);       // reads the delta written above
+  EAMD_LAUNCH_CHECK();
+  if (const int rc = attn_launch<rel_bwd_dpos_kernel<E, DROP>>(DP_LDS, attn_grid(a.ndb, B, H), STR_NT, DP_LDS, s, a)) return rc;
+  hipLaunchKernelGGL((rel_bwd_dpos_sum_kernel<E>), dim3((unsigned)(((long)T1 * D4 + 255) / 256)), dim3(256), 0, s, a);
+  EAMD_LAUNCH_CHECK();
+  return EAMD_OK;
+}
+
 template <typename E>
 int rel_bwd_entry(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq, const void* qv, int64_t ldqv,
                   const void* k, int64_t ldk, const void* v, int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask,
                   int64_t mb, int64_t mi, const float* lse, const int32_t* shift_len, float* delta_ws, float* dqv_ws, float* dpos_ws,
                   float* dqu, int64_t lddqu, float* dqv, int64_t lddqv, void* dk_out, int64_t lddk, void* dv, int64_t lddv, float* dpos,
-                  int64_t lddpos, int B, int H, int T1, int T2, int dk, float scale, void* stream) {
+                  int64_t lddpos, int B, int H, int T1, int T2, int dk, float scale, void* stream, float drop_p = 0.f,
+                  const uint64_t* drop_step = nullptr, uint64_t drop_salt = 0) {
   RelBwdArgs<E> a;
   a.dctx = (const E*)dctx; a.ctx = (const E*)ctx; a.qu = (const E*)qu; a.qv = (const E*)qv; a.k = (const E*)k; a.v = (const E*)v;
   a.pos = (const E*)pos; a.mask = mask; a.lse = lse; a.tshift = shift_len;
@@ -709,25 +743,12 @@ int rel_bwd_entry(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, c
   a.ldd = ldd; a.ldc = ldc; a.ldq = ldq; a.ldqv = ldqv; a.ldk = ldk; a.ldv = ldv; a.ldpos = ldpos; a.mb = mb; a.mi = mi;
   a.lddqu = lddqu; a.lddqv = lddqv; a.lddk = lddk; a.lddv = lddv; a.lddpos = lddpos;
   a.B = B; a.H = H; a.T = T1; a.scale = scale;
+  a.drop_p = drop_p; a.drop_step = (const unsigned long long*)drop_step; a.drop_salt = drop_salt; a.ldp = stream_ldp(T2);
   if (const int rc = rel_bwd_check(a, T1, T2, dk)) return rc;
   a.nqb = (T1 + STR_QB - 1) / STR_QB;
   a.ndb = (2 * T1 + STR_QB - 1) / STR_QB;                    // flat columns 0 .. 2 T - 1
   hipStream_t s = (hipStream_t)stream;
-  const long D4 = (long)H * ATT_DK / 4;
-  if constexpr (sizeof(E) == 2) {                            // bf16 storage: delta from its own sweep, not from the rounded ctx
-    hipLaunchKernelGGL((rel_bwd_q_kernel<E, true>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);
-    EAMD_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL((rel_bwd_q_kernel<E, false>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);
-  EAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL((rel_bwd_dqv_shift_kernel<E>), dim3((unsigned)(((long)B * T1 * D4 + 255) / 256)), dim3(256), 0, s, a);
-  EAMD_LAUNCH_CHECK();
-  hipLaunchKernelGGL((rel_bwd_kv_kernel<E>), dim3(attn_grid(a.nqb, B, H)), dim3(STR_NT), 0, s, a);       // reads the delta written above
-  EAMD_LAUNCH_CHECK();
-  if (const int rc = attn_launch<rel_bwd_dpos_kernel<E>>(DP_LDS, attn_grid(a.ndb, B, H), STR_NT, DP_LDS, s, a)) return rc;
-  hipLaunchKernelGGL((rel_bwd_dpos_sum_kernel<E>), dim3((unsigned)(((long)T1 * D4 + 255) / 256)), dim3(256), 0, s, a);
-  EAMD_LAUNCH_CHECK();
-  return EAMD_OK;
+  return drop_p > 0.f ? rel_bwd_launch<E, true>(a, s) : rel_bwd_launch<E, false>(a, s);
 }
 
 }  // namespace
@@ -754,4 +775,33 @@ extern "C" int eamd_attn_bwd_stream_rel(const void* dctx, int64_t ldd, const voi
   return rel_bwd_entry<bf16_t>(dctx, ldd, ctx, ldc, qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, lse,
                                shift_len, delta_ws, dqv_ws, dpos_ws, dqu, lddqu, dqv, lddqv, dk_bf16, lddk, dv_bf16, lddv, dpos, lddpos,
                                B, H, T1, T2, dk, scale, stream);
+}
+
+// the backward of eamd_attn_fwd_stream_drop[_f32] called with qv / pos, at the same (drop_p, drop_step, drop_salt): the keep bits are
+// drawn again per tile in all three sweeps (and in bf16 storage's delta sweep).  drop_p == 0 launches the kernels of the entry
+// points above: their bits
+extern "C" int eamd_attn_bwd_stream_rel_drop_f32(const float* dctx, int64_t ldd, const float* ctx, int64_t ldc, const float* qu,
+                                                 int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk, const float* v,
+                                                 int64_t ldv, const float* pos, int64_t ldpos, const unsigned char* mask,
+                                                 int64_t mask_bstride, int64_t mask_qstride, const float* lse, const int32_t* shift_len,
+                                                 float* delta_ws, float* dqv_ws, float* dpos_ws, float* dqu, int64_t lddqu, float* dqv,
+                                                 int64_t lddqv, float* dk_out, int64_t lddk, float* dv, int64_t lddv, float* dpos,
+                                                 int64_t lddpos, int B, int H, int T1, int T2, int dk, float scale, float drop_p,
+                                                 const uint64_t* drop_step, uint64_t drop_salt, void* stream) {
+  return rel_bwd_entry<float>(dctx, ldd, ctx, ldc, qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, lse,
+                              shift_len, delta_ws, dqv_ws, dpos_ws, dqu, lddqu, dqv, lddqv, dk_out, lddk, dv, lddv, dpos, lddpos, B, H,
+                              T1, T2, dk, scale, stream, drop_p, drop_step, drop_salt);
+}
+
+extern "C" int eamd_attn_bwd_stream_rel_drop(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq,
+                                             const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                             const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                                             int64_t mask_qstride, const float* lse, const int32_t* shift_len, float* delta_ws,
+                                             float* dqv_ws, float* dpos_ws, float* dqu, int64_t lddqu, float* dqv, int64_t lddqv,
+                                             void* dk_bf16, int64_t lddk, void* dv_bf16, int64_t lddv, float* dpos, int64_t lddpos,
+                                             int B, int H, int T1, int T2, int dk, float scale, float drop_p,
+                                             const uint64_t* drop_step, uint64_t drop_salt, void* stream) {
+  return rel_bwd_entry<bf16_t>(dctx, ldd, ctx, ldc, qu, ldq, qv, ldqv, k, ldk, v, ldv, pos, ldpos, mask, mask_bstride, mask_qstride, lse,
+                               shift_len, delta_ws, dqv_ws, dpos_ws, dqu, lddqu, dqv, lddqv, dk_bf16, lddk, dv_bf16, lddv, dpos, lddpos,
+                               B, H, T1, T2, dk, scale, stream, drop_p, drop_step, drop_salt);
 }

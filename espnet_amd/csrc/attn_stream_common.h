@@ -44,6 +44,34 @@ __device__ __forceinline__ int band_pos_row(int c, int Ts) {
   return min(max(m, 0), Ts - 1);
 }
 
+// ---- attention dropout (the *_drop entry points) ----
+// No probability is stored, but the keep bits are those the stored route draws (attn_f32.hip / attn_fused.hip, ops.dropout on P):
+// element (z = h B + b, i, j) of P in ITS layout [H*B][T1][ldp] is kept iff eamd_dropout keeps index (z T1 + i) ldp + j at
+// (drop_step, drop_salt) - a 64-bit index: H B T1 ldp passes 2^32 at the lengths these kernels exist for.  The generator is
+// counter-based, so forward and the three backward sweeps regenerate a tile's bits from the indices of the score elements a lane
+// holds in its accumulator, and the two routes are interchangeable at a given (step, salt).
+// the row stride the stored route gives P (functional._ldp): T2 rounded up to 8 elements
+inline long stream_ldp(int T2) { return ((long)T2 + 7) / 8 * 8; }
+// a row's layout (query side): w[kt][r] = key j0 + 16 kt + 4 fq + r of the query whose P row starts at element pro - eight
+// four-key pieces of a staged tile per row, two per lane, each drawn as attn_keep4 draws it (clamped at the row's last piece:
+// only pieces wholly past T2 are, and their probabilities are zero by index).  w <- keep ? w / (1 - p) : 0
+__device__ __forceinline__ void stream_drop_row(const AttnDrop& d, long pro, int j0, int fq, long ldp, f32x4 (&w)[STR_NKT]) {
+#pragma unroll
+  for (int kt = 0; kt < STR_NKT; ++kt) {
+    bool kp[4];
+    attn_keep4(d, pro, j0 + 16 * kt + 4 * fq, ldp, kp);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) w[kt][r] = kp[r] ? w[kt][r] * d.dinv : 0.f;
+  }
+}
+// a column's layout (key side, position side): the lane's four elements lie `stride` apart in P (ldp: four queries of one key;
+// ldp + 1: four queries of one diagonal), so each takes the half of its own pair's hash.  m[r] = keep ? 1 / (1 - p) : 0 of
+// element e0 + r stride; elements outside the matrix draw bits nobody uses (their probability is zero by index)
+__device__ __forceinline__ void stream_keep_col(const AttnDrop& d, long e0, long stride, float (&m)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) m[r] = eamd_drop_keep(d.seed, (unsigned long long)(e0 + r * stride), d.thr) ? d.dinv : 0.f;
+}
+
 // operand rules of both directions; a matrix that breaks one makes the entry point decline (EAMD_EUNSUPPORTED) before any launch.
 // Read in 16-byte pieces: 16-byte aligned, row stride a multiple of 16 bytes
 template <typename T>

@@ -508,7 +508,7 @@ def attn_fwd_fused(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=None, shift_len
                         shift_len=shift_len)
 
 
-# Without autograd (F_.run's inference branch), attention dropout and the attention tap, rows of MORE keys than this run the
+# Without autograd (F_.run's inference branch) and the attention tap, rows of MORE keys than this run the
 # memory-linear forward of csrc/attn_stream.hip, which stores no probabilities.  The default leaves every shape that has a fused
 # stored-P path on it, bit for bit; lower it (0: always) to trade the stored-P kernels for O(T') memory at shorter lengths.
 ATTN_STREAM_KEYS = 4096
@@ -520,19 +520,26 @@ ATTN_STREAM_TRAIN_KEYS = 4096
 # lse of the scores with the position term, and backward rebuilds the probabilities and forms the position-side gradients (dqv,
 # dpos) tile by tile (csrc/attn_stream_bwd_rel.hip).  Up to it they train on the stored-P kernels, as before.
 ATTN_STREAM_TRAIN_REL_KEYS = 4096
+# With attention dropout (p_att > 0) a block takes any of the three routes above only on rows of more keys than this as well.  The
+# streamed kernels regenerate the stored route's keep bits tile by tile (csrc/attn_stream_common.h), so at a given (step, salt)
+# both routes drop the same probabilities; the hashing costs 5 - 11 %.  A threshold of its own, so that a setup
+# that lowered the ones above while training with attention dropout keeps the stored-P kernels it ran before the streamed ones
+# carried dropout; lower it with them (0: always) to stream such blocks at shorter lengths too.
+ATTN_STREAM_DROP_KEYS = 4096
 
 
-def attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, lse=None):
-    """ctx from eamd_attn_fwd_stream (with lse: eamd_attn_fwd_stream_lse), or None when the library declines the operands"""
+def attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, lse=None, drop=None):
+    """ctx from eamd_attn_fwd_stream (with lse: eamd_attn_fwd_stream_lse; with drop = (p, salt): eamd_attn_fwd_stream_drop), or
+    None when the library declines the operands"""
     qv, p = _rel_views(qv, p)
     return ops.attn_fwd_stream(_mv(qu), qv, _mv(k), _mv(v), p, mask, B, T1, T2, H, dk, scale=1.0 / math.sqrt(dk),
-                               shift_len=shift_len, lse=lse)
+                               shift_len=shift_len, lse=lse, drop=drop)
 
 
-def attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T1, T2, H, dk, dqkv=None, dkv_out=None):
+def attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T1, T2, H, dk, dqkv=None, dkv_out=None, drop=None):
     """backward of the streamed forward without relative positions -> (dq, dk, dv) in the GEMM-operand dtype, or None when the
     library declines the operands.  dqkv / dkv_out as in attn_core_bwd: the three gradients are written into the column blocks
-    of dqkv (dq is then returned as None), dk / dv into dkv_out's."""
+    of dqkv (dq is then returned as None), dk / dv into dkv_out's.  drop = (p, salt) of the forward's attention dropout, or None."""
     D = H * dk
     dev, adt = dctx.device, ops.act_dtype()
     qu, k, v = _mv(qu), _mv(k), _mv(v)
@@ -551,15 +558,15 @@ def attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T1, T2, H, dk, dqkv=None, 
         else:
             dkm, dvm = (_MV(torch.empty(B * T2, D, device=dev, dtype=adt), 0, D) for _ in range(2))
     if not ops.attn_bwd_stream(_MV(dctx, 0, D), _MV(cx, 0, D), qu, k, v, mask, lse, dqm, dkm, dvm, B, T1, T2, H, dk,
-                               1.0 / math.sqrt(dk)):
+                               1.0 / math.sqrt(dk), drop=drop):
         return None
     return dq, dkm.t, dvm.t
 
 
-def attn_stream_rel_bwd(dctx, cx, lse, qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, dqkv=None, dp_out=None):
+def attn_stream_rel_bwd(dctx, cx, lse, qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=None, dqkv=None, dp_out=None, drop=None):
     """backward of the streamed forward with relative positions -> (dqu, dqv, dk, dv, dp) as attn_core_bwd returns them (dqu / dqv
     fp32; dk / dv into column blocks 1 / 2 of dqkv; dp added into dp_out and returned as None), or None when the library
-    declines the operands"""
+    declines the operands.  drop = (p, salt) of the forward's attention dropout, or None."""
     D = H * dk
     dev, adt = dctx.device, ops.act_dtype()
     qu, qv, k, v, p = _mv(qu), _mv(qv), _mv(k), _mv(v), _mv(p)
@@ -573,7 +580,7 @@ def attn_stream_rel_bwd(dctx, cx, lse, qu, qv, k, v, p, mask, B, T1, T2, H, dk, 
     dp = torch.zeros(T2, D, device=dev, dtype=torch.float32) if dp_out is None else None
     if not ops.attn_bwd_stream_rel(_MV(dctx, 0, D), _MV(cx, 0, D), qu, qv, k, v, p, mask, lse, _MV(dqu, 0, D), _MV(dqv, 0, D), dkm, dvm,
                                    _MV(dp, 0, D) if dp_out is None else dp_out, B, T1, T2, H, dk, 1.0 / math.sqrt(dk),
-                                   shift_len=shift_len):
+                                   shift_len=shift_len, drop=drop):
         return None
     return dqu, dqv, dkm.t, dvm.t, dp
 
@@ -715,24 +722,26 @@ def attn_block_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop, shift_len, gra
     """-> (ctx [B*T1, H*dk], AttnKept) of one attention block.  drop = (p, salt) of the attention dropout; grad: autograd is on;
     stream_bwd_ok: a shared k / v projection collects gradients in the operand dtype, which the streamed backward writes."""
     p_att = drop[0]
-    unread = ATTN_TAP is None and p_att <= 0.0 and dk == 64       # nobody reads the probabilities, and the streamed kernels fit
+    # nobody reads the probabilities, the streamed kernels fit, and with attention dropout the row is past ATTN_STREAM_DROP_KEYS
+    unread = ATTN_TAP is None and dk == 64 and (p_att <= 0.0 or T2 > ATTN_STREAM_DROP_KEYS)
+    sdrop = drop if p_att > 0.0 else None        # attention dropout inside the streamed kernels: the stored route's mask
     if not grad and unread and T2 > ATTN_STREAM_KEYS:
         # inference on long rows: online softmax, O(T') memory, any number of keys
-        cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=shift_len)
+        cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=shift_len, drop=sdrop)
         if cx is not None:
             return cx, AttnKept("stream")
     if grad and unread and p is None and not last_query_only and T2 > ATTN_STREAM_TRAIN_KEYS and stream_bwd_ok:
         # training on long rows without relative positions: keep ctx and the row statistic, no probabilities; backward
         # rebuilds them tile by tile (attn_stream_bwd)
         lse = torch.empty(H * B * T1, device=_mv(qu).t.device, dtype=torch.float32)
-        cx = attn_fwd_stream(qu, None, k, v, None, mask, B, T1, T2, H, dk, lse=lse)
+        cx = attn_fwd_stream(qu, None, k, v, None, mask, B, T1, T2, H, dk, lse=lse, drop=sdrop)
         if cx is not None:
             return cx, AttnKept("stream", lse=lse, mask=mask)
     if grad and unread and p is not None and T1 == T2 and not last_query_only and T2 > ATTN_STREAM_TRAIN_REL_KEYS:
         # training on long rows with relative positions: the same, the row statistic taken over the scores with the position
         # term; backward rebuilds them and the position-side gradients (attn_stream_rel_bwd)
         lse = torch.empty(H * B * T1, device=_mv(qu).t.device, dtype=torch.float32)
-        cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=shift_len, lse=lse)
+        cx = attn_fwd_stream(qu, qv, k, v, p, mask, B, T1, T2, H, dk, shift_len=shift_len, lse=lse, drop=sdrop)
         if cx is not None:
             return cx, AttnKept("stream", lse=lse, mask=mask)
     P, Pd, cx, fused = attn_stored_fwd(qu, qv, k, v, p, mask, B, T1, T2, H, dk, drop=drop if p_att > 0.0 else None,
@@ -752,19 +761,23 @@ def attn_block_bwd(kept, dctx, cx, qu, qv, k, v, p, B, T1, T2, H, dk, drop, shif
     """backward of attn_block_fwd -> (dqu, dqv, dk, dv, dp) as attn_core_bwd returns them (dqkv / dkv_out / dp_out as there).
     After the streamed backward dqu is already a GEMM operand (ops.to_act passes it through), or None with dqkv."""
     P, Pd = kept.P, kept.Pd
+    sdrop = drop if drop[0] > 0.0 else None
     if kept.route == "stream" and p is not None:
         sb = attn_stream_rel_bwd(dctx, cx, kept.lse, qu, qv, k, v, p, kept.mask, B, T1, T2, H, dk, shift_len=shift_len, dqkv=dqkv,
-                                 dp_out=dp_out)
+                                 dp_out=dp_out, drop=sdrop)
         if sb is not None:
             return sb
         # the library declined the streamed backward: the probabilities of the stored route, rebuilt with the position term
-        P = attn_stored_fwd(qu, qv, k, v, p, kept.mask, B, T1, T2, H, dk, shift_len=shift_len, context=False)[0]
+        # (and, with attention dropout, their dropped copy: the same mask)
+        P, Pd = attn_stored_fwd(qu, qv, k, v, p, kept.mask, B, T1, T2, H, dk, drop=sdrop, shift_len=shift_len, context=False)[:2]
+        Pd = Pd if sdrop is not None else None
     elif kept.route == "stream":
-        sb = attn_stream_bwd(dctx, cx, kept.lse, qu, k, v, kept.mask, B, T1, T2, H, dk, dqkv=dqkv, dkv_out=dkv_out)
+        sb = attn_stream_bwd(dctx, cx, kept.lse, qu, k, v, kept.mask, B, T1, T2, H, dk, dqkv=dqkv, dkv_out=dkv_out, drop=sdrop)
         if sb is not None:
             return sb[0], None, sb[1], sb[2], None
-        # the library declined the streamed backward: the probabilities of the stored route, rebuilt
-        P = attn_stored_fwd(qu, None, k, v, None, kept.mask, B, T1, T2, H, dk, context=False)[0]
+        # the library declined the streamed backward: the probabilities of the stored route, rebuilt (with their dropped copy)
+        P, Pd = attn_stored_fwd(qu, None, k, v, None, kept.mask, B, T1, T2, H, dk, drop=sdrop, context=False)[:2]
+        Pd = Pd if sdrop is not None else None
     elif kept.route == "recompute":
         # the probabilities this block did not keep: the fused forward once more (attn_block_fwd, ATTN_RECOMPUTE_MB)
         fwd = attn_fwd_fused(qu, qv, k, v, p, kept.mask, B, T1, T2, H, dk, drop=drop if drop[0] > 0.0 else None, shift_len=shift_len)

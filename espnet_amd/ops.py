@@ -1179,12 +1179,22 @@ def _mask_strides(mask, B, T1, T2):
     return (0 if mask.shape[0] == 1 else mask.shape[1] * mask.shape[2]), (0 if mask.shape[1] == 1 else T2)
 
 
-def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1.0, shift_len=None, out=None, lse=None):
-    """ctx [B*T1, ldc] (ldc: H*dk unless given) of attn_fwd without dropout, by the online-softmax kernel of
+def _stream_drop(name, drop, device):
+    """the *_drop twin of a streamed entry point and its (drop_p, drop_step, drop_salt) arguments; drop = (p, salt) or None: the
+    entry point itself, no arguments"""
+    if drop is None:
+        return name, ()
+    head, f32 = (name[:-4], "_f32") if name.endswith("_f32") else (name, "")
+    return head + "_drop" + f32, (drop[0], ptr(rng_state(device)), drop[1])
+
+
+def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1.0, shift_len=None, out=None, lse=None, drop=None):
+    """ctx [B*T1, ldc] (ldc: H*dk unless given) of attn_fwd, by the online-softmax kernel of
     csrc/attn_stream.hip: no probabilities are stored, any number of keys.  Views as for attn_fwd;
     out: such a view to write ctx into (its tensor is returned) instead of a fresh tensor.  lse: an fp32 [H*B*T1] tensor that
-    receives the row statistic attn_bwd_stream rebuilds the probabilities from (training; eamd_attn_fwd_stream_lse).  Returns
-    None if the library declines the operands (EAMD_EUNSUPPORTED)."""
+    receives the row statistic attn_bwd_stream rebuilds the probabilities from (training; eamd_attn_fwd_stream_lse).
+    drop = (p, salt): attention dropout under the mask attn_fwd draws (eamd_attn_fwd_stream_drop; lse stays that of the undropped
+    scores).  Returns None if the library declines the operands (EAMD_EUNSUPPORTED)."""
     dev = qu[0].device
     dt = qu[0].dtype
     D = H * dk
@@ -1204,15 +1214,20 @@ def attn_fwd_stream(qu, qv, k, v, pos, mask, B, T1, T2, H, dk, ldc=None, scale=1
     name = "eamd_attn_fwd_stream" if dt == torch.bfloat16 else "eamd_attn_fwd_stream_f32"
     if lse is not None:
         assert lse.dtype == torch.float32 and lse.is_cuda and lse.is_contiguous() and lse.numel() >= H * B * T1
+    if drop is not None:                   # one entry point for both forms: lse may be NULL
+        name, dargs = _stream_drop(name, drop, dev)
+        args = args + (ptr(lse),) + dargs
+    elif lse is not None:
         name = name.replace("_stream", "_stream_lse")
         args = args + (ptr(lse),)
     return cx if _attn_launch(name, args, (qu, qv, k, v, pos, mask, cx, lse)) else None
 
 
-def attn_bwd_stream(dctx, ctx, qu, k, v, mask, lse, dq, dk_, dv, B, T1, T2, H, dk, scale):
+def attn_bwd_stream(dctx, ctx, qu, k, v, mask, lse, dq, dk_, dv, B, T1, T2, H, dk, scale, drop=None):
     """The backward of attn_fwd_stream(..., lse=lse) without relative positions (csrc/attn_stream_bwd.hip): dq, dk_ and dv are
     written from dctx, the forward's ctx and lse and the operands, the probabilities rebuilt tile by tile - no [T1, T2] tensor.
     All nine matrices are (tensor, element offset, row stride) views in one dtype (bf16: eamd_attn_bwd_stream, fp32: _f32).
+    drop = (p, salt): the forward's attention dropout (eamd_attn_bwd_stream_drop), its mask drawn again tile by tile.
     Returns False if the library declines the operands (EAMD_EUNSUPPORTED)."""
     dt = qu[0].dtype
     assert dt in (torch.bfloat16, torch.float32)
@@ -1222,17 +1237,19 @@ def attn_bwd_stream(dctx, ctx, qu, k, v, mask, lse, dq, dk_, dv, B, T1, T2, H, d
     mb, mi = _mask_strides(mask, B, T1, T2)
     ws = torch.empty(H * B * T1, device=lse.device, dtype=torch.float32)      # delta: query side -> key side
     args = _view_args(dctx, ctx, qu, k, v) + (ptr(mask), mb, mi, ptr(lse), ptr(ws)) + _view_args(dq, dk_, dv) + (B, H, T1, T2, dk, scale)
-    name = "eamd_attn_bwd_stream" if dt == torch.bfloat16 else "eamd_attn_bwd_stream_f32"
-    return _attn_launch(name, args, (dctx, ctx, qu, k, v, mask, lse, ws, dq, dk_, dv))
+    name, dargs = _stream_drop("eamd_attn_bwd_stream" if dt == torch.bfloat16 else "eamd_attn_bwd_stream_f32", drop, lse.device)
+    return _attn_launch(name, args + dargs, (dctx, ctx, qu, k, v, mask, lse, ws, dq, dk_, dv))
 
 
-def attn_bwd_stream_rel(dctx, ctx, qu, qv, k, v, pos, mask, lse, dqu, dqv, dk_, dv, dpos, B, T1, T2, H, dk, scale, shift_len=None):
+def attn_bwd_stream_rel(dctx, ctx, qu, qv, k, v, pos, mask, lse, dqu, dqv, dk_, dv, dpos, B, T1, T2, H, dk, scale, shift_len=None,
+                        drop=None):
     """The backward of attn_fwd_stream(qu, qv, k, v, pos, ..., lse=lse) WITH relative positions (csrc/attn_stream_bwd_rel.hip):
     the probabilities are rebuilt tile by tile with the position term - no [T1, T2] tensor.  dctx / ctx / qu / qv / k / v / pos and
     dk_ / dv are (tensor, element offset, row stride) views in one dtype (bf16: eamd_attn_bwd_stream_rel, fp32: _f32); dqu / dqv /
     dpos are such views of fp32 tensors.  dqu, dqv, dk_ and dv are written, dpos [T2, H*dk] is ADDED INTO (shared by the batch
     and, through a shared positional projection, by the layers).  The fp32 workspaces are sized here from the shapes the header
     documents: delta [H*B*T1], the upper-part row sums [B*T1, H*dk], the per-batch diagonal sums [B, 2*T1, H*dk].
+    drop = (p, salt): the forward's attention dropout (eamd_attn_bwd_stream_rel_drop), its mask drawn again tile by tile.
     Returns False if the library declines the operands (EAMD_EUNSUPPORTED)."""
     dt = qu[0].dtype
     assert dt in (torch.bfloat16, torch.float32)
@@ -1248,8 +1265,8 @@ def attn_bwd_stream_rel(dctx, ctx, qu, qv, k, v, pos, mask, lse, dqu, dqv, dk_, 
     args = _view_args(dctx, ctx, qu, qv, k, v, pos) + (ptr(mask), mb, mi, ptr(lse), ptr(shift_len) if T1 == T2 else None,
                                                        ptr(ws), ptr(ws, n0), ptr(ws, n0 + B * T1 * D))
     args = args + _view_args(dqu, dqv, dk_, dv, dpos) + (B, H, T1, T2, dk, scale)
-    name = "eamd_attn_bwd_stream_rel" if dt == torch.bfloat16 else "eamd_attn_bwd_stream_rel_f32"
-    return _attn_launch(name, args, (dctx, ctx, qu, qv, k, v, pos, mask, lse, shift_len, ws, dqu, dqv, dk_, dv, dpos))
+    name, dargs = _stream_drop("eamd_attn_bwd_stream_rel" if dt == torch.bfloat16 else "eamd_attn_bwd_stream_rel_f32", drop, lse.device)
+    return _attn_launch(name, args + dargs, (dctx, ctx, qu, qv, k, v, pos, mask, lse, shift_len, ws, dqu, dqv, dk_, dv, dpos))
 
 
 def attn_bwd_q(dctx, k, v, P, dS, dbd, dq, B, T1, T2, H, dk, ldp, scale, drop=None, shift_len=None):

@@ -440,6 +440,53 @@ int eamd_attn_bwd_stream_rel_f32(const float* dctx, int64_t ldd, const float* ct
                                  float* dk_out, int64_t lddk, float* dv, int64_t lddv, float* dpos, int64_t lddpos, int B,
                                  int H, int T1, int T2, int dk, float scale, void* stream);
 
+/* The streamed forward and both streamed backwards WITH attention dropout (attention.py:91): ctx = dropout(P) v, still without a
+ * stored probability.  The keep bits are the ones eamd_attn_fwd draws for (drop_step, drop_salt): element (z = h*B + b, i, j) is
+ * kept iff eamd_dropout keeps index (z*T1 + i)*ldp + j of P's stored layout [H*B][T1][ldp], ldp = T2 rounded up to 8 - so the
+ * stored and the streamed route are interchangeable at a given (step, salt).  The generator is counter-based: every sweep draws
+ * a tile's bits again from the indices of the elements it holds, nothing is kept between forward and backward but ctx and lse.
+ * Arguments of eamd_attn_fwd_stream_lse / eamd_attn_bwd_stream / eamd_attn_bwd_stream_rel with drop_p, drop_step (device step
+ * counter), drop_salt in front of `stream`; lse is the statistic of the UNDROPPED scores (its p = 0 bits) and may be NULL in the
+ * forward when no backward follows.  delta = dctx . ctx as without dropout (sum_j P dP = sum_j Pd dPd); dv = Pd^T dctx;
+ * dS = scale P (M / (1 - p) (dctx v^T) - delta).  drop_p outside [0, 1), or drop_p > 0 without drop_step: EAMD_EINVAL; everything
+ * else as the entry points above, all before any launch.  drop_p == 0 runs their kernels: their bits. */
+int eamd_attn_fwd_stream_drop(const void* qu, int64_t ldq, const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v,
+                              int64_t ldv, const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                              int64_t mask_qstride, void* ctx_bf16, int64_t ldc, int B, int H, int T1, int T2, int dk, float scale,
+                              const int32_t* shift_len, float* lse, float drop_p, const uint64_t* drop_step, uint64_t drop_salt,
+                              void* stream);
+int eamd_attn_fwd_stream_drop_f32(const float* qu, int64_t ldq, const float* qv, int64_t ldqv, const float* k, int64_t ldk,
+                                  const float* v, int64_t ldv, const float* pos, int64_t ldpos, const unsigned char* mask,
+                                  int64_t mask_bstride, int64_t mask_qstride, float* ctx, int64_t ldc, int B, int H, int T1, int T2,
+                                  int dk, float scale, const int32_t* shift_len, float* lse, float drop_p, const uint64_t* drop_step,
+                                  uint64_t drop_salt, void* stream);
+int eamd_attn_bwd_stream_drop(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq, const void* k,
+                              int64_t ldk, const void* v, int64_t ldv, const unsigned char* mask, int64_t mask_bstride,
+                              int64_t mask_qstride, const float* lse, float* delta_ws, void* dq_bf16, int64_t lddq, void* dk_bf16,
+                              int64_t lddk, void* dv_bf16, int64_t lddv, int B, int H, int T1, int T2, int dk, float scale,
+                              float drop_p, const uint64_t* drop_step, uint64_t drop_salt, void* stream);
+int eamd_attn_bwd_stream_drop_f32(const float* dctx, int64_t ldd, const float* ctx, int64_t ldc, const float* qu, int64_t ldq,
+                                  const float* k, int64_t ldk, const float* v, int64_t ldv, const unsigned char* mask,
+                                  int64_t mask_bstride, int64_t mask_qstride, const float* lse, float* delta_ws, float* dq,
+                                  int64_t lddq, float* dk_out, int64_t lddk, float* dv, int64_t lddv, int B, int H, int T1, int T2,
+                                  int dk, float scale, float drop_p, const uint64_t* drop_step, uint64_t drop_salt, void* stream);
+int eamd_attn_bwd_stream_rel_drop(const void* dctx, int64_t ldd, const void* ctx, int64_t ldc, const void* qu, int64_t ldq,
+                                  const void* qv, int64_t ldqv, const void* k, int64_t ldk, const void* v, int64_t ldv,
+                                  const void* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                                  int64_t mask_qstride, const float* lse, const int32_t* shift_len, float* delta_ws,
+                                  float* dqv_ws, float* dpos_ws, float* dqu, int64_t lddqu, float* dqv, int64_t lddqv,
+                                  void* dk_bf16, int64_t lddk, void* dv_bf16, int64_t lddv, float* dpos, int64_t lddpos, int B,
+                                  int H, int T1, int T2, int dk, float scale, float drop_p, const uint64_t* drop_step,
+                                  uint64_t drop_salt, void* stream);
+int eamd_attn_bwd_stream_rel_drop_f32(const float* dctx, int64_t ldd, const float* ctx, int64_t ldc, const float* qu, int64_t ldq,
+                                      const float* qv, int64_t ldqv, const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                      const float* pos, int64_t ldpos, const unsigned char* mask, int64_t mask_bstride,
+                                      int64_t mask_qstride, const float* lse, const int32_t* shift_len, float* delta_ws,
+                                      float* dqv_ws, float* dpos_ws, float* dqu, int64_t lddqu, float* dqv, int64_t lddqv,
+                                      float* dk_out, int64_t lddk, float* dv, int64_t lddv, float* dpos, int64_t lddpos, int B,
+                                      int H, int T1, int T2, int dk, float scale, float drop_p, const uint64_t* drop_step,
+                                      uint64_t drop_salt, void* stream);
+
 /* Key side of the attention backward in one launch (fp32 tensors, d_k = 64; any T1 / T2): dv = Pd^T dctx, dk = dS^T qu and,
  * with relative positions (dbd, qv, dpos all set; T1 == T2), dpos += dbd^T qv summed over the batch (dpos is ACCUMULATED
  * into: positions are shared by the batch; zero it first).  Pd / dS / dbd: [H][B][T1][ldp] as eamd_attn_fwd_f32 /

@@ -72,20 +72,19 @@ def train_rows(args, res):
             qu, k, v = (F_._MV(qkv, i * D, 3 * D) for i in range(3))
             mask = torch.ones(B, 1, T, dtype=torch.uint8, device=dev)
             stored = ops.attn_fwd_supported(T, T, dk, False)
+            drop = (args.drop, 7) if args.drop > 0.0 else None       # attention dropout: both routes draw the same mask
 
             def stream():
                 lse = torch.empty(H * B * T, device=dev, dtype=torch.float32)
-                cx = F_.attn_fwd_stream(qu, None, k, v, None, mask, B, T, T, H, dk, lse=lse)
-                assert F_.attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T, T, H, dk, dqkv=dqkv) is not None
+                cx = F_.attn_fwd_stream(qu, None, k, v, None, mask, B, T, T, H, dk, lse=lse, drop=drop)
+                assert F_.attn_stream_bwd(dctx, cx, lse, qu, k, v, mask, B, T, T, H, dk, dqkv=dqkv, drop=drop) is not None
 
             def other():
-                P = F_.attn_fwd_fused(qu, None, k, v, None, mask, B, T, T, H, dk)[0] if stored else F_.attn_scores_fwd(qu, None, k, None, mask, B, T, T, H, dk)
-                if not stored:
-                    F_.attn_context_fwd(P, v, B, T, T, H, dk)
-                F_.attn_core_bwd(dctx, P, qu, None, k, v, None, B, T, T, H, dk, dqkv=dqkv)
-            need = H * B * T * T * (2 * qkv.element_size() if stored else 8 if prec == "fp32" else 12)
+                P, Pd = F_.attn_stored_fwd(qu, None, k, v, None, mask, B, T, T, H, dk, drop=drop)[:2]
+                F_.attn_core_bwd(dctx, P, qu, None, k, v, None, B, T, T, H, dk, Pd=Pd if drop else None, attn_drop=drop or (0.0, 0), dqkv=dqkv)
+            need = H * B * T * T * (2 * qkv.element_size() if stored else 8 if prec == "fp32" else 12) * (2 if drop else 1)
             fits = need < 0.8 * torch.cuda.mem_get_info()[0]
-            row = dict(precision=prec, T=T, other="stored_p" if stored else "gemm_softmax", rounds=[], stream_peak_bytes=peak_rise(stream),
+            row = dict(precision=prec, T=T, drop=args.drop, other="stored_p" if stored else "gemm_softmax", rounds=[], stream_peak_bytes=peak_rise(stream),
                        other_peak_bytes=None)
             try:
                 if fits:
@@ -124,18 +123,19 @@ def train_rel_rows(args, res):
             dqkv = torch.empty_like(qkv)
             k, v = F_._MV(qkv, D, 3 * D), F_._MV(qkv, 2 * D, 3 * D)
             mask = torch.ones(B, 1, T, dtype=torch.uint8, device=dev)
+            drop = (args.drop, 7)                                    # attention dropout: both routes draw the same mask
 
             def block(keys, route):
                 F_.ATTN_STREAM_TRAIN_REL_KEYS = keys
                 try:
-                    cx, kept = F_.attn_block_fwd(qu, qv, k, v, p, mask, B, T, T, H, dk, (0.0, 0), None, True, False, True)
+                    cx, kept = F_.attn_block_fwd(qu, qv, k, v, p, mask, B, T, T, H, dk, drop, None, True, False, True)
                     assert kept.route == route, kept.route
-                    F_.attn_block_bwd(kept, dctx, cx, qu, qv, k, v, p, B, T, T, H, dk, (0.0, 0), None, dqkv=dqkv)
+                    F_.attn_block_bwd(kept, dctx, cx, qu, qv, k, v, p, B, T, T, H, dk, drop, None, dqkv=dqkv)
                 finally:
                     F_.ATTN_STREAM_TRAIN_REL_KEYS = default
             stream, other = (lambda: block(default, "stream")), (lambda: block(1 << 30, "gemm"))
-            fits = H * B * T * T * (16 if prec == "fp32" else 20) < 0.8 * torch.cuda.mem_get_info()[0]
-            row = dict(precision=prec, T=T, B=B, other="gemm_softmax", rounds=[], stream_peak_bytes=peak_rise(stream),
+            fits = H * B * T * T * ((16 if prec == "fp32" else 20) + (8 if args.drop > 0.0 else 0)) < 0.8 * torch.cuda.mem_get_info()[0]
+            row = dict(precision=prec, T=T, B=B, drop=args.drop, other="gemm_softmax", rounds=[], stream_peak_bytes=peak_rise(stream),
                        other_peak_bytes=peak_rise(other) if fits else None)
             for _ in range(args.rounds):
                 r = dict(stream_ms=timed(stream, args.warmup, args.iters))
@@ -155,6 +155,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--train", action="store_true", help="forward + backward rows (no relative positions)")
     ap.add_argument("--rel", action="store_true", help="with --train: one rel-pos block, streamed against GEMM + softmax, at --T (default 8192)")
+    ap.add_argument("--drop", type=float, default=0.0, help="with --train: attention dropout p inside both routes (same mask)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--T", type=int, nargs="+", default=None)
@@ -170,6 +171,8 @@ def main():
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "attn_stream_train_rel_bench.json" if rel_train else
                                 "attn_stream_train_bench.json" if args.train else "attn_stream_bench.json")
+        if args.train and args.drop > 0.0:
+            args.out = args.out.replace("_bench", "_drop_bench")
     import espnet_amd
     from espnet_amd import functional as F_, ops
     commit = args.commit
